@@ -195,22 +195,28 @@ class Leg:
 
     PROF_KEYS = ("march4", "march_pl", "march_corr", "march3", "march2", "sweep", "red_prolong", "resid_restrict", "resid_correct", "resid_max", "rhs")
 
-    def run(self, steps, warmup):
+    def run(self, steps, warmup, keep_outputs=False):
         """W warm-up steps, then EXACTLY `steps` timed steps between barriers.  Inside the timed steps only the chained smoother
         passes (the dominant kernel of the roofline entry) are bracketed by HIP events (option profile = 2): an event pair costs
         ~10 us of stream time, and with every kernel bracketed the step is 1.4 % (4096^2 x 6) to 20 % (512^2 x 3) slower.  The
-        other kernels are timed the same way in a second, untimed pass of up to 20 steps right after."""
+        other kernels are timed the same way in a second, untimed pass of up to 20 steps right after.  keep_outputs: what the
+        last timed step hands its caller (psi, q, dt) is read back into self.outputs before that second pass moves the state."""
         g = self.g
         for _ in range(warmup):
             g.step()
         g.option("profile", 2)
         g.profile_reset()
         self.barrier()
+        dt = None
         t0 = time.perf_counter()
         for _ in range(steps):
-            g.step()
+            dt = g.step()
         self.barrier()
         elapsed = time.perf_counter() - t0
+        if keep_outputs:
+            from msom_amd import FIELDS as F
+
+            self.outputs = {"psi": g.get(F["PSI"]), "q": g.get(F["Q"]), "dt": np.array([dt], dtype=np.float64)}
         g.option("profile", 0)
         self.prof = {k: g.profile_read(k) for k in self.PROF_KEYS}
         g.profile_reset()
@@ -340,6 +346,29 @@ def vertex_sqg_leg(N=2048, nl=3, steps=6):
     return out
 
 
+DUMP_POINTS = 1 << 21   # per field of a sampled dump: 16 MB of float64, so psi + q + sample_index stay under 64 MB
+
+
+def dump_outputs(outdir, outputs, suffix=""):
+    """--dump-outputs: every array as <outdir>/<name><suffix>.npy in float64.  Fields of more than DUMP_POINTS values are
+    reduced to the same fixed, seeded sample of flat indices (a function of the field size only), which is written beside
+    them as sample_index (float64 holds every index exactly)."""
+    created = not os.path.isdir(outdir)
+    os.makedirs(outdir, exist_ok=True)
+    if created:   # a dump directory made inside a checkout keeps itself out of `git status`
+        with open(os.path.join(outdir, ".gitignore"), "w") as f:
+            f.write("*\n")
+    fields = {k: v for k, v in outputs.items() if v.size > 1}
+    n = max(v.size for v in fields.values())
+    out = dict(outputs)
+    if n > DUMP_POINTS:
+        idx = np.unique(np.random.default_rng(0).integers(0, n, DUMP_POINTS))
+        out.update({k: v.reshape(-1)[idx] for k, v in fields.items()})
+        out["sample_index"] = idx.astype(np.float64)
+    for k, v in out.items():
+        np.save(os.path.join(outdir, f"{k}{suffix}.npy"), np.ascontiguousarray(v, dtype=np.float64))
+
+
 def roofline(leg, world, leg_steps=1):
     ks, w, plain_bytes, uniform = leg.kernels()
     nl = leg.nl
@@ -402,7 +431,11 @@ def main():
     ap.add_argument("--no-extra", action="store_true", help="skip the secondary legs (other configs at N = 1, split grid at N > 1)")
     ap.add_argument("--cpu-n", type=int, default=0, help="grid of the cpu_baseline leg (0: the configuration's own N)")
     ap.add_argument("--opt", action="append", default=[], help="key=value library option (tuning A/B), repeatable")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write psi, q and dt of the last timed step as DIR/<name>.npy (float64; a fixed sample of large fields)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -435,7 +468,7 @@ def main():
         for kv in args.opt:
             k, v = kv.split("=")
             leg.g.option(k, float(v))
-        elapsed = leg.run(args.steps, args.warmup)
+        elapsed = leg.run(args.steps, args.warmup, keep_outputs=args.dump_outputs is not None)
     except Exception as e:  # noqa: BLE001  -- say what failed in the one line the driver reads, then fail
         if rank == 0:
             print(json.dumps({"metric": "grid-point-updates/s", "value": 0.0, "unit": "grid-point-updates/s", "n_gpus": world, "steps": args.steps,
@@ -443,6 +476,9 @@ def main():
         raise
     main_sum = leg.summary(args.steps, elapsed)
     roof = roofline(leg, world, args.steps) if rank == 0 else None
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, leg.outputs, suffix=f"_rank{rank}" if world > 1 else "")
+        leg.outputs = None
     uniform = leg.g.param("uniform_S") == 1.0
     leg.g.close()
 
