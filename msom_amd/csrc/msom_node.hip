@@ -366,6 +366,7 @@ extern "C" double msomn_get_param(msomn_t *m, const char *k) {
   if (!strcmp(k, "bc_fac")) return m->p.bc_fac;
   if (!strcmp(k, "sqg")) return m->sqg;
   if (!strcmp(k, "s2_xuniform")) return m->s2_xuniform;
+  if (!strcmp(k, "node_march_s")) return m->node_march_s;   // split levels of >= this many vertices a side take k_n_relax_march_s
   if (!strncmp(k, "split_", 6)) { int l = atoi(k + 6); return l >= 0 && l < m->nlev ? m->lev[l].sp : NAN; }
   if (!strncmp(k, "idh0_", 5)) { int l = atoi(k + 5); return l >= 0 && l < MSOM_MAXNL ? m->lc.idh0[l] : NAN; }
   if (!strncmp(k, "idh1_", 5)) { int l = atoi(k + 5); return l >= 0 && l < MSOM_MAXNL ? m->lc.idh1[l] : NAN; }

@@ -343,8 +343,8 @@ def test_error_convention():
 
 @pytest.mark.parametrize("N,nl", [(2048, 3), (4096, 6)])
 def test_full_size_properties(N, nl):
-    """Size-independent properties at BASELINE.json's sizes, where the oracle is too slow:
-    analytic eigenfunction of lap + Gamma (closed-form q and closed-form inverse), linearity
+    """Size-independent properties at BASELINE.json's sizes (the oracle comparison at these sizes is
+    tests/test_gpu_oracle_fullsize.py): analytic eigenfunction of lap + Gamma (closed-form q and closed-form inverse), linearity
     of comp_q, and self-consistency of the reported residual."""
     txt = orc.double_gyre_params(N, nl)
     g = QG(txt)
