@@ -784,6 +784,7 @@ extern "C" double msom_get_param(msom_t *m, const char *key) {
   if (!strcmp(key, "nlevels")) return m->nlev;
   if (!strcmp(key, "uniform_S")) return m->uniformS;
   if (!strcmp(key, "agg_level")) return m->agg_level;
+  if (!strcmp(key, "overlap")) return m->overlap;
   // which kernels the dispatch picks for this handle (bench.py names what ran from these, not from a table)
   if (!strcmp(key, "resmax_marching")) { extern int g_resmax_rows; return m->uniformS && m->nl <= MSOM_FASTNL && m->g.nx >= 64 && m->g.ny >= 16 && g_resmax_rows >= 0; }
   if (!strcmp(key, "march_lean")) { extern int g_march_lean; return g_march_lean; }

@@ -51,6 +51,7 @@ struct orc {
   double dhf[ORC_MAXNL], dhc[ORC_MAXNL], idh0[ORC_MAXNL], idh1[ORC_MAXNL];
   /* stochastic variant msqg/qg_stochastic.h */
   int stochastic, corrector_step;
+  int noise_given;              /* extension: the NOISE field is set by the caller, generate_noise is skipped */
   double tr_stoch, itr_stoch, amp_stoch;
   /* solver controls, mspg/elliptic.h:111-112, msqg/qg.h:159 */
   double tolerance;
@@ -318,6 +319,7 @@ int orc_set_option(orc_t *o, const char *key, double v) {
   else if (!strcmp(key, "NITERMAX")) o->nitermax = (int)v;
   else if (!strcmp(key, "NITERMIN")) o->nitermin = (int)v;
   else if (!strcmp(key, "stochastic")) o->stochastic = (int)v;
+  else if (!strcmp(key, "noise_given")) o->noise_given = (int)v;
   else if (!strcmp(key, "quiet")) o->quiet = (int)v;
   else if (!strcmp(key, "flag_topo")) o->flag_topo = (int)v;
   else if (!strcmp(key, "DT")) o->DT = v;
@@ -1111,7 +1113,7 @@ static void advance_qg(orc_t *o, fld *out, fld *in, fld *dq, double dt) {
     o->corrector_step = (o->corrector_step + 1) % 2;
     float dts = sqrt(dt);
     if (o->corrector_step) {
-      generate_noise(o);
+      if (!o->noise_given) generate_noise(o);
       dts = dts / sqrt(2);
     }
     fld *n = &o->f[ORC_NOISE];

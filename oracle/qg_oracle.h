@@ -50,7 +50,7 @@ typedef struct orc orc_t;
 /* lifecycle: read_params -> set_vars -> (user sets fields) -> set_const */
 orc_t *orc_create_str(const char *params_text);   /* msqg/qg.h:689-761 + set_vars :837-925 */
 void   orc_destroy(orc_t *o);
-int    orc_set_option(orc_t *o, const char *key, double v);  /* smoother, TOLERANCE, NITERMAX, ... */
+int    orc_set_option(orc_t *o, const char *key, double v);  /* smoother, TOLERANCE, NITERMAX, stochastic, noise_given, ... */
 double orc_get_param(orc_t *o, const char *key);
 void   orc_set_const(orc_t *o);                   /* msqg/qg.h:931-1116 (without file discovery) */
 

@@ -158,6 +158,11 @@ class Oracle:
     def remove_mean(self, field):
         self.L.orc_remove_mean(self.h, field)
 
+    def set_noise(self, n):
+        """stochastic variant: the next draws use `n` as given (option noise_given) instead of the serial rand() stream"""
+        self.option("noise_given", 1)
+        self.set(NOISE, n)
+
     def comp_del2(self, fin, fout, add, fac):
         self.L.orc_comp_del2(self.h, fin, fout, add, fac)
 
