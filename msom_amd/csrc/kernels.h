@@ -136,6 +136,8 @@ struct MarchHalo { const double *in_s, *in_n, *res_s, *res_n; size_t ls; int row
 int launch_relax_march(hipStream_t st, const double *in, double *out, const double *res, const SplitGeom &sg, int nl, const RelaxCoef &rc, int c1,
                        int K, int walls, int chunk_rows = 0, const MarchHalo *h = nullptr, const double *coarse = nullptr, const SplitGeom *cg = nullptr,
                        const MarchCorrect *mc = nullptr, int more_follow = 0, const MarchHalo *coarse_halo = nullptr, int region = 0);
+// can the lean interior body of the pass address every layer of the level (sg) and, with the correction, of psi (ng)?
+bool march_lean_fits(int nl, const SplitGeom &sg, const NatGeom *ng);
 
 // ---- kernels_wavelet.hip
 void launch_wv_restrict(hipStream_t st, const double *f, const NatGeom &fg, double *c, const NatGeom &cg, int nl);

@@ -1162,6 +1162,14 @@ static int march_dispatch(hipStream_t st, const MarchArgs &a, int K, int rows) {
   return -1;
 }
 
+// the lean body addresses all layers of a field through 32-bit unsigned per-lane byte offsets (voffL, voffC): admitted while
+// nl + 1 layers of the level's split fields -- and of the natural psi, for the pass that applies the correction -- span
+// fewer than 2^32 bytes
+bool march_lean_fits(int nl, const SplitGeom &sg, const NatGeom *ng) {
+  const size_t lim = (size_t)1 << 32;
+  return (size_t)(nl + 1) * sg.ls * 8 < lim && (!ng || (size_t)(nl + 1) * ng->ls * 8 < lim);
+}
+
 // K (2..4) half-sweeps starting with colour c1, in -> out; returns -1 if (nl, K) has no instantiation
 int launch_relax_march(hipStream_t st, const double *in, double *out, const double *res, const SplitGeom &sg, int nl, const RelaxCoef &rc, int c1,
                        int K, int walls, int chunk_rows, const MarchHalo *h, const double *coarse, const SplitGeom *cg, const MarchCorrect *mc, int more_follow, const MarchHalo *ch,
@@ -1181,8 +1189,8 @@ int launch_relax_march(hipStream_t st, const double *in, double *out, const doub
   extern int g_march_flip;
   extern int g_march_dbg;
   extern int g_march_lean;
-  // lean body: 32-bit per-lane byte offsets span all layers of a field; the prolongation variant is written for c1 = 0
-  a.lean = !g_march_lean ? 0 : g_march_lean * (int)((size_t)(nl + 1) * sg.ls * 8 < ((size_t)1 << 32) && (!mc || (size_t)(nl + 1) * mc->g.ls * 8 < ((size_t)1 << 32)) && (!coarse || c1 == 0));
+  // lean body: see march_lean_fits; the prolongation variant is written for c1 = 0
+  a.lean = !g_march_lean ? 0 : g_march_lean * (int)(march_lean_fits(nl, sg, mc ? &mc->g : nullptr) && (!coarse || c1 == 0));
   a.in = in; a.out = out; a.res = res; a.g = sg; a.c1 = c1; a.walls = walls; a.rc = rc; a.remap = g_march_remap; a.flip = g_march_flip; a.dbg = g_march_dbg;
   if (nl >= 7 && K > 3) return -1;  // 4 windows of 7 or 8 layers do not fit 256 VGPRs
   switch (nl) {

@@ -759,6 +759,8 @@ extern "C" int msom_set_option(msom_t *m, const char *key, double v) {
 }
 
 static int march_levels(msom *m);
+static int march_kmax(const msom *m);
+static bool march_lean_fine(msom *m);
 static bool restrict2_ok(const msom *m);
 extern "C" double msom_get_param(msom_t *m, const char *key) {
   if (!m || !key) return NAN;
@@ -792,6 +794,9 @@ extern "C" double msom_get_param(msom_t *m, const char *key) {
   if (!strcmp(key, "mg_coarse_lean")) return m->mgc_first >= 0 && m->mgc_lean;   // the coarse group runs in k_mg_coarse_lean
   if (!strcmp(key, "march_levels")) return march_levels(m);   // tile levels whose half-sweeps are chained (kernels_march.hip)
   if (!strcmp(key, "march_min")) return m->march_min;   // log2 of the cell-layers a single-tile level needs for the chained pass
+  if (!strcmp(key, "march_kmax")) return march_kmax(m);   // half-sweeps per marching pass that relax_sweeps allows
+  if (!strcmp(key, "march_lean_fine")) return march_lean_fine(m);   // the finest level's interior chunks take the lean body
+  if (!strcmp(key, "split_ls")) return m->nlev > 0 ? (double)m->sg[0].ls : NAN;   // doubles per layer of the finest split field
   auto idx = [](const char *s, int n) { const int k = atoi(s); return k >= 0 && k < n ? k : -1; };
   if (!strncmp(key, "idh0_", 5)) { const int k = idx(key + 5, MSOM_MAXNL); return k < 0 ? NAN : m->lc.idh0[k]; }
   if (!strncmp(key, "idh1_", 5)) { const int k = idx(key + 5, MSOM_MAXNL); return k < 0 ? NAN : m->lc.idh1[k]; }
@@ -1174,12 +1179,21 @@ static int march_levels(msom *m) {
   }
   return n;
 }
+// is the finest level marched, with its interior chunks in the lean body (option march_lean, byte offsets within reach:
+// march_lean_fits, as launch_relax_march decides it for the passes of the level)?
+static bool march_lean_fine(msom *m) {
+  extern int g_march_lean;
+  return m->nlev > 0 && g_march_lean && march_ok(m, tile_lev(m, 0)) && march_lean_fits(m->nl, m->sg[0], &m->g);
+}
 // is the prolongation coarse -> L folded into the first smoothing pass of L?
 static bool fuse_prolong(msom *m, const Lev &L, int nrelax) {
   if (block_ok(m, L) && nrelax >= 2) return true;
   if (block8_ok(m, L) && nrelax >= 1) return true;
   return m->prolong_fused && m->nl <= MSOM_FASTNL && nrelax >= 1 && L.sg->nx >= 4 && L.sg->ny >= 4;
 }
+
+// half-sweeps per marching pass: march_k, but 4 register windows of 7 or 8 layers do not fit (launch_relax_march)
+static int march_kmax(const msom *m) { return m->nl >= 7 && m->march_k > 3 ? 3 : m->march_k; }
 
 // nrelax red-black relaxations of L.da against L.res (each followed by boundary_level).
 // coarse != nullptr: L.da has not been prolongated yet -- the first pass interpolates it from
@@ -1232,7 +1246,7 @@ static void relax_sweeps(msom *m, Lev &L, const Lev *coarse, int nrelax, int cor
       deep_halo(const_cast<double *>(L.res), *L.sg, m->mh_res_s[L.k], m->mh_res_n[L.k], hg);
       res_halo_done = true;
     };
-    const int kmax = nl >= 7 && m->march_k > 3 ? 3 : m->march_k;
+    const int kmax = march_kmax(m);
     // tiles: the pass then needs MARCH_HALO cells / rows of the COARSE correction beyond the tile edges too (LDS-DMA kernel, nl <= 6)
     const bool pl_tiled = deep && coarse && coarse->k >= 0 && nl <= 6 && m->march_prolong >= 1 && coarse->sg->nx >= 2 * MARCH_HALO && coarse->sg->ny >= 2 * MARCH_HALO;
     if (coarse && n >= 3 && kmax >= 3 && (!deep || pl_tiled) && m->march_prolong) {

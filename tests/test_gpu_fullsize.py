@@ -4,7 +4,8 @@ passes, one-layer-per-wavefront tendency kernel with the advance folded in -- ag
 kernel-per-reference-loop chain (march = 0, block8 = 0, fused = 0, mg_fused = 0, mg_coarse = 0, prolong_fused = 0: the path
 the small-grid tests hold to the oracle bit for bit).  Strict build: bit-identical; product build: <= 1e-10 relative.
 The strip / chunk logic of the marching kernels only meets many interior chunks, both marching directions and several
-workgroup rounds at these sizes (a hazard of the lean smoother body showed at 2048^2 x 6 and nowhere below).  A defect shared
+workgroup rounds at these sizes (a hazard of the lean smoother body showed at 2048^2 x 6 and nowhere below).  The lean body is
+also held to the general one at 8192^2 x 5, the smallest size whose per-lane byte offsets pass 2^31.  A defect shared
 by both paths passes here: tests/test_gpu_oracle_fullsize.py holds the same defaults to the CPU oracle at these sizes."""
 import numpy as np
 import pytest
@@ -69,6 +70,69 @@ def test_lean_body_of_the_chained_smoother_equals_the_general_body(N, nl):
         c = run(N, nl, False, dict(march_lean=1), steps=2, tol=1e-3)
         for k in ("dq", "q", "psi"):
             assert np.array_equal(a[k], b[k]) and np.array_equal(c[k], b[k]), k
+    finally:
+        h.option("march_lean", default)
+        h.close()
+    assert QG(orc.double_gyre_params(32, 1)).param("march_lean") == default
+
+
+def modal_psi(nl, N, amp=1e-3):
+    """orc.synthetic_psi (the same 16 sine modes per layer, zero on the walls), each layer formed as one product of rank 4
+    instead of 16 outer products: the same field up to rounding, in seconds at 8192^2"""
+    x = (np.arange(N) + 0.5) / N
+    k = np.arange(1, 5)
+    sx = np.sin(np.pi * k[:, None] * x[None, :])           # (mode, cell)
+    psi = np.empty((nl, N, N))
+    for l in range(nl):
+        c = np.sin(1.7 * k[None, :] + 2.3 * k[:, None] + 0.9 * l) / (k[:, None] * k[None, :])   # c[m, k]
+        np.matmul(sx.T @ c, sx, out=psi[l])
+        psi[l] *= amp * (1.0 - 0.15 * l)
+    return psi
+
+
+def test_lean_body_equals_the_general_body_at_byte_offsets_above_2_31():
+    """8192^2 x 5, product build, defaults, reference tolerance, one RK2 step: the lean body addresses every layer of a split
+    field through a 32-bit unsigned per-lane byte offset (voffL); its largest, (nl - 1) ls 8 bytes, lies above 2^31 here (by
+    0.8 %; nl = 6 gives 2.71e9 should a layout change move it below), where any signed intermediate would break.  The general
+    body forms its offsets in 64 bits, so it is an independent addressing path: march_lean = 2 against march_lean = 0, bit
+    for bit.  Host memory: the initial psi and one run's outputs (2.7 GB per field)"""
+    N, nl = 8192, 5
+    txt = orc.double_gyre_params(N, nl)
+    psi0 = modal_psi(nl, N)
+
+    def run_fields(lean, sink):
+        g = QG(txt)
+        try:
+            g.option("quiet", 1)
+            g.option("TOLERANCE", 1e-3)
+            g.set(F["PSI"], psi0)
+            g.set_const()
+            g.option("march_lean", lean)
+            assert g.param("uniform_S") == 1 and g.param("march_levels") >= 1
+            assert g.param("march_lean_fine") == (lean != 0)
+            if lean:
+                assert (nl - 1) * g.param("split_ls") * 8 >= 2 ** 31
+            g.set_tnext(float("inf"))
+            dq, dtmax = g.update()
+            sink("dq", dq)
+            del dq
+            sink("dt", np.array([dtmax, g.step()]))
+            sink("q", g.get(F["Q"]))
+            sink("psi", g.get(F["PSI"]))
+        finally:
+            g.close()
+
+    h = QG(orc.double_gyre_params(32, 1))
+    default = h.param("march_lean")
+    try:
+        lean = {}
+        run_fields(2, lean.__setitem__)
+
+        def same(k, b):
+            a = lean.pop(k)
+            ok = np.array_equal(a, b)
+            assert ok, (k, rel(a, b), int(np.count_nonzero(a != b)))   # field, rel(max), cells that differ
+        run_fields(0, same)
     finally:
         h.option("march_lean", default)
         h.close()
