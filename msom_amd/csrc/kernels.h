@@ -135,7 +135,13 @@ struct MarchCorrect { const double *psi; double *psi_out; NatGeom g; };
 struct MarchHalo { const double *in_s, *in_n, *res_s, *res_n; size_t ls; int rows; };
 int launch_relax_march(hipStream_t st, const double *in, double *out, const double *res, const SplitGeom &sg, int nl, const RelaxCoef &rc, int c1,
                        int K, int walls, int chunk_rows = 0, const MarchHalo *h = nullptr, const double *coarse = nullptr, const SplitGeom *cg = nullptr,
-                       const MarchCorrect *mc = nullptr, int more_follow = 0, const MarchHalo *coarse_halo = nullptr, int region = 0);
+                       const MarchCorrect *mc = nullptr, int more_follow = 0, const MarchHalo *coarse_halo = nullptr, int region = 0,
+                       const int *skip = nullptr);
+// the finest level's visit, 4 + 4 half-sweeps with the prolongation and the correction, fused where chunks are interior (k_relax_visit);
+// returns -1 (nothing launched) where it does not apply.  rows: the visit's chunk height (0: automatic); pairs: wave pairs per workgroup
+int launch_relax_visit(hipStream_t st, double *da, double *da_alt, const double *res, const SplitGeom &sg, int nl, const RelaxCoef &rc, int walls,
+                       const double *coarse, const SplitGeom &cg, const MarchCorrect &mc, int rows, int pairs, int ring_rows);
+bool relax_visit_fits(int nl, const SplitGeom &sg, int rows, int pairs);
 // can the lean interior body of the pass address every layer of the level (sg) and, with the correction, of psi (ng)?
 bool march_lean_fits(int nl, const SplitGeom &sg, const NatGeom *ng);
 

@@ -90,6 +90,10 @@ struct MarchArgs {
   int dbg;  // timing experiments only (results wrong): 1 = no stores, 2 = no loads after the first step
   int lean; // interior chunks take the lean body (march_lean below)
   int region;  // tiles, overlap with the deep halo exchange: 0 all chunks, 1 only those that read no halo cell, 2 only the others
+  // fused finest-level visit (k_relax_visit): row and half-row column (kx) where its chunk grid starts; the passes around it skip
+  // the chunks whose own cells all lie in rows [sy0, sy1) x columns [sx0, sx1) (sy1 <= sy0: none)
+  int vy0, vx0;
+  int sy0, sy1, sx0, sx1;
   RelaxCoef rc;
 };
 
@@ -333,11 +337,13 @@ __global__ void __launch_bounds__(64, 2) k_relax_march(MarchArgs p) {
 //    BEFORE the stores of step t, so the wait at the top of a step is vmcnt(number of stores): the write
 //    acknowledgements are no longer waited for.
 // Arithmetic: the expressions of the general body, same order => bit-identical (tests/test_gpu_march.py).
-template <int NL, int K, int HL, int WPB, bool PL, bool CORR>
+// VIS (k_relax_visit): 0 a pass of its own; 1 the leading wave of a fused visit (its half-sweep K goes to the hand-over rows
+// in LDS instead of HBM); 2 the trailing wave (its input rows come from there; no input block in its ring)
+template <int NL, int K, int HL, int WPB, bool PL, bool CORR, int VIS = 0>
 struct MarchLeanRows {
   static constexpr int NLE = (NL + 1) & ~1;                 // two layer-rows per DMA instruction; odd NL repeats its last layer
   static constexpr int CB = 2 * NLE;                        // PL: coarse ring (4 slots of NLE rows)
-  static constexpr int PBL = 3 * NLE;                       // CORR: psi block (NL x 128 doubles)
+  static constexpr int PBL = (VIS == 2 ? 2 : 3) * NLE;      // CORR: psi block (NL x 128 doubles)
   static constexpr int XBL = PBL + 2 * NL;                  // CORR: values of half-sweep K waiting one step for their psi row
   static constexpr int ROWS = PL ? CB + 4 * NLE : (CORR ? XBL + NL : 3 * NLE);
   // DEEP (requests two steps ahead; not with CORR, whose psi block and parked values leave no room): two buffers of
@@ -351,10 +357,11 @@ struct MarchLeanRows {
 #define MARCH_VMCNT(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
 typedef double v2d __attribute__((ext_vector_type(2)));
 
-template <int NL, int K, int HL, int WPB, bool PL, bool CORR, bool DEEP>
+template <int NL, int K, int HL, int WPB, bool PL, bool CORR, bool DEEP, int VIS = 0>
 __device__ __forceinline__ void march_lean(const MarchArgs &p, double (*ring)[64], const int lane, const int kx0, const int y0, const int y1,
-                                           const bool down) {
-  using LR = MarchLeanRows<NL, K, HL, WPB, PL, CORR>;
+                                           const bool down, double (*hand)[64] = nullptr) {
+  static_assert(VIS == 0 || (VIS == 1 && PL && !CORR) || (VIS == 2 && CORR), "fused visit: prolongation leads, correction trails");
+  using LR = MarchLeanRows<NL, K, HL, WPB, PL, CORR, VIS>;
   constexpr int D1 = K >= 3 ? 3 : 1, D2 = K >= 4 ? 3 : 1;
   static_assert(!(DEEP && CORR), "no LDS for a second buffer beside the psi block");
   constexpr int NLE = LR::NLE, ND = NLE / 2, CB = DEEP ? LR::CBD : LR::CB, PBL = LR::PBL, XBL = LR::XBL, RB = LR::RB;
@@ -418,7 +425,7 @@ __device__ __forceinline__ void march_lean(const MarchArgs &p, double (*ring)[64
     for (int q = 0; q < ND; q++) MARCH_DMA(voffL[q], b1, r0 + 2 * q);
 #pragma unroll
     for (int q = 0; q < ND; q++) MARCH_DMA(voffL[q], b2, r0 + NLE + 2 * q);
-    if constexpr (!PL) {
+    if constexpr (!PL && VIS != 2) {
       const char *b3 = in8 + ro;
 #pragma unroll
       for (int q = 0; q < ND; q++) MARCH_DMA(voffL[q], b3, r0 + 2 * NLE + 2 * q);
@@ -474,9 +481,29 @@ __device__ __forceinline__ void march_lean(const MarchArgs &p, double (*ring)[64
     request(rowoff + (((ra + p.c1) & 1) ? strideB : strideA), 0, false, 1);
     issued += NREQ; markR[1] = issued;
   }
+  // fused visit: one barrier per marching step of the pair; the leading wave finished the previous step's hand-over row
+  auto visit_sync = [&]() {
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): this wave's LDS writes (and reads) are done
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+  };
+  // hand-over rows: two slots of NL layer-rows, slot = marching coordinate & 1
+  auto hrow = [&](int tm, int l) -> double * { return &hand[(tm & 1) * NL + l][lane]; };
+  if constexpr (VIS == 2) {
+    // the leading wave's chain starts at y0 - 2 K + 1: it writes marching row tm in its step tm + K - 1, the interval after barrier
+    // tm - y0 + 3 K - 2.  Rows y0 - K, y0 - K + 1 (first window) are read after barriers 2 K - 1 and 2 K, row tm + 1 in step tm
+    // (after barrier tm - y0 + 3 K); its slot is written again after barrier tm - y0 + 3 K + 1
+    for (int i = 0; i < 2 * K; i++) visit_sync();
+#pragma unroll
+    for (int l = 0; l < NL; l++) W[0][0][l] = *hrow(tA - 1, l);
+    visit_sync();
+#pragma unroll
+    for (int l = 0; l < NL; l++) W[0][1][l] = *hrow(tA, l);
+  }
   // rows y0 - K and y0 - K + 1 (marching coordinates) of the input fill the first window (plain loads, once per chunk)
 #pragma unroll
-  for (int q = 0; q < 2; q++) {
+  for (int q = 0; q < (VIS == 2 ? 0 : 2); q++) {
     const int r = ra + d * (q - 1);
     const int half = (r + 1 - p.c1) & 1;
     if constexpr (PL) {
@@ -505,7 +532,8 @@ __device__ __forceinline__ void march_lean(const MarchArgs &p, double (*ring)[64
     constexpr int PHI = decltype(phic)::value;    // position in the pair of steps: window slots (old, mid, new)
     constexpr int O = PHI ? 1 : 0, M = PHI ? 2 : 1, NW = PHI ? 0 : 2;
     constexpr int RA0 = PHI ? 2 : 0, RA2 = PHI ? 1 : 2;   // residual windows: slots of age 0 (new) and age 2
-    if (WPB > 1) __builtin_amdgcn_s_barrier();
+    if constexpr (VIS != 0) visit_sync();
+    else if (WPB > 1) __builtin_amdgcn_s_barrier();
     if constexpr (DEEP) {
       const unsigned need = PL ? max(markR[PHI], markC) : markR[PHI];
       const unsigned n = issued - need;
@@ -532,7 +560,8 @@ __device__ __forceinline__ void march_lean(const MarchArgs &p, double (*ring)[64
     for (int l = 0; l < NL; l++) {
       R1[D1 == 3 ? RA0 : 0][l] = ring[R0 + l][lane];
       R2[D2 == 3 ? RA0 : 0][l] = ring[R0 + NLE + l][lane];
-      if constexpr (!PL) W[0][NW][l] = ring[R0 + 2 * NLE + l][lane];
+      if constexpr (VIS == 2) W[0][NW][l] = *hrow(t + 1, l);
+      else if constexpr (!PL) W[0][NW][l] = ring[R0 + 2 * NLE + l][lane];
     }
     // CORR: the row half-sweep K finished in the previous step: its psi and its values wait in the ring
     const bool corr_now = CORR && t - K >= y0;
@@ -612,7 +641,11 @@ __device__ __forceinline__ void march_lean(const MarchArgs &p, double (*ring)[64
       }
     }
     bool full = false;
-    if constexpr (CORR) {
+    if constexpr (VIS == 1) {
+      // every row and lane: the trailing wave's cone reaches K rows and lanes beyond its own cells
+#pragma unroll
+      for (int l = 0; l < NL; l++) *hrow(t - (K - 1), l) = x[l];
+    } else if constexpr (CORR) {
 #pragma unroll
       for (int l = 0; l < NL; l++) ring[XBL + l][lane] = x[l];
       full = corr_now && !(p.dbg & 1);
@@ -658,6 +691,7 @@ __device__ __forceinline__ void march_lean(const MarchArgs &p, double (*ring)[64
   } else {
     for (int t = tA; t < tB; t += 2) { step(I0{}, I0{}, t); step(I1{}, I1{}, t + 1); }
   }
+  if constexpr (VIS == 1) visit_sync();   // the trailing wave's last step
   if constexpr (CORR) {   // the last row of the chunk
     MARCH_VMCNT(0);
     if (own_lane && !(p.dbg & 1)) {
@@ -736,6 +770,7 @@ __global__ void __launch_bounds__(64 * WPB, 2) k_relax_march_dma(MarchArgs p) {
   // ended no longer takes part in the workgroup's barriers
   const bool inner = y0 - K >= 0 && y1 + K <= ny && kx0 >= 0 && kx0 + 63 <= hk - 1;
   if (p.region && (p.region == 1) != inner) return;
+  if (p.sy1 > p.sy0 && y0 >= p.sy0 && y1 <= p.sy1 && kx0 + HL >= p.sx0 && min(kx0 + 64 - HL, hk) <= p.sx1) return;
   if (p.lean && inner && !((y1 - y0) & 1)) {
     if constexpr (!CORR) {
       if (p.lean >= 2) { march_lean<NL, K, HL, WPB, PL, CORR, true>(p, ring, lane, kx0, y0, y1, down); return; }
@@ -1173,9 +1208,11 @@ bool march_lean_fits(int nl, const SplitGeom &sg, const NatGeom *ng) {
 // K (2..4) half-sweeps starting with colour c1, in -> out; returns -1 if (nl, K) has no instantiation
 int launch_relax_march(hipStream_t st, const double *in, double *out, const double *res, const SplitGeom &sg, int nl, const RelaxCoef &rc, int c1,
                        int K, int walls, int chunk_rows, const MarchHalo *h, const double *coarse, const SplitGeom *cg, const MarchCorrect *mc, int more_follow, const MarchHalo *ch,
-                       int region) {
+                       int region, const int *skip) {
   MarchArgs a;
   a.region = region;
+  a.vy0 = a.vx0 = 0;
+  a.sy0 = skip ? skip[0] : 0; a.sy1 = skip ? skip[1] : 0; a.sx0 = skip ? skip[2] : 0; a.sx1 = skip ? skip[3] : 0;
   a.coarse_s = ch ? ch->in_s : nullptr; a.coarse_n = ch ? ch->in_n : nullptr; a.chls = ch ? ch->ls : 0; a.cKR = ch ? ch->rows : 0;
   a.partial = more_follow != 0;
   a.psi = mc ? mc->psi : nullptr; a.psi_out = mc ? mc->psi_out : nullptr;
@@ -1204,4 +1241,104 @@ int launch_relax_march(hipStream_t st, const double *in, double *out, const doub
     case 8: return march_dispatch<8>(st, a, K, chunk_rows);
   }
   return -1;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// k_relax_visit: the finest level's visit -- prolongation + 4 half-sweeps, 4 half-sweeps + correction -- in ONE launch on
+// the interior chunks.  Two passes move 1.75 w + 3.5 w (w = one layered field); here the colour that the first pass stores
+// and the second one reloads (w / 2 + w / 2) stays on the chip.
+//  * a pair of wavefronts per strip, marching in step (one s_barrier per step): wave A runs march_lean<PL> over the chunk
+//    widened by K rows on both sides (the cone of the trailing half-sweeps), wave B runs march_lean<CORR> over the chunk and
+//    trails A by K + 1 steps.  A writes the values of its half-sweep K, every row and lane, into two hand-over slots of LDS
+//    instead of HBM; B takes its input rows from there instead of HBM;
+//  * HL = 8 halo lanes: A's values are exact on lanes [3, 61) (PL: K / 2 + 1 lanes of cone), B's on [5, 59); 8 keeps the
+//    strip start at kx = 0 mod 4 (16-byte coarse pieces);
+//  * only interior chunks: every row A reads (y0 - 2 K .. y1 + 2 K - 1) and every lane lies inside the level.  The rest of the
+//    level takes the two passes (launch_relax_visit); the second pass reads the first pass's values K rows / lanes into
+//    the visit's chunks, so the first pass also runs on a band of them;
+//  * arithmetic: the lean bodies unchanged => every cell bit-identical to the two passes (tests/test_gpu_march_visit.py).
+// LDS per pair at nl = 6: A 36 layer-rows, B 30 (no input block), hand-over 12: 78 x 512 B = 39 KB (4 pairs per CU).
+// one role of the pair; everything from the launch coordinates, inside the role's branch (shared values live across both
+// bodies cost registers: 3 spilled VGPRs at nl = 6 when computed before the branch)
+template <int NL, int PAIRS, int VIS>
+__device__ __forceinline__ void visit_role(const MarchArgs &p, double (*lds)[64], const int pair) {
+  constexpr int K = 4, HL = 8;
+  constexpr int OW = 64 - 2 * HL;
+  constexpr int RA = MarchLeanRows<NL, K, HL, 2, true, false>::ROWSD, RB = MarchLeanRows<NL, K, HL, 2, false, true, 2>::ROWS;
+  const int lane = threadIdx.x & 63;
+  unsigned bx = blockIdx.x, by = blockIdx.y;
+  if (p.remap) xcd_remap(bx, by);
+  const int kx0 = p.vx0 + ((int)bx * PAIRS + pair) * OW - HL;
+  const int y0 = p.vy0 + (int)by * p.H, y1 = y0 + p.H;
+  const bool down = p.flip && (by & 1);
+  double(*ring)[64] = lds + pair * (RA + RB + 2 * NL);
+  double(*hand)[64] = ring + RA + RB;
+  if constexpr (VIS == 2) march_lean<NL, K, HL, 2, false, true, false, 2>(p, ring + RA, lane, kx0, y0, y1, down, hand);
+  else march_lean<NL, K, HL, 2, true, false, true, 1>(p, ring, lane, kx0, y0 - K, y1 + K, down, hand);
+}
+template <int NL, int PAIRS>
+__global__ void __launch_bounds__(128 * PAIRS, 2) k_relax_visit(MarchArgs p) {
+  constexpr int K = 4, HL = 8;
+  constexpr int RA = MarchLeanRows<NL, K, HL, 2, true, false>::ROWSD, RB = MarchLeanRows<NL, K, HL, 2, false, true, 2>::ROWS;
+  __shared__ __align__(16) double lds[PAIRS * (RA + RB + 2 * NL)][64];
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (wv & 1) visit_role<NL, PAIRS, 2>(p, lds, wv >> 1);
+  else visit_role<NL, PAIRS, 1>(p, lds, wv >> 1);
+}
+
+int g_visit_rows = 0;   // chunk height of k_relax_visit (option march_visit_rows; 0: automatic)
+int g_visit_pairs = 2;  // wave pairs per workgroup of k_relax_visit (option march_visit_pairs: 1 or 2; 4096^2 x 6: 0.866 / 0.873 ms with 2, 0.881 / 0.883 with 1)
+
+// the visit's chunk grid: nc chunks of H rows from row vy0, ns strips of 48 own lanes from kx = vx0 (a multiple of pairs)
+struct VisitGeom { int H, vy0, nc, vx0, ns; };
+static bool visit_geom(const SplitGeom &sg, int rows, int pairs, VisitGeom &v) {
+  constexpr int K = 4, HL = 8, OW = 64 - 2 * HL;
+  v.H = rows > 0 ? (rows + 1) & ~1 : 28;   // 4096^2 x 6: 14 rows 0.946 ms, 20: 0.900, 28: 0.881, 42: 0.886 (one pair per workgroup)
+  v.vy0 = 2 * K;                           // wave A reads down to row y0 - 2 K
+  v.nc = (sg.ny - 2 * K - v.vy0) / v.H;    // ... and up to y1 + 2 K - 1
+  v.vx0 = HL;                              // strip s: kx0 = 48 s
+  v.ns = sg.hk >= 64 ? ((sg.hk - 64) / OW + 1) / pairs * pairs : 0;   // kx0 + 63 <= hk - 1
+  return v.nc > 0 && v.ns > 0;
+}
+bool relax_visit_fits(int nl, const SplitGeom &sg, int rows, int pairs) {
+  VisitGeom v;
+  return nl >= 2 && nl <= 6 && (pairs == 1 || pairs == 2) && visit_geom(sg, rows, pairs, v);
+}
+
+template <int NL>
+static void visit_dispatch(hipStream_t st, const MarchArgs &a, const VisitGeom &v, int pairs) {
+  if (pairs == 2) hipLaunchKernelGGL((k_relax_visit<NL, 2>), dim3(v.ns / 2, v.nc), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((k_relax_visit<NL, 1>), dim3(v.ns, v.nc), dim3(128), 0, st, a);
+}
+
+// PL + 4 half-sweeps (colour 0 first) and 4 + correction, the prolongation from `coarse`; da_alt receives the first pass's values
+// where the two passes run, da is not used.  The passes run on the chunks that are not the visit's: the second one (CORR) on
+// those with own cells outside the visit's rows / columns; it reads the first one's values up to ring_rows + K rows and 64 lanes
+// from its own cells, so the first one runs on all chunks with own cells that far from the visit's interior
+int launch_relax_visit(hipStream_t st, double *da, double *da_alt, const double *res, const SplitGeom &sg, int nl, const RelaxCoef &rc, int walls,
+                       const double *coarse, const SplitGeom &cg, const MarchCorrect &mc, int rows, int pairs, int ring_rows) {
+  VisitGeom v;
+  if (!relax_visit_fits(nl, sg, rows, pairs)) return -1;
+  visit_geom(sg, rows, pairs, v);
+  constexpr int K = 4;
+  const int Hc = ring_rows > 0 ? (ring_rows + 1) & ~1 : 14, my = Hc + K;
+  const int vy1 = v.vy0 + v.nc * v.H, vx1 = v.vx0 + v.ns * 48;
+  const int skip_pl[4] = {v.vy0 + my, vy1 - my, v.vx0 + 64, vx1 - 64};
+  const int skip_corr[4] = {v.vy0, vy1, v.vx0, vx1};
+  if (launch_relax_march(st, nullptr, da_alt, res, sg, nl, rc, 0, K, walls, Hc, nullptr, coarse, &cg, nullptr, 1, nullptr, 0, skip_pl)) return -1;
+  MarchArgs a{};
+  a.res = res; a.g = sg; a.c1 = 0; a.walls = walls; a.rc = rc;
+  a.coarse = coarse; a.cg = cg;
+  a.psi = mc.psi; a.psi_out = mc.psi_out; a.ng = mc.g;
+  a.partial = 1; a.lean = 2;
+  a.remap = g_march_remap; a.flip = g_march_flip;
+  a.H = v.H; a.vy0 = v.vy0; a.vx0 = v.vx0;
+  switch (nl) {
+    case 2: visit_dispatch<2>(st, a, v, pairs); break;
+    case 3: visit_dispatch<3>(st, a, v, pairs); break;
+    case 4: visit_dispatch<4>(st, a, v, pairs); break;
+    case 5: visit_dispatch<5>(st, a, v, pairs); break;
+    case 6: visit_dispatch<6>(st, a, v, pairs); break;
+  }
+  return launch_relax_march(st, da_alt, da, res, sg, nl, rc, 0, K, walls, Hc, nullptr, nullptr, nullptr, &mc, 0, nullptr, 0, skip_corr);
 }

@@ -143,6 +143,9 @@ struct msom {
   int march_min = 23;    // log2 of the cell-layers a level needs for the chained pass (2^23: 2048^2 x 3 1.83 -> 1.78 ms/step, and the 2048 x 1024 x 6 tiles of BASELINE's 2 x 4 layout qualify; 2^22 loses: 1024^2 x 6 2.76 -> 2.87)
   int march_correct = 1; // the last pass of the finest level writes psi + da instead of da (psi rows by LDS-DMA, deferred write): 7.02 -> 6.86 ms per step at 4096^2 x 6
   int corr_req = 0, corr_done = 0;  // set around mg_cycle_levels by mg_solve / by the pass that did it
+  int march_visit = 1;   // the finest level's visit (PL + 4, 4 + correction) in one launch on its interior chunks (k_relax_visit);
+                         // 1: on levels of at least 2^march_visit_min cell-layers, 2: wherever it applies (tests)
+  int march_visit_min = 25;  // 4096^2 x 6: 1.01 -> 0.87 ms per visit; 2048^2 x 3 (2^23.6) loses: 0.17 -> 0.21 ms (too few chunks to hide latency)
   int march_prolong = 1; // whole levels: prolongation folded into the first pass ((PL + 4) + 4 half-sweeps; coarse rows by LDS-DMA, kernels_march.hip): 7.63 -> 7.09 ms per step at 4096^2 x 6
   int mg_fused = 1;  // fused residual+restriction and correction+residual passes of the multigrid cycle
   double *psi_alt = nullptr;  // second psi buffer (the fused correction writes out of place)
@@ -180,6 +183,7 @@ struct msom {
   int profile = 0;
   ProfSlot prof_sweep, prof_resid, prof_block, prof_march[5];  // prof_march[K]: passes of K chained half-sweeps
   ProfSlot prof_march_pl;  // first pass of a level with the prolongation folded in
+  ProfSlot prof_march_visit;  // the finest level's fused visit (k_relax_visit and the two passes on the chunks around it)
   ProfSlot prof_march_corr, prof_resmax;  // last pass of the finest level with the correction folded in; max-only residual pass after it
   ProfSlot prof_rhs, prof_redprol, prof_rescorr, prof_respre;   // tendency pass, finest red+prolongation, post- / pre-cycle residual passes
 };
@@ -228,7 +232,7 @@ static int sync_stream(msom *m) {
 // profile = 1: every slot; 2: only the chained smoother passes (the dominant kernel of the bench line) -- an event pair costs
 // ~10 us of stream time, 1.4 % of a 4096^2 x 6 step and 20 % of a 512^2 x 3 step with every slot on
 static bool prof_on(const msom *m, const ProfSlot &ps) {
-  if (m->profile == 2) return &ps == &m->prof_march_corr || (&ps >= &m->prof_march[0] && &ps <= &m->prof_march[4]);
+  if (m->profile == 2) return &ps == &m->prof_march_corr || &ps == &m->prof_march_visit || (&ps >= &m->prof_march[0] && &ps <= &m->prof_march[4]);
   return m->profile != 0;
 }
 static void prof_begin(msom *m, ProfSlot &ps) {
@@ -669,7 +673,7 @@ extern "C" int msom_destroy(msom_t *m) {
   if (m->d_scal) hipFree(m->d_scal);
   if (m->h_scal) hipHostFree(m->h_scal);
   if (m->d_wind) hipFree(m->d_wind);
-  for (auto *ps : {&m->prof_sweep, &m->prof_resid, &m->prof_block, &m->prof_march[2], &m->prof_march[3], &m->prof_march[4], &m->prof_rhs, &m->prof_redprol, &m->prof_rescorr, &m->prof_respre, &m->prof_march_pl, &m->prof_march_corr, &m->prof_resmax})
+  for (auto *ps : {&m->prof_sweep, &m->prof_resid, &m->prof_block, &m->prof_march[2], &m->prof_march[3], &m->prof_march[4], &m->prof_rhs, &m->prof_redprol, &m->prof_rescorr, &m->prof_respre, &m->prof_march_pl, &m->prof_march_corr, &m->prof_march_visit, &m->prof_resmax})
     for (auto e : ps->ev) hipEventDestroy(e);
   if (m->comm) comm_destroy(m->comm);
   if (m->ev_c2x) hipEventDestroy(m->ev_c2x);
@@ -708,6 +712,10 @@ extern "C" int msom_set_option(msom_t *m, const char *key, double v) {
   else if (!strcmp(key, "march_partial")) m->march_partial = (int)v;
   else if (!strcmp(key, "march_prolong")) m->march_prolong = (int)v;
   else if (!strcmp(key, "march_correct")) m->march_correct = (int)v;
+  else if (!strcmp(key, "march_visit")) m->march_visit = (int)v;
+  else if (!strcmp(key, "march_visit_min")) m->march_visit_min = (int)v;
+  else if (!strcmp(key, "march_visit_rows")) { extern int g_visit_rows; g_visit_rows = (int)v; }
+  else if (!strcmp(key, "march_visit_pairs")) { extern int g_visit_pairs; g_visit_pairs = (int)v; }
   else if (!strcmp(key, "march_xcd")) { extern int g_march_remap; g_march_remap = (int)v; }
   else if (!strcmp(key, "march_flip")) { extern int g_march_flip; g_march_flip = (int)v; }
   else if (!strcmp(key, "march_dma")) { extern int g_march_dma; g_march_dma = (int)v; }
@@ -761,6 +769,7 @@ extern "C" int msom_set_option(msom_t *m, const char *key, double v) {
 static int march_levels(msom *m);
 static int march_kmax(const msom *m);
 static bool march_lean_fine(msom *m);
+static bool march_visit_fine(msom *m);
 static bool restrict2_ok(const msom *m);
 extern "C" double msom_get_param(msom_t *m, const char *key) {
   if (!m || !key) return NAN;
@@ -796,6 +805,7 @@ extern "C" double msom_get_param(msom_t *m, const char *key) {
   if (!strcmp(key, "march_min")) return m->march_min;   // log2 of the cell-layers a single-tile level needs for the chained pass
   if (!strcmp(key, "march_kmax")) return march_kmax(m);   // half-sweeps per marching pass that relax_sweeps allows
   if (!strcmp(key, "march_lean_fine")) return march_lean_fine(m);   // the finest level's interior chunks take the lean body
+  if (!strcmp(key, "march_visit")) return march_visit_fine(m);   // the finest level's 4 + 4 half-sweeps with the correction take k_relax_visit
   if (!strcmp(key, "split_ls")) return m->nlev > 0 ? (double)m->sg[0].ls : NAN;   // doubles per layer of the finest split field
   auto idx = [](const char *s, int n) { const int k = atoi(s); return k >= 0 && k < n ? k : -1; };
   if (!strncmp(key, "idh0_", 5)) { const int k = idx(key + 5, MSOM_MAXNL); return k < 0 ? NAN : m->lc.idh0[k]; }
@@ -1185,6 +1195,17 @@ static bool march_lean_fine(msom *m) {
   extern int g_march_lean;
   return m->nlev > 0 && g_march_lean && march_ok(m, tile_lev(m, 0)) && march_lean_fits(m->nl, m->sg[0], &m->g);
 }
+// does the finest level's visit take k_relax_visit when it relaxes 4 + 4 half-sweeps with the prolongation and the correction?
+// One tile with walls, uniform S, nl = 2..6, the lean body, a level wide enough for one of its chunks and (march_visit = 1)
+// big enough to gain
+static bool march_visit_fine(msom *m) {
+  extern int g_march_dma, g_visit_rows, g_visit_pairs;
+  if (!m->march_visit || m->nlev < 2 || !g_march_dma || !m->uniformS || m->nl < 2) return false;
+  const Lev L = tile_lev(m, 0);
+  if (m->march_visit < 2 && (size_t)L.sg->nx * L.sg->ny * m->nl < ((size_t)1 << m->march_visit_min)) return false;
+  return !L.tiled && L.walls == WALL_ALL && march_kmax(m) == 4 && m->march_prolong && m->march_partial && m->march_correct && m->mg_fused &&
+         march_lean_fine(m) && relax_visit_fits(m->nl, m->sg[0], g_visit_rows, g_visit_pairs);
+}
 // is the prolongation coarse -> L folded into the first smoothing pass of L?
 static bool fuse_prolong(msom *m, const Lev &L, int nrelax) {
   if (block_ok(m, L) && nrelax >= 2) return true;
@@ -1250,6 +1271,17 @@ static void relax_sweeps(msom *m, Lev &L, const Lev *coarse, int nrelax, int cor
     // tiles: the pass then needs MARCH_HALO cells / rows of the COARSE correction beyond the tile edges too (LDS-DMA kernel, nl <= 6)
     const bool pl_tiled = deep && coarse && coarse->k >= 0 && nl <= 6 && m->march_prolong >= 1 && coarse->sg->nx >= 2 * MARCH_HALO && coarse->sg->ny >= 2 * MARCH_HALO;
     if (coarse && n >= 3 && kmax >= 3 && (!deep || pl_tiled) && m->march_prolong) {
+      // the finest level's whole visit: one fused launch on the interior chunks, the two passes around it
+      if (n == 8 && L.fine && m->corr_req && march_visit_fine(m)) {
+        extern int g_visit_rows, g_visit_pairs;
+        MarchCorrect mc{m->f[MSOM_PSI], m->psi_alt, m->g};
+        if (prof) prof_begin(m, m->prof_march_visit);
+        if (launch_relax_visit(m->st, *L.da, *L.da_alt, L.res, *L.sg, nl, *L.rc, kwalls, *coarse->da, *coarse->sg, mc, g_visit_rows, g_visit_pairs, g_march_rows))
+          m->sticky = MSOM_ERR_ARG;
+        if (prof) prof_end(m, m->prof_march_visit);
+        m->corr_done = 1;
+        return;
+      }
       // whole levels: the prolongation rides in the first PASS (its input is interpolated from the coarse level on
       // the fly), so the 2 nrelax half-sweeps are 4 + 4 instead of (red + prolongation) + 4 + 3
       int K = n < kmax ? n : kmax;
@@ -2970,14 +3002,14 @@ extern "C" int msom_dbg_op(msom_t *m, const char *op, int f_in, int f_out, doubl
 
 extern "C" int msom_profile_reset(msom_t *m) {
   if (!m) return MSOM_ERR_ARG;
-  for (auto *ps : {&m->prof_sweep, &m->prof_resid, &m->prof_block, &m->prof_march[2], &m->prof_march[3], &m->prof_march[4], &m->prof_rhs, &m->prof_redprol, &m->prof_rescorr, &m->prof_respre, &m->prof_march_pl, &m->prof_march_corr, &m->prof_resmax}) { ps->used = 0; ps->total_ms = 0; ps->launches = 0; }
+  for (auto *ps : {&m->prof_sweep, &m->prof_resid, &m->prof_block, &m->prof_march[2], &m->prof_march[3], &m->prof_march[4], &m->prof_rhs, &m->prof_redprol, &m->prof_rescorr, &m->prof_respre, &m->prof_march_pl, &m->prof_march_corr, &m->prof_march_visit, &m->prof_resmax}) { ps->used = 0; ps->total_ms = 0; ps->launches = 0; }
   return MSOM_OK;
 }
 extern "C" int msom_profile_read(msom_t *m, const char *kernel, double *avg_ms, long *launches) {
   if (!m || !kernel) return MSOM_ERR_ARG;
   ProfSlot *ps = !strcmp(kernel, "sweep") ? &m->prof_sweep : !strcmp(kernel, "residual") ? &m->prof_resid : !strcmp(kernel, "block2") ? &m->prof_block :
                  !strcmp(kernel, "march2") ? &m->prof_march[2] : !strcmp(kernel, "march3") ? &m->prof_march[3] : !strcmp(kernel, "march4") ? &m->prof_march[4] :
-                 !strcmp(kernel, "march_pl") ? &m->prof_march_pl : !strcmp(kernel, "march_corr") ? &m->prof_march_corr : !strcmp(kernel, "resid_max") ? &m->prof_resmax : !strcmp(kernel, "rhs") ? &m->prof_rhs : !strcmp(kernel, "red_prolong") ? &m->prof_redprol : !strcmp(kernel, "resid_correct") ? &m->prof_rescorr :
+                 !strcmp(kernel, "march_pl") ? &m->prof_march_pl : !strcmp(kernel, "march_corr") ? &m->prof_march_corr : !strcmp(kernel, "march_visit") ? &m->prof_march_visit : !strcmp(kernel, "resid_max") ? &m->prof_resmax : !strcmp(kernel, "rhs") ? &m->prof_rhs : !strcmp(kernel, "red_prolong") ? &m->prof_redprol : !strcmp(kernel, "resid_correct") ? &m->prof_rescorr :
                  !strcmp(kernel, "resid_restrict") ? &m->prof_respre : nullptr;
   if (!ps) { msom_set_error("unknown kernel %s", kernel); return MSOM_ERR_ARG; }
   prof_collect(m, *ps);
