@@ -14,10 +14,13 @@ overridden, synthetic seed-free initial stream function, fp64):
 N = 1: the whole grid on one GPU.  N > 1 (one process per GPU, RCCL): by default WEAK scaling -- every rank owns one
 tile of the configuration's N = 1 size (`--tile NXxNY` overrides it), the domain grows with the tile grid and the
 grid spacing stays fixed; `--split` instead splits the configuration's own grid over the ranks (BASELINE C4 as
-written: 4096^2 x 6 on 2 x 4 tiles of 2048 x 1024 at N = 8).  After the timed weak-scaling leg a multi-rank run also
-times that split layout and reports it as `split_global_grid` in the same line.
+written: 4096^2 x 6 on 2 x 4 tiles of 2048 x 1024 at N = 8).  After the timed weak-scaling leg a multi-rank `--full` run
+also times that split layout and reports it as `split_global_grid` in the same line.
 
-Prints ONE JSON line on rank 0.  `roofline` describes the dominant kernel of the step (the finest-level smoother pass);
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the
+headline figure; everything else it can measure needs `--full` (off by default): the roofline, the other legs (the other
+configurations and S / boundary variants at N = 1, the split layout at N > 1) and the CPU baseline.  The timed steps are the
+same in both modes.  `roofline` describes the dominant kernel of the step (the finest-level smoother pass);
 its duration is the average of HIP-event pairs recorded on the library's own stream around every such launch INSIDE
 the timed steps (option "profile"), `frac` = the pass's own compulsory HBM bytes / that duration / 8 TB/s.  The other
 finest-level kernels (PV tendency, residual passes, red + prolongation) are timed the same way and listed under
@@ -195,12 +198,13 @@ class Leg:
 
     PROF_KEYS = ("march4", "march_pl", "march_corr", "march3", "march2", "sweep", "red_prolong", "resid_restrict", "resid_correct", "resid_max", "rhs")
 
-    def run(self, steps, warmup, keep_outputs=False):
+    def run(self, steps, warmup, keep_outputs=False, kernels=False):
         """W warm-up steps, then EXACTLY `steps` timed steps between barriers.  Inside the timed steps only the chained smoother
         passes (the dominant kernel of the roofline entry) are bracketed by HIP events (option profile = 2): an event pair costs
-        ~10 us of stream time, and with every kernel bracketed the step is 1.4 % (4096^2 x 6) to 20 % (512^2 x 3) slower.  The
-        other kernels are timed the same way in a second, untimed pass of up to 20 steps right after.  keep_outputs: what the
-        last timed step hands its caller (psi, q, dt) is read back into self.outputs before that second pass moves the state."""
+        ~10 us of stream time, and with every kernel bracketed the step is 1.4 % (4096^2 x 6) to 20 % (512^2 x 3) slower.  With
+        `kernels` (what self.kernels() reads) the other kernels are timed the same way in a second, untimed pass of up to 20
+        steps right after.  keep_outputs: what the last timed step hands its caller (psi, q, dt) is read back into self.outputs
+        before that second pass moves the state."""
         g = self.g
         for _ in range(warmup):
             g.step()
@@ -218,15 +222,16 @@ class Leg:
 
             self.outputs = {"psi": g.get(F["PSI"]), "q": g.get(F["Q"]), "dt": np.array([dt], dtype=np.float64)}
         g.option("profile", 0)
-        self.prof = {k: g.profile_read(k) for k in self.PROF_KEYS}
-        g.profile_reset()
-        g.option("profile", 1)
-        for _ in range(min(steps, 20)):
-            g.step()
-        g.option("profile", 0)
-        for k in self.PROF_KEYS:
-            if self.prof[k][1] == 0:
-                self.prof[k] = g.profile_read(k)
+        if kernels:
+            self.prof = {k: g.profile_read(k) for k in self.PROF_KEYS}
+            g.profile_reset()
+            g.option("profile", 1)
+            for _ in range(min(steps, 20)):
+                g.step()
+            g.option("profile", 0)
+            for k in self.PROF_KEYS:
+                if self.prof[k][1] == 0:
+                    self.prof[k] = g.profile_read(k)
         if self.dist is not None:
             import torch
 
@@ -427,8 +432,10 @@ def main():
     ap.add_argument("--tile", default=None, help="NXxNY: tile per rank (weak scaling), overrides the configuration's grid")
     ap.add_argument("--split", action="store_true", help="split the configuration's own grid over the ranks (strong)")
     ap.add_argument("--nl", type=int, default=None)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary legs (other configs at N = 1, split grid at N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline figure: roofline (one more profiled pass), secondary legs and the CPU baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary legs (other configs at N = 1, split grid at N > 1)")
     ap.add_argument("--cpu-n", type=int, default=0, help="grid of the cpu_baseline leg (0: the configuration's own N)")
     ap.add_argument("--opt", action="append", default=[], help="key=value library option (tuning A/B), repeatable")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -468,14 +475,14 @@ def main():
         for kv in args.opt:
             k, v = kv.split("=")
             leg.g.option(k, float(v))
-        elapsed = leg.run(args.steps, args.warmup, keep_outputs=args.dump_outputs is not None)
+        elapsed = leg.run(args.steps, args.warmup, keep_outputs=args.dump_outputs is not None, kernels=args.full)
     except Exception as e:  # noqa: BLE001  -- say what failed in the one line the driver reads, then fail
         if rank == 0:
             print(json.dumps({"metric": "grid-point-updates/s", "value": 0.0, "unit": "grid-point-updates/s", "n_gpus": world, "steps": args.steps,
                               "warmup": args.warmup, "higher_is_better": True, "error": repr(e)}), flush=True)
         raise
     main_sum = leg.summary(args.steps, elapsed)
-    roof = roofline(leg, world, args.steps) if rank == 0 else None
+    roof = roofline(leg, world, args.steps) if rank == 0 and args.full else None
     if args.dump_outputs is not None:
         dump_outputs(args.dump_outputs, leg.outputs, suffix=f"_rank{rank}" if world > 1 else "")
         leg.outputs = None
@@ -483,7 +490,7 @@ def main():
     leg.g.close()
 
     extra = {}
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         if world == 1 and args.config == "C4" and not args.tile:
             # the other BASELINE configurations on one GPU, short legs (their kernels are timed the same way)
             # (a leg that fails is recorded as such: the headline line must still be printed)
@@ -492,7 +499,7 @@ def main():
                 try:
                     lg = Leg(c["N"], c["N"], c["nl"], 1, 1, 0, None, c["N"], stochastic=c["stochastic"], local_rank=local_rank)
                     steps = 100 if c["N"] <= 512 else 40
-                    el = lg.run(steps, 10)
+                    el = lg.run(steps, 10, kernels=True)
                     s = lg.summary(steps, el)
                     ks, _, _, _ = lg.kernels()
                     s["kernels"] = {k: {"avg_launch_ms": v["avg_launch_ms"], "frac_hbm": v["frac_hbm"]} for k, v in ks.items()}
@@ -510,7 +517,7 @@ def main():
                 try:
                     c = CONFIGS["C4"]
                     lg = Leg(c["N"], c["N"], c["nl"], 1, 1, 0, None, c["N"], local_rank=local_rank, **kw)
-                    el = lg.run(10, 3)
+                    el = lg.run(10, 3, kernels=True)
                     s_ = lg.summary(10, el)
                     ks, _, _, _ = lg.kernels()
                     s_["kernels"] = {k: {"avg_launch_ms": v["avg_launch_ms"], "frac_hbm": v["frac_hbm"]} for k, v in ks.items()}
@@ -540,7 +547,7 @@ def main():
                 dist.all_reduce(bad, op=dist.ReduceOp.MAX)
                 if float(bad.item()) > 0:
                     raise err if err is not None else RuntimeError("another rank could not create its tile of the split layout")
-                el = lg.run(args.steps, args.warmup)
+                el = lg.run(args.steps, args.warmup, kernels=True)
                 extra["split_global_grid"] = lg.summary(args.steps, el)
                 if rank == 0:
                     ks, _, _, _ = lg.kernels()
@@ -572,11 +579,12 @@ def main():
                 "ke_1": main_sum["ke_1"], "uniform_S_fast_path": bool(uniform),
                 **({"options": args.opt} if args.opt else {}),
             },
-            "roofline": roof,
         }
+        if args.full:
+            out["roofline"] = roof
         if extra:
             out["other_legs"] = extra
-        if not args.no_cpu and world == 1:   # CPU baseline: rank 0 at N = 1 only
+        if args.full and not args.no_cpu and world == 1:   # CPU baseline: rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(nl, n_cpu=args.cpu_n or cfg["N"])
             out["cpu_baseline"]["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
             out["cpu_baseline"]["variants"] = cpu_variants(nl)
