@@ -104,15 +104,16 @@ int msom_destroy(msom_t *m);
  * "resmax_rows" [0 = 32] rows per chunk of the marching max-only residual pass (-1: the LDS-tiled kernel), "march" [1] chained half-sweep smoother on HBM-bound single-GPU levels (2: on every level that is
  * wide enough), "march_k" [4] half-sweeps per pass, "march_rows" [0 = auto] chunk height, "march_min" [23] log2 of the cell-layers a level needs, "march_prolong" [1] prolongation folded
  * into the first pass, "march_dma" [2] memory side of the pass (0: register-window loads, 1: LDS-DMA prefetch with one strip per
- * workgroup, 2: four strips per workgroup marching in step; PROCESS-WIDE tuning knob like march_rows / march_xcd / march_flip /
- * march_dbg / rhs_dbg / block_variant, which are globals of the library rather than fields of the handle), "graph" [0] replay the launches of a multigrid cycle from a captured hipGraph on the launch-bound grids
+ * workgroup, 2: four strips per workgroup marching in step), "graph" [0] replay the launches of a multigrid cycle from a captured hipGraph on the launch-bound grids
  * (measured neutral), "march_partial" [1], "march_correct" [1] correction folded into the last pass, "march_xcd" [1] XCD-contiguous block numbering, "march_flip" [1] odd chunks march downwards, "block_sweeps" [0] LDS-tiled blocked smoother (2 sweeps per launch, every level), "restrict2" [1] the pre-cycle residual pass restricts two levels down, "restrict_pyr" [1] the rest of the restriction chain in launches of up to five levels, "step_sync" [-1] (see msom_sync), "block8" [1] / "block8_max" [1024] round 3: prolongation + up to 8 half-sweeps of a
  * visit of a launch-bound level (64 .. block8_max cells a side, not marched; one GPU, walls or doubly periodic, nl <= 8; uniform or general S) in one launch of that kernel with a halo of 8, "agglomerate" [1] / "agg_size" [256]
- * gathered coarse levels of tiled runs, "mg_global_sum" [0]; "rhs_dbg", "block_variant": timing
- * experiments of tools/. */
+ * gathered coarse levels of tiled runs, "mg_global_sum" [0]; "march_visit_rows" [0 = 28] / "march_visit_pairs" [2] chunk height /
+ * wave pairs per workgroup of the fused finest-level visit; "march_dbg", "rhs_dbg", "lpw_dbg", "block_variant": timing experiments of
+ * tools/.  Every option, these tuning keys included, is a setting of the handle it is set on and reaches no other handle. */
 int msom_set_option(msom_t *m, const char *key, double value);
 /* parsed / derived parameters: N nx ny nl L0 DT iRe iRe4 CFL Rom tend dtout beta tau0 Ekb Eks
- * sbc idh0_<l> idh1_<l> Fr_<l> dh_<l> nlevels */
+ * sbc idh0_<l> idh1_<l> Fr_<l> dh_<l> nlevels; the handle's kernel options march_rows march_xcd march_flip march_dbg
+ * march_lean march_dma march_visit_rows march_visit_pairs resmax_rows block_variant rhs_dbg lpw_dbg */
 double msom_get_param(msom_t *m, const char *key);
 
 /* pyset_field / pyget_field, msqg/qg.h:1164-1188 (array [layer][y][x]; BC applied after set) */
@@ -282,14 +283,14 @@ void msomn_destroy(msomn_t *m);                                 /* trash_vars qg
 /* keys: TOLERANCE NITERMAX NITERMIN (nodal-poisson.h:19-23) DT quiet stochastic seed; implementation switches (result-preserving in
  * the strict build): node_split [65] levels of >= that many vertices a side keep correction / residual / mask / S2 copies in the
  * x-parity split layout (0: off), s2_rows [1] row tables for an S2 that does not depend on x, node_pfused [1] prolongation folded into the first colour pass of the split levels, mg_coarse [32] levels of at most that
- * many cells a side in one launch, tiled_relax [0], node_march [0] (measured slower, kept for the tests); round 3: node_march_s [2049] split
+ * many cells a side in one launch, tiled_relax [0], node_march [0] (measured slower, kept for the tests), node_march_rows [0 = automatic] chunk height of the marching passes; round 3: node_march_s [2049] split
  * levels of >= that many vertices a side chain up to 4 colour half-sweeps per pass (node_march_tail1 [1]: 9 half-sweeps as 4 + 4 + a colour
  * launch, 0: 4 + 3 + 2), node_tile_s [65] / node_tile_max [513] / node_tile_k [8]
  * the split levels between those sizes run up to node_tile_k colour half-sweeps per LDS-tiled launch (nl <= 4), node_rhs_fused [1] the
  * baroclinic tendency in three passes instead of the twelve loops of the reference, node_corr_fused [2] the correction of a cycle applied
  * inside the residual pass of the next (2: rows marched, 1: one thread per vertex, 0: separate passes), profile [0] */
 int msomn_set_option(msomn_t *m, const char *key, double value);
-/* keys: N nl L0 DT tend dtout nlevels iRd2_low bc_fac idh0_<l> idh1_<l>; NaN if unknown */
+/* keys: N nl L0 DT tend dtout nlevels iRd2_low bc_fac idh0_<l> idh1_<l>, the options node_march_s node_march_rows; NaN if unknown */
 double msomn_get_param(msomn_t *m, const char *key);
 int msomn_field_layers(msomn_t *m, int field);
 int msomn_set_field(msomn_t *m, int field, const double *a);   /* a: [layers][N+1][N+1] */

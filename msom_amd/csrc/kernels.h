@@ -21,6 +21,23 @@ struct RelaxCoef {
   double S[MSOM_MAXNL];       // uniform S_l (residual, stretching)
 };
 
+// kernel-selection options of one handle, named after their msom_set_option keys; the defaults are the product configuration
+struct KernelOpts {
+  int march_rows = 0;         // chunk height of k_relax_march (0: automatic)
+  int march_xcd = 1;          // XCD-contiguous block numbering of the marching passes
+  int march_flip = 1;         // odd chunks march down
+  int march_dbg = 0;          // timing experiments of the marching passes
+  int march_lean = 2;         // interior chunks of the LDS-DMA pass take the lean body (2: requests two steps ahead where LDS allows)
+  int march_dma = 2;          // LDS-DMA version of the pass (0 register-window kernel, 1 one strip, 2 four strips per workgroup)
+  int march_visit_rows = 0;   // chunk height of k_relax_visit (0: automatic)
+  int march_visit_pairs = 2;  // wave pairs per workgroup of k_relax_visit (1 or 2; 4096^2 x 6: 0.866 / 0.873 ms with 2, 0.881 / 0.883 with 1)
+  int resmax_rows = 0;        // rows per chunk of k_resmax_march (0: 32), -1: the LDS-tiled kernel instead
+  int block_variant = 0;      // tile shape of k_relax_block (tools/bench_kernels.py)
+  int rhs_dbg = 0;            // bits 128, 256, 512: plain residual / red-prolongation kernels; rows << 8 overrides k_rhs_lpw's chunk height
+  int lpw_dbg = 0;            // bits 1, 2 timing experiments of k_rhs_lpw; 4: every wavefront takes the instantiation with the ghost-line code
+};
+int device_cu_count();   // CUs of the current device, asked once per device
+
 // ---- kernels_rhs.hip
 void launch_fill_ghost(hipStream_t st, double *f, const NatGeom &g, int nl, int bc, int walls, int depth = 1);
 void launch_fill_periodic(hipStream_t st, double *f, const NatGeom &g, int nl, int depth);
@@ -74,16 +91,16 @@ struct RhsResid {
   SplitGeom sg, cg;
 };
 int rhs_fused_blocks(const NatGeom &g);
-void launch_rhs_fused(hipStream_t st, const double *psi, const double *S, const double *qforc, const double *wind, double *dq,
+void launch_rhs_fused(hipStream_t st, const KernelOpts &o, const double *psi, const double *S, const double *qforc, const double *wind, double *dq,
                       double *umax_partial, double *umax_out, const NatGeom &g, int nl, int walls, int uniformS, const double *Su,
                       int have_qforc, double D, double beta, double iRe, double iRe4, double cs, double cb, double slip_c,
                       const LayerCoef &lc, int variant, const double *q_in = nullptr, double *q_out = nullptr, double dt = 0.,
                       const RhsResid *rr = nullptr, int region = 0, const double *dt_ptr = nullptr);
 int rhs_pipe_blocks(const NatGeom &g);
-// ---- kernels_lpw.hip: same pass, one layer per wavefront, register windows + DPP (chunk_rows <= 0: automatic)
-void launch_rhs_lpw(hipStream_t st, const double *psi, const double *S, const double *qforc, const double *wind, double *dq, const NatGeom &g,
-                    int nl, int walls, int uniformS, const double *Su, int have_qforc, double D, double beta, double iRe, double iRe4, double cs,
-                    double cb, double slip_c, const LayerCoef &lc, const double *q_in, double *q_out, double dt, int chunk_rows, int stoch = 0,
+// ---- kernels_lpw.hip: same pass, one layer per wavefront, register windows + DPP (chunk height: rhs_dbg >> 8, 0: automatic)
+void launch_rhs_lpw(hipStream_t st, const KernelOpts &o, const double *psi, const double *S, const double *qforc, const double *wind, double *dq,
+                    const NatGeom &g, int nl, int walls, int uniformS, const double *Su, int have_qforc, double D, double beta, double iRe, double iRe4,
+                    double cs, double cb, double slip_c, const LayerCoef &lc, const double *q_in, double *q_out, double dt, int stoch = 0,
                     const double *q_stage = nullptr, const double *noise = nullptr, double crelax = 0., double dts = 0., int region = 0,
                     const double *dt_ptr = nullptr);
 
@@ -105,7 +122,7 @@ void launch_split_unpack(hipStream_t st, const double *sp, const SplitGeom &sg, 
 void launch_residual(hipStream_t st, const double *a, const double *b, const double *S, const NatGeom &g, double *res, const SplitGeom &sg,
                      int nl, const RelaxCoef &rc, int uniformS, double *maxres, double *sum_partial, int want_sum);
 int residual2_blocks(const NatGeom &g);
-void launch_residual2(hipStream_t st, int mode, const double *a, const double *da, double *a_out, const double *b, const double *S,
+void launch_residual2(hipStream_t st, const KernelOpts &o, int mode, const double *a, const double *da, double *a_out, const double *b, const double *S,
                       const NatGeom &g, double *res, const SplitGeom &sg, double *res_c, const SplitGeom &cg, int nl, const RelaxCoef &rc,
                       int uniformS, int walls, double *maxres, double *sum_partial, int want_sum, double *umax_partial, double *umax_out,
                       int umax_clean = 0,
@@ -117,11 +134,11 @@ void launch_relax_color(hipStream_t st, double *da, const double *res, const dou
                         int uniformS, int color, int walls, int fine, int region = 0);
 void launch_relax_ring(hipStream_t st, double *da, const double *res, const double *S, const SplitGeom &sg, int nl, const RelaxCoef &rc,
                        int uniformS, int color, int walls);
-int launch_relax_block8(hipStream_t st, const double *da_in, const double *coarse, const SplitGeom &cg, const double *res, double *da_out,
+int launch_relax_block8(hipStream_t st, const KernelOpts &o, const double *da_in, const double *coarse, const SplitGeom &cg, const double *res, double *da_out,
                         const SplitGeom &sg, int nl, const RelaxCoef &rc, int walls, int nh, int c0, const double *S = nullptr);
-void launch_relax_block2(hipStream_t st, const double *da_in, const double *coarse, const SplitGeom &cg, const double *res, double *da_out,
+void launch_relax_block2(hipStream_t st, const KernelOpts &o, const double *da_in, const double *coarse, const SplitGeom &cg, const double *res, double *da_out,
                          const SplitGeom &sg, int nl, const RelaxCoef &rc, int walls, int fine);
-void launch_relax_red_prolong(hipStream_t st, double *da, const double *coarse, const SplitGeom &cg, const double *res, const double *S,
+void launch_relax_red_prolong(hipStream_t st, const KernelOpts &o, double *da, const double *coarse, const SplitGeom &cg, const double *res, const double *S,
                               const SplitGeom &sg, int nl, const RelaxCoef &rc, int uniformS, int walls);
 void launch_correct(hipStream_t st, double *a, const NatGeom &g, const double *da, const SplitGeom &sg, int nl, int walls);
 
@@ -133,14 +150,14 @@ void launch_correct(hipStream_t st, double *a, const NatGeom &g, const double *d
 // (the other colour is recomputed by the next half-sweep before anything reads it): w/2 fewer bytes written
 struct MarchCorrect { const double *psi; double *psi_out; NatGeom g; };
 struct MarchHalo { const double *in_s, *in_n, *res_s, *res_n; size_t ls; int rows; };
-int launch_relax_march(hipStream_t st, const double *in, double *out, const double *res, const SplitGeom &sg, int nl, const RelaxCoef &rc, int c1,
+int launch_relax_march(hipStream_t st, const KernelOpts &o, const double *in, double *out, const double *res, const SplitGeom &sg, int nl, const RelaxCoef &rc, int c1,
                        int K, int walls, int chunk_rows = 0, const MarchHalo *h = nullptr, const double *coarse = nullptr, const SplitGeom *cg = nullptr,
                        const MarchCorrect *mc = nullptr, int more_follow = 0, const MarchHalo *coarse_halo = nullptr, int region = 0,
                        const int *skip = nullptr);
 // the finest level's visit, 4 + 4 half-sweeps with the prolongation and the correction, fused where chunks are interior (k_relax_visit);
-// returns -1 (nothing launched) where it does not apply.  rows: the visit's chunk height (0: automatic); pairs: wave pairs per workgroup
-int launch_relax_visit(hipStream_t st, double *da, double *da_alt, const double *res, const SplitGeom &sg, int nl, const RelaxCoef &rc, int walls,
-                       const double *coarse, const SplitGeom &cg, const MarchCorrect &mc, int rows, int pairs, int ring_rows);
+// returns -1 (nothing launched) where it does not apply.  Chunk height and wave pairs per workgroup: options march_visit_rows / _pairs
+int launch_relax_visit(hipStream_t st, const KernelOpts &o, double *da, double *da_alt, const double *res, const SplitGeom &sg, int nl, const RelaxCoef &rc,
+                       int walls, const double *coarse, const SplitGeom &cg, const MarchCorrect &mc);
 bool relax_visit_fits(int nl, const SplitGeom &sg, int rows, int pairs);
 // can the lean interior body of the pass address every layer of the level (sg) and, with the correction, of psi (ng)?
 bool march_lean_fits(int nl, const SplitGeom &sg, const NatGeom *ng);
@@ -187,9 +204,9 @@ void launch_n_rowfill(hipStream_t st, double *f, const double *row, const NatGeo
 void launch_n_relax(hipStream_t st, double *a, const double *b, const double *mk, const double *S2, const NatGeom &g, int nl, int color, double D,
                     double iRd2, const LayerCoef &lc, int sp = 0, const double *S2row = nullptr);
 int launch_n_relax_march(hipStream_t st, const double *a_in, double *a_out, const double *b, const double *mk, const double *S2, const NatGeom &g, int nl,
-                         int color, int K, double D, double iRd2, const LayerCoef &lc);
+                         int color, int K, double D, double iRd2, const LayerCoef &lc, int rows);
 int launch_n_relax_march_s(hipStream_t st, const double *a_in, double *a_out, const double *b, const double *mk, const NatGeom &g, int nl, int color, int K,
-                           double D, double iRd2, const LayerCoef &lc, const double *S2row, int partial);
+                           double D, double iRd2, const LayerCoef &lc, const double *S2row, int partial, int rows);
 int launch_n_relax_tile_s(hipStream_t st, const double *a_in, double *a_out, const double *b, const double *mk, const NatGeom &g, int nl, int color, int K,
                           double D, double iRd2, const LayerCoef &lc, const double *S2row);
 int launch_n_relax_tile(hipStream_t st, const double *a_in, double *a_out, const double *b, const double *mk, const double *S2, const NatGeom &g,

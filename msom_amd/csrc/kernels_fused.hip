@@ -635,22 +635,20 @@ __global__ void __launch_bounds__(FNT, 2) k_rhs_fused_pipe(RhsArgs a) {
   }
 }
 
-int g_rhs_dbg = 0;
 int rhs_pipe_blocks(const NatGeom &g) { return ((g.nx + FTX - 1) / FTX) * ((g.ny + 31) / 32); }
 int rhs_fused_blocks(const NatGeom &g) { return ((g.nx + FTX - 1) / FTX) * ((g.ny + 7) / 8); }  // upper bound (smallest FTY)
 
-void launch_rhs_fused(hipStream_t st, const double *psi, const double *S, const double *qforc, const double *wind, double *dq,
+void launch_rhs_fused(hipStream_t st, const KernelOpts &o, const double *psi, const double *S, const double *qforc, const double *wind, double *dq,
                       double *umax_partial, double *umax_out, const NatGeom &g, int nl, int walls, int uniformS, const double *Su,
                       int have_qforc, double D, double beta, double iRe, double iRe4, double cs, double cb, double slip_c,
                       const LayerCoef &lc, int variant, const double *q_in, double *q_out, double dt, const RhsResid *rr, int region, const double *dt_ptr) {
-  extern int g_rhs_dbg;
   if (variant == 6) {
-    launch_rhs_lpw(st, psi, S, qforc, wind, dq, g, nl, walls, uniformS, Su, have_qforc, D, beta, iRe, iRe4, cs, cb, slip_c, lc, q_in, q_out, dt,
-                   g_rhs_dbg >> 8, 0, nullptr, nullptr, 0., 0., region, dt_ptr);  // tuning: rhs_dbg = rows << 8 overrides the chunk height
+    launch_rhs_lpw(st, o, psi, S, qforc, wind, dq, g, nl, walls, uniformS, Su, have_qforc, D, beta, iRe, iRe4, cs, cb, slip_c, lc, q_in, q_out, dt,
+                   0, nullptr, nullptr, 0., 0., region, dt_ptr);
     return;
   }
   RhsArgs a;
-  a.dbg = g_rhs_dbg;
+  a.dbg = o.rhs_dbg;
   a.res = a.res_c = a.res_max = a.bsum_partial = nullptr;
   if (rr && variant == 1 && q_out) {
     a.res = rr->res; a.res_c = rr->res_c; a.res_max = rr->res_max; a.bsum_partial = rr->bsum_partial; a.sg = rr->sg; a.cg = rr->cg;

@@ -359,25 +359,22 @@ __global__ void __launch_bounds__(64 * LPW_MAXW) k_rhs_lpw(LpwArgs a) {
   else lpw_body<R, UNI, QF, ADV, STOCH, false>(a, ring);
 }
 
-int g_lpw_dbg = 0;  // option lpw_dbg: bits 1, 2 timing experiments; 4: every wavefront takes the instantiation with the ghost-line code
-
-void launch_rhs_lpw(hipStream_t st, const double *psi, const double *S, const double *qforc, const double *wind, double *dq, const NatGeom &g,
-                    int nl, int walls, int uniformS, const double *Su, int have_qforc, double D, double beta, double iRe, double iRe4, double cs,
-                    double cb, double slip_c, const LayerCoef &lc, const double *q_in, double *q_out, double dt, int chunk_rows, int stoch,
+void launch_rhs_lpw(hipStream_t st, const KernelOpts &o, const double *psi, const double *S, const double *qforc, const double *wind, double *dq,
+                    const NatGeom &g, int nl, int walls, int uniformS, const double *Su, int have_qforc, double D, double beta, double iRe, double iRe4,
+                    double cs, double cb, double slip_c, const LayerCoef &lc, const double *q_in, double *q_out, double dt, int stoch,
                     const double *q_stage, const double *noise, double crelax, double dts, int region, const double *dt_ptr) {
   LpwArgs a;
   a.region = region;
   a.dt_ptr = dt_ptr;
   a.q_stage = q_stage; a.noise = noise; a.crelax = crelax; a.dts = dts;
   a.psi = psi; a.S = S; a.qforc = qforc; a.wind = wind; a.q_in = q_in; a.dq = dq; a.q_out = q_out; a.dt = dt;
-  extern int g_lpw_dbg;
-  a.dbg = g_lpw_dbg & 3;
-  a.noedge_off = (g_lpw_dbg & 4) != 0;
+  a.dbg = o.lpw_dbg & 3;
+  a.noedge_off = (o.lpw_dbg & 4) != 0;
   a.g = g; a.nl = nl; a.walls = walls; a.uniformS = uniformS; a.have_qforc = have_qforc;
   a.D = D; a.beta = beta; a.iRe = iRe; a.iRe4 = iRe4; a.cs = cs; a.cb = cb; a.slip_c = slip_c; a.lc = lc;
   for (int l = 0; l < MSOM_MAXNL; l++) a.Su[l] = Su ? Su[l] : 0.;
   const int strips = (g.nx + LPW_W - 1) / LPW_W;
-  int H = chunk_rows;
+  int H = o.rhs_dbg >> 8;   // tuning: rhs_dbg = rows << 8 overrides the chunk height
   a.NS = LPW_MAXW / nl < 1 ? 1 : LPW_MAXW / nl;
   if (a.NS > strips) a.NS = strips;
   if (H <= 0) {
@@ -385,12 +382,7 @@ void launch_rhs_lpw(hipStream_t st, const double *psi, const double *S, const do
     // ceil(workgroups / CUs) rounds of H + 6 row steps (6 warm-up rows per chunk).  Round 3: the chunk height that minimises that product
     // -- the former rule (about 1024 / strips chunks, at most 64 rows) gave 2048^2 x 3 288 workgroups of 64 rows = 1.125 rounds, i.e. two
     // rounds of 70 steps where 40 rows give two of 46 (0.117 -> 0.09 ms per launch); 4096^2 x 6 keeps its 64 rows (9 rounds)
-    static int ncu = 0;
-    if (!ncu) {
-      int dev = 0;
-      hipDeviceProp_t pr;
-      ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
-    }
+    const int ncu = device_cu_count();
     const int wgx = (strips + a.NS - 1) / a.NS;
     // (workgroups do not end together: past three rounds the idle tail is taken as half a round rather than a whole one -- with whole
     // rounds 4096^2 x 3 would take 32 rows, measured 3 % slower than 64)

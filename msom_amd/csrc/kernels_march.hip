@@ -1084,8 +1084,21 @@ __global__ void __launch_bounds__(64 * WPB, 2) k_relax_march_dma(MarchArgs p) {
   }
 }
 
-int g_march_remap = 1;  // XCD-contiguous block numbering (option march_xcd)
-int g_march_flip = 1;   // odd chunks march down (option march_flip)
+// CUs of the current device, asked once per device; tiled tests drive the launchers from several host threads
+int device_cu_count() {
+  static std::mutex mu;
+  static std::map<int, int> cache;
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = cache.find(dev);
+  if (it != cache.end()) return it->second;
+  hipDeviceProp_t pr;
+  int ncu = hipGetDeviceProperties(&pr, dev) == hipSuccess ? pr.multiProcessorCount : 0;
+  if (ncu <= 0) ncu = 256;
+  cache[dev] = ncu;
+  return ncu;
+}
 
 // Chunk height.  All workgroups of a pass take the same time, so the pass ends with an idle tail unless their number
 // is close to a whole number of rounds (resident wavefronts per CU x CUs, from the occupancy calculator for the
@@ -1110,25 +1123,21 @@ static void march_launch(hipStream_t st, Kern kern, MarchArgs a, int ow, int chu
   if (H <= 0) {
     // occupancy per (device, instantiation), asked once; tiled tests drive this from several host threads
     static std::mutex mu;
-    static std::map<std::pair<int, const void *>, std::pair<int, int>> cache;  // -> (blocks per CU, CUs)
+    static std::map<std::pair<int, const void *>, int> cache;  // -> blocks per CU
     int dev = 0;
     (void)hipGetDevice(&dev);
-    int per_cu = 0, ncu = 0;
+    int per_cu = 0;
     {
       std::lock_guard<std::mutex> lock(mu);
       auto it = cache.find({dev, (const void *)kern});
       if (it == cache.end()) {
-        hipDeviceProp_t pr;
-        if (hipGetDeviceProperties(&pr, dev) == hipSuccess) ncu = pr.multiProcessorCount;
-        if (ncu <= 0) ncu = 256;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, nthreads, 0) != hipSuccess || per_cu <= 0) per_cu = 512 / nthreads;
-        cache[{dev, (const void *)kern}] = {per_cu, ncu};
+        cache[{dev, (const void *)kern}] = per_cu;
       } else {
-        per_cu = it->second.first;
-        ncu = it->second.second;
+        per_cu = it->second;
       }
     }
-    const int slots = per_cu * ncu;
+    const int slots = per_cu * device_cu_count();
     H = 0;
     for (int m = 3; m >= 1 && !H; m--) {
       const int chunks = m * slots / strips;
@@ -1143,17 +1152,14 @@ static void march_launch(hipStream_t st, Kern kern, MarchArgs a, int ow, int chu
   hipLaunchKernelGGL(kern, dim3(strips, (a.g.ny + H - 1) / H), dim3(nthreads), 0, st, a);
 }
 
-int g_march_dbg = 0;    // timing experiments (option march_dbg)
-int g_march_lean = 2;   // interior chunks of the LDS-DMA pass take the lean body (option march_lean; 2: requests two steps ahead where LDS allows)
-int g_march_dma = 2;    // LDS-DMA version of the pass (option march_dma: 0 register-window kernel, 1 one strip, 2 four strips per workgroup)
-
+// dma: option march_dma
 template <int NL>
-static int march_dispatch(hipStream_t st, const MarchArgs &a, int K, int rows) {
-  if (g_march_dma && !(K == 4 && NL > 6) && !((a.coarse || a.psi_out) && NL > 6)) {
+static int march_dispatch(hipStream_t st, const MarchArgs &a, int K, int rows, int dma) {
+  if (dma && !(K == 4 && NL > 6) && !((a.coarse || a.psi_out) && NL > 6)) {
     // 1: one strip per workgroup; 2 (default): four adjacent strips per workgroup, marching in step, for the plain pass
     // (the pass with the prolongation measured faster with one: 7.09 vs 7.25 ms per RK2 step); 3: four for both
     constexpr int NLS = NL;
-    const bool four = a.coarse ? g_march_dma >= 3 : g_march_dma >= 2;
+    const bool four = a.coarse ? dma >= 3 : dma >= 2;
 #define MARCH_DMA_K(KK)                                                                                                      \
     if constexpr (NL <= 6) {   /* four strips per workgroup: 4 x the LDS ring; at nl = 7, 8 that leaves one workgroup per CU */   \
       if (a.coarse && four) { march_launch(st, k_relax_march_dma<NLS, KK, 4, 4, true>, a, 56 * 4, rows, 256); return 0; }        \
@@ -1206,7 +1212,7 @@ bool march_lean_fits(int nl, const SplitGeom &sg, const NatGeom *ng) {
 }
 
 // K (2..4) half-sweeps starting with colour c1, in -> out; returns -1 if (nl, K) has no instantiation
-int launch_relax_march(hipStream_t st, const double *in, double *out, const double *res, const SplitGeom &sg, int nl, const RelaxCoef &rc, int c1,
+int launch_relax_march(hipStream_t st, const KernelOpts &o, const double *in, double *out, const double *res, const SplitGeom &sg, int nl, const RelaxCoef &rc, int c1,
                        int K, int walls, int chunk_rows, const MarchHalo *h, const double *coarse, const SplitGeom *cg, const MarchCorrect *mc, int more_follow, const MarchHalo *ch,
                        int region, const int *skip) {
   MarchArgs a;
@@ -1222,23 +1228,19 @@ int launch_relax_march(hipStream_t st, const double *in, double *out, const doub
   if (coarse && (K < 3 || (h && !ch))) return -1;  // the prolongation variant exists for K = 3, 4; on tiles it needs the coarse halo
   a.in_s = h ? h->in_s : nullptr; a.in_n = h ? h->in_n : nullptr; a.res_s = h ? h->res_s : nullptr; a.res_n = h ? h->res_n : nullptr;
   a.hls = h ? h->ls : 0; a.KR = h ? h->rows : 0;
-  extern int g_march_remap;
-  extern int g_march_flip;
-  extern int g_march_dbg;
-  extern int g_march_lean;
   // lean body: see march_lean_fits; the prolongation variant is written for c1 = 0
-  a.lean = !g_march_lean ? 0 : g_march_lean * (int)(march_lean_fits(nl, sg, mc ? &mc->g : nullptr) && (!coarse || c1 == 0));
-  a.in = in; a.out = out; a.res = res; a.g = sg; a.c1 = c1; a.walls = walls; a.rc = rc; a.remap = g_march_remap; a.flip = g_march_flip; a.dbg = g_march_dbg;
+  a.lean = !o.march_lean ? 0 : o.march_lean * (int)(march_lean_fits(nl, sg, mc ? &mc->g : nullptr) && (!coarse || c1 == 0));
+  a.in = in; a.out = out; a.res = res; a.g = sg; a.c1 = c1; a.walls = walls; a.rc = rc; a.remap = o.march_xcd; a.flip = o.march_flip; a.dbg = o.march_dbg;
   if (nl >= 7 && K > 3) return -1;  // 4 windows of 7 or 8 layers do not fit 256 VGPRs
   switch (nl) {
-    case 1: return march_dispatch<1>(st, a, K, chunk_rows);
-    case 2: return march_dispatch<2>(st, a, K, chunk_rows);
-    case 3: return march_dispatch<3>(st, a, K, chunk_rows);
-    case 4: return march_dispatch<4>(st, a, K, chunk_rows);
-    case 5: return march_dispatch<5>(st, a, K, chunk_rows);
-    case 6: return march_dispatch<6>(st, a, K, chunk_rows);
-    case 7: return march_dispatch<7>(st, a, K, chunk_rows);
-    case 8: return march_dispatch<8>(st, a, K, chunk_rows);
+    case 1: return march_dispatch<1>(st, a, K, chunk_rows, o.march_dma);
+    case 2: return march_dispatch<2>(st, a, K, chunk_rows, o.march_dma);
+    case 3: return march_dispatch<3>(st, a, K, chunk_rows, o.march_dma);
+    case 4: return march_dispatch<4>(st, a, K, chunk_rows, o.march_dma);
+    case 5: return march_dispatch<5>(st, a, K, chunk_rows, o.march_dma);
+    case 6: return march_dispatch<6>(st, a, K, chunk_rows, o.march_dma);
+    case 7: return march_dispatch<7>(st, a, K, chunk_rows, o.march_dma);
+    case 8: return march_dispatch<8>(st, a, K, chunk_rows, o.march_dma);
   }
   return -1;
 }
@@ -1286,9 +1288,6 @@ __global__ void __launch_bounds__(128 * PAIRS, 2) k_relax_visit(MarchArgs p) {
   else visit_role<NL, PAIRS, 1>(p, lds, wv >> 1);
 }
 
-int g_visit_rows = 0;   // chunk height of k_relax_visit (option march_visit_rows; 0: automatic)
-int g_visit_pairs = 2;  // wave pairs per workgroup of k_relax_visit (option march_visit_pairs: 1 or 2; 4096^2 x 6: 0.866 / 0.873 ms with 2, 0.881 / 0.883 with 1)
-
 // the visit's chunk grid: nc chunks of H rows from row vy0, ns strips of 48 own lanes from kx = vx0 (a multiple of pairs)
 struct VisitGeom { int H, vy0, nc, vx0, ns; };
 static bool visit_geom(const SplitGeom &sg, int rows, int pairs, VisitGeom &v) {
@@ -1314,24 +1313,25 @@ static void visit_dispatch(hipStream_t st, const MarchArgs &a, const VisitGeom &
 // PL + 4 half-sweeps (colour 0 first) and 4 + correction, the prolongation from `coarse`; da_alt receives the first pass's values
 // where the two passes run, da is not used.  The passes run on the chunks that are not the visit's: the second one (CORR) on
 // those with own cells outside the visit's rows / columns; it reads the first one's values up to ring_rows + K rows and 64 lanes
-// from its own cells, so the first one runs on all chunks with own cells that far from the visit's interior
-int launch_relax_visit(hipStream_t st, double *da, double *da_alt, const double *res, const SplitGeom &sg, int nl, const RelaxCoef &rc, int walls,
-                       const double *coarse, const SplitGeom &cg, const MarchCorrect &mc, int rows, int pairs, int ring_rows) {
+// from its own cells, so the first one runs on all chunks with own cells that far from the visit's interior (chunks of march_rows)
+int launch_relax_visit(hipStream_t st, const KernelOpts &o, double *da, double *da_alt, const double *res, const SplitGeom &sg, int nl, const RelaxCoef &rc,
+                       int walls, const double *coarse, const SplitGeom &cg, const MarchCorrect &mc) {
+  const int rows = o.march_visit_rows, pairs = o.march_visit_pairs;
   VisitGeom v;
   if (!relax_visit_fits(nl, sg, rows, pairs)) return -1;
   visit_geom(sg, rows, pairs, v);
   constexpr int K = 4;
-  const int Hc = ring_rows > 0 ? (ring_rows + 1) & ~1 : 14, my = Hc + K;
+  const int Hc = o.march_rows > 0 ? (o.march_rows + 1) & ~1 : 14, my = Hc + K;
   const int vy1 = v.vy0 + v.nc * v.H, vx1 = v.vx0 + v.ns * 48;
   const int skip_pl[4] = {v.vy0 + my, vy1 - my, v.vx0 + 64, vx1 - 64};
   const int skip_corr[4] = {v.vy0, vy1, v.vx0, vx1};
-  if (launch_relax_march(st, nullptr, da_alt, res, sg, nl, rc, 0, K, walls, Hc, nullptr, coarse, &cg, nullptr, 1, nullptr, 0, skip_pl)) return -1;
+  if (launch_relax_march(st, o, nullptr, da_alt, res, sg, nl, rc, 0, K, walls, Hc, nullptr, coarse, &cg, nullptr, 1, nullptr, 0, skip_pl)) return -1;
   MarchArgs a{};
   a.res = res; a.g = sg; a.c1 = 0; a.walls = walls; a.rc = rc;
   a.coarse = coarse; a.cg = cg;
   a.psi = mc.psi; a.psi_out = mc.psi_out; a.ng = mc.g;
   a.partial = 1; a.lean = 2;
-  a.remap = g_march_remap; a.flip = g_march_flip;
+  a.remap = o.march_xcd; a.flip = o.march_flip;
   a.H = v.H; a.vy0 = v.vy0; a.vx0 = v.vx0;
   switch (nl) {
     case 2: visit_dispatch<2>(st, a, v, pairs); break;
@@ -1340,5 +1340,5 @@ int launch_relax_visit(hipStream_t st, double *da, double *da_alt, const double 
     case 5: visit_dispatch<5>(st, a, v, pairs); break;
     case 6: visit_dispatch<6>(st, a, v, pairs); break;
   }
-  return launch_relax_march(st, da_alt, da, res, sg, nl, rc, 0, K, walls, Hc, nullptr, nullptr, nullptr, &mc, 0, nullptr, 0, skip_corr);
+  return launch_relax_march(st, o, da_alt, da, res, sg, nl, rc, 0, K, walls, Hc, nullptr, nullptr, nullptr, &mc, 0, nullptr, 0, skip_corr);
 }

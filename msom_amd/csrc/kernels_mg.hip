@@ -469,7 +469,6 @@ __global__ void __launch_bounds__(BX *BY, UNIFORM ? 4 : 3) k_correct_residual(Re
 // and 2 rows per chunk: the pass reads psi and q once.  Uniform S only; the expressions are those of k_correct_residual, so
 // both maxima are the same numbers.
 #define RM_OW 62
-int g_resmax_rows = 0;  // option resmax_rows: rows per chunk of k_resmax_march (0: 32), -1: the LDS-tiled kernel instead
 template <int NL>
 __global__ void __launch_bounds__(256) k_resmax_march(Res2Args p, int H) {
   __shared__ double smm[4];
@@ -594,15 +593,14 @@ int residual2_blocks(const NatGeom &g) {
   return gr.x * gr.y;
 }
 // mode bits: 1 = CORRECT, 2 = WRITE, 4 = RESTRICT
-void launch_residual2(hipStream_t st, int mode, const double *a, const double *da, double *a_out, const double *b, const double *S,
+void launch_residual2(hipStream_t st, const KernelOpts &o, int mode, const double *a, const double *da, double *a_out, const double *b, const double *S,
                       const NatGeom &g, double *res, const SplitGeom &sg, double *res_c, const SplitGeom &cg, int nl, const RelaxCoef &rc,
                       int uniformS, int walls, double *maxres, double *sum_partial, int want_sum, double *umax_partial, double *umax_out, int umax_clean,
                       double *res_c2, const SplitGeom *cg2) {
   Res2Args p;
   p.res_c2 = res_c2;
   if (cg2) p.cg2 = *cg2; else p.cg2 = cg;
-  extern int g_rhs_dbg;
-  p.dbg = g_rhs_dbg;
+  p.dbg = o.rhs_dbg;
   p.umax_partial = umax_partial;
   p.a = a; p.b = b; p.S = S; p.da = da; p.a_out = a_out; p.res = res; p.res_c = res_c; p.maxres = maxres; p.sum_partial = sum_partial;
   p.g = g; p.sg = sg; p.cg = cg; p.nl = nl; p.uniformS = uniformS; p.want_sum = want_sum; p.walls = walls; p.rc = rc;
@@ -622,8 +620,8 @@ void launch_residual2(hipStream_t st, int mode, const double *a, const double *d
     case 6: hipLaunchKernelGGL((k_residual2<false, true, true>), gr, block2d(), (size_t)nl * (BY * BX * 2 + 2 * BX) * sizeof(double), st, p); break;
     case 0: hipLaunchKernelGGL((k_residual2<false, false, false>), gr, block2d(), 0, st, p); break;
     case 8:  // max |res(a)| and max |u(a)| of an a that is already corrected
-      if (uniformS && g.nx >= 64 && g.ny >= 16 && g_resmax_rows >= 0 && nl <= MSOM_FASTNL) {
-        gr = launch_resmax_march(st, p, g_resmax_rows ? g_resmax_rows : 32);
+      if (uniformS && g.nx >= 64 && g.ny >= 16 && o.resmax_rows >= 0 && nl <= MSOM_FASTNL) {   // option resmax_rows
+        gr = launch_resmax_march(st, p, o.resmax_rows ? o.resmax_rows : 32);
       } else if (g.nx % 2 == 0 && g.nx >= CR_TW && g.ny >= CR_TR && !(p.dbg & 128)) {
         gr = dim3((g.nx + CR_TW - 1) / CR_TW, (g.ny + CR_TR - 1) / CR_TR);
         if (uniformS) hipLaunchKernelGGL((k_correct_residual<true, false>), gr, block2d(), 0, st, p);
@@ -1644,15 +1642,14 @@ __global__ void __launch_bounds__(BX *BY) k_relax_red_prolong(RelaxPArgs p) {
   else relax_red_prolong_body<NL, UNIFORM, 1>(p);
 }
 template <int NL>
-static void relax_red_prolong_dispatch(hipStream_t st, const RelaxPArgs &p, int uniformS) {
+static void relax_red_prolong_dispatch(hipStream_t st, const RelaxPArgs &p, int uniformS, int dbg) {   // dbg: option rhs_dbg
   dim3 gr = grid2d(p.g.hk, (p.g.ny + 1) / 2);
-  extern int g_rhs_dbg;
-  if (!(g_rhs_dbg & 256) && p.g.hk >= 128 && !(g_rhs_dbg & 512)) {  // wide levels: coarse windows through LDS
+  if (!(dbg & 256) && p.g.hk >= 128 && !(dbg & 512)) {  // wide levels: coarse windows through LDS
     if (uniformS) hipLaunchKernelGGL((k_relax_red_prolong3<NL, true>), gr, block2d(), 0, st, p);
     else hipLaunchKernelGGL((k_relax_red_prolong3<NL, false>), gr, block2d(), 0, st, p);
     return;
   }
-  if (!(g_rhs_dbg & 256)) {  // both row parities per thread
+  if (!(dbg & 256)) {  // both row parities per thread
     if (uniformS) hipLaunchKernelGGL((k_relax_red_prolong2<NL, true>), gr, block2d(), 0, st, p);
     else hipLaunchKernelGGL((k_relax_red_prolong2<NL, false>), gr, block2d(), 0, st, p);
     return;
@@ -1661,19 +1658,19 @@ static void relax_red_prolong_dispatch(hipStream_t st, const RelaxPArgs &p, int 
   if (uniformS) hipLaunchKernelGGL((k_relax_red_prolong<NL, true>), gr, block2d(), 0, st, p);
   else hipLaunchKernelGGL((k_relax_red_prolong<NL, false>), gr, block2d(), 0, st, p);
 }
-void launch_relax_red_prolong(hipStream_t st, double *da, const double *coarse, const SplitGeom &cg, const double *res, const double *S,
+void launch_relax_red_prolong(hipStream_t st, const KernelOpts &o, double *da, const double *coarse, const SplitGeom &cg, const double *res, const double *S,
                               const SplitGeom &sg, int nl, const RelaxCoef &rc, int uniformS, int walls) {
   RelaxPArgs p;
   p.da = da; p.res = res; p.S = S; p.coarse = coarse; p.g = sg; p.cg = cg; p.walls = walls; p.rc = rc;
   switch (nl) {
-    case 1: relax_red_prolong_dispatch<1>(st, p, uniformS); break;
-    case 2: relax_red_prolong_dispatch<2>(st, p, uniformS); break;
-    case 3: relax_red_prolong_dispatch<3>(st, p, uniformS); break;
-    case 4: relax_red_prolong_dispatch<4>(st, p, uniformS); break;
-    case 5: relax_red_prolong_dispatch<5>(st, p, uniformS); break;
-    case 6: relax_red_prolong_dispatch<6>(st, p, uniformS); break;
-    case 7: relax_red_prolong_dispatch<7>(st, p, uniformS); break;
-    case 8: relax_red_prolong_dispatch<8>(st, p, uniformS); break;
+    case 1: relax_red_prolong_dispatch<1>(st, p, uniformS, o.rhs_dbg); break;
+    case 2: relax_red_prolong_dispatch<2>(st, p, uniformS, o.rhs_dbg); break;
+    case 3: relax_red_prolong_dispatch<3>(st, p, uniformS, o.rhs_dbg); break;
+    case 4: relax_red_prolong_dispatch<4>(st, p, uniformS, o.rhs_dbg); break;
+    case 5: relax_red_prolong_dispatch<5>(st, p, uniformS, o.rhs_dbg); break;
+    case 6: relax_red_prolong_dispatch<6>(st, p, uniformS, o.rhs_dbg); break;
+    case 7: relax_red_prolong_dispatch<7>(st, p, uniformS, o.rhs_dbg); break;
+    case 8: relax_red_prolong_dispatch<8>(st, p, uniformS, o.rhs_dbg); break;
     default: break;
   }
 }
@@ -1952,7 +1949,6 @@ __global__ void __launch_bounds__(BNT) k_relax_block(BlockArgs p) {
   }
 }
 
-int g_block_variant = 0;  // tuning knob (tools/bench_kernels.py)
 template <int NL, int BTY, int BNT>
 static void block_launch(hipStream_t st, const BlockArgs &p, int prolong, int fine) {
   dim3 gr((p.g.nx + BTX - 1) / BTX, (p.g.ny + BTY - 1) / BTY);
@@ -1965,10 +1961,10 @@ static void block_launch(hipStream_t st, const BlockArgs &p, int prolong, int fi
   }
 }
 template <int NL>
-static void block_dispatch(hipStream_t st, const BlockArgs &p, int prolong, int fine) {
+static void block_dispatch(hipStream_t st, const BlockArgs &p, int prolong, int fine, int variant) {   // variant: option block_variant
   // LDS: NL * (BTY + 8) * 72 * 8 B; two workgroups per CU need <= 80 KiB each
   if (NL == 6) {
-    switch (g_block_variant) {
+    switch (variant) {
       case 1: block_launch<NL, 8, 256>(st, p, prolong, fine); return;
       case 2: block_launch<NL, 8, 512>(st, p, prolong, fine); return;
       case 3: block_launch<NL, 16, 1024>(st, p, prolong, fine); return;
@@ -1980,21 +1976,21 @@ static void block_dispatch(hipStream_t st, const BlockArgs &p, int prolong, int 
   block_launch<NL, BTY, 512>(st, p, prolong, fine);
 }
 // two full sweeps: da_out = RB^2(da_in or prolong(coarse)); uniform-S constant-coefficient path
-void launch_relax_block2(hipStream_t st, const double *da_in, const double *coarse, const SplitGeom &cg, const double *res, double *da_out,
+void launch_relax_block2(hipStream_t st, const KernelOpts &o, const double *da_in, const double *coarse, const SplitGeom &cg, const double *res, double *da_out,
                          const SplitGeom &sg, int nl, const RelaxCoef &rc, int walls, int fine) {
   BlockArgs p;
   p.da_in = da_in; p.res = res; p.coarse = coarse; p.da_out = da_out; p.g = sg; p.cg = cg; p.walls = walls; p.rc = rc;
   p.nh = 4; p.c0 = 0; p.S = nullptr;
   const int prolong = coarse != nullptr;
   switch (nl) {
-    case 1: block_dispatch<1>(st, p, prolong, fine); break;
-    case 2: block_dispatch<2>(st, p, prolong, fine); break;
-    case 3: block_dispatch<3>(st, p, prolong, fine); break;
-    case 4: block_dispatch<4>(st, p, prolong, fine); break;
-    case 5: block_dispatch<5>(st, p, prolong, fine); break;
-    case 6: block_dispatch<6>(st, p, prolong, fine); break;
-    case 7: block_dispatch<7>(st, p, prolong, fine); break;
-    case 8: block_dispatch<8>(st, p, prolong, fine); break;
+    case 1: block_dispatch<1>(st, p, prolong, fine, o.block_variant); break;
+    case 2: block_dispatch<2>(st, p, prolong, fine, o.block_variant); break;
+    case 3: block_dispatch<3>(st, p, prolong, fine, o.block_variant); break;
+    case 4: block_dispatch<4>(st, p, prolong, fine, o.block_variant); break;
+    case 5: block_dispatch<5>(st, p, prolong, fine, o.block_variant); break;
+    case 6: block_dispatch<6>(st, p, prolong, fine, o.block_variant); break;
+    case 7: block_dispatch<7>(st, p, prolong, fine, o.block_variant); break;
+    case 8: block_dispatch<8>(st, p, prolong, fine, o.block_variant); break;
     default: break;
   }
 }
@@ -2012,7 +2008,7 @@ static void block8_launch_t(hipStream_t st, const BlockArgs &p, int prolong) {
 // take 32 x 16.  Measured at nl = 6 / nl = 3 (block_variant 6 = 64 x 16 everywhere, 3 = 16 x 16 everywhere): 4096^2 x 6 6.55 / 6.46 /
 // 6.39 ms per step with 64 x 16 / 16 x 16 / this rule, 512^2 x 3 0.447 / 0.400 / 0.388; 64 x 16 on the 1024^2 level only: 6.49 vs 6.43
 template <int NL>
-static void block8_launch(hipStream_t st, const BlockArgs &p, int prolong) {
+static void block8_launch(hipStream_t st, const BlockArgs &p, int prolong, int variant) {   // variant: option block_variant
   if (p.S) {   // general S field: the default tile shapes only
     if constexpr (NL > 1) {
       if (p.g.nx <= 256) block8_launch_t<NL, 16, 16, 512, true>(st, p, prolong);
@@ -2020,7 +2016,7 @@ static void block8_launch(hipStream_t st, const BlockArgs &p, int prolong) {
     }
     return;
   }
-  switch (g_block_variant) {
+  switch (variant) {
     case 1: block8_launch_t<NL, 32, 16, 768>(st, p, prolong); return;
     case 2: block8_launch_t<NL, 32, 8, 576>(st, p, prolong); return;
     case 3: block8_launch_t<NL, 16, 16, 512>(st, p, prolong); return;
@@ -2032,7 +2028,7 @@ static void block8_launch(hipStream_t st, const BlockArgs &p, int prolong) {
   if (p.g.nx <= 256) block8_launch_t<NL, 16, 16, 512>(st, p, prolong);
   else block8_launch_t<NL, 32, 16, 768>(st, p, prolong);
 }
-int launch_relax_block8(hipStream_t st, const double *da_in, const double *coarse, const SplitGeom &cg, const double *res, double *da_out,
+int launch_relax_block8(hipStream_t st, const KernelOpts &o, const double *da_in, const double *coarse, const SplitGeom &cg, const double *res, double *da_out,
                         const SplitGeom &sg, int nl, const RelaxCoef &rc, int walls, int nh, int c0, const double *S) {
   if (nh < 1 || nh > 8 || nl > MSOM_FASTNL) return -1;
   BlockArgs p;
@@ -2041,14 +2037,14 @@ int launch_relax_block8(hipStream_t st, const double *da_in, const double *coars
   p.nh = nh; p.c0 = c0;
   const int prolong = coarse != nullptr;
   switch (nl) {
-    case 1: block8_launch<1>(st, p, prolong); break;
-    case 2: block8_launch<2>(st, p, prolong); break;
-    case 3: block8_launch<3>(st, p, prolong); break;
-    case 4: block8_launch<4>(st, p, prolong); break;
-    case 5: block8_launch<5>(st, p, prolong); break;
-    case 6: block8_launch<6>(st, p, prolong); break;
-    case 7: block8_launch<7>(st, p, prolong); break;
-    case 8: block8_launch<8>(st, p, prolong); break;
+    case 1: block8_launch<1>(st, p, prolong, o.block_variant); break;
+    case 2: block8_launch<2>(st, p, prolong, o.block_variant); break;
+    case 3: block8_launch<3>(st, p, prolong, o.block_variant); break;
+    case 4: block8_launch<4>(st, p, prolong, o.block_variant); break;
+    case 5: block8_launch<5>(st, p, prolong, o.block_variant); break;
+    case 6: block8_launch<6>(st, p, prolong, o.block_variant); break;
+    case 7: block8_launch<7>(st, p, prolong, o.block_variant); break;
+    case 8: block8_launch<8>(st, p, prolong, o.block_variant); break;
     default: return -1;
   }
   return 0;

@@ -709,19 +709,17 @@ __global__ void __launch_bounds__(64) k_n_relax_march(NRelaxArgs p, const double
     }
   }
 }
-int g_node_march_rows = 0;  // tuning knob (option node_march_rows)
 template <int NL>
-static int n_relax_march_dispatch(hipStream_t st, const NRelaxArgs &p, const double *a_in, int K) {
+static int n_relax_march_dispatch(hipStream_t st, const NRelaxArgs &p, const double *a_in, int K, int rows) {
   const int n1 = p.g.nx;
   // chunk height: about 2 rounds of the resident wavefronts, never below 16 rows (2 K of them are re-computed)
   auto launch = [&](auto kern, int ow) {
     const int strips = (n1 + ow - 1) / ow;
-    extern int g_node_march_rows;
     int chunks = 2 * 256 * 8 / strips;
     if (chunks < 1) chunks = 1;
     int H = (n1 + chunks - 1) / chunks;
     if (H < 16) H = 16;
-    if (g_node_march_rows > 0) H = g_node_march_rows;
+    if (rows > 0) H = rows;
     hipLaunchKernelGGL(kern, dim3(strips, (n1 + H - 1) / H), dim3(64), 0, st, p, a_in, H);
   };
   switch (K) {
@@ -847,9 +845,8 @@ __global__ void __launch_bounds__(64) k_n_relax_march_s(NRelaxArgs p, const doub
   }
 }
 template <int NL>
-static int n_relax_march_s_dispatch(hipStream_t st, const NRelaxArgs &p, const double *a_in, int K, int partial) {
-  extern int g_node_march_rows;
-  const int n = p.g.nx - 1, H = g_node_march_rows > 0 ? g_node_march_rows : 12;
+static int n_relax_march_s_dispatch(hipStream_t st, const NRelaxArgs &p, const double *a_in, int K, int partial, int rows) {
+  const int n = p.g.nx - 1, H = rows > 0 ? rows : 12;
   auto launch = [&](auto kern, int ow) { hipLaunchKernelGGL(kern, dim3(((n >> 1) + 1 + ow - 1) / ow, (n + 1 + H - 1) / H), dim3(64), 0, st, p, a_in, H, partial); };
   switch (K) {
     case 2: launch(k_n_relax_march_s<NL, 2>, 62); return 0;
@@ -858,37 +855,38 @@ static int n_relax_march_s_dispatch(hipStream_t st, const NRelaxArgs &p, const d
   }
   return -1;
 }
-// K (2..4) half-sweeps of a split level starting with colour `color`, a_in -> a_out (both in the split layout g); S2 by row tables
+// K (2..4) half-sweeps of a split level starting with colour `color`, a_in -> a_out (both in the split layout g); S2 by row tables;
+// chunks of `rows` rows (0: 12)
 int launch_n_relax_march_s(hipStream_t st, const double *a_in, double *a_out, const double *b, const double *mk, const NatGeom &g, int nl, int color, int K,
-                           double D, double iRd2, const LayerCoef &lc, const double *S2row, int partial) {
+                           double D, double iRd2, const LayerCoef &lc, const double *S2row, int partial, int rows) {
   NRelaxArgs p;
   p.a = a_out; p.b = b; p.mk = mk; p.S2 = nullptr; p.g = g; p.color = color; p.sqD = D * D; p.iRd2 = iRd2; p.lc = lc; p.S2row = S2row;
   if (nl > 1 && !S2row) return -1;
   switch (nl) {
-    case 1: return n_relax_march_s_dispatch<1>(st, p, a_in, K, partial);
-    case 2: return n_relax_march_s_dispatch<2>(st, p, a_in, K, partial);
-    case 3: return n_relax_march_s_dispatch<3>(st, p, a_in, K, partial);
-    case 4: return n_relax_march_s_dispatch<4>(st, p, a_in, K, partial);
-    case 5: return n_relax_march_s_dispatch<5>(st, p, a_in, K, partial);
-    case 6: return n_relax_march_s_dispatch<6>(st, p, a_in, K, partial);
+    case 1: return n_relax_march_s_dispatch<1>(st, p, a_in, K, partial, rows);
+    case 2: return n_relax_march_s_dispatch<2>(st, p, a_in, K, partial, rows);
+    case 3: return n_relax_march_s_dispatch<3>(st, p, a_in, K, partial, rows);
+    case 4: return n_relax_march_s_dispatch<4>(st, p, a_in, K, partial, rows);
+    case 5: return n_relax_march_s_dispatch<5>(st, p, a_in, K, partial, rows);
+    case 6: return n_relax_march_s_dispatch<6>(st, p, a_in, K, partial, rows);
   }
   return -1;
 }
 
-// K (2..4) half-sweeps starting with colour `color`, a_in -> a_out; returns -1 if K is not supported
+// K (2..4) half-sweeps starting with colour `color`, a_in -> a_out, chunks of `rows` rows (0: automatic); returns -1 if K is not supported
 int launch_n_relax_march(hipStream_t st, const double *a_in, double *a_out, const double *b, const double *mk, const double *S2, const NatGeom &g, int nl,
-                         int color, int K, double D, double iRd2, const LayerCoef &lc) {
+                         int color, int K, double D, double iRd2, const LayerCoef &lc, int rows) {
   NRelaxArgs p;
   p.a = a_out; p.b = b; p.mk = mk; p.S2 = S2; p.g = g; p.color = color; p.sqD = D * D; p.iRd2 = iRd2; p.lc = lc;
   switch (nl) {
-    case 1: return n_relax_march_dispatch<1>(st, p, a_in, K);
-    case 2: return n_relax_march_dispatch<2>(st, p, a_in, K);
-    case 3: return n_relax_march_dispatch<3>(st, p, a_in, K);
-    case 4: return n_relax_march_dispatch<4>(st, p, a_in, K);
-    case 5: return n_relax_march_dispatch<5>(st, p, a_in, K);
-    case 6: return n_relax_march_dispatch<6>(st, p, a_in, K);
-    case 7: return n_relax_march_dispatch<7>(st, p, a_in, K);
-    case 8: return n_relax_march_dispatch<8>(st, p, a_in, K);
+    case 1: return n_relax_march_dispatch<1>(st, p, a_in, K, rows);
+    case 2: return n_relax_march_dispatch<2>(st, p, a_in, K, rows);
+    case 3: return n_relax_march_dispatch<3>(st, p, a_in, K, rows);
+    case 4: return n_relax_march_dispatch<4>(st, p, a_in, K, rows);
+    case 5: return n_relax_march_dispatch<5>(st, p, a_in, K, rows);
+    case 6: return n_relax_march_dispatch<6>(st, p, a_in, K, rows);
+    case 7: return n_relax_march_dispatch<7>(st, p, a_in, K, rows);
+    case 8: return n_relax_march_dispatch<8>(st, p, a_in, K, rows);
   }
   return -1;
 }

@@ -39,8 +39,6 @@
 enum { SC_BSUM = 2, SC_KE = 3, SC_SCRATCH = 4, SC_RES0 = 6, SC_RES1 = 7, SC_UMAX = 8 /* MAXNL */, SC_RESF = 8 + MSOM_MAXNL /* max|res| from the fused tendency pass */, SC_LSUM = 32 /* MAXNL */, SC_SPEC = 48 /* k_step_dt: dt limit, dt, tnext, dt / 2 */, SC_COUNT = 64 };
 static_assert(SC_RESF < SC_LSUM && SC_LSUM + MSOM_MAXNL <= SC_SPEC && SC_SPEC + 4 <= SC_COUNT, "scalar slots overlap");
 
-static int g_dbg_interleave = 0;  // timing experiment of msom_bench_kernel (march passes)
-static int g_march_rows = 0;  // tuning knob: chunk height of k_relax_march (0 = automatic)
 #define MARCH_HALO 4    // rows (= cells in x) of neighbour data a pass of up to 4 chained half-sweeps reads
 struct ProfSlot {
   std::vector<hipEvent_t> ev;  // pairs (start, stop)
@@ -61,6 +59,7 @@ struct msom {
   int sticky = MSOM_OK;  // first error of a void helper (exchange inside fill_bc / mg_cycle)
   int comm_hold = 0;     // see comm_begin
   int dbg_nosync = 0;    // option dbg_nosync (timing experiment)
+  KernelOpts opt;        // options that pick kernel variants and launch shapes (kernels.h)
   // Speculative tendency pass (round 3, one tile): right after the first multigrid cycle of a solve the tendency kernel is queued
   // BEFORE the host has read max|res| and max|u| -- with dt computed on the device (k_step_dt) in the first RK stage -- so the
   // GPU works through the host round trip instead of idling (0.49 -> 0.43 ms per step at 256^2 x 3 with the read skipped
@@ -688,6 +687,17 @@ static int build_coefs(msom *m);
 static void free_agglomeration(msom *m);
 
 static void clear_graphs(msom *m);
+// the field of KernelOpts under an option key (its name; null: not one of them)
+static int *kernel_opt(KernelOpts &o, const char *key) {
+#define KOPT(f) {#f, &KernelOpts::f}
+  static const struct { const char *key; int KernelOpts::*f; } keys[] = {
+      KOPT(march_rows), KOPT(march_xcd), KOPT(march_flip), KOPT(march_dbg), KOPT(march_lean), KOPT(march_dma),
+      KOPT(march_visit_rows), KOPT(march_visit_pairs), KOPT(resmax_rows), KOPT(block_variant), KOPT(rhs_dbg), KOPT(lpw_dbg)};
+#undef KOPT
+  for (const auto &k : keys)
+    if (!strcmp(key, k.key)) return &(o.*k.f);
+  return nullptr;
+}
 extern "C" int msom_set_option(msom_t *m, const char *key, double v) {
   if (!m || !key) return MSOM_ERR_ARG;
   clear_graphs(m);   // captured cycles hold kernel arguments by value: any option may change them
@@ -706,7 +716,6 @@ extern "C" int msom_set_option(msom_t *m, const char *key, double v) {
   else if (!strcmp(key, "fused")) m->fused = (int)v;
   else if (!strcmp(key, "mg_fused")) m->mg_fused = (int)v;
   else if (!strcmp(key, "march")) m->march = (int)v;
-  else if (!strcmp(key, "march_rows")) g_march_rows = (int)v;
   else if (!strcmp(key, "march_min")) m->march_min = (int)v;
   else if (!strcmp(key, "march_min_tiled")) m->march_min_tiled = (int)v;
   else if (!strcmp(key, "march_partial")) m->march_partial = (int)v;
@@ -714,17 +723,9 @@ extern "C" int msom_set_option(msom_t *m, const char *key, double v) {
   else if (!strcmp(key, "march_correct")) m->march_correct = (int)v;
   else if (!strcmp(key, "march_visit")) m->march_visit = (int)v;
   else if (!strcmp(key, "march_visit_min")) m->march_visit_min = (int)v;
-  else if (!strcmp(key, "march_visit_rows")) { extern int g_visit_rows; g_visit_rows = (int)v; }
-  else if (!strcmp(key, "march_visit_pairs")) { extern int g_visit_pairs; g_visit_pairs = (int)v; }
-  else if (!strcmp(key, "march_xcd")) { extern int g_march_remap; g_march_remap = (int)v; }
-  else if (!strcmp(key, "march_flip")) { extern int g_march_flip; g_march_flip = (int)v; }
-  else if (!strcmp(key, "march_dma")) { extern int g_march_dma; g_march_dma = (int)v; }
-  else if (!strcmp(key, "march_dbg")) { extern int g_march_dbg; g_march_dbg = (int)v; }
-  else if (!strcmp(key, "dbg_interleave")) g_dbg_interleave = (int)v;
   else if (!strcmp(key, "dbg_nosync")) m->dbg_nosync = (int)v;
   else if (!strcmp(key, "async_solve")) m->async_solve = (int)v;
   else if (!strcmp(key, "step_sync")) m->step_sync = (int)v;
-  else if (!strcmp(key, "march_lean")) { extern int g_march_lean; g_march_lean = (int)v; }
   else if (!strcmp(key, "march_k")) m->march_k = (int)v < 2 ? 2 : ((int)v > 4 ? 4 : (int)v);
   else if (!strcmp(key, "block_small")) m->block_small = (int)v;
   else if (!strcmp(key, "block8")) m->block8 = (int)v;
@@ -739,10 +740,7 @@ extern "C" int msom_set_option(msom_t *m, const char *key, double v) {
   else if (!strcmp(key, "mg_coarse")) { m->mgc_opt = (int)v; if (m->const_set) return build_coefs(m); }
   else if (!strcmp(key, "mgc_pfused")) { m->mgc_pfused = (int)v; if (m->const_set) return build_coefs(m); }
   else if (!strcmp(key, "mg_coarse_dim")) { m->mgc_dim = (int)v; if (m->const_set) return build_coefs(m); }
-  else if (!strcmp(key, "block_variant")) { extern int g_block_variant; g_block_variant = (int)v; }
-  else if (!strcmp(key, "lpw_dbg")) { extern int g_lpw_dbg; g_lpw_dbg = (int)v; }
-  else if (!strcmp(key, "rhs_dbg")) { extern int g_rhs_dbg; g_rhs_dbg = (int)v; }
-  else if (!strcmp(key, "resmax_rows")) { extern int g_resmax_rows; g_resmax_rows = (int)v; }
+  else if (int *o = kernel_opt(m->opt, key)) *o = (int)v;
   else if (!strcmp(key, "rhs_variant")) m->rhs_variant = (int)v;
   else if (!strcmp(key, "adv_fused")) m->adv_fused = (int)v;
   else if (!strcmp(key, "overlap")) m->overlap = (int)v;
@@ -797,8 +795,8 @@ extern "C" double msom_get_param(msom_t *m, const char *key) {
   if (!strcmp(key, "agg_level")) return m->agg_level;
   if (!strcmp(key, "overlap")) return m->overlap;
   // which kernels the dispatch picks for this handle (bench.py names what ran from these, not from a table)
-  if (!strcmp(key, "resmax_marching")) { extern int g_resmax_rows; return m->uniformS && m->nl <= MSOM_FASTNL && m->g.nx >= 64 && m->g.ny >= 16 && g_resmax_rows >= 0; }
-  if (!strcmp(key, "march_lean")) { extern int g_march_lean; return g_march_lean; }
+  if (!strcmp(key, "resmax_marching")) return m->uniformS && m->nl <= MSOM_FASTNL && m->g.nx >= 64 && m->g.ny >= 16 && m->opt.resmax_rows >= 0;
+  if (const int *o = kernel_opt(m->opt, key)) return *o;   // the handle's kernel options (march_rows, march_lean, ... rhs_dbg)
   if (!strcmp(key, "restrict2")) return restrict2_ok(m);   // the pre-cycle residual pass restricts two levels down
   if (!strcmp(key, "mg_coarse_lean")) return m->mgc_first >= 0 && m->mgc_lean;   // the coarse group runs in k_mg_coarse_lean
   if (!strcmp(key, "march_levels")) return march_levels(m);   // tile levels whose half-sweeps are chained (kernels_march.hip)
@@ -1192,19 +1190,17 @@ static int march_levels(msom *m) {
 // is the finest level marched, with its interior chunks in the lean body (option march_lean, byte offsets within reach:
 // march_lean_fits, as launch_relax_march decides it for the passes of the level)?
 static bool march_lean_fine(msom *m) {
-  extern int g_march_lean;
-  return m->nlev > 0 && g_march_lean && march_ok(m, tile_lev(m, 0)) && march_lean_fits(m->nl, m->sg[0], &m->g);
+  return m->nlev > 0 && m->opt.march_lean && march_ok(m, tile_lev(m, 0)) && march_lean_fits(m->nl, m->sg[0], &m->g);
 }
 // does the finest level's visit take k_relax_visit when it relaxes 4 + 4 half-sweeps with the prolongation and the correction?
 // One tile with walls, uniform S, nl = 2..6, the lean body, a level wide enough for one of its chunks and (march_visit = 1)
 // big enough to gain
 static bool march_visit_fine(msom *m) {
-  extern int g_march_dma, g_visit_rows, g_visit_pairs;
-  if (!m->march_visit || m->nlev < 2 || !g_march_dma || !m->uniformS || m->nl < 2) return false;
+  if (!m->march_visit || m->nlev < 2 || !m->opt.march_dma || !m->uniformS || m->nl < 2) return false;
   const Lev L = tile_lev(m, 0);
   if (m->march_visit < 2 && (size_t)L.sg->nx * L.sg->ny * m->nl < ((size_t)1 << m->march_visit_min)) return false;
   return !L.tiled && L.walls == WALL_ALL && march_kmax(m) == 4 && m->march_prolong && m->march_partial && m->march_correct && m->mg_fused &&
-         march_lean_fine(m) && relax_visit_fits(m->nl, m->sg[0], g_visit_rows, g_visit_pairs);
+         march_lean_fine(m) && relax_visit_fits(m->nl, m->sg[0], m->opt.march_visit_rows, m->opt.march_visit_pairs);
 }
 // is the prolongation coarse -> L folded into the first smoothing pass of L?
 static bool fuse_prolong(msom *m, const Lev &L, int nrelax) {
@@ -1273,10 +1269,9 @@ static void relax_sweeps(msom *m, Lev &L, const Lev *coarse, int nrelax, int cor
     if (coarse && n >= 3 && kmax >= 3 && (!deep || pl_tiled) && m->march_prolong) {
       // the finest level's whole visit: one fused launch on the interior chunks, the two passes around it
       if (n == 8 && L.fine && m->corr_req && march_visit_fine(m)) {
-        extern int g_visit_rows, g_visit_pairs;
         MarchCorrect mc{m->f[MSOM_PSI], m->psi_alt, m->g};
         if (prof) prof_begin(m, m->prof_march_visit);
-        if (launch_relax_visit(m->st, *L.da, *L.da_alt, L.res, *L.sg, nl, *L.rc, kwalls, *coarse->da, *coarse->sg, mc, g_visit_rows, g_visit_pairs, g_march_rows))
+        if (launch_relax_visit(m->st, m->opt, *L.da, *L.da_alt, L.res, *L.sg, nl, *L.rc, kwalls, *coarse->da, *coarse->sg, mc))
           m->sticky = MSOM_ERR_ARG;
         if (prof) prof_end(m, m->prof_march_visit);
         m->corr_done = 1;
@@ -1300,7 +1295,7 @@ static void relax_sweeps(msom *m, Lev &L, const Lev *coarse, int nrelax, int cor
         ch.in_s = has_nb(DIR_S) ? m->mh_da_s[ck] : nullptr; ch.in_n = has_nb(DIR_N) ? m->mh_da_n[ck] : nullptr;
       }
       auto pl_pass = [&](int region) {
-        if (launch_relax_march(m->st, nullptr, *L.da_alt, L.res, *L.sg, nl, *L.rc, 0, K, kwalls, g_march_rows, deep ? &mh : nullptr, *coarse->da, coarse->sg, nullptr,
+        if (launch_relax_march(m->st, m->opt, nullptr, *L.da_alt, L.res, *L.sg, nl, *L.rc, 0, K, kwalls, m->opt.march_rows, deep ? &mh : nullptr, *coarse->da, coarse->sg, nullptr,
                                m->march_partial && n - K >= 1, deep ? &ch : nullptr, region))
           m->sticky = MSOM_ERR_ARG;
       };
@@ -1324,7 +1319,7 @@ static void relax_sweeps(msom *m, Lev &L, const Lev *coarse, int nrelax, int cor
       n -= K; c = K & 1;
     } else if (coarse && n > 0) {
       if (prof) prof_begin(m, m->prof_redprol);
-      launch_relax_red_prolong(m->st, *L.da, *coarse->da, *coarse->sg, L.res, L.S, *L.sg, nl, *L.rc, m->uniformS, L.walls);
+      launch_relax_red_prolong(m->st, m->opt, *L.da, *coarse->da, *coarse->sg, L.res, L.S, *L.sg, nl, *L.rc, m->uniformS, L.walls);
       if (prof) prof_end(m, m->prof_redprol);
       n--; c = 1;
     }
@@ -1335,7 +1330,7 @@ static void relax_sweeps(msom *m, Lev &L, const Lev *coarse, int nrelax, int cor
       const bool corr = m->corr_req && L.fine && n == K;
       MarchCorrect mc{m->f[MSOM_PSI], m->psi_alt, m->g};
       auto pass = [&](int region) {
-        if (launch_relax_march(m->st, *L.da, *L.da_alt, L.res, *L.sg, nl, *L.rc, c, K, kwalls, g_march_rows, deep ? &mh : nullptr, nullptr, nullptr,
+        if (launch_relax_march(m->st, m->opt, *L.da, *L.da_alt, L.res, *L.sg, nl, *L.rc, c, K, kwalls, m->opt.march_rows, deep ? &mh : nullptr, nullptr, nullptr,
                                corr ? &mc : nullptr, m->march_partial && n - K >= 1, nullptr, region))
           m->sticky = MSOM_ERR_ARG;
       };
@@ -1375,7 +1370,7 @@ static void relax_sweeps(msom *m, Lev &L, const Lev *coarse, int nrelax, int cor
     while (n > 0) {
       const int K = n < 8 ? n : 8;
       if (K == 1) { launch_relax_color(m->st, *L.da, L.res, L.S, *L.sg, nl, *L.rc, m->uniformS, c, L.walls, L.fine); break; }
-      if (launch_relax_block8(m->st, *L.da, src ? *src->da : nullptr, src ? *src->sg : *L.sg, L.res, *L.da_alt, *L.sg, nl, *L.rc, L.walls, K, c, m->uniformS ? nullptr : L.S)) m->sticky = MSOM_ERR_ARG;
+      if (launch_relax_block8(m->st, m->opt, *L.da, src ? *src->da : nullptr, src ? *src->sg : *L.sg, L.res, *L.da_alt, *L.sg, nl, *L.rc, L.walls, K, c, m->uniformS ? nullptr : L.S)) m->sticky = MSOM_ERR_ARG;
       std::swap(*L.da, *L.da_alt);
       src = nullptr; n -= K; c = (c + K) & 1;
       // periodic: the pass stored no ghost cell; boundary_level(da, l) = the wrapped copies, corners included (a following colour
@@ -1388,7 +1383,7 @@ static void relax_sweeps(msom *m, Lev &L, const Lev *coarse, int nrelax, int cor
     for (; it + 2 <= nrelax; it += 2) {
       const bool pl = coarse && it == 0;
       if (prof && !pl) prof_begin(m, m->prof_block);
-      launch_relax_block2(m->st, *L.da, pl ? *coarse->da : nullptr, pl ? *coarse->sg : *L.sg, L.res, *L.da_alt, *L.sg, nl, *L.rc, L.walls, L.fine);
+      launch_relax_block2(m->st, m->opt, *L.da, pl ? *coarse->da : nullptr, pl ? *coarse->sg : *L.sg, L.res, *L.da_alt, *L.sg, nl, *L.rc, L.walls, L.fine);
       if (prof && !pl) prof_end(m, m->prof_block);
       std::swap(*L.da, *L.da_alt);
     }
@@ -1410,7 +1405,7 @@ static void relax_sweeps(msom *m, Lev &L, const Lev *coarse, int nrelax, int cor
       }
       if (pl && c == 0) {
         if (prof) prof_begin(m, m->prof_redprol);
-        launch_relax_red_prolong(m->st, *L.da, *coarse->da, *coarse->sg, L.res, L.S, *L.sg, nl, *L.rc, m->uniformS, L.walls);
+        launch_relax_red_prolong(m->st, m->opt, *L.da, *coarse->da, *coarse->sg, L.res, L.S, *L.sg, nl, *L.rc, m->uniformS, L.walls);
         if (prof) prof_end(m, m->prof_redprol);
       } else
         launch_relax_color(m->st, *L.da, L.res, L.S, *L.sg, nl, *L.rc, m->uniformS, c, L.walls, L.fine);
@@ -1547,7 +1542,7 @@ static void residual2(msom *m, int mode, const double *b, int slot, int want_sum
   ProfSlot &which = (mode & 8) ? m->prof_resmax : (mode & 1) ? m->prof_rescorr : m->prof_respre;
   if (m->profile) { prof_begin(m, m->prof_resid); prof_begin(m, which); }
   const bool r2 = (mode & 4) && restrict2_ok(m);
-  launch_residual2(m->st, mode, m->f[MSOM_PSI], m->da[0], m->psi_alt, b, m->f[MSOM_S], m->g, m->res[0], m->sg[0],
+  launch_residual2(m->st, m->opt, mode, m->f[MSOM_PSI], m->da[0], m->psi_alt, b, m->f[MSOM_S], m->g, m->res[0], m->sg[0],
                    m->nlev > 1 ? m->res[1] : nullptr, m->sg[m->nlev > 1 ? 1 : 0], m->nl, m->rc[0], m->uniformS, m->walls, m->d_scal + slot,
                    m->partial, want_sum, m->partial_umax, m->d_scal + SC_UMAX, m->umax_clean, r2 ? m->res[2] : nullptr, r2 ? &m->sg[2] : nullptr);
   if (mode & (1 | 8)) m->umax_clean = 0;
@@ -1767,7 +1762,6 @@ static int rhs_terms(msom *m, int qfield, int dqfield, int with_qforcing, double
     };
     // one pass over psi: zeta, Jacobians, beta, dissipation, drag, forcing, max|u| (kernels_fused.hip)
     if (stoch_fused) {
-      extern int g_rhs_dbg;
       double dts;
       int r = stoch_prepare(m, adv_dt, &dts);
       if (r) return r;
@@ -1775,10 +1769,10 @@ static int rhs_terms(msom *m, int qfield, int dqfield, int with_qforcing, double
       // the relaxation -q_stage / tau and the noise are read in the finalisation of the pass: q_out = q_in - (dt / tau) q_stage + dts n + dt dq
       prof_begin(m, m->prof_rhs);
       with_psi_halo(true, [&](int region) {
-        launch_rhs_lpw(m->st, m->f[MSOM_PSI], m->f[MSOM_S], m->f[MSOM_QFORC], m->d_wind, nullptr, m->g, nl, m->walls & WALL_ALL, m->uniformS,
+        launch_rhs_lpw(m->st, m->opt, m->f[MSOM_PSI], m->f[MSOM_S], m->f[MSOM_QFORC], m->d_wind, nullptr, m->g, nl, m->walls & WALL_ALL, m->uniformS,
                        m->rc[0].S, with_qforcing && m->have_qforc, D, p.beta, iRe, iRe4, Eks / (p.Rom * 2 * m->dhf[0]),
                        Ekb / (p.Rom * 2 * m->dhf[nl - 1]), p.sbc > 0 ? p.sbc / ((0.5 * p.sbc + 1) * D * D) : 0., m->lc, m->f[adv_in],
-                       m->f[adv_out], adv_dt, g_rhs_dbg >> 8, 1, m->f[qfield], m->f[MSOM_NOISE], -adv_dt * p.itr_stoch, dts, region);
+                       m->f[adv_out], adv_dt, 1, m->f[qfield], m->f[MSOM_NOISE], -adv_dt * p.itr_stoch, dts, region);
       });
       prof_end(m, m->prof_rhs);
       if (advanced) *advanced = 1;
@@ -1786,7 +1780,7 @@ static int rhs_terms(msom *m, int qfield, int dqfield, int with_qforcing, double
     }
     prof_begin(m, m->prof_rhs);
     with_psi_halo(variant == 6, [&](int region) {
-      launch_rhs_fused(m->st, m->f[MSOM_PSI], m->f[MSOM_S], m->f[MSOM_QFORC], m->d_wind, m->f[dqfield], nullptr,
+      launch_rhs_fused(m->st, m->opt, m->f[MSOM_PSI], m->f[MSOM_S], m->f[MSOM_QFORC], m->d_wind, m->f[dqfield], nullptr,
                        nullptr, m->g, nl, m->walls & WALL_ALL, m->uniformS, m->rc[0].S, with_qforcing && m->have_qforc, D, p.beta, iRe,
                        iRe4, Eks / (p.Rom * 2 * m->dhf[0]), Ekb / (p.Rom * 2 * m->dhf[nl - 1]),
                        p.sbc > 0 ? p.sbc / ((0.5 * p.sbc + 1) * D * D) : 0., m->lc, variant, adv_out >= 0 ? m->f[adv_in] : nullptr,
@@ -3037,17 +3031,14 @@ extern "C" int msom_bench_kernel(msom_t *m, const char *kernel, int reps, double
     } else if (!strncmp(kernel, "march", 5) && kernel[5] >= '2' && kernel[5] <= '4') {
       const bool rev = kernel[6] == 'r';  // "march3r": da_alt -> da (the direction of the second pass of a level)
       const bool pl = kernel[6] == 'p';   // "march4p": the pass with the prolongation (coarse = level 1)
-      // timing experiment (option dbg_interleave; results meaningless): the same buffers addressed as [row][layer][x]
-      // instead of [layer][row][x] -- all layers of a row within one 2-MB fragment
-      SplitGeom g0 = m->sg[0], g1 = m->sg[m->nlev > 1 ? 1 : 0];
-      if (g_dbg_interleave) { g0.ls = g0.rp; g0.rp *= m->nl; g1.ls = g1.rp; g1.rp *= m->nl; }
-      if (pl) launch_relax_march(m->st, nullptr, m->da_alt[0], m->res[0], g0, m->nl, m->rc[0], 0, kernel[5] - '0', m->walls, g_march_rows, nullptr, m->da[1], &g1, nullptr, 1);
-      else launch_relax_march(m->st, rev ? m->da_alt[0] : m->da[0], rev ? m->da[0] : m->da_alt[0], m->res[0], g0, m->nl, m->rc[0], 1, kernel[5] - '0', m->walls,
-                         g_march_rows);
+      if (pl) launch_relax_march(m->st, m->opt, nullptr, m->da_alt[0], m->res[0], m->sg[0], m->nl, m->rc[0], 0, kernel[5] - '0', m->walls, m->opt.march_rows, nullptr,
+                                 m->da[1], &m->sg[m->nlev > 1 ? 1 : 0], nullptr, 1);
+      else launch_relax_march(m->st, m->opt, rev ? m->da_alt[0] : m->da[0], rev ? m->da[0] : m->da_alt[0], m->res[0], m->sg[0], m->nl, m->rc[0], 1,
+                              kernel[5] - '0', m->walls, m->opt.march_rows);
     } else if (!strcmp(kernel, "block2")) {
-      launch_relax_block2(m->st, m->da[0], nullptr, m->sg[0], m->res[0], m->da_alt[0], m->sg[0], m->nl, m->rc[0], m->walls, 1);
+      launch_relax_block2(m->st, m->opt, m->da[0], nullptr, m->sg[0], m->res[0], m->da_alt[0], m->sg[0], m->nl, m->rc[0], m->walls, 1);
     } else if (!strcmp(kernel, "block2p")) {
-      launch_relax_block2(m->st, m->da[0], m->da[1], m->sg[1], m->res[0], m->da_alt[0], m->sg[0], m->nl, m->rc[0], m->walls, 1);
+      launch_relax_block2(m->st, m->opt, m->da[0], m->da[1], m->sg[1], m->res[0], m->da_alt[0], m->sg[0], m->nl, m->rc[0], m->walls, 1);
     } else if (!strcmp(kernel, "rhs")) {
       rhs_terms(m, MSOM_Q, MSOM_DQ, 1, m->p.iRe, m->p.iRe4, m->p.Eks, m->p.Ekb);
     } else if (!strcmp(kernel, "resid_correct")) {
@@ -3055,7 +3046,7 @@ extern "C" int msom_bench_kernel(msom_t *m, const char *kernel, int reps, double
     } else if (!strcmp(kernel, "resid_restrict")) {
       residual2(m, 2 | 4, m->f[MSOM_Q], SC_RES1, 1);
     } else if (!strcmp(kernel, "red_prolong")) {
-      launch_relax_red_prolong(m->st, m->da[0], m->da[1], m->sg[1], m->res[0], m->S[0], m->sg[0], m->nl, m->rc[0], m->uniformS, m->walls);
+      launch_relax_red_prolong(m->st, m->opt, m->da[0], m->da[1], m->sg[1], m->res[0], m->S[0], m->sg[0], m->nl, m->rc[0], m->uniformS, m->walls);
     } else if (!strcmp(kernel, "rhs_adv")) {
       int adv = 0;
       rhs_terms(m, MSOM_Q, MSOM_DQ, 1, m->p.iRe, m->p.iRe4, m->p.Eks, m->p.Ekb, MSOM_QPRED, MSOM_Q, 1e-9, &adv);

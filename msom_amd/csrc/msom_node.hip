@@ -73,6 +73,7 @@ struct msomn {
   std::vector<NatGeom> cg;
   std::vector<double *> cs, cr, csig;  // cs[0] = n_stoch
   int mg_coarse = 32;   // the levels of <= (mg_coarse + 1)^2 vertices of a cycle in one launch (k_n_mg_coarse); 0: off
+  int node_march_rows = 0;  // option: chunk height of the marching passes (0: automatic; k_n_relax_march_s: 12)
   int node_march = 0;   // levels of >= node_march vertices per side: K = 4 chained colour half-sweeps per pass (k_n_relax_march, rows
                         // software-prefetched one step ahead).  Measured at 2049^2 x 3: 27.1 vs 26.6 ms per step, 513^2 x 3: 4.2 vs 3.1 --
                         // half the bytes, but in the natural layout half of the lanes idle in every half-sweep and the vertex column
@@ -327,7 +328,7 @@ extern "C" int msomn_set_option(msomn_t *m, const char *key, double v) {
   else if (!strcmp(key, "node_split")) { m->node_split = (int)v; if (m->const_set) return choose_layouts(m); }
   else if (!strcmp(key, "node_march")) m->node_march = (int)v;
   else if (!strcmp(key, "node_march_s")) m->node_march_s = (int)v;
-  else if (!strcmp(key, "node_march_rows")) { extern int g_node_march_rows; g_node_march_rows = (int)v; }
+  else if (!strcmp(key, "node_march_rows")) m->node_march_rows = (int)v;
   else if (!strcmp(key, "mg_coarse")) { m->mg_coarse = (int)v; if (m->const_set) return choose_layouts(m); }
   else if (!strcmp(key, "stochastic")) m->stochastic = (int)v;
   else if (!strcmp(key, "seed")) srand((unsigned)v);
@@ -367,6 +368,7 @@ extern "C" double msomn_get_param(msomn_t *m, const char *k) {
   if (!strcmp(k, "sqg")) return m->sqg;
   if (!strcmp(k, "s2_xuniform")) return m->s2_xuniform;
   if (!strcmp(k, "node_march_s")) return m->node_march_s;   // split levels of >= this many vertices a side take k_n_relax_march_s
+  if (!strcmp(k, "node_march_rows")) return m->node_march_rows;
   if (!strncmp(k, "split_", 6)) { int l = atoi(k + 6); return l >= 0 && l < m->nlev ? m->lev[l].sp : NAN; }
   if (!strncmp(k, "idh0_", 5)) { int l = atoi(k + 5); return l >= 0 && l < MSOM_MAXNL ? m->lc.idh0[l] : NAN; }
   if (!strncmp(k, "idh1_", 5)) { int l = atoi(k + 5); return l >= 0 && l < MSOM_MAXNL ? m->lc.idh1[l] : NAN; }
@@ -513,7 +515,7 @@ static void relax_sweeps(msomn *m, int k, int nsweeps, int prolong = 0) {
       if (k == 0) nprof_begin(m, NP_MARCH);
       // a pass stores only the colour of its last half-sweep if ANOTHER PASS follows (which recomputes the other colour before anything
       // reads it); a single colour pass that follows updates interior vertices only, so the pass before it stores both colours
-      launch_n_relax_march_s(m->st, L.da, L.da2, L.res, L.mask_s, L.ga, m->nl, c, K, L.D, m->iRd2_low, m->lc, L.S2row, nh - K >= 2);
+      launch_n_relax_march_s(m->st, L.da, L.da2, L.res, L.mask_s, L.ga, m->nl, c, K, L.D, m->iRd2_low, m->lc, L.S2row, nh - K >= 2, m->node_march_rows);
       if (k == 0) nprof_end(m, NP_MARCH);
       std::swap(L.da, L.da2);
       nh -= K; c = (c + K) & 1;
@@ -562,7 +564,7 @@ static void relax_sweeps(msomn *m, int k, int nsweeps, int prolong = 0) {
     while (nh >= 2) {
       int K = nh < 4 ? nh : 4;
       if (nh - K == 1) K--;            // never leave a single half-sweep behind
-      launch_n_relax_march(m->st, L.da, L.da2, L.res, L.mask, L.S2, L.g, m->nl, c, K, L.D, m->iRd2_low, m->lc);
+      launch_n_relax_march(m->st, L.da, L.da2, L.res, L.mask, L.S2, L.g, m->nl, c, K, L.D, m->iRd2_low, m->lc, m->node_march_rows);
       std::swap(L.da, L.da2);
       nh -= K; c = (c + K) & 1;
     }

@@ -60,20 +60,11 @@ def test_lean_body_of_the_chained_smoother_equals_the_general_body(N, nl):
     """product build, defaults, reference tolerance: interior chunks through march_lean (requests two steps ahead,
     counted waits, inline-assembly stores) against the same pass with every chunk in the general body, bit for bit --
     the two bodies share every expression"""
-    # march_lean is process-global (g_march_lean): read its default first and put it back whatever happens, so that the
-    # tests after this one run the product default
-    h = QG(orc.double_gyre_params(32, 1))
-    default = h.param("march_lean")
-    try:
-        a = run(N, nl, False, dict(march_lean=2), steps=2, tol=1e-3)
-        b = run(N, nl, False, dict(march_lean=0), steps=2, tol=1e-3)
-        c = run(N, nl, False, dict(march_lean=1), steps=2, tol=1e-3)
-        for k in ("dq", "q", "psi"):
-            assert np.array_equal(a[k], b[k]) and np.array_equal(c[k], b[k]), k
-    finally:
-        h.option("march_lean", default)
-        h.close()
-    assert QG(orc.double_gyre_params(32, 1)).param("march_lean") == default
+    a = run(N, nl, False, dict(march_lean=2), steps=2, tol=1e-3)
+    b = run(N, nl, False, dict(march_lean=0), steps=2, tol=1e-3)
+    c = run(N, nl, False, dict(march_lean=1), steps=2, tol=1e-3)
+    for k in ("dq", "q", "psi"):
+        assert np.array_equal(a[k], b[k]) and np.array_equal(c[k], b[k]), k
 
 
 def modal_psi(nl, N, amp=1e-3):
@@ -122,21 +113,14 @@ def test_lean_body_equals_the_general_body_at_byte_offsets_above_2_31():
         finally:
             g.close()
 
-    h = QG(orc.double_gyre_params(32, 1))
-    default = h.param("march_lean")
-    try:
-        lean = {}
-        run_fields(2, lean.__setitem__)
+    lean = {}
+    run_fields(2, lean.__setitem__)
 
-        def same(k, b):
-            a = lean.pop(k)
-            ok = np.array_equal(a, b)
-            assert ok, (k, rel(a, b), int(np.count_nonzero(a != b)))   # field, rel(max), cells that differ
-        run_fields(0, same)
-    finally:
-        h.option("march_lean", default)
-        h.close()
-    assert QG(orc.double_gyre_params(32, 1)).param("march_lean") == default
+    def same(k, b):
+        a = lean.pop(k)
+        ok = np.array_equal(a, b)
+        assert ok, (k, rel(a, b), int(np.count_nonzero(a != b)))   # field, rel(max), cells that differ
+    run_fields(0, same)
 
 
 def test_tendency_kernel_instantiations_round_alike_at_c4():

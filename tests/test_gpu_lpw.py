@@ -39,7 +39,6 @@ def test_lpw_chunk_heights(rows):
     o.update()
     g.option("rhs_variant", 6); g.option("rhs_dbg", rows << 8)
     dq, _ = g.update()
-    g.option("rhs_dbg", 0)
     assert np.array_equal(dq, o.get(orc.DQ))
 
 

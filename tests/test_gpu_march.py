@@ -189,7 +189,6 @@ def test_tiled_level_visit_equals_half_sweep_per_launch(nx, ny, nl, strict):
             assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[2] == b[2], variant
         else:
             assert rel(b[0], a[0]) <= 1e-10 and a[2][0] == b[2][0], variant
-    g = QG(txt); g.option("block_variant", 0); g.close()      # the knob is a global of the library: back to the default
 
 
 @pytest.mark.parametrize("nx,ny,nl", [(64, 64, 3), (256, 128, 2), (512, 512, 6), (128, 64, 1)])
@@ -205,7 +204,6 @@ def test_tiled_level_visit_on_the_periodic_domain(nx, ny, nl, strict):
             assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[2] == b[2], variant
         else:
             assert rel(b[0], a[0]) <= 1e-10 and a[2][0] == b[2][0], variant
-    g = QG(txt); g.option("block_variant", 0); g.close()
 
 
 def test_tiled_level_visit_against_oracle():

@@ -458,7 +458,6 @@ def test_lds_correct_residual_equals_plain(nx, ny, nl, extra, strict):
         dts = [g.step() for _ in range(3)]
         st = g.mgstats()
         out[dbg] = (g.get(F["PSI"]), g.get(F["Q"]), dts, (st.i, st.resb, st.resa))
-        g.option("rhs_dbg", 0)
         g.close()
     if strict:
         assert np.array_equal(out[0][0], out[384][0]) and np.array_equal(out[0][1], out[384][1])
@@ -887,3 +886,35 @@ def test_restriction_chain_in_one_launch(nx, ny, nl, coarse, strict):
         g.close()
     assert out[0][2] == out[1][2]
     assert np.array_equal(out[0][0], out[1][0]) and np.array_equal(out[0][1], out[1][1])
+
+
+# the kernel-selection options of msom_set_option and their defaults
+KERNEL_OPTIONS = dict(march_rows=0, march_xcd=1, march_flip=1, march_dbg=0, march_lean=2, march_dma=2, march_visit_rows=0,
+                      march_visit_pairs=2, resmax_rows=0, block_variant=0, rhs_dbg=0, lpw_dbg=0)
+
+
+def test_kernel_options_belong_to_the_handle():
+    """an option set on one handle reaches no other: handles created before and after it report the defaults (a distinct value per
+    key, so two keys that shared one field would show); the same for the vertex model's node_march_rows"""
+    from msom_amd import NodeQG
+    import orn
+
+    txt = orc.double_gyre_params(32, 3)
+    a = QG(txt)
+    b = QG(txt)
+    for i, k in enumerate(KERNEL_OPTIONS):
+        b.option(k, 10 + i)
+    c = QG(txt)
+    for i, (k, v) in enumerate(KERNEL_OPTIONS.items()):
+        assert (a.param(k), b.param(k), c.param(k)) == (v, 10 + i, v), k
+    for g in (a, b, c):
+        g.close()
+
+    par = orn.node_params(32, 2)
+    a = NodeQG(par)
+    b = NodeQG(par)
+    b.set_option("node_march_rows", 20)
+    c = NodeQG(par)
+    assert (a.param("node_march_rows"), b.param("node_march_rows"), c.param("node_march_rows")) == (0, 20, 0)
+    for g in (a, b, c):
+        g.close()
