@@ -290,7 +290,13 @@ void msomn_destroy(msomn_t *m);                                 /* trash_vars qg
  * baroclinic tendency in three passes instead of the twelve loops of the reference, node_corr_fused [2] the correction of a cycle applied
  * inside the residual pass of the next (2: rows marched, 1: one thread per vertex, 0: separate passes), profile [0] */
 int msomn_set_option(msomn_t *m, const char *key, double value);
-/* keys: N nl L0 DT tend dtout nlevels iRd2_low bc_fac idh0_<l> idh1_<l>, the options node_march_s node_march_rows; NaN if unknown */
+/* keys: N nl L0 DT tend dtout nlevels iRd2_low bc_fac idh0_<l> idh1_<l>, the options node_march_s node_march_rows; NaN if unknown.
+ * The paths the solve takes (after msomn_set_const), each from the same function the dispatch calls: sqg, s2_xuniform (S2 does not
+ * depend on x: row tables), split_<k> (level k in the x-parity split layout), node_march_kmax (K cap of the chained split pass
+ * k_n_relax_march_s: 4 for nl <= 4, 3 for nl 5-6, 0 where it cannot run: nl > 6 or no row tables), relax_path_<k> (level k's sweeps:
+ * 0 natural colour passes, 1 split colour passes, 2 LDS-tiled split passes k_n_relax_tile_s (taken for 2 sweeps or more), 3 chained
+ * split passes, 4 inside the one-launch coarse group k_n_mg_coarse, 5 option node_march, 6 option tiled_relax), corr_march (1: the
+ * correction rides in the next residual pass as rows marched by k_n_correct_residual_m) */
 double msomn_get_param(msomn_t *m, const char *key);
 int msomn_field_layers(msomn_t *m, int field);
 int msomn_set_field(msomn_t *m, int field, const double *a);   /* a: [layers][N+1][N+1] */

@@ -354,6 +354,34 @@ extern "C" int msomn_profile_reset(msomn_t *m) {
   for (auto &ps : m->prof) { ps.used = 0; ps.total_ms = 0; ps.launches = 0; }
   return MSOM_OK;
 }
+// K cap of the chained split pass (k_n_relax_march_s) on level L: windows of K stages x nl layers in registers.  0 where the pass
+// cannot run: nl > 6, or nl > 1 without row tables of S2.  relax_sweeps and msomn_get_param("node_march_kmax")
+static int node_march_kmax(const msomn *m, const NLevel &L) {
+  if (m->nl > 6 || (m->nl > 1 && !L.S2row)) return 0;
+  return m->nl <= 4 ? 4 : 3;
+}
+// the path of level k's sweeps (msomn_get_param("relax_path_<k>")): natural colour passes, split colour passes, LDS-tiled split passes
+// (k_n_relax_tile_s; relax_sweeps takes them only for 2 sweeps or more), chained split passes (k_n_relax_march_s), inside the one-launch
+// coarse group (k_n_mg_coarse), and the natural-layout options node_march (k_n_relax_march) and tiled_relax (k_n_relax_tile)
+enum { NRP_COLOR = 0, NRP_SPLIT = 1, NRP_TILE_S = 2, NRP_MARCH_S = 3, NRP_COARSE = 4, NRP_MARCH = 5, NRP_TILE = 6 };
+static int sweep_path(const msomn *m, int k) {
+  const NLevel &L = m->lev[k];
+  if (L.sp && m->node_march_s && L.n + 1 >= m->node_march_s && node_march_kmax(m, L)) return NRP_MARCH_S;
+  if (L.sp && m->node_tile_s && L.n + 1 >= m->node_tile_s && L.n + 1 <= m->node_tile_max && m->nl <= 4 && (m->nl == 1 || L.S2row)) return NRP_TILE_S;
+  if (L.sp) return NRP_SPLIT;
+  if (m->node_march && L.n + 1 >= m->node_march && L.n + 1 >= 64) return NRP_MARCH;
+  if (m->tiled_relax && L.n + 1 >= 64) return NRP_TILE;
+  return NRP_COLOR;
+}
+// first level of the group that one workgroup handles in one launch (k_n_mg_coarse: <= 33^2 vertices, at least two levels); nlev: none
+static int coarse_first(const msomn *m) {
+  if (!m->mg_coarse) return m->nlev;
+  int k0 = 0;
+  while (k0 < m->nlev && m->lev[k0].n > m->mg_coarse) k0++;
+  return m->nlev - k0 >= 2 && m->nlev - k0 <= NMGC_MAXLEV ? k0 : m->nlev;
+}
+// the correction of a cycle rides in the next residual pass as rows marched by k_n_correct_residual_m<NL> (node_corr_fused 2)
+static int node_corr_march(const msomn *m) { return m->node_corr_fused >= 2 && m->nl <= MSOM_FASTNL; }
 extern "C" double msomn_get_param(msomn_t *m, const char *k) {
   if (!m || !k) return NAN;
   if (!strcmp(k, "N")) return m->N;
@@ -370,6 +398,11 @@ extern "C" double msomn_get_param(msomn_t *m, const char *k) {
   if (!strcmp(k, "node_march_s")) return m->node_march_s;   // split levels of >= this many vertices a side take k_n_relax_march_s
   if (!strcmp(k, "node_march_rows")) return m->node_march_rows;
   if (!strncmp(k, "split_", 6)) { int l = atoi(k + 6); return l >= 0 && l < m->nlev ? m->lev[l].sp : NAN; }
+  // the paths the solve takes (set_const decides the layouts and row tables): the K cap of the chained split pass (level 0's row
+  // tables), the path of level k's sweeps (NRP_*), the correction marched inside the residual pass
+  if (!strcmp(k, "node_march_kmax")) return m->nlev ? node_march_kmax(m, m->lev[0]) : NAN;
+  if (!strncmp(k, "relax_path_", 11)) { int l = atoi(k + 11); return l >= 0 && l < m->nlev ? (l >= coarse_first(m) ? NRP_COARSE : sweep_path(m, l)) : NAN; }
+  if (!strcmp(k, "corr_march")) return node_corr_march(m);
   if (!strncmp(k, "idh0_", 5)) { int l = atoi(k + 5); return l >= 0 && l < MSOM_MAXNL ? m->lc.idh0[l] : NAN; }
   if (!strncmp(k, "idh1_", 5)) { int l = atoi(k + 5); return l >= 0 && l < MSOM_MAXNL ? m->lc.idh1[l] : NAN; }
   return NAN;
@@ -496,7 +529,8 @@ static void relax_level(msomn *m, int k, double *da, const double *res) {
 // prolong = 1: the correction of level k + 1 has not been prolongated yet; the first colour pass does it on the fly (split levels)
 static void relax_sweeps(msomn *m, int k, int nsweeps, int prolong = 0) {
   NLevel &L = m->lev[k];
-  if (L.sp && m->node_march_s && L.n + 1 >= m->node_march_s && m->nl <= 6 && (m->nl == 1 || L.S2row)) {
+  const int path = sweep_path(m, k);
+  if (path == NRP_MARCH_S) {
     // chained colour half-sweeps (round 3): the first colour may ride with the prolongation as before; the remaining 2 nsweeps - 1
     // (or 2 nsweeps) half-sweeps go in passes of up to 4, ping-ponging between the two correction buffers; a pass that is
     // followed by more half-sweeps stores only the colour of its last one; a single left-over half-sweep runs in place
@@ -509,7 +543,7 @@ static void relax_sweeps(msomn *m, int k, int nsweeps, int prolong = 0) {
       nh--; c = 1;
     }
     while (nh >= 2) {
-      const int kmax = m->nl <= 4 ? 4 : (m->nl <= 6 ? 3 : 2);   // windows of K stages x nl layers in registers
+      const int kmax = node_march_kmax(m, L);
       int K = nh < kmax ? nh : kmax;
       if (nh - K == 1 && K > 2 && !m->node_march_tail1) K--;   // leave no single half-sweep behind (node_march_tail1 = 1: do, it then runs as a colour pass)
       if (k == 0) nprof_begin(m, NP_MARCH);
@@ -523,7 +557,7 @@ static void relax_sweeps(msomn *m, int k, int nsweeps, int prolong = 0) {
     if (nh == 1) launch_n_relax(m->st, L.da, L.res, L.mask_s, L.S2_s, L.ga, m->nl, c, L.D, m->iRd2_low, m->lc, 1, L.S2row);
     return;
   }
-  if (L.sp && m->node_tile_s && L.n + 1 >= m->node_tile_s && L.n + 1 <= m->node_tile_max && m->nl <= 4 && (m->nl == 1 || L.S2row) && nsweeps >= 2) {
+  if (path == NRP_TILE_S && nsweeps >= 2) {
     // launch-bound split levels (round 3): first colour with the prolongation as before, then LDS-tiled passes
     // (k_n_relax_tile_s, out of place; up to node_tile_k = 8 half-sweeps each), a single left-over half-sweep as a colour pass
     int nh = 2 * nsweeps, c = 0;
@@ -545,7 +579,7 @@ static void relax_sweeps(msomn *m, int k, int nsweeps, int prolong = 0) {
     if (nh == 1) launch_n_relax(m->st, L.da, L.res, L.mask_s, L.S2_s, L.ga, m->nl, c, L.D, m->iRd2_low, m->lc, 1, L.S2row);
     return;
   }
-  if (L.sp) {  // split layout: a colour pass already moves only the bytes it uses
+  if (path == NRP_SPLIT || path == NRP_TILE_S) {  // split layout: a colour pass already moves only the bytes it uses
     for (int s = 0; s < nsweeps; s++) {
       if (prolong && s == 0) {
         const NLevel &C = m->lev[k + 1];
@@ -558,7 +592,7 @@ static void relax_sweeps(msomn *m, int k, int nsweeps, int prolong = 0) {
     }
     return;
   }
-  if (m->node_march && L.n + 1 >= m->node_march && L.n + 1 >= 64) {
+  if (path == NRP_MARCH) {
     // 2 nsweeps colour half-sweeps (red, black, red, ...) in passes of up to 4, ping-ponging between the two correction buffers
     int nh = 2 * nsweeps, c = 0;
     while (nh >= 2) {
@@ -571,7 +605,7 @@ static void relax_sweeps(msomn *m, int k, int nsweeps, int prolong = 0) {
     if (nh == 1) launch_n_relax(m->st, L.da, L.res, L.mask, L.S2, L.g, m->nl, c, L.D, m->iRd2_low, m->lc);
     return;
   }
-  if (!m->tiled_relax || L.n + 1 < 64) {
+  if (path == NRP_COLOR) {
     for (int s = 0; s < nsweeps; s++) relax_level(m, k, L.da, L.res);
     return;
   }
@@ -644,7 +678,7 @@ static int vpoisson(msomn *m, double *&a, const double *b) {
       nprof_begin(m, NP_CORR_RES);
       launch_n_correct_residual(m->st, a, m->psi_alt, m->lev[0].da, m->lev[0].sp ? &m->lev[0].ga : nullptr, m->psi_bc, b, m->lev[0].mask, m->lev[0].S2,
                                 m->lev[0].res, m->d_scal + NSC_RES, m->g, nl, m->D, m->iRd2_low, m->lc, m->lev[0].sp ? &m->lev[0].ga : nullptr, m->lev[0].S2row,
-                                m->node_corr_fused >= 2);
+                                node_corr_march(m));
       nprof_end(m, NP_CORR_RES);
       std::swap(a, m->psi_alt);
     } else {
@@ -667,12 +701,7 @@ static int vpoisson(msomn *m, double *&a, const double *b) {
     if (!m->ev_res) HIPCHK(hipEventCreateWithFlags(&m->ev_res, hipEventDisableTiming));
     HIPCHK(hipEventRecord(m->ev_res, m->st));
     // kc: first level of the group that one workgroup handles in one launch (<= 33^2 vertices, at least two levels)
-    int kc = nlev;
-    if (m->mg_coarse) {
-      int k0 = 0;
-      while (k0 < nlev && m->lev[k0].n > m->mg_coarse) k0++;
-      if (nlev - k0 >= 2 && nlev - k0 <= NMGC_MAXLEV) kc = k0;
-    }
+    const int kc = coarse_first(m);
     for (int k = 1; k < nlev && k <= kc; k++)
       launch_n_restrict(m->st, m->lev[k - 1].res, m->lev[k - 1].ga, m->lev[k].res, m->lev[k].ga, nl, 0, m->lev[k - 1].sp, m->lev[k].sp, 1);
     HIPCHK(hipEventSynchronize(m->ev_res));
