@@ -113,7 +113,7 @@ int msom_destroy(msom_t *m);
 int msom_set_option(msom_t *m, const char *key, double value);
 /* parsed / derived parameters: N nx ny nl L0 DT iRe iRe4 CFL Rom tend dtout beta tau0 Ekb Eks
  * sbc idh0_<l> idh1_<l> Fr_<l> dh_<l> nlevels; the handle's kernel options march_rows march_xcd march_flip march_dbg
- * march_lean march_dma march_visit_rows march_visit_pairs resmax_rows block_variant rhs_dbg lpw_dbg */
+ * march_lean march_dma march_visit_rows march_visit_pairs march_visit_ring march_visit_split resmax_rows block_variant rhs_dbg lpw_dbg */
 double msom_get_param(msom_t *m, const char *key);
 
 /* pyset_field / pyget_field, msqg/qg.h:1164-1188 (array [layer][y][x]; BC applied after set) */

@@ -18,6 +18,7 @@
 //  * out of place (in -> out): a chunk re-computes K rows of its neighbours (cone of dependence), which those
 //    neighbours overwrite; lanes: 2 x ceil(K/2) halo lanes of 64.
 // Used on one GPU (no halo exchange between half-sweeps), walls (not the periodic domain), uniform S, nl >= 2.
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <type_traits>
@@ -94,8 +95,36 @@ struct MarchArgs {
   // the chunks whose own cells all lie in rows [sy0, sy1) x columns [sx0, sx1) (sy1 <= sy0: none)
   int vy0, vx0;
   int sy0, sy1, sx0, sx1;
+  // march_visit_ring >= 1: the passes around the visit enumerate the chunks the skip rule admits (four bands, visit_ring_bands)
+  // instead of launching the whole chunk grid; wavefront i of the launch takes chunk i of the table (rb.n = 0: the chunk grid)
+  VisitRingBands rb;
+  // march_visit_ring = 2: a k_relax_visit launch is a 1-D grid whose first ring_wg workgroups take ring chunks (ring_kind 1: the
+  // PL pass, 2: the CORR pass) and the others the fused chunks of rows [fby0, fby0 + fnby) x fnbx strip groups.  The ring role
+  // has fields of its own where the two differ: chunk height, lean body, input and output of the pass
+  int ring_kind, ring_wg, fby0, fnbx, fnby;
+  int rH, rlean;
+  const double *rin;
+  double *rout;
   RelaxCoef rc;
 };
+
+static void visit_ring_bands(int hk, int ny, int ow, int H, const int *skip, VisitRingBands &rb);   // host: fills the table
+
+// chunk i of the compact ring grid -> (strip, chunk row); the bands are disjoint, strips run fastest inside a band
+__device__ __forceinline__ void visit_ring_chunk(const VisitRingBands &rb, int i, int &strip, unsigned &by) {
+  int b = 0;
+#pragma unroll
+  for (int q = 0; q < 3; q++) {
+    const int cnt = rb.ns[q] * rb.nc[q];
+    if (b == q && i >= cnt) { i -= cnt; b = q + 1; }
+  }
+  const int ns = b == 0 ? rb.ns[0] : (b == 1 ? rb.ns[1] : (b == 2 ? rb.ns[2] : rb.ns[3]));
+  const int s0 = b == 0 ? rb.s0[0] : (b == 1 ? rb.s0[1] : (b == 2 ? rb.s0[2] : rb.s0[3]));
+  const int c0 = b == 0 ? rb.c0[0] : (b == 1 ? rb.c0[1] : (b == 2 ? rb.c0[2] : rb.c0[3]));
+  const int r = i / ns;
+  strip = s0 + (i - r * ns);
+  by = (unsigned)(c0 + r);
+}
 
 template <int NL, int K, bool PL, bool CORR>
 __global__ void __launch_bounds__(64, 2) k_relax_march(MarchArgs p) {
@@ -735,30 +764,33 @@ __device__ __forceinline__ void march_lean(const MarchArgs &p, double (*ring)[64
 //    row that half-sweep K finished in step t - 1 is requested with the rows of step t + 1 (LDS-DMA, 16 bytes per lane =
 //    the lane's cell pair in the natural layout) and psi_out = psi + da of that row is written at the top of step t + 1,
 //    right after the wait that covers the request: nothing of the chain waits for psi, and da is never stored.
-template <int NL, int K, int HL, int WPB, bool PL, bool CORR = false>
-__global__ void __launch_bounds__(64 * WPB, 2) k_relax_march_dma(MarchArgs p) {
+// LDS ring of one wavefront of the pass, in layer-rows of 64 doubles.  Rows: [0, NL) residual of colour c1 (row t), [NL, 2 NL)
+// residual of colour c0 (row t - 1), then either the input row t + 1 (NL rows) or, PL, a ring of 4 coarse rows (slot = J & 3;
+// NL rows each: [even half | odd half] x 32 cells): a coarse row serves 4 fine rows and is fetched ONCE, one new row every
+// second step.  The lean body has its own layout (MarchLeanRows); the ring holds the larger of the two
+template <int NL, int K, int HL, int WPB, bool PL, bool CORR>
+struct MarchDmaRows {
+  static constexpr int NLE = (NL + 1) & ~1;                       // two layer-rows per DMA instruction
+  static constexpr int CB = 2 * NLE;                              // first coarse ring row
+  static constexpr int PB = 2 * ((3 * NL + 1) / 2);               // CORR: first row of the psi block (NL x 128 doubles)
+  static constexpr int XB = PB + 2 * NL;                          // CORR: values of half-sweep K waiting one step for their psi row
+  static constexpr int LROWS0 = PL ? CB + 4 * NLE : (CORR ? XB + NL : 2 * ((3 * NL + 1) / 2));
+  using LRows = MarchLeanRows<NL, K, HL, WPB, PL, CORR>;
+  static constexpr int LROWSL = (!CORR && LRows::ROWSD > LRows::ROWS) ? LRows::ROWSD : LRows::ROWS;
+  static constexpr int LROWS = LROWS0 > LROWSL ? LROWS0 : LROWSL;
+};
+
+// one chunk of the pass: strip `strip` (own half-columns [strip OW, (strip + 1) OW)), chunk row `by`, on one wavefront with
+// its LDS ring.  Called by k_relax_march_dma and by the ring workgroups of k_relax_visit
+template <int NL, int K, int HL, int WPB, bool PL, bool CORR>
+__device__ __forceinline__ void march_dma_chunk(const MarchArgs &p, double (*ring)[64], const int lane, const int strip, const unsigned by) {
   static_assert(!(PL && CORR), "the prolongation and the correction never ride in the same pass");
   static_assert(HL % 2 == 0 && (!PL || HL % 4 == 0), "16-byte pieces: strips start at even kx (PL: at kx = 0 mod 4)");
   constexpr int OW = 64 - 2 * HL;
   constexpr int D1 = K >= 3 ? 3 : 1, D2 = K >= 4 ? 3 : 1;
-  // ring rows: [0, NL) residual of colour c1 (row t), [NL, 2 NL) residual of colour c0 (row t - 1), then either the input
-  // row t + 1 (NL rows) or, PL, a ring of 4 coarse rows (slot = J & 3; NL rows each: [even half | odd half] x 32 cells):
-  // a coarse row serves 4 fine rows and is fetched ONCE, one new row every second step
-  constexpr int NLE = (NL + 1) & ~1;                       // two layer-rows per DMA instruction
-  constexpr int CB = 2 * NLE;                              // first coarse ring row
-  constexpr int PB = 2 * ((3 * NL + 1) / 2);                // CORR: first row of the psi block (NL x 128 doubles)
-  constexpr int XB = PB + 2 * NL;                           // CORR: values of half-sweep K waiting one step for their psi row
-  constexpr int LROWS0 = PL ? CB + 4 * NLE : (CORR ? XB + NL : 2 * ((3 * NL + 1) / 2));
-  using LRows = MarchLeanRows<NL, K, HL, WPB, PL, CORR>;
-  constexpr int LROWSL = (!CORR && LRows::ROWSD > LRows::ROWS) ? LRows::ROWSD : LRows::ROWS;
-  constexpr int LROWS = LROWS0 > LROWSL ? LROWS0 : LROWSL;
-  __shared__ __align__(16) double ring_all[WPB][LROWS][64];
-  const int lane = threadIdx.x & 63;
-  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  double(*ring)[64] = ring_all[wv];
-  unsigned bx = blockIdx.x, by = blockIdx.y;
-  if (p.remap) xcd_remap(bx, by);
-  const int kx0 = ((int)bx * WPB + wv) * OW - HL;
+  using DR = MarchDmaRows<NL, K, HL, WPB, PL, CORR>;
+  constexpr int NLE = DR::NLE, CB = DR::CB, PB = DR::PB, XB = DR::XB;
+  const int kx0 = strip * OW - HL;
   const int kx = kx0 + lane;
   const int y0 = by * p.H, y1 = min(p.g.ny, y0 + p.H);
   const int hk = p.g.hk, ny = p.g.ny, hp = p.g.hp;
@@ -1084,6 +1116,26 @@ __global__ void __launch_bounds__(64 * WPB, 2) k_relax_march_dma(MarchArgs p) {
   }
 }
 
+template <int NL, int K, int HL, int WPB, bool PL, bool CORR = false>
+__global__ void __launch_bounds__(64 * WPB, 2) k_relax_march_dma(MarchArgs p) {
+  __shared__ __align__(16) double ring_all[WPB][MarchDmaRows<NL, K, HL, WPB, PL, CORR>::LROWS][64];
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  int strip;
+  unsigned by;
+  if (p.rb.n) {   // compact ring grid: one chunk of the band table per wavefront (launched with WPB = 1: no barriers)
+    const int i = (int)blockIdx.x * WPB + wv;
+    if (i >= p.rb.n) return;
+    visit_ring_chunk(p.rb, i, strip, by);
+  } else {
+    unsigned bx = blockIdx.x;
+    by = blockIdx.y;
+    if (p.remap) xcd_remap(bx, by);
+    strip = (int)bx * WPB + wv;
+  }
+  march_dma_chunk<NL, K, HL, WPB, PL, CORR>(p, ring_all[wv], lane, strip, by);
+}
+
 // CUs of the current device, asked once per device; tiled tests drive the launchers from several host threads
 int device_cu_count() {
   static std::mutex mu;
@@ -1149,6 +1201,13 @@ static void march_launch(hipStream_t st, Kern kern, MarchArgs a, int ow, int chu
   }
   if (a.lean) H = (H + 1) & ~1;   // the lean body marches in pairs of steps
   a.H = H;
+  if (a.rb.n < 0) {   // compact ring grid: the chunks the skip rectangle admits, one wavefront each
+    const int skip[4] = {a.sy0, a.sy1, a.sx0, a.sx1};
+    visit_ring_bands(a.g.hk, a.g.ny, ow, H, skip, a.rb);
+    a.sy0 = a.sy1 = 0;
+    if (a.rb.n > 0) hipLaunchKernelGGL(kern, dim3(a.rb.n), dim3(nthreads), 0, st, a);
+    return;
+  }
   hipLaunchKernelGGL(kern, dim3(strips, (a.g.ny + H - 1) / H), dim3(nthreads), 0, st, a);
 }
 
@@ -1159,7 +1218,7 @@ static int march_dispatch(hipStream_t st, const MarchArgs &a, int K, int rows, i
     // 1: one strip per workgroup; 2 (default): four adjacent strips per workgroup, marching in step, for the plain pass
     // (the pass with the prolongation measured faster with one: 7.09 vs 7.25 ms per RK2 step); 3: four for both
     constexpr int NLS = NL;
-    const bool four = a.coarse ? dma >= 3 : dma >= 2;
+    const bool four = a.rb.n ? false : (a.coarse ? dma >= 3 : dma >= 2);   // compact ring grid: one chunk per workgroup
 #define MARCH_DMA_K(KK)                                                                                                      \
     if constexpr (NL <= 6) {   /* four strips per workgroup: 4 x the LDS ring; at nl = 7, 8 that leaves one workgroup per CU */   \
       if (a.coarse && four) { march_launch(st, k_relax_march_dma<NLS, KK, 4, 4, true>, a, 56 * 4, rows, 256); return 0; }        \
@@ -1214,8 +1273,10 @@ bool march_lean_fits(int nl, const SplitGeom &sg, const NatGeom *ng) {
 // K (2..4) half-sweeps starting with colour c1, in -> out; returns -1 if (nl, K) has no instantiation
 int launch_relax_march(hipStream_t st, const KernelOpts &o, const double *in, double *out, const double *res, const SplitGeom &sg, int nl, const RelaxCoef &rc, int c1,
                        int K, int walls, int chunk_rows, const MarchHalo *h, const double *coarse, const SplitGeom *cg, const MarchCorrect *mc, int more_follow, const MarchHalo *ch,
-                       int region, const int *skip) {
-  MarchArgs a;
+                       int region, const int *skip, int skip_compact) {
+  MarchArgs a{};
+  // the compact grid exists in the LDS-DMA kernels (march_launch fills the table once the chunk height is known)
+  a.rb.n = skip && skip_compact && o.march_dma && nl <= 6 && K == 4 ? -1 : 0;
   a.region = region;
   a.vy0 = a.vx0 = 0;
   a.sy0 = skip ? skip[0] : 0; a.sy1 = skip ? skip[1] : 0; a.sx0 = skip ? skip[2] : 0; a.sx1 = skip ? skip[3] : 0;
@@ -1260,16 +1321,31 @@ int launch_relax_march(hipStream_t st, const KernelOpts &o, const double *in, do
 //    the visit's chunks, so the first pass also runs on a band of them;
 //  * arithmetic: the lean bodies unchanged => every cell bit-identical to the two passes (tests/test_gpu_march_visit.py).
 // LDS per pair at nl = 6: A 36 layer-rows, B 30 (no input block), hand-over 12: 78 x 512 B = 39 KB (4 pairs per CU).
+// xcd_remap (mg_inl.h) for a sub-grid of nbx x (total / nbx) workgroups numbered lin: in a mixed launch the fused chunks are
+// renumbered among themselves, so neighbouring strip groups stay on one XCD
+__device__ __forceinline__ void xcd_remap_lin(const unsigned lin, const unsigned nbx, const unsigned total, unsigned &bx, unsigned &by) {
+  const unsigned c = lin & 7, q = total >> 3, r = total & 7;
+  const unsigned flat = c * q + (c < r ? c : r) + (lin >> 3);
+  bx = flat % nbx;
+  by = flat / nbx;
+}
 // one role of the pair; everything from the launch coordinates, inside the role's branch (shared values live across both
 // bodies cost registers: 3 spilled VGPRs at nl = 6 when computed before the branch)
-template <int NL, int PAIRS, int VIS>
+template <int NL, int PAIRS, int VIS, int KIND>
 __device__ __forceinline__ void visit_role(const MarchArgs &p, double (*lds)[64], const int pair) {
   constexpr int K = 4, HL = 8;
   constexpr int OW = 64 - 2 * HL;
   constexpr int RA = MarchLeanRows<NL, K, HL, 2, true, false>::ROWSD, RB = MarchLeanRows<NL, K, HL, 2, false, true, 2>::ROWS;
   const int lane = threadIdx.x & 63;
   unsigned bx = blockIdx.x, by = blockIdx.y;
-  if (p.remap) xcd_remap(bx, by);
+  if constexpr (KIND != 0) {   // mixed launch: the fused chunks follow the ring workgroups
+    const unsigned lin = blockIdx.x - (unsigned)p.ring_wg;
+    if (p.remap) xcd_remap_lin(lin, p.fnbx, (unsigned)p.fnbx * p.fnby, bx, by);
+    else { bx = lin % (unsigned)p.fnbx; by = lin / (unsigned)p.fnbx; }
+    by += p.fby0;
+  } else {
+    if (p.remap) xcd_remap(bx, by);
+  }
   const int kx0 = p.vx0 + ((int)bx * PAIRS + pair) * OW - HL;
   const int y0 = p.vy0 + (int)by * p.H, y1 = y0 + p.H;
   const bool down = p.flip && (by & 1);
@@ -1278,61 +1354,117 @@ __device__ __forceinline__ void visit_role(const MarchArgs &p, double (*lds)[64]
   if constexpr (VIS == 2) march_lean<NL, K, HL, 2, false, true, false, 2>(p, ring + RA, lane, kx0, y0, y1, down, hand);
   else march_lean<NL, K, HL, 2, true, false, true, 1>(p, ring, lane, kx0, y0 - K, y1 + K, down, hand);
 }
-template <int NL, int PAIRS>
+// a ring workgroup of a mixed launch: each wavefront takes one chunk of the band table through the one-strip forms of the pass
+// (no workgroup barrier in them), with the ring role's own chunk height, lean option, input and output
+template <int NL, int KIND>
+__device__ __forceinline__ void visit_ring_role(const MarchArgs &p, double (*lds)[64], const int wv, const int nwv) {
+  constexpr int K = 4;
+  const int i = (int)blockIdx.x * nwv + wv;
+  if (i >= p.rb.n) return;
+  int strip;
+  unsigned by;
+  visit_ring_chunk(p.rb, i, strip, by);
+  MarchArgs q = p;
+  q.H = p.rH; q.lean = p.rlean; q.in = p.rin; q.out = p.rout;
+  q.partial = KIND == 1;
+  q.rb.n = 0; q.region = 0; q.sy0 = q.sy1 = 0;
+  const int lane = threadIdx.x & 63;
+  if constexpr (KIND == 1) march_dma_chunk<NL, K, 4, 1, true, false>(q, lds + wv * MarchDmaRows<NL, K, 4, 1, true, false>::LROWS, lane, strip, by);
+  else march_dma_chunk<NL, K, 2, 1, false, true>(q, lds + wv * MarchDmaRows<NL, K, 2, 1, false, true>::LROWS, lane, strip, by);
+}
+// KIND: 0 the fused chunks alone on a 2-D grid; 1 / 2 a mixed launch whose leading workgroups are the ring chunks of the PL / CORR
+// pass.  One kind per instantiation: each carries only the bodies it runs
+template <int NL, int PAIRS, int KIND>
 __global__ void __launch_bounds__(128 * PAIRS, 2) k_relax_visit(MarchArgs p) {
   constexpr int K = 4, HL = 8;
   constexpr int RA = MarchLeanRows<NL, K, HL, 2, true, false>::ROWSD, RB = MarchLeanRows<NL, K, HL, 2, false, true, 2>::ROWS;
-  __shared__ __align__(16) double lds[PAIRS * (RA + RB + 2 * NL)][64];
+  // the pair layout or, where it is larger (nl = 3), one ring per wavefront of a ring workgroup
+  constexpr int RPL = MarchDmaRows<NL, K, 4, 1, true, false>::LROWS, RCO = MarchDmaRows<NL, K, 2, 1, false, true>::LROWS;
+  constexpr int RFUSED = PAIRS * (RA + RB + 2 * NL), RRING = KIND == 0 ? 0 : 2 * PAIRS * (KIND == 1 ? RPL : RCO);
+  __shared__ __align__(16) double lds[RFUSED > RRING ? RFUSED : RRING][64];
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (wv & 1) visit_role<NL, PAIRS, 2>(p, lds, wv >> 1);
-  else visit_role<NL, PAIRS, 1>(p, lds, wv >> 1);
+  if constexpr (KIND != 0) {
+    if ((int)blockIdx.x < p.ring_wg) {   // uniform per workgroup
+      visit_ring_role<NL, KIND>(p, lds, wv, 2 * PAIRS);
+      return;
+    }
+  }
+  if (wv & 1) visit_role<NL, PAIRS, 2, KIND>(p, lds, wv >> 1);
+  else visit_role<NL, PAIRS, 1, KIND>(p, lds, wv >> 1);
 }
 
 // the visit's chunk grid: nc chunks of H rows from row vy0, ns strips of 48 own lanes from kx = vx0 (a multiple of pairs)
 struct VisitGeom { int H, vy0, nc, vx0, ns; };
-static bool visit_geom(const SplitGeom &sg, int rows, int pairs, VisitGeom &v) {
+static bool visit_geom(int hk, int ny, int rows, int pairs, VisitGeom &v) {
   constexpr int K = 4, HL = 8, OW = 64 - 2 * HL;
   v.H = rows > 0 ? (rows + 1) & ~1 : 28;   // 4096^2 x 6: 14 rows 0.946 ms, 20: 0.900, 28: 0.881, 42: 0.886 (one pair per workgroup)
   v.vy0 = 2 * K;                           // wave A reads down to row y0 - 2 K
-  v.nc = (sg.ny - 2 * K - v.vy0) / v.H;    // ... and up to y1 + 2 K - 1
+  v.nc = (ny - 2 * K - v.vy0) / v.H;       // ... and up to y1 + 2 K - 1
   v.vx0 = HL;                              // strip s: kx0 = 48 s
-  v.ns = sg.hk >= 64 ? ((sg.hk - 64) / OW + 1) / pairs * pairs : 0;   // kx0 + 63 <= hk - 1
+  v.ns = hk >= 64 ? ((hk - 64) / OW + 1) / pairs * pairs : 0;   // kx0 + 63 <= hk - 1
   return v.nc > 0 && v.ns > 0;
 }
 bool relax_visit_fits(int nl, const SplitGeom &sg, int rows, int pairs) {
   VisitGeom v;
-  return nl >= 2 && nl <= 6 && (pairs == 1 || pairs == 2) && visit_geom(sg, rows, pairs, v);
+  return nl >= 2 && nl <= 6 && (pairs == 1 || pairs == 2) && visit_geom(sg.hk, sg.ny, rows, pairs, v);
+}
+
+// The chunks of a pass around the visit (strips of ow own half-columns, chunks of H rows) that its skip rule admits: chunk
+// (s, c) is skipped when its own cells, rows [c H, min(ny, (c + 1) H)) x half-columns [s ow, min(hk, (s + 1) ow)), all lie inside
+// rows [skip[0], skip[1]) x half-columns [skip[2], skip[3]).  Both conditions are monotone, so the skipped chunks are a
+// rectangle [s_lo, s_hi) x [c_lo, c_hi) of the chunk grid and the others four bands: the chunk rows below it, those above it,
+// the strips left of it and right of it within its rows.  Pure host arithmetic (tests/test_visit_ring_host.py).
+static void visit_ring_bands(int hk, int ny, int ow, int H, const int *skip, VisitRingBands &rb) {
+  const int ns = (hk + ow - 1) / ow, nc = (ny + H - 1) / H;
+  int s_lo = std::min(ns, (std::max(skip[2], 0) + ow - 1) / ow), s_hi = hk <= skip[3] ? ns : std::max(skip[3], 0) / ow;
+  int c_lo = std::min(nc, (std::max(skip[0], 0) + H - 1) / H), c_hi = ny <= skip[1] ? nc : std::max(skip[1], 0) / H;
+  if (skip[1] <= skip[0] || s_lo >= s_hi || c_lo >= c_hi) { c_lo = c_hi = nc; s_lo = s_hi = ns; }   // nothing is skipped: one band
+  const int s0[4] = {0, 0, 0, s_hi}, n_s[4] = {ns, ns, s_lo, ns - s_hi}, c0[4] = {0, c_hi, c_lo, c_lo}, n_c[4] = {c_lo, nc - c_hi, c_hi - c_lo, c_hi - c_lo};
+  rb.n = 0;
+  for (int b = 0; b < 4; b++) {
+    rb.s0[b] = s0[b]; rb.ns[b] = n_s[b]; rb.c0[b] = c0[b]; rb.nc[b] = n_c[b];
+    rb.n += n_s[b] * n_c[b];
+  }
+}
+// skip rectangles of the two passes around the visit (see launch_relax_visit)
+static void visit_skips(const VisitGeom &v, int Hc, int *skip_pl, int *skip_corr) {
+  constexpr int K = 4;
+  const int my = Hc + K, vy1 = v.vy0 + v.nc * v.H, vx1 = v.vx0 + v.ns * 48;
+  skip_pl[0] = v.vy0 + my; skip_pl[1] = vy1 - my; skip_pl[2] = v.vx0 + 64; skip_pl[3] = vx1 - 64;
+  skip_corr[0] = v.vy0; skip_corr[1] = vy1; skip_corr[2] = v.vx0; skip_corr[3] = vx1;
+}
+static int visit_ring_rows(int march_rows) { return march_rows > 0 ? (march_rows + 1) & ~1 : 14; }
+
+// host view of the visit's geometry for a level of hk half-columns x ny rows, no device needed: geom = {H, vy0, nc, vx0, ns} of
+// the fused chunk grid, bands = {s0[4], ns[4], c0[4], nc[4]} of the compact ring grid of the PL pass (corr = 0: strips of 56) or
+// the CORR pass (corr = 1: strips of 60) with chunks of march_rows.  Returns the number of ring chunks, -1 where the visit does not fit
+extern "C" int msom_visit_ring(int hk, int ny, int march_rows, int visit_rows, int pairs, int corr, int *geom, int *bands) {
+  VisitGeom v;
+  if (hk <= 0 || ny <= 0 || (pairs != 1 && pairs != 2) || !visit_geom(hk, ny, visit_rows, pairs, v)) return -1;
+  int skip_pl[4], skip_corr[4];
+  const int Hc = visit_ring_rows(march_rows);
+  visit_skips(v, Hc, skip_pl, skip_corr);
+  VisitRingBands rb;
+  visit_ring_bands(hk, ny, corr ? 60 : 56, Hc, corr ? skip_corr : skip_pl, rb);
+  if (geom) { geom[0] = v.H; geom[1] = v.vy0; geom[2] = v.nc; geom[3] = v.vx0; geom[4] = v.ns; }
+  if (bands)
+    for (int b = 0; b < 4; b++) { bands[b] = rb.s0[b]; bands[4 + b] = rb.ns[b]; bands[8 + b] = rb.c0[b]; bands[12 + b] = rb.nc[b]; }
+  return rb.n;
 }
 
 template <int NL>
 static void visit_dispatch(hipStream_t st, const MarchArgs &a, const VisitGeom &v, int pairs) {
-  if (pairs == 2) hipLaunchKernelGGL((k_relax_visit<NL, 2>), dim3(v.ns / 2, v.nc), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((k_relax_visit<NL, 1>), dim3(v.ns, v.nc), dim3(128), 0, st, a);
+  // mixed launch (ring_kind): a 1-D grid, the ring workgroups first so that their latency-bound chains start with the launch
+  const dim3 grid = a.ring_kind ? dim3(a.ring_wg + a.fnbx * a.fnby) : dim3(v.ns / pairs, v.nc);
+#define VISIT_KIND(KIND)                                                                            \
+  if (pairs == 2) hipLaunchKernelGGL((k_relax_visit<NL, 2, KIND>), grid, dim3(256), 0, st, a); \
+  else hipLaunchKernelGGL((k_relax_visit<NL, 1, KIND>), grid, dim3(128), 0, st, a);
+  if (a.ring_kind == 1) { VISIT_KIND(1) }
+  else if (a.ring_kind == 2) { VISIT_KIND(2) }
+  else { VISIT_KIND(0) }
+#undef VISIT_KIND
 }
-
-// PL + 4 half-sweeps (colour 0 first) and 4 + correction, the prolongation from `coarse`; da_alt receives the first pass's values
-// where the two passes run, da is not used.  The passes run on the chunks that are not the visit's: the second one (CORR) on
-// those with own cells outside the visit's rows / columns; it reads the first one's values up to ring_rows + K rows and 64 lanes
-// from its own cells, so the first one runs on all chunks with own cells that far from the visit's interior (chunks of march_rows)
-int launch_relax_visit(hipStream_t st, const KernelOpts &o, double *da, double *da_alt, const double *res, const SplitGeom &sg, int nl, const RelaxCoef &rc,
-                       int walls, const double *coarse, const SplitGeom &cg, const MarchCorrect &mc) {
-  const int rows = o.march_visit_rows, pairs = o.march_visit_pairs;
-  VisitGeom v;
-  if (!relax_visit_fits(nl, sg, rows, pairs)) return -1;
-  visit_geom(sg, rows, pairs, v);
-  constexpr int K = 4;
-  const int Hc = o.march_rows > 0 ? (o.march_rows + 1) & ~1 : 14, my = Hc + K;
-  const int vy1 = v.vy0 + v.nc * v.H, vx1 = v.vx0 + v.ns * 48;
-  const int skip_pl[4] = {v.vy0 + my, vy1 - my, v.vx0 + 64, vx1 - 64};
-  const int skip_corr[4] = {v.vy0, vy1, v.vx0, vx1};
-  if (launch_relax_march(st, o, nullptr, da_alt, res, sg, nl, rc, 0, K, walls, Hc, nullptr, coarse, &cg, nullptr, 1, nullptr, 0, skip_pl)) return -1;
-  MarchArgs a{};
-  a.res = res; a.g = sg; a.c1 = 0; a.walls = walls; a.rc = rc;
-  a.coarse = coarse; a.cg = cg;
-  a.psi = mc.psi; a.psi_out = mc.psi_out; a.ng = mc.g;
-  a.partial = 1; a.lean = 2;
-  a.remap = o.march_xcd; a.flip = o.march_flip;
-  a.H = v.H; a.vy0 = v.vy0; a.vx0 = v.vx0;
+static void visit_dispatch_nl(hipStream_t st, const MarchArgs &a, const VisitGeom &v, int pairs, int nl) {
   switch (nl) {
     case 2: visit_dispatch<2>(st, a, v, pairs); break;
     case 3: visit_dispatch<3>(st, a, v, pairs); break;
@@ -1340,5 +1472,60 @@ int launch_relax_visit(hipStream_t st, const KernelOpts &o, double *da, double *
     case 5: visit_dispatch<5>(st, a, v, pairs); break;
     case 6: visit_dispatch<6>(st, a, v, pairs); break;
   }
-  return launch_relax_march(st, o, da_alt, da, res, sg, nl, rc, 0, K, walls, Hc, nullptr, nullptr, nullptr, &mc, 0, nullptr, 0, skip_corr);
+}
+
+// PL + 4 half-sweeps (colour 0 first) and 4 + correction, the prolongation from `coarse`; da_alt receives the first pass's values
+// where the two passes run, da is not used.  The passes run on the chunks that are not the visit's: the second one (CORR) on
+// those with own cells outside the visit's rows / columns; it reads the first one's values up to ring_rows + K rows and 64 lanes
+// from its own cells, so the first one runs on all chunks with own cells that far from the visit's interior (chunks of march_rows).
+// march_visit_ring: 0 the two passes launch their whole chunk grids around the fused launch and the chunks inside the skip
+// rectangles return at once; 1 they launch only the ring chunks (visit_ring_bands); 2 the ring chunks are workgroups of the fused
+// launches: launch A = ring PL + the first fused chunk rows, launch B = ring CORR + the other fused chunk rows.  The ring CORR
+// chunks read what the ring PL chunks wrote, which the stream order of A and B provides; fused chunks depend on neither
+int launch_relax_visit(hipStream_t st, const KernelOpts &o, double *da, double *da_alt, const double *res, const SplitGeom &sg, int nl, const RelaxCoef &rc,
+                       int walls, const double *coarse, const SplitGeom &cg, const MarchCorrect &mc) {
+  const int rows = o.march_visit_rows, pairs = o.march_visit_pairs;
+  VisitGeom v;
+  if (!relax_visit_fits(nl, sg, rows, pairs)) return -1;
+  visit_geom(sg.hk, sg.ny, rows, pairs, v);
+  constexpr int K = 4;
+  const int Hc = visit_ring_rows(o.march_rows);
+  int skip_pl[4], skip_corr[4];
+  visit_skips(v, Hc, skip_pl, skip_corr);
+  if (o.march_dbg & 16) {   // timing experiment (results wrong): every ring chunk is skipped -- what the dispatch of the empty grids costs
+    for (int *s : {skip_pl, skip_corr}) { s[0] = 0; s[1] = sg.ny; s[2] = 0; s[3] = sg.hk; }
+  }
+  const int ringopt = o.march_visit_ring;
+  MarchArgs a{};
+  a.res = res; a.g = sg; a.c1 = 0; a.walls = walls; a.rc = rc;
+  a.coarse = coarse; a.cg = cg;
+  a.psi = mc.psi; a.psi_out = mc.psi_out; a.ng = mc.g;
+  a.partial = 1; a.lean = 2;
+  a.remap = o.march_xcd; a.flip = o.march_flip;
+  a.H = v.H; a.vy0 = v.vy0; a.vx0 = v.vx0;
+  if (ringopt >= 2) {
+    const int nwv = 2 * pairs;
+    a.fnbx = v.ns / pairs;
+    a.rH = Hc;
+    a.rlean = o.march_lean ? o.march_lean * (int)march_lean_fits(nl, sg, &mc.g) : 0;
+    // fused chunk rows of launch A: an even number, so that odd chunk rows stay the ones that march down.  A third of them:
+    // 4096^2 x 6 (145 chunk rows), ms per visit with 48 / 72 / 96 rows in launch A: 0.755 / 0.770 / 0.779
+    const int n1 = std::min(v.nc, (o.march_visit_split > 0 ? o.march_visit_split : v.nc / 3)) & ~1;
+    a.ring_kind = 1;
+    visit_ring_bands(sg.hk, sg.ny, 56, Hc, skip_pl, a.rb);
+    a.ring_wg = (a.rb.n + nwv - 1) / nwv;
+    a.fby0 = 0; a.fnby = n1;
+    a.rin = nullptr; a.rout = da_alt;
+    visit_dispatch_nl(st, a, v, pairs, nl);
+    a.ring_kind = 2;
+    visit_ring_bands(sg.hk, sg.ny, 60, Hc, skip_corr, a.rb);
+    a.ring_wg = (a.rb.n + nwv - 1) / nwv;
+    a.fby0 = n1; a.fnby = v.nc - n1;
+    a.rin = da_alt; a.rout = da;
+    visit_dispatch_nl(st, a, v, pairs, nl);
+    return 0;
+  }
+  if (launch_relax_march(st, o, nullptr, da_alt, res, sg, nl, rc, 0, K, walls, Hc, nullptr, coarse, &cg, nullptr, 1, nullptr, 0, skip_pl, ringopt == 1)) return -1;
+  visit_dispatch_nl(st, a, v, pairs, nl);
+  return launch_relax_march(st, o, da_alt, da, res, sg, nl, rc, 0, K, walls, Hc, nullptr, nullptr, nullptr, &mc, 0, nullptr, 0, skip_corr, ringopt == 1);
 }

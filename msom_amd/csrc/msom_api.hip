@@ -692,7 +692,7 @@ static int *kernel_opt(KernelOpts &o, const char *key) {
 #define KOPT(f) {#f, &KernelOpts::f}
   static const struct { const char *key; int KernelOpts::*f; } keys[] = {
       KOPT(march_rows), KOPT(march_xcd), KOPT(march_flip), KOPT(march_dbg), KOPT(march_lean), KOPT(march_dma),
-      KOPT(march_visit_rows), KOPT(march_visit_pairs), KOPT(resmax_rows), KOPT(block_variant), KOPT(rhs_dbg), KOPT(lpw_dbg)};
+      KOPT(march_visit_rows), KOPT(march_visit_pairs), KOPT(march_visit_ring), KOPT(march_visit_split), KOPT(resmax_rows), KOPT(block_variant), KOPT(rhs_dbg), KOPT(lpw_dbg)};
 #undef KOPT
   for (const auto &k : keys)
     if (!strcmp(key, k.key)) return &(o.*k.f);
@@ -796,6 +796,8 @@ extern "C" double msom_get_param(msom_t *m, const char *key) {
   if (!strcmp(key, "overlap")) return m->overlap;
   // which kernels the dispatch picks for this handle (bench.py names what ran from these, not from a table)
   if (!strcmp(key, "resmax_marching")) return m->uniformS && m->nl <= MSOM_FASTNL && m->g.nx >= 64 && m->g.ny >= 16 && m->opt.resmax_rows >= 0;
+  // how the wall-ring chunks around the fused visit run (-1: no fused visit on this handle), as launch_relax_visit reads the option
+  if (!strcmp(key, "march_visit_ring")) return !march_visit_fine(m) ? -1 : (m->opt.march_visit_ring >= 2 ? 2 : (m->opt.march_visit_ring == 1 ? 1 : 0));
   if (const int *o = kernel_opt(m->opt, key)) return *o;   // the handle's kernel options (march_rows, march_lean, ... rhs_dbg)
   if (!strcmp(key, "restrict2")) return restrict2_ok(m);   // the pre-cycle residual pass restricts two levels down
   if (!strcmp(key, "mg_coarse_lean")) return m->mgc_first >= 0 && m->mgc_lean;   // the coarse group runs in k_mg_coarse_lean
