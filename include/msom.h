@@ -113,7 +113,14 @@ int msom_destroy(msom_t *m);
 int msom_set_option(msom_t *m, const char *key, double value);
 /* parsed / derived parameters: N nx ny nl L0 DT iRe iRe4 CFL Rom tend dtout beta tau0 Ekb Eks
  * sbc idh0_<l> idh1_<l> Fr_<l> dh_<l> nlevels; the handle's kernel options march_rows march_xcd march_flip march_dbg
- * march_lean march_dma march_visit_rows march_visit_pairs march_visit_ring march_visit_split resmax_rows block_variant rhs_dbg lpw_dbg */
+ * march_lean march_dma march_visit_rows march_visit_pairs march_visit_ring march_visit_split resmax_rows block_variant rhs_dbg lpw_dbg.
+ * The paths the solve takes (after msom_set_const), each from the same function the dispatch calls: relax_path_<k> (level k's sweeps:
+ * 0 per-colour launches, 1 block2 -- two sweeps per LDS-tiled launch, an odd last sweep per colour, 2 block8 -- up to 8 half-sweeps
+ * per launch, 3 chained half-sweeps k_relax_march, 4 inside the one-launch coarse group k_mg_coarse; 8 + one of 0..3 for a level
+ * on the gathered global grid of a tiled run), march_levels (how many levels report 3), march_kmax (half-sweeps per chained pass),
+ * march_lean_fine (level 0 is chained with its interior chunks in the lean body), march_visit (1: the first action of level 0's
+ * visit in a cycle of 4 relaxations, asked the way the solve asks it, is the fused visit k_relax_visit) and march_visit_ring (how
+ * that visit runs its wall-ring chunks, 0 / 1 / 2; -1 where march_visit is 0, which overrides the option of the same name) */
 double msom_get_param(msom_t *m, const char *key);
 
 /* pyset_field / pyget_field, msqg/qg.h:1164-1188 (array [layer][y][x]; BC applied after set) */

@@ -138,7 +138,7 @@ struct msom {
                        // bound by the duration of their ~5-us kernels on the GPU, not by the host's launch rate: option "graph", off
   std::map<long, hipGraphExec_t> cyc_graph;
   int march_partial = 1; // a pass that is followed by more half-sweeps stores only the colour of its last half-sweep
-  int march_min_tiled = 22;  // the same threshold on tiles (see march_ok)
+  int march_min_tiled = 22;  // the same threshold on tiles (see sweep_path)
   int march_min = 23;    // log2 of the cell-layers a level needs for the chained pass (2^23: 2048^2 x 3 1.83 -> 1.78 ms/step, and the 2048 x 1024 x 6 tiles of BASELINE's 2 x 4 layout qualify; 2^22 loses: 1024^2 x 6 2.76 -> 2.87)
   int march_correct = 1; // the last pass of the finest level writes psi + da instead of da (psi rows by LDS-DMA, deferred write): 7.02 -> 6.86 ms per step at 4096^2 x 6
   int corr_req = 0, corr_done = 0;  // set around mg_cycle_levels by mg_solve / by the pass that did it
@@ -764,10 +764,11 @@ extern "C" int msom_set_option(msom_t *m, const char *key, double v) {
   return MSOM_OK;
 }
 
-static int march_levels(msom *m);
+static int march_levels(const msom *m);
 static int march_kmax(const msom *m);
-static bool march_lean_fine(msom *m);
-static bool march_visit_fine(msom *m);
+static bool march_lean_fine(const msom *m);
+static bool fine_visit_fused(const msom *m);
+static int level_path(const msom *m, int k);
 static bool restrict2_ok(const msom *m);
 extern "C" double msom_get_param(msom_t *m, const char *key) {
   if (!m || !key) return NAN;
@@ -797,7 +798,7 @@ extern "C" double msom_get_param(msom_t *m, const char *key) {
   // which kernels the dispatch picks for this handle (bench.py names what ran from these, not from a table)
   if (!strcmp(key, "resmax_marching")) return m->uniformS && m->nl <= MSOM_FASTNL && m->g.nx >= 64 && m->g.ny >= 16 && m->opt.resmax_rows >= 0;
   // how the wall-ring chunks around the fused visit run (-1: no fused visit on this handle), as launch_relax_visit reads the option
-  if (!strcmp(key, "march_visit_ring")) return !march_visit_fine(m) ? -1 : (m->opt.march_visit_ring >= 2 ? 2 : (m->opt.march_visit_ring == 1 ? 1 : 0));
+  if (!strcmp(key, "march_visit_ring")) return !fine_visit_fused(m) ? -1 : (m->opt.march_visit_ring >= 2 ? 2 : (m->opt.march_visit_ring == 1 ? 1 : 0));
   if (const int *o = kernel_opt(m->opt, key)) return *o;   // the handle's kernel options (march_rows, march_lean, ... rhs_dbg)
   if (!strcmp(key, "restrict2")) return restrict2_ok(m);   // the pre-cycle residual pass restricts two levels down
   if (!strcmp(key, "mg_coarse_lean")) return m->mgc_first >= 0 && m->mgc_lean;   // the coarse group runs in k_mg_coarse_lean
@@ -805,7 +806,8 @@ extern "C" double msom_get_param(msom_t *m, const char *key) {
   if (!strcmp(key, "march_min")) return m->march_min;   // log2 of the cell-layers a single-tile level needs for the chained pass
   if (!strcmp(key, "march_kmax")) return march_kmax(m);   // half-sweeps per marching pass that relax_sweeps allows
   if (!strcmp(key, "march_lean_fine")) return march_lean_fine(m);   // the finest level's interior chunks take the lean body
-  if (!strcmp(key, "march_visit")) return march_visit_fine(m);   // the finest level's 4 + 4 half-sweeps with the correction take k_relax_visit
+  if (!strcmp(key, "march_visit")) return fine_visit_fused(m);   // the finest level's 4 + 4 half-sweeps with the correction take k_relax_visit
+  if (!strncmp(key, "relax_path_", 11)) { const int k = atoi(key + 11); return k >= 0 && k < m->nlev ? level_path(m, k) : NAN; }   // RP_*
   if (!strcmp(key, "split_ls")) return m->nlev > 0 ? (double)m->sg[0].ls : NAN;   // doubles per layer of the finest split field
   auto idx = [](const char *s, int n) { const int k = atoi(s); return k >= 0 && k < n ? k : -1; };
   if (!strncmp(key, "idh0_", 5)) { const int k = idx(key + 5, MSOM_MAXNL); return k < 0 ? NAN : m->lc.idh0[k]; }
@@ -1139,80 +1141,157 @@ struct Lev {
   bool fine;    // level 0 (profiling tag)
   int k;        // tile level index (-1: gathered global level)
 };
-static Lev tile_lev(msom *m, int k) {
-  return Lev{&m->da[k], &m->da_alt[k], m->res[k], m->S[k], &m->sg[k], &m->rc[k], m->walls, m->nranks > 1, k == 0, k};
+static Lev tile_lev(const msom *m, int k) {   // (const handle: the functions that decide; the smoother swaps da / da_alt through the Lev)
+  return Lev{const_cast<double **>(&m->da[k]), const_cast<double **>(&m->da_alt[k]), m->res[k], m->S[k], &m->sg[k], &m->rc[k], m->walls, m->nranks > 1, k == 0, k};
 }
-static Lev glob_lev(msom *m, int k) {
+static Lev glob_lev(const msom *m, int k) {
   const int q = k - m->agg_level;
-  return Lev{&m->gda[q], &m->gda_alt[q], m->gres[q], nullptr, &m->gsg[q], &m->rc[k], m->bc == BC_PERIODIC ? WALL_PER : WALL_ALL, false, false, -1};
+  return Lev{const_cast<double **>(&m->gda[q]), const_cast<double **>(&m->gda_alt[q]), m->gres[q], nullptr, &m->gsg[q], &m->rc[k], m->bc == BC_PERIODIC ? WALL_PER : WALL_ALL, false, false, -1};
 }
 
-// can the level use the temporally blocked smoother (k_relax_block: 2 sweeps per pass)?
-static bool block_ok(msom *m, const Lev &L) {
-  const bool want = m->block_sweeps || (m->block_small && L.sg->nx <= m->block_small);
-  return want && m->uniformS && m->nl <= MSOM_FASTNL && !L.tiled && !(m->walls & WALL_PER) && L.sg->nx >= 64 && L.sg->ny >= 16;
-}
-// launch-bound levels (round 3): the prolongation and up to 8 colour half-sweeps of a level visit in ONE launch of the LDS-tiled
-// smoother with a halo of 8 (k_relax_block<.., 8>, option block8; levels of 64 .. block8_max cells a side that are not marched).
-// One GPU, walls or doubly periodic, nl <= 8 (the fast kernels' limit); uniform S, one layer, or a general S field.  Measured at 4096^2 x 6 / 512^2 x 3: see DESIGN.md section 4
-static bool march_ok(msom *m, const Lev &L);
-static bool block8_ok(msom *m, const Lev &L) {
-  // (a general S field: the kernel's GENERAL instantiation, S of the owned cells in registers; the gathered levels of a tiled run have no S array)
-  if (!m->block8 || m->block_sweeps || !(m->uniformS || m->nl == 1 || L.S) || m->nl > MSOM_FASTNL || L.tiled || (L.walls != WALL_ALL && L.walls != WALL_PER)) return false;
-  if (L.sg->nx < 64 || L.sg->ny < 16 || L.sg->nx > m->block8_max) return false;
-  // doubly periodic single tile: the kernel wraps its loads; the region (<= 48 x 32 cells) must not meet its own image; the gathered
-  // coarse levels of tiled runs keep their per-colour launches
-  if (L.walls == WALL_PER && (L.k < 0 || L.sg->ny < 64)) return false;
-  return !march_ok(m, L);
-}
-// can the level chain its half-sweeps in registers (k_relax_march)?  One GPU (no halo exchange between half-sweeps),
-// walls, uniform S, and a level big enough to be HBM-bound: a marching wavefront pays one memory latency per row, which
-// only ~2000 concurrent chunks hide (measured at nl = 6: 4096^2 1.54 -> 1.05 ms per 7 half-sweeps, 2048^2 385 -> 310 us,
-// but 1024^2 105 -> 238 us).  march = 2 forces it on every level that is wide enough (tests)
-static bool march_ok(msom *m, const Lev &L) {
-  // round 3: one layer (no vertical coupling: the column system is x = rhs / 4) and the doubly periodic single tile (deep
-  // halo = the field's own other side, launch_split_wrap) take the pass too
-  const bool walls_ok = L.tiled || L.walls == WALL_ALL || L.walls == WALL_PER;
-  if (!m->march || m->block_sweeps || !(m->uniformS || m->nl == 1) || m->nl > MSOM_FASTNL || !walls_ok || L.sg->nx < 512 || L.sg->ny < 64) return false;
-  if (!L.tiled && L.walls == WALL_PER && L.k < 0) return false;   // gathered coarse levels keep their per-colour launches
-  // tiles: one level more (2^22 cell-layers: 1024^2 x 6) -- on one GPU marching that level is neutral with the round-3 body (6.69 vs
+// which smoother a level visit takes -- the one statement of that choice: relax_sweeps, fuse_prolong, mg_cycle, march_levels and
+// msom_get_param("relax_path_<k>") all read it.  Precedence march > block8 > block2 > per-colour launches
+enum { RP_COLOUR = 0, RP_BLOCK2 = 1, RP_BLOCK8 = 2, RP_MARCH = 3, RP_COARSE = 4, RP_GATHERED = 8 };
+static int sweep_path(const msom *m, const Lev &L) {
+  const SplitGeom &g = *L.sg;
+  // chained half-sweeps in registers (k_relax_march).  One GPU (no halo exchange between half-sweeps) or tiles with deep halos,
+  // walls or the doubly periodic single tile (deep halo = the field's own other side, launch_split_wrap), uniform S or one layer
+  // (no vertical coupling: the column system is x = rhs / 4), and a level big enough to be HBM-bound: a marching wavefront pays one
+  // memory latency per row, which only ~2000 concurrent chunks hide (measured at nl = 6: 4096^2 1.54 -> 1.05 ms per 7 half-sweeps,
+  // 2048^2 385 -> 310 us, but 1024^2 105 -> 238 us).  march = 2 forces it on every level that is wide enough (tests).
+  // Tiles: one level more (2^22 cell-layers: 1024^2 x 6) -- on one GPU marching that level is neutral with the round-3 body (6.69 vs
   // 6.66 ms per step at 4096^2 x 6, 1.57 vs 1.56 at 2048^2 x 3), on tiles it replaces 8 per-colour halo exchanges of a level visit
-  // by 3 deep ones; unmeasured on more than one GPU (none available), so the threshold is a separate option
-  const int lg = L.tiled ? m->march_min_tiled : m->march_min;
-  return m->march >= 2 || (size_t)L.sg->nx * L.sg->ny * m->nl >= ((size_t)1 << lg);
+  // by 3 deep ones; unmeasured on more than one GPU (none available), so the threshold is a separate option.
+  // The gathered coarse levels of a periodic tiled run keep their per-colour launches
+  if (m->march && !m->block_sweeps && (m->uniformS || m->nl == 1) && m->nl <= MSOM_FASTNL && g.nx >= 512 && g.ny >= 64 &&
+      (L.tiled || L.walls == WALL_ALL || (L.walls == WALL_PER && L.k >= 0)) &&
+      (m->march >= 2 || (size_t)g.nx * g.ny * m->nl >= ((size_t)1 << (L.tiled ? m->march_min_tiled : m->march_min))))
+    return RP_MARCH;
+  // launch-bound levels (round 3): the prolongation and up to 8 colour half-sweeps of a level visit in ONE launch of the LDS-tiled
+  // smoother with a halo of 8 (k_relax_block<.., 8>, option block8; levels of 64 .. block8_max cells a side that are not marched).
+  // One GPU, walls or doubly periodic, nl <= 8 (the fast kernels' limit); uniform S, one layer, or a general S field (the kernel's
+  // GENERAL instantiation, S of the owned cells in registers; the gathered levels of a tiled run have no S array).  Doubly periodic
+  // single tile: the kernel wraps its loads; the region (<= 48 x 32 cells) must not meet its own image; the gathered coarse levels
+  // of tiled runs keep their per-colour launches.  Measured at 4096^2 x 6 / 512^2 x 3: see DESIGN.md section 4
+  if (m->block8 && !m->block_sweeps && (m->uniformS || m->nl == 1 || L.S) && m->nl <= MSOM_FASTNL && !L.tiled && g.nx >= 64 && g.ny >= 16 &&
+      g.nx <= m->block8_max && (L.walls == WALL_ALL || (L.walls == WALL_PER && L.k >= 0 && g.ny >= 64)))
+    return RP_BLOCK8;
+  // the temporally blocked smoother (k_relax_block: 2 sweeps per pass; an odd last sweep takes the per-colour launches): every
+  // level (option block_sweeps, which excludes the two paths above) or the levels of at most block_small cells a side
+  if ((m->block_sweeps || (m->block_small && g.nx <= m->block_small)) && m->uniformS && m->nl <= MSOM_FASTNL && !L.tiled &&
+      !(m->walls & WALL_PER) && g.nx >= 64 && g.ny >= 16)
+    return RP_BLOCK2;
+  return RP_COLOUR;
 }
-static int march_levels(msom *m) {
+// the path of level k as mg_cycle_levels visits it: inside the one-launch coarse group (k_mg_coarse), on the gathered global grid
+// of a tiled run (RP_GATHERED + the path there), or on this rank's tile
+static int level_path(const msom *m, int k) {
+  if (m->mgc_first >= 0 && k >= m->mgc_first) return RP_COARSE;
+  if (m->agg_level >= 0 && k >= m->agg_level) return RP_GATHERED + sweep_path(m, glob_lev(m, k));
+  return sweep_path(m, tile_lev(m, k));
+}
+// tile levels whose half-sweeps are chained
+static int march_levels(const msom *m) {
   int n = 0;
-  for (int k = 0; k < m->nlev && (m->agg_level < 0 || k < m->agg_level); k++) {
-    Lev L = tile_lev(m, k);
-    n += march_ok(m, L);
-  }
+  for (int k = 0; k < m->nlev; k++) n += level_path(m, k) == RP_MARCH;
   return n;
 }
 // is the finest level marched, with its interior chunks in the lean body (option march_lean, byte offsets within reach:
 // march_lean_fits, as launch_relax_march decides it for the passes of the level)?
-static bool march_lean_fine(msom *m) {
-  return m->nlev > 0 && m->opt.march_lean && march_ok(m, tile_lev(m, 0)) && march_lean_fits(m->nl, m->sg[0], &m->g);
-}
-// does the finest level's visit take k_relax_visit when it relaxes 4 + 4 half-sweeps with the prolongation and the correction?
-// One tile with walls, uniform S, nl = 2..6, the lean body, a level wide enough for one of its chunks and (march_visit = 1)
-// big enough to gain
-static bool march_visit_fine(msom *m) {
-  if (!m->march_visit || m->nlev < 2 || !m->opt.march_dma || !m->uniformS || m->nl < 2) return false;
-  const Lev L = tile_lev(m, 0);
-  if (m->march_visit < 2 && (size_t)L.sg->nx * L.sg->ny * m->nl < ((size_t)1 << m->march_visit_min)) return false;
-  return !L.tiled && L.walls == WALL_ALL && march_kmax(m) == 4 && m->march_prolong && m->march_partial && m->march_correct && m->mg_fused &&
-         march_lean_fine(m) && relax_visit_fits(m->nl, m->sg[0], m->opt.march_visit_rows, m->opt.march_visit_pairs);
+static bool march_lean_fine(const msom *m) {
+  return m->nlev > 0 && m->opt.march_lean && level_path(m, 0) == RP_MARCH && march_lean_fits(m->nl, m->sg[0], &m->g);
 }
 // is the prolongation coarse -> L folded into the first smoothing pass of L?
-static bool fuse_prolong(msom *m, const Lev &L, int nrelax) {
-  if (block_ok(m, L) && nrelax >= 2) return true;
-  if (block8_ok(m, L) && nrelax >= 1) return true;
+static bool fuse_prolong(const msom *m, const Lev &L, int nrelax) {
+  const int path = sweep_path(m, L);
+  if (path == RP_BLOCK2 && nrelax >= 2) return true;
+  if (path == RP_BLOCK8 && nrelax >= 1) return true;
   return m->prolong_fused && m->nl <= MSOM_FASTNL && nrelax >= 1 && L.sg->nx >= 4 && L.sg->ny >= 4;
 }
+// does the solve ask the last pass of the finest level for the correction (psi_alt = psi + da)?
+static bool corr_wanted(const msom *m) { return m->mg_fused && m->nlev > 1 && m->march_correct; }
 
 // half-sweeps per marching pass: march_k, but 4 register windows of 7 or 8 layers do not fit (launch_relax_march)
 static int march_kmax(const msom *m) { return m->nl >= 7 && m->march_k > 3 ? 3 : m->march_k; }
+
+// The schedule of a marched level visit, one action at a time: n half-sweeps are left, coarse != nullptr while L.da still has to
+// be interpolated from it, corr_req: the solve wants the finest level's last pass to apply the correction.
+//   MA_VISIT    the finest level's whole visit (prolongation + 4, 4 + correction) in k_relax_visit and the passes around it
+//   MA_PL       a pass of K half-sweeps whose input is interpolated from the coarse level on the fly, so that 2 nrelax half-sweeps are
+//               4 + 4 instead of (red + prolongation) + 4 + 3
+//   MA_REDPROL  the red half-sweep with the prolongation (in place), where the pass cannot carry it
+//   MA_PASS     a pass of K half-sweeps, out of place; corr: it applies the correction itself
+//   MA_HALF     a single left-over half-sweep, in place;  MA_DONE  nothing left
+// partial: more half-sweeps follow, the pass stores only the colour of its last one.  No pass leaves a single half-sweep behind
+// where a shorter one avoids it (K = 4 -> 3; a plain pass also 3 -> 2)
+enum { MA_DONE, MA_VISIT, MA_PL, MA_REDPROL, MA_PASS, MA_HALF };
+struct MarchAct { int kind, K; bool corr, partial; };
+static MarchAct march_next(const msom *m, const Lev &L, const Lev *coarse, int n, bool corr_req) {
+  const int kmax = march_kmax(m), nl = m->nl;
+  const bool deep = L.tiled || (L.walls & WALL_PER);   // the pass reads rows beyond the tile (relax_sweeps)
+  auto pass = [&](int kind, int kmin, bool corr_ok) {
+    int K = n < kmax ? n : kmax;
+    if (n - K == 1 && K > kmin) K--;
+    return MarchAct{kind, K, corr_ok && n == K, m->march_partial && n - K >= 1};
+  };
+  if (coarse && n > 0) {
+    // tiles: the pass then needs MARCH_HALO cells / rows of the COARSE correction beyond the tile edges too (LDS-DMA kernel, nl <= 6)
+    const bool pl_tiled = coarse->k >= 0 && nl <= 6 && m->march_prolong >= 1 && coarse->sg->nx >= 2 * MARCH_HALO && coarse->sg->ny >= 2 * MARCH_HALO;
+    if (n < 3 || kmax < 3 || !m->march_prolong || (deep && !pl_tiled)) return MarchAct{MA_REDPROL, 1, false, false};
+    // the fused visit: one tile with walls, uniform S, nl = 2..6, the lean body, a level wide enough for one of its chunks and
+    // (march_visit = 1) big enough to gain
+    if (n == 8 && kmax == 4 && L.fine && corr_req && m->march_visit && m->opt.march_dma && m->uniformS && nl >= 2 && m->march_partial &&
+        (m->march_visit >= 2 || (size_t)L.sg->nx * L.sg->ny * nl >= ((size_t)1 << m->march_visit_min)) && !L.tiled && L.walls == WALL_ALL &&
+        march_lean_fine(m) && relax_visit_fits(nl, *L.sg, m->opt.march_visit_rows, m->opt.march_visit_pairs))
+      return MarchAct{MA_VISIT, 8, true, false};
+    return pass(MA_PL, 3, false);
+  }
+  if (n >= 2) return pass(MA_PASS, 2, corr_req && L.fine);   // the very last pass of the finest level can apply the correction (mg_solve swaps)
+  return MarchAct{n == 1 ? MA_HALF : MA_DONE, n, false, false};
+}
+// the first action of the finest level's visit, asked the way mg_solve and level_solve ask it for nrelax = 4
+// (msom_get_param("march_visit"), ("march_visit_ring"))
+static bool fine_visit_fused(const msom *m) {
+  if (m->nlev < 2 || level_path(m, 0) != RP_MARCH) return false;
+  const Lev L = tile_lev(m, 0), C = tile_lev(m, 1);
+  return march_next(m, L, fuse_prolong(m, L, 4) ? &C : nullptr, 8, corr_wanted(m)).kind == MA_VISIT;
+}
+
+// level k's four deep-halo arrays of the chained smoother (MARCH_HALO rows each), allocated when a pass first needs them, as the
+// kernels take them: those of the correction and, res, of the residual; wrap: the doubly periodic single tile is its own neighbour
+static bool march_halo(msom *m, int k, bool wrap, bool res, MarchHalo *h) {
+  const auto arrays = {&m->mh_da_s, &m->mh_da_n, &m->mh_res_s, &m->mh_res_n};
+  if (m->mh_da_s.size() < (size_t)m->nlev)
+    for (auto *v : arrays) v->assign(m->nlev, nullptr);
+  const size_t ls = make_split(m->sg[k].nx, MARCH_HALO).ls, bytes = ls * m->nl * sizeof(double);
+  if (!m->mh_da_s[k])
+    for (auto *v : arrays) {
+      if (hipMalloc(&(*v)[k], bytes) != hipSuccess) { m->sticky = MSOM_ERR_HIP; return false; }
+      hipMemsetAsync((*v)[k], 0, bytes, m->st);
+    }
+  const bool s = wrap || m->nb[DIR_S] >= 0, n = wrap || m->nb[DIR_N] >= 0;
+  *h = MarchHalo{s ? m->mh_da_s[k] : nullptr, n ? m->mh_da_n[k] : nullptr, s && res ? m->mh_res_s[k] : nullptr, n && res ? m->mh_res_n[k] : nullptr, ls, MARCH_HALO};
+  return true;
+}
+// One marching pass.  launch(region) queues its chunks, halos() fills the deep halos it reads.  Tiles (option overlap): a pass is two
+// launches -- the chunks that read nothing beyond the tile (region 1) are queued on the compute stream FIRST, the deep halo exchanges
+// of the pass then run beside them on the communication stream, the chunks along the tile edges (region 2) follow once the halos
+// have arrived.  Chunks are independent (out of place), so the order changes no bit
+template <class Launch, class Halos>
+static void march_pass(msom *m, bool overlap, ProfSlot *ps, Launch launch, Halos halos) {
+  if (ps) prof_begin(m, *ps);
+  if (overlap) {
+    comm_begin(m); m->comm_hold = 1;
+    launch(1);
+    halos();
+    m->comm_hold = 0; comm_end(m);
+    launch(2);
+  } else {
+    halos();
+    launch(0);
+  }
+  if (ps) prof_end(m, *ps);
+}
 
 // nrelax red-black relaxations of L.da against L.res (each followed by boundary_level).
 // coarse != nullptr: L.da has not been prolongated yet -- the first pass interpolates it from
@@ -1220,144 +1299,65 @@ static int march_kmax(const msom *m) { return m->nl >= 7 && m->march_k > 3 ? 3 :
 static void relax_sweeps(msom *m, Lev &L, const Lev *coarse, int nrelax, int corners_last) {
   const bool prof = m->profile && L.fine;
   const int nl = m->nl;
+  const int path = sweep_path(m, L);
   int it = 0;
-  if (march_ok(m, L)) {
-    // 2 nrelax half-sweeps; the first red one may carry the prolongation (in place), the others go in passes of
-    // up to march_k, ping-ponging between the two correction buffers; a single left-over half-sweep runs in place.
+  if (path == RP_MARCH) {
+    // 2 nrelax half-sweeps in the actions of march_next; the passes ping-pong between the two correction buffers.
     // Tiles: a pass reads MARCH_HALO cells / rows of its neighbours (exchanged once per pass instead of once per
-    // half-sweep; the cone of dependence is re-computed, bit-identically, on both sides of the edge)
-    int n = 2 * nrelax, c = 0;
-    // doubly periodic single tile: the pass sees a tile without walls whose four neighbours are the tile itself; the deep
+    // half-sweep; the cone of dependence is re-computed, bit-identically, on both sides of the edge).
+    // Doubly periodic single tile: the pass sees a tile without walls whose four neighbours are the tile itself; the deep
     // halo (pads W / E, halo arrays S / N) is filled by local copies (launch_split_wrap) where tiles exchange
-    const bool wrap = !L.tiled && (L.walls & WALL_PER);
-    const bool deep = L.tiled || wrap;
+    const bool wrap = !L.tiled && (L.walls & WALL_PER), deep = L.tiled || wrap;
     const int kwalls = wrap ? 0 : L.walls;
-    auto deep_halo = [&](double *f, const SplitGeom &sg, double *fs, double *fn, const SplitGeom &hgeo) {
-      if (L.tiled) STICKY(m, exch_split_deep(m, f, sg, fs, fn, hgeo, nl));
-      else { launch_split_wrap(m->st, f, sg, fs, fn, hgeo, nl, MARCH_HALO, 0); launch_split_wrap(m->st, f, sg, fs, fn, hgeo, nl, MARCH_HALO, 1); }
+    // deep halo of level k's correction (pads W / E, halo arrays S / N) and, res, of its residual
+    auto fill_halo = [&](int k, bool res) {
+      double *f = res ? m->res[k] : m->da[k], *fs = res ? m->mh_res_s[k] : m->mh_da_s[k], *fn = res ? m->mh_res_n[k] : m->mh_da_n[k];
+      const SplitGeom hgeo = make_split(m->sg[k].nx, MARCH_HALO);
+      if (L.tiled) STICKY(m, exch_split_deep(m, f, m->sg[k], fs, fn, hgeo, nl));
+      else { launch_split_wrap(m->st, f, m->sg[k], fs, fn, hgeo, nl, MARCH_HALO, 0); launch_split_wrap(m->st, f, m->sg[k], fs, fn, hgeo, nl, MARCH_HALO, 1); }
     };
-    auto has_nb = [&](int dir) { return wrap || m->nb[dir] >= 0; };
-    MarchHalo mh{nullptr, nullptr, nullptr, nullptr, 0, MARCH_HALO};
-    SplitGeom hg = make_split(L.sg->nx, MARCH_HALO);
-    if (deep) {
-      const int k = L.k;
-      if (m->mh_da_s.size() < (size_t)m->nlev) {
-        m->mh_da_s.assign(m->nlev, nullptr); m->mh_da_n.assign(m->nlev, nullptr); m->mh_res_s.assign(m->nlev, nullptr); m->mh_res_n.assign(m->nlev, nullptr);
-      }
-      if (!m->mh_da_s[k]) {
-        for (auto *v : {&m->mh_da_s, &m->mh_da_n, &m->mh_res_s, &m->mh_res_n}) {
-          if (hipMalloc(&(*v)[k], hg.ls * nl * sizeof(double)) != hipSuccess) { m->sticky = MSOM_ERR_HIP; return; }
-          hipMemsetAsync((*v)[k], 0, hg.ls * nl * sizeof(double), m->st);
-        }
-      }
-      mh.ls = hg.ls;
-      mh.in_s = has_nb(DIR_S) ? m->mh_da_s[k] : nullptr; mh.in_n = has_nb(DIR_N) ? m->mh_da_n[k] : nullptr;
-      mh.res_s = has_nb(DIR_S) ? m->mh_res_s[k] : nullptr; mh.res_n = has_nb(DIR_N) ? m->mh_res_n[k] : nullptr;
-    }
-    // Tiles (option overlap): a pass is two launches -- the chunks that read nothing beyond the tile (region 1) are queued on
-    // the compute stream FIRST, the deep halo exchanges of the pass then run beside them on the communication stream, the
-    // chunks along the tile edges (region 2) follow once the halos have arrived.  Chunks are independent (out of place), so
-    // the order changes no bit.  The residual's deep halo is constant during the sweeps: it rides with the first pass.
+    MarchHalo mh{nullptr, nullptr, nullptr, nullptr, 0, MARCH_HALO}, ch = mh;
+    if (deep && !march_halo(m, L.k, wrap, true, &mh)) return;
     const bool ovl = L.tiled && m->overlap;
-    bool res_halo_done = !deep;
-    auto residual_halo = [&]() {
-      if (res_halo_done) return;
-      deep_halo(const_cast<double *>(L.res), *L.sg, m->mh_res_s[L.k], m->mh_res_n[L.k], hg);
-      res_halo_done = true;
-    };
-    const int kmax = march_kmax(m);
-    // tiles: the pass then needs MARCH_HALO cells / rows of the COARSE correction beyond the tile edges too (LDS-DMA kernel, nl <= 6)
-    const bool pl_tiled = deep && coarse && coarse->k >= 0 && nl <= 6 && m->march_prolong >= 1 && coarse->sg->nx >= 2 * MARCH_HALO && coarse->sg->ny >= 2 * MARCH_HALO;
-    if (coarse && n >= 3 && kmax >= 3 && (!deep || pl_tiled) && m->march_prolong) {
-      // the finest level's whole visit: one fused launch on the interior chunks, the two passes around it
-      if (n == 8 && L.fine && m->corr_req && march_visit_fine(m)) {
-        MarchCorrect mc{m->f[MSOM_PSI], m->psi_alt, m->g};
+    bool res_halo = deep;   // the residual's deep halo is constant during the sweeps: it rides with the first pass
+    const MarchCorrect mc{m->f[MSOM_PSI], m->psi_alt, m->g};
+    const Lev *src = coarse;
+    int n = 2 * nrelax, c = 0;
+    for (;;) {
+      const MarchAct a = march_next(m, L, src, n, m->corr_req);
+      if (a.kind == MA_HALF || a.kind == MA_DONE) break;
+      if (a.kind == MA_VISIT) {
         if (prof) prof_begin(m, m->prof_march_visit);
-        if (launch_relax_visit(m->st, m->opt, *L.da, *L.da_alt, L.res, *L.sg, nl, *L.rc, kwalls, *coarse->da, *coarse->sg, mc))
+        if (launch_relax_visit(m->st, m->opt, *L.da, *L.da_alt, L.res, *L.sg, nl, *L.rc, kwalls, *src->da, *src->sg, mc))
           m->sticky = MSOM_ERR_ARG;
         if (prof) prof_end(m, m->prof_march_visit);
         m->corr_done = 1;
         return;
-      }
-      // whole levels: the prolongation rides in the first PASS (its input is interpolated from the coarse level on
-      // the fly), so the 2 nrelax half-sweeps are 4 + 4 instead of (red + prolongation) + 4 + 3
-      int K = n < kmax ? n : kmax;
-      if (n - K == 1 && K > 3) K--;
-      MarchHalo ch{nullptr, nullptr, nullptr, nullptr, 0, MARCH_HALO};
-      if (deep) {   // deep halo of the coarse correction: pads W / E, halo arrays S / N (those of the coarse level's own passes)
-        const int ck = coarse->k;
-        SplitGeom chg = make_split(coarse->sg->nx, MARCH_HALO);
-        if (!m->mh_da_s[ck]) {
-          for (auto *v : {&m->mh_da_s, &m->mh_da_n, &m->mh_res_s, &m->mh_res_n}) {
-            if (hipMalloc(&(*v)[ck], chg.ls * nl * sizeof(double)) != hipSuccess) { m->sticky = MSOM_ERR_HIP; return; }
-            hipMemsetAsync((*v)[ck], 0, chg.ls * nl * sizeof(double), m->st);
-          }
-        }
-        ch.ls = chg.ls;
-        ch.in_s = has_nb(DIR_S) ? m->mh_da_s[ck] : nullptr; ch.in_n = has_nb(DIR_N) ? m->mh_da_n[ck] : nullptr;
-      }
-      auto pl_pass = [&](int region) {
-        if (launch_relax_march(m->st, m->opt, nullptr, *L.da_alt, L.res, *L.sg, nl, *L.rc, 0, K, kwalls, m->opt.march_rows, deep ? &mh : nullptr, *coarse->da, coarse->sg, nullptr,
-                               m->march_partial && n - K >= 1, deep ? &ch : nullptr, region))
-          m->sticky = MSOM_ERR_ARG;
-      };
-      auto pl_halos = [&]() {
-        residual_halo();
-        if (deep) deep_halo(*coarse->da, *coarse->sg, m->mh_da_s[coarse->k], m->mh_da_n[coarse->k], make_split(coarse->sg->nx, MARCH_HALO));
-      };
-      if (prof) prof_begin(m, m->prof_march_pl);
-      if (ovl) {
-        comm_begin(m); m->comm_hold = 1;
-        pl_pass(1);
-        pl_halos();
-        m->comm_hold = 0; comm_end(m);
-        pl_pass(2);
+      } else if (a.kind == MA_REDPROL) {
+        if (prof) prof_begin(m, m->prof_redprol);
+        launch_relax_red_prolong(m->st, m->opt, *L.da, *src->da, *src->sg, L.res, L.S, *L.sg, nl, *L.rc, m->uniformS, L.walls);
+        if (prof) prof_end(m, m->prof_redprol);
       } else {
-        pl_halos();
-        pl_pass(0);
+        const Lev *pl = a.kind == MA_PL ? src : nullptr;   // the pass reads the coarse level (and, deep, its halo) instead of L.da
+        if (pl && deep && !march_halo(m, pl->k, wrap, false, &ch)) return;
+        march_pass(m, ovl, !prof ? nullptr : (pl ? &m->prof_march_pl : (a.corr ? &m->prof_march_corr : &m->prof_march[a.K])),
+                   [&](int region) {
+                     if (launch_relax_march(m->st, m->opt, pl ? nullptr : *L.da, *L.da_alt, L.res, *L.sg, nl, *L.rc, c, a.K, kwalls, m->opt.march_rows, deep ? &mh : nullptr,
+                                            pl ? *pl->da : nullptr, pl ? pl->sg : nullptr, a.corr ? &mc : nullptr, a.partial, pl && deep ? &ch : nullptr, region))
+                       m->sticky = MSOM_ERR_ARG;
+                   },
+                   [&]() {
+                     if (res_halo) fill_halo(L.k, true);
+                     res_halo = false;
+                     if (deep) fill_halo(pl ? pl->k : L.k, false);
+                   });
+        if (a.corr) { m->corr_done = 1; return; }  // da of this level was consumed in registers; nothing reads it any more
+        std::swap(*L.da, *L.da_alt);
       }
-      if (prof) prof_end(m, m->prof_march_pl);
-      std::swap(*L.da, *L.da_alt);
-      n -= K; c = K & 1;
-    } else if (coarse && n > 0) {
-      if (prof) prof_begin(m, m->prof_redprol);
-      launch_relax_red_prolong(m->st, m->opt, *L.da, *coarse->da, *coarse->sg, L.res, L.S, *L.sg, nl, *L.rc, m->uniformS, L.walls);
-      if (prof) prof_end(m, m->prof_redprol);
-      n--; c = 1;
-    }
-    while (n >= 2) {
-      int K = n < kmax ? n : kmax;
-      if (n - K == 1 && K > 2) K--;
-      // the very last pass of the finest level can apply the correction itself: psi_alt = psi + da (mg_solve swaps)
-      const bool corr = m->corr_req && L.fine && n == K;
-      MarchCorrect mc{m->f[MSOM_PSI], m->psi_alt, m->g};
-      auto pass = [&](int region) {
-        if (launch_relax_march(m->st, m->opt, *L.da, *L.da_alt, L.res, *L.sg, nl, *L.rc, c, K, kwalls, m->opt.march_rows, deep ? &mh : nullptr, nullptr, nullptr,
-                               corr ? &mc : nullptr, m->march_partial && n - K >= 1, nullptr, region))
-          m->sticky = MSOM_ERR_ARG;
-      };
-      auto halos = [&]() {
-        residual_halo();
-        if (deep) deep_halo(*L.da, *L.sg, m->mh_da_s[L.k], m->mh_da_n[L.k], hg);
-      };
-      if (prof) prof_begin(m, corr ? m->prof_march_corr : m->prof_march[K]);
-      if (ovl) {
-        comm_begin(m); m->comm_hold = 1;
-        pass(1);
-        halos();
-        m->comm_hold = 0; comm_end(m);
-        pass(2);
-      } else {
-        halos();
-        pass(0);
-      }
-      if (prof) prof_end(m, corr ? m->prof_march_corr : m->prof_march[K]);
-      n -= K; c = (c + K) & 1;
-      if (corr) { m->corr_done = 1; return; }  // da of this level was consumed in registers; nothing reads it any more
-      std::swap(*L.da, *L.da_alt);
+      src = nullptr; n -= a.K; c = (c + a.K) & 1;
     }
     // periodic single tile: the passes wrote no ghost cell; boundary_level(da, l) = the wrapped copies, corners included
-    if (wrap) launch_split_wrap(m->st, *L.da, *L.sg, nullptr, nullptr, hg, nl, MARCH_HALO, 2);
+    if (wrap) launch_split_wrap(m->st, *L.da, *L.sg, nullptr, nullptr, make_split(L.sg->nx, MARCH_HALO), nl, MARCH_HALO, 2);
     if (n == 1) {
       if (L.tiled) STICKY(m, exch_split(m, *L.da, *L.sg, nl, 0));
       launch_relax_color(m->st, *L.da, L.res, L.S, *L.sg, nl, *L.rc, m->uniformS, c, L.walls, L.fine);
@@ -1366,7 +1366,7 @@ static void relax_sweeps(msom *m, Lev &L, const Lev *coarse, int nrelax, int cor
     if (L.tiled) STICKY(m, exch_split(m, *L.da, *L.sg, nl, corners_last));
     return;
   }
-  if (block8_ok(m, L)) {
+  if (path == RP_BLOCK8) {
     int n = 2 * nrelax, c = 0;
     const Lev *src = coarse;   // first pass: the correction is interpolated from the coarser level on the fly
     while (n > 0) {
@@ -1381,7 +1381,7 @@ static void relax_sweeps(msom *m, Lev &L, const Lev *coarse, int nrelax, int cor
     }
     return;
   }
-  if (block_ok(m, L)) {
+  if (path == RP_BLOCK2) {
     for (; it + 2 <= nrelax; it += 2) {
       const bool pl = coarse && it == 0;
       if (prof && !pl) prof_begin(m, m->prof_block);
@@ -1508,7 +1508,7 @@ static void mg_cycle(msom *m, int nrelax, int first_restrict) {
   bool ok = m->use_graph && m->nranks == 1 && !m->profile;   // (corr_req only acts inside a marching pass, excluded below)
   for (int k = 0; ok && k < m->nlev; k++) {
     Lev L = tile_lev(m, k);
-    if (march_ok(m, L) || block_ok(m, L) || block8_ok(m, L)) ok = false;   // those passes ping-pong between two buffers: pointers differ from cycle to cycle
+    if (sweep_path(m, L) != RP_COLOUR) ok = false;   // those passes ping-pong between two buffers: pointers differ from cycle to cycle
   }
   if (!ok) { mg_cycle_levels(m, nrelax, first_restrict); return; }
   const long key = (long)nrelax * 8 + first_restrict;
@@ -1622,7 +1622,7 @@ static int mg_solve(msom *m, const double *b, msom_mgstats *s) {
     have_first = true;
   }
   for (s->i = 0; s->i < p.nitermax && (s->i < p.nitermin || s->resa > p.tolerance); s->i++) {
-    m->corr_req = fused && m->march_correct;
+    m->corr_req = corr_wanted(m);
     m->corr_done = 0;
     // restrictions still to do: from level 1 (plain path), 2 (the residual pass restricted once) or 3 (twice; not when the residual
     // came out of the tendency pass, option rhs_resid)

@@ -1,7 +1,8 @@
 """The finest level's fused visit (k_relax_visit, option march_visit): prolongation + 4 half-sweeps and 4 half-sweeps +
 correction in one launch on the interior chunks, the two passes on the chunks around them.  Same lean bodies, same
 expression order => bit-identical to the two passes (option 0) in both builds; the dispatch is asserted through
-msom_get_param("march_visit") and the profile slot of the same name."""
+msom_get_param("march_visit"), which asks the schedule function the dispatch runs on (march_next), and the profile slot of the
+same name."""
 import numpy as np
 import pytest
 
@@ -80,6 +81,41 @@ def test_visit_fallback_with_adapted_nrelax(strict):
     a = run(2048, 2048, 3, strict, 1, 2, tol=1e-9)
     b = run(2048, 2048, 3, strict, 0, 2, tol=1e-9)
     same(a, b)
+
+
+@pytest.mark.parametrize("block_small", [0, 1024])
+@pytest.mark.parametrize("strict", [True, False])
+def test_visit_parameter_follows_the_dispatch_without_fused_prolongation(strict, block_small):
+    """prolong_fused = 0: the level is prolongated by its own kernel, the visit has no coarse level to interpolate and takes
+    neither k_relax_visit nor the PL pass -- the parameter says so (0, ring -1) and the profile slots count no launch; the
+    result is that of march_visit = 0 under the same option, bit for bit.  block_small = 1024 would admit block2 on every
+    level here, but only where neither march nor block8 applies: the marched finest level stays marched (path 3) and follows
+    prolong_fused like any marched level"""
+    nx, ny, nl = 1024, 512, 4
+
+    def one(visit):
+        txt = orc.double_gyre_params(nx, nl, extra=f"Ny = {ny}\n")
+        g = QG(txt, strict=strict)
+        g.option("quiet", 1)
+        g.set(F["PSI"], orc.synthetic_psi(nl, ny, nx))
+        g.set_const()
+        if strict:
+            g.option("uniform_S", 1)
+        for k, v in dict(march=2, march_visit=visit, prolong_fused=0, block_small=block_small).items():
+            g.option(k, v)
+        assert g.param("march_levels") >= 1 and g.param("relax_path_0") == 3.0
+        assert g.param("march_visit") == 0.0 and g.param("march_visit_ring") == -1.0
+        g.option("profile", 2)
+        g.profile_reset()
+        g.set_tnext(float("inf"))
+        out = dict(dts=[g.step() for _ in range(2)], psi=g.get(F["PSI"]), q=g.get(F["Q"]))
+        assert g.profile_read("march_visit")[1] == 0 and g.profile_read("march_pl")[1] == 0
+        assert g.profile_read("march_corr")[1] > 0     # the marched passes themselves ran
+        g.close()
+        return out
+    a, b = one(2), one(0)
+    assert a["dts"] == b["dts"]
+    assert np.array_equal(a["psi"], b["psi"]) and np.array_equal(a["q"], b["q"])
 
 
 def test_visit_against_oracle():

@@ -66,6 +66,30 @@ def run_cell(m, N, nl, tol, pre=None):
                 st=(st.i, st.resb, st.resa, st.nrelax))
 
 
+def expected_relax_paths(N, nl, march_min=23):
+    """msom_get_param("relax_path_<k>") of every level (N, N / 2, ... 2 cells a side) of one walled tile of N^2 x nl cells with
+    uniform S (or one layer) and no option set, written down from the documented thresholds (include/msom.h) and not read from
+    the build: 3 marched -- at least 512 x 64 cells and 2^march_min cell-layers; 2 block8 -- 64 .. 1024 cells a side where not
+    marched; 4 the one-launch coarse group, from 32 cells a side down; 0 per-colour launches -- whatever is left, and every
+    level above MSOM_FASTNL = 8 layers, where none of the register-resident kernels exists"""
+    paths, n = [], N
+    while n >= 2:
+        if nl > 8:
+            paths.append(0)
+        elif n <= 32:
+            paths.append(4)
+        elif n >= 512 and n * n * nl >= 2 ** march_min:
+            paths.append(3)
+        else:
+            paths.append(2 if 64 <= n <= 1024 else 0)
+        n //= 2
+    return tuple(paths)
+
+
+def relax_paths(g):
+    return tuple(int(g.param(f"relax_path_{k}")) for k in range(int(g.param("nlevels"))))
+
+
 def oracle_cell(case, smoother=orc.GS_RB):
     def compute():
         N, nl, tol = CASES[case]
@@ -88,6 +112,7 @@ def gpu_cell(case, strict):
         assert g.param("uniform_S") == 1
         assert N * N * nl >= 2 ** g.param("march_min")
         assert g.param("march_levels") >= 1
+        assert relax_paths(g) == expected_relax_paths(N, nl), relax_paths(g)   # C3: one marched level, C4: two
     g.close()
     return out
 

@@ -4,8 +4,8 @@ body, k_resmax_march<NL>, k_mg_coarse(_lean)<NL>, k_relax_block<NL, ..>, k_relax
 allocation and instruction schedule, and the one real bug of these paths (a hazard of the lean body's inline
 assembly) showed only at 2048^2 x 6 and 4096^2 x 6.  No kernel option is set.
 
-  nl1   4096^2 x 1   one layer (x = rhs / 4, no vertical coupling; uniform_S stays 0, march_ok admits nl = 1 in both builds)
-  nl2   2048^2 x 2   exactly 2^23 cell-layers: the >= of march_ok
+  nl1   4096^2 x 1   one layer (x = rhs / 4, no vertical coupling; uniform_S stays 0, sweep_path admits nl = 1 in both builds)
+  nl2   2048^2 x 2   exactly 2^23 cell-layers: the >= of sweep_path
   nl4   2048^2 x 4   NL = 4
   nl5   2048^2 x 5   odd: the lean body's DMA repeats the last layer (NLE = 6)
   nl7   2048^2 x 7   at most 3 half-sweeps per pass (march_kmax); odd; the coarse group too large for the lean LDS form
@@ -17,7 +17,8 @@ Each case runs at the reference tolerance 1e-3 (one cycle per solve: psi depends
 oracle's last solve for every case, asserted >= 3: nrelax adapts and passes of every allowed K run).  Three checks per case:
   1. strict build against the oracle, bit for bit (dq, q, psi, dtmax, dt, mgstats);
   2. product build against the oracle: equal cycle count and nrelax, dt to 1e-12, rel <= 1e-10 on dq, q and psi, after the path
-     switches of the handle are asserted (a moved threshold must fail here instead of quietly testing something else);
+     switches of the handle and the smoother of every level (relax_path_<k> against expected_relax_paths, a table written from
+     the documented thresholds) are asserted (a moved threshold must fail here instead of quietly testing something else);
   3. strict build with uniform_S = 1 (the strict build never takes the uniform-S path, so check 1 does not march except at
      nl = 1) against the same through REFERENCE_CHAIN (test_gpu_fullsize.py), bit for bit: this one sees an ulp in one cell.
 First measured product maxima (MI355X), rel(dq), rel(q), rel(psi), the larger of the two tolerances:
@@ -35,7 +36,7 @@ import pytest
 import orc
 from msom_amd import QG
 from test_gpu_fullsize import REFERENCE_CHAIN
-from test_gpu_oracle_fullsize import _cache, cached, run_cell
+from test_gpu_oracle_fullsize import _cache, cached, expected_relax_paths, relax_paths, run_cell
 from test_gpu_parity import rel
 
 pytestmark = pytest.mark.gpu
@@ -78,6 +79,7 @@ def gpu_layers(case, strict, opts=None):
     out = run_cell(g, N, nl, tol, pre)
     out["switch"] = {k: g.param(k) for k in ("uniform_S", "march_levels", "march_min", "march_kmax", "resmax_marching",
                                              "mg_coarse_lean", "restrict2")}
+    out["paths"] = relax_paths(g)
     g.close()
     return out
 
@@ -108,6 +110,7 @@ def test_default_kernels_equal_oracle_at_every_layer_count(case, strict):
     assert sw["march_levels"] == levels, sw
     assert sw["resmax_marching"] == resmax and sw["mg_coarse_lean"] == lean and sw["restrict2"] == 1, sw
     assert sw["march_kmax"] == kmax, sw
+    assert g["paths"] == expected_relax_paths(N, nl), g["paths"]   # the smoother of every level
     assert (g["st"][0], g["st"][3]) == (o["st"][0], o["st"][3])
     assert g["dt"] == pytest.approx(o["dt"], rel=1e-12)
     errs = {k: rel(g[k], o[k]) for k in ("dq", "q", "psi")}
@@ -121,7 +124,9 @@ def test_strict_chained_defaults_equal_reference_chain_at_every_layer_count(case
     nl, tol = CASES[case]
     a = gpu_layers(case, True, dict(uniform_S=1))
     b = gpu_layers(case, True, dict(REFERENCE_CHAIN, uniform_S=1))
-    assert b["switch"]["march_levels"] == 0
+    assert b["switch"]["march_levels"] == 0 and set(b["paths"]) == {0}     # march, block8 and mg_coarse are off: colour launches
+    assert a["switch"]["march_min"] == 23           # the threshold expected_relax_paths is written for
+    assert a["paths"] == expected_relax_paths(LAYERS[nl][0], nl), a["paths"]
     if nl <= 8:
         assert a["switch"]["march_levels"] == LAYERS[nl][1] >= 1, a["switch"]
     else:
