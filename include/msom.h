@@ -187,7 +187,7 @@ int msom_read_nc(msom_t *m, int field, const char *path, const char *varname, in
  * coefficients sig_lev from sig_filt = min(afilt * Rd, Lfmax), :1059-1090).  Saves q in tmp, inverts
  * q -> psi, removes from every layer of psi the wavelet details selected by sig_lev, recomputes q and
  * sets qof = (q_before - q_after) / dtflt; dtflt < 0 (energy diagnostics, qg_energy.h:213) restores q.
- * Single tile only. */
+ * Single tile or tiles (the pyramid levels above those that hold a cell of every tile are gathered on every rank). */
 int msom_wavelet_filter(msom_t *m, double dtflt);
 /* ---- energy / PV budgets, msqg/qg_energy.h (params key ediag: -1 off, 0: terms x (-psi), 1: PV terms).
  * msom_energy_tend = energy_tend (:227-241, event comp_diag :289-291): accumulates de_j1/j2/j3, de_vd,
@@ -287,7 +287,8 @@ typedef struct msomn msomn_t;
 msomn_t *msomn_create(const char *params_path);
 msomn_t *msomn_create_str(const char *params_text);
 void msomn_destroy(msomn_t *m);                                 /* trash_vars qg.h:537-544 */
-/* keys: TOLERANCE NITERMAX NITERMIN (nodal-poisson.h:19-23) DT quiet stochastic seed; implementation switches (result-preserving in
+/* keys: TOLERANCE NITERMAX NITERMIN (nodal-poisson.h:19-23) DT quiet stochastic seed (kept in the handle, and srand) noise_mode [0] (0: the
+ * noise is drawn from the serial rand() stream on the host, 1: on the device by k_n_noise; other values: MSOM_ERR_ARG); implementation switches (result-preserving in
  * the strict build): node_split [65] levels of >= that many vertices a side keep correction / residual / mask / S2 copies in the
  * x-parity split layout (0: off), s2_rows [1] row tables for an S2 that does not depend on x, node_pfused [1] prolongation folded into the first colour pass of the split levels, mg_coarse [32] levels of at most that
  * many cells a side in one launch, tiled_relax [0], node_march [0] (measured slower, kept for the tests), node_march_rows [0 = automatic] chunk height of the marching passes; round 3: node_march_s [2049] split
@@ -297,7 +298,8 @@ void msomn_destroy(msomn_t *m);                                 /* trash_vars qg
  * baroclinic tendency in three passes instead of the twelve loops of the reference, node_corr_fused [2] the correction of a cycle applied
  * inside the residual pass of the next (2: rows marched, 1: one thread per vertex, 0: separate passes), profile [0] */
 int msomn_set_option(msomn_t *m, const char *key, double value);
-/* keys: N nl L0 DT tend dtout nlevels iRd2_low bc_fac idh0_<l> idh1_<l>, the options node_march_s node_march_rows; NaN if unknown.
+/* keys: N nl L0 DT tend dtout nlevels iRd2_low bc_fac idh0_<l> idh1_<l>, the options node_march_s node_march_rows noise_mode seed,
+ * noise_draw (number of the next draw of the device generator; msomn_set_const: 0); NaN if unknown.
  * The paths the solve takes (after msomn_set_const), each from the same function the dispatch calls: sqg, s2_xuniform (S2 does not
  * depend on x: row tables), split_<k> (level k in the x-parity split layout), node_march_kmax (K cap of the chained split pass
  * k_n_relax_march_s: 4 for nl <= 4, 3 for nl 5-6, 0 where it cannot run: nl > 6 or no row tables), relax_path_<k> (level k's sweeps:
@@ -358,8 +360,14 @@ int msomn_dbg_del2_zeta(msomn_t *m);
 /* stochastic forcing of the vertex model (-D_STOCHASTIC: qg-node/qg_stochastic.h, qg-node/qg.h:306-320; params keys
  * amp_stoch, L_filt; option "stochastic" before msomn_set_const, option "seed" = srand).  The noise is a CELL
  * scalar (N x N), wavelet-filtered with the coefficients of the uniform length L_filt.  msomn_dbg_noise: optionally
- * set n_stoch, optionally filter it, optionally read it back; msomn_dbg_csig: sig_lev of one level. */
+ * set n_stoch, optionally filter it, optionally read it back; msomn_dbg_csig: sig_lev of one level.
+ * Option "noise_mode" = 1 draws on the device instead (k_n_noise): Philox-4x32-10 with the counter (cell j * N + i, 0, draw, "msom")
+ * and the key (seed, "MI35"), the layout of the cell-centred model's generator; the draw counter belongs to the handle, so handles
+ * with the same seed give the same sequence whatever else the process does.  msomn_noise_draw: the next draw into n_stoch (mode 1:
+ * device generator, advances the draw counter; mode 0: host stream), wavelet-filtered if filter != 0; MSOM_ERR_STATE when
+ * stochastic forcing is off. */
 int msomn_dbg_noise(msomn_t *m, const double *set, int filter, double *get);
+int msomn_noise_draw(msomn_t *m, int filter);
 int msomn_dbg_csig(msomn_t *m, int level, double *out);
 
 #ifdef __cplusplus

@@ -134,6 +134,7 @@ def load_library(strict=False):
         "msomn_dbg_del2_zeta": (ci, [vp]),
         "msomn_dbg_noise": (ci, [vp, vp, ci, vp]),
         "msomn_dbg_csig": (ci, [vp, ci, vp]),
+        "msomn_noise_draw": (ci, [vp, ci]),
         "msomn_wavelet_filter": (ci, [vp, cd]),
         "msomn_dbg_wv_get": (ci, [vp, ci, ci, vp]),
         "msomn_dbg_wv_apply": (ci, [vp, vp, vp]),
@@ -642,6 +643,11 @@ class NodeQG:
         a = None if set is None else _f64(set, (self.N, self.N))
         self._chk(self.L.msomn_dbg_noise(self.h, _ptr(a), int(filter), _ptr(out)))
         return out
+
+    def noise_draw(self, filter=True):
+        """the next draw into n_stoch (option noise_mode 1: device generator, 0: host rand() stream), wavelet-filtered if `filter`;
+        read it back with noise()"""
+        self._chk(self.L.msomn_noise_draw(self.h, int(filter)))
 
     def csig(self, k):
         n = self.N >> k

@@ -238,6 +238,7 @@ void launch_n_relax_prolong(hipStream_t st, double *a, const double *b, const do
                             double iRd2, const LayerCoef &lc, const double *S2row, const double *coarse, const NatGeom &cg, int csp);
 void launch_n_relayout(hipStream_t st, const double *src, const NatGeom &sg, int ssp, double *dst, const NatGeom &dg, int dsp, int nl);
 void launch_n_umax(hipStream_t st, const double *psi, double *out, const NatGeom &g, int nl, double D);
+void launch_n_noise(hipStream_t st, double *n, const NatGeom &g, double amp, unsigned seed, unsigned draw);  // cells and their ghost ring
 void launch_n_add_noise(hipStream_t st, double *q, const double *n, const NatGeom &g, const NatGeom &cg, double dts);
 void launch_n_diag1d(hipStream_t st, const double *psi, const double *q, const double *qf, double *partial, double *out3, const NatGeom &g, double nu, double D);
 void launch_n_ke(hipStream_t st, const double *psi, double *partial, double *out, const NatGeom &g, double D);

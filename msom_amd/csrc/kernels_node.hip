@@ -13,6 +13,7 @@
 // solve in red-black order ((i + j) even first), as for the cell-centred model.
 #include "kernels.h"
 #include "rhs_inl.h"
+#include "noise_inl.h"
 
 #ifdef MSOM_STRICT
 #define DIVC(x, c, rc) ((x) / (c))
@@ -1500,6 +1501,22 @@ void launch_n_ke(hipStream_t st, const double *psi, double *partial, double *out
   dim3 gr = grid2d(g.nx, g.ny);
   hipLaunchKernelGGL(k_n_ke, gr, block2d(), 0, st, psi, partial, g, D * D, 1. / (D * D));
   launch_sum_final(st, partial, out, (int)(gr.x * gr.y));
+}
+
+// device noise of the vertex model (option noise_mode = 1): one draw of the cell scalar n_stoch = amp * N(0, 1), the generator of
+// k_noise (noise_inl.h) with layer 0 and a grid g.nx cells wide, so cell (i, j) has the counter (j * nx + i, 0, draw, "msom").
+// The launch covers the (nx + 2) x (ny + 2) cells with the ghost ring (thread index n + 1 wraps to the ghost -1, so the interior
+// stores stay aligned); a ghost cell recomputes the draw of the cell it mirrors: the values launch_fill_ghost(BC_NEUMANN,
+// WALL_ALL) would write, corners included
+__global__ void k_n_noise(double *n, NatGeom g, double amp, unsigned seed, unsigned draw) {
+  const int ti = blockIdx.x * BX + threadIdx.x, tj = blockIdx.y * BY + threadIdx.y;
+  if (ti > g.nx + 1 || tj > g.ny + 1) return;
+  const int i = ti <= g.nx ? ti : -1, j = tj <= g.ny ? tj : -1;
+  const int si = i < 0 ? 0 : i >= g.nx ? g.nx - 1 : i, sj = j < 0 ? 0 : j >= g.ny ? g.ny - 1 : j;
+  n[nat_idx(g, 0, j, i)] = amp * philox_normal((uint32_t)sj * (uint32_t)g.nx + (uint32_t)si, 0u, draw, seed);
+}
+void launch_n_noise(hipStream_t st, double *n, const NatGeom &g, double amp, unsigned seed, unsigned draw) {
+  hipLaunchKernelGGL(k_n_noise, grid2d(g.nx + 2, g.ny + 2), block2d(), 0, st, n, g, amp, seed, draw);
 }
 
 // stochastic forcing, qg-node/qg.h:316-317: q_0[vertex (i, j)] += n_stoch[cell (i, j)] * dts; the cell field has N x N

@@ -62,6 +62,10 @@ struct msomn {
   int nitermax = 100, nitermin = 1, nrelax = 5, quiet = 0;  // nodal-poisson.h:19-23
   // stochastic forcing (-D_STOCHASTIC of the reference): cell-scalar noise n_stoch, wavelet-filtered (qg-node/qg_stochastic.h)
   int stochastic = 0, corrector_step = 0, cnlev = 0;
+  // option noise_mode: 0 the reference's serial rand() stream on the host (one per process), 1 the counter-based device generator
+  // k_n_noise, keyed by the handle's seed and numbered by the handle's draw counter (set_const: 0)
+  int noise_mode = 0;
+  unsigned seed = 1, noise_draw = 0;
   int pg_set = 0, topo_set = 0;   // psi_pg / topo have been set (zero until then: their terms of the tendency are skipped by k_n_rhs_all)
   int forcing_3d = 0;  // -DFORCING_3D: switched on by setting MSOMN_QFORC3D
   int sqg = 0;         // surface-QG variant (params key sqg): sqg_baroclinic_ms.h:77-98,502,545-547
@@ -331,7 +335,11 @@ extern "C" int msomn_set_option(msomn_t *m, const char *key, double v) {
   else if (!strcmp(key, "node_march_rows")) m->node_march_rows = (int)v;
   else if (!strcmp(key, "mg_coarse")) { m->mg_coarse = (int)v; if (m->const_set) return choose_layouts(m); }
   else if (!strcmp(key, "stochastic")) m->stochastic = (int)v;
-  else if (!strcmp(key, "seed")) srand((unsigned)v);
+  else if (!strcmp(key, "seed")) { m->seed = (unsigned)v; srand(m->seed); }
+  else if (!strcmp(key, "noise_mode")) {
+    if (v != 0. && v != 1.) { msom_set_error("noise_mode = %g: 0 (serial rand() stream on the host) or 1 (device generator)", v); return MSOM_ERR_ARG; }
+    m->noise_mode = (int)v;
+  }
   else { msom_set_error("unknown option %s", key); return MSOM_ERR_ARG; }
   return MSOM_OK;
 }
@@ -395,6 +403,9 @@ extern "C" double msomn_get_param(msomn_t *m, const char *k) {
   if (!strcmp(k, "bc_fac")) return m->p.bc_fac;
   if (!strcmp(k, "sqg")) return m->sqg;
   if (!strcmp(k, "s2_xuniform")) return m->s2_xuniform;
+  if (!strcmp(k, "noise_mode")) return m->noise_mode;
+  if (!strcmp(k, "seed")) return m->seed;
+  if (!strcmp(k, "noise_draw")) return m->noise_draw;   // number of the next draw of the device generator
   if (!strcmp(k, "node_march_s")) return m->node_march_s;   // split levels of >= this many vertices a side take k_n_relax_march_s
   if (!strcmp(k, "node_march_rows")) return m->node_march_rows;
   if (!strncmp(k, "split_", 6)) { int l = atoi(k + 6); return l >= 0 && l < m->nlev ? m->lev[l].sp : NAN; }
@@ -826,9 +837,10 @@ static int stoch_setup(msomn *m) {  // pyramids of the cell scalar + wavelet coe
 }
 static void cell_bc(msomn *m, double *f, const NatGeom &g) { launch_fill_ghost(m->st, f, g, 1, BC_NEUMANN, WALL_ALL); }
 // wavelet -> scale by sig_lev -> inverse wavelet of the cell field cs[0] (kernels_wavelet.hip, one layer, default BC)
-static int cell_wavelet_filter(msomn *m) {
+// ghosts_set: the ghost ring of cs[0] is already what cell_bc would write (k_n_noise)
+static int cell_wavelet_filter(msomn *m, int ghosts_set = 0) {
   const int K = m->cnlev;
-  cell_bc(m, m->cs[0], m->cg[0]);
+  if (!ghosts_set) cell_bc(m, m->cs[0], m->cg[0]);
   for (int k = 1; k < K; k++) {
     launch_wv_restrict(m->st, m->cs[k - 1], m->cg[k - 1], m->cs[k], m->cg[k], 1);
     cell_bc(m, m->cs[k], m->cg[k]);
@@ -853,9 +865,16 @@ static int upload_cells(msomn *m, const double *a) {
   cell_bc(m, m->cs[0], g);
   return MSOM_OK;
 }
-// reference-exact noise: Box-Muller on the serial rand() stream in foreach order (x outer, y inner), qg_stochastic.h:13,51-53
-static int generate_noise(msomn *m) {
+// noise_mode 0, reference-exact noise: Box-Muller on the serial rand() stream in foreach order (x outer, y inner),
+// qg_stochastic.h:13,51-53.  noise_mode 1: the handle's next draw of the device generator with its ghost ring, then the filter,
+// all queued on the handle's stream (no host buffer, no synchronisation)
+static int generate_noise(msomn *m, int filter = 1) {
   const int N = m->N;
+  if (m->noise_mode == 1) {
+    launch_n_noise(m->st, m->cs[0], m->cg[0], m->p.amp_stoch, m->seed, m->noise_draw++);
+    HIPCHK(hipGetLastError());
+    return filter ? cell_wavelet_filter(m, 1) : MSOM_OK;
+  }
   std::vector<double> h((size_t)N * N);
   for (int i = 0; i < N; i++)
     for (int j = 0; j < N; j++) {
@@ -863,7 +882,12 @@ static int generate_noise(msomn *m) {
       h[(size_t)j * N + i] = m->p.amp_stoch * (a * cos(2 * M_PI * rand() / (double)RAND_MAX));
     }
   int r = upload_cells(m, h.data());
-  return r ? r : cell_wavelet_filter(m);
+  return r || !filter ? r : cell_wavelet_filter(m);
+}
+extern "C" int msomn_noise_draw(msomn_t *m, int filter) {
+  NEED_NCONST(m);
+  if (m->cnlev == 0) { msom_set_error("stochastic forcing is off"); return MSOM_ERR_STATE; }
+  return generate_noise(m, filter);
 }
 extern "C" int msomn_dbg_noise(msomn_t *m, const double *set, int filter, double *get) {
   NEED_NCONST(m);
@@ -1060,6 +1084,7 @@ extern "C" int msomn_set_const(msomn_t *m) {
   } else if (p.gp_low != 0.) m->iRd2_low = p.f0 * p.f0 / (p.gp_low * p.dh[nl - 1]);
   if ((r = build_levels(m))) return r;
   if (m->stochastic && (r = stoch_setup(m))) return r;  // event init_stoch
+  m->noise_draw = 0;
   bnd_psi(m);
   if (p.nu != 0) p.DT = 0.5 * fmin(p.DT, m->D * m->D / p.nu / 4.);  // qg-node/qg.h:511-512
   if (p.beta != 0) p.DT = fmin(p.DT, 1 / (2. * p.beta * p.L0));
