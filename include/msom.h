@@ -61,7 +61,13 @@ enum {
   /* energy / PV budgets (msqg/qg_energy.h:7-15), nl layers each, allocated on first use */
   MSOM_DE_BF = 21, MSOM_DE_VD = 22, MSOM_DE_J1 = 23, MSOM_DE_J2 = 24, MSOM_DE_J3 = 25, MSOM_DE_FT = 26,
   MSOM_TMP2 = 27, MSOM_PO_MFT = 28,
-  MSOM_NFIELDS = 29
+  /* back-and-forth nudging on the device (msom_bfn_*): the arrays of the loop of msqg/qg_bfn.py:47-73, nl layers each, allocated on first use */
+  MSOM_BFN_F1 = 29,   /* F1  newest AB3 history slot: the nudged tendency of the step being taken (msqg/qg_bfn.py:49,65-68) */
+  MSOM_BFN_F2 = 30,   /* F2  second AB3 history slot (:50,73) */
+  MSOM_BFN_F3 = 31,   /* F3  oldest AB3 history slot (:51,72) */
+  MSOM_BFN_OBS = 32,  /* observed PV, the target of the nudging term ("BFN nudging goes here", :67-68) */
+  MSOM_BFN_GAIN = 33, /* nudging gain per cell-layer, zero where nothing is observed; never set: 1 everywhere */
+  MSOM_NFIELDS = 34
 };
 
 /* mgstats of Basilisk (text: mspg/elliptic.h:118-123), kept by the reference in `mgpsi`
@@ -153,6 +159,25 @@ int pystep_bfn(msom_t *m, double *varin_py, int len1, int len2, int len3, double
                int len6, double direction, int vartype);
 int pyq2p(msom_t *m, double *po_py, int len7, int len8, int len9, double *qo_py, int len10, int len11, int len12);
 int pyp2q(msom_t *m, double *po_py, int len13, int len14, int len15, double *qo_py, int len16, int len17, int len18);
+/* ---- the time loop around pystep_bfn, msqg/qg_bfn.py:47-73 (Adams-Bashforth 3 in numpy on the caller's side, "BFN nudging goes
+ * here" :67-68), run on the library's stream with the state in device memory.  The evolving variable is the handle's MSOM_Q
+ * (msom_set_field), the observations and the gain are MSOM_BFN_OBS / MSOM_BFN_GAIN, the history is MSOM_BFN_F1..F3; all five take
+ * msom_set_field / msom_get_field (observation input, restart of the history).
+ * msom_bfn_begin: F1 = F2 = F3 = 0 (:49-51; the AB3 weights apply from the first step on, as there).
+ * msom_bfn_steps, nsteps times: F1 = tendency of q exactly as pystep_bfn(vartype = 1, direction) computes it (:65; the sign flips of
+ * iRe, iRe4, Eks, Ekb persist in the handle, the warm start psi and the dt limiter end up where nsteps pystep_bfn calls leave them);
+ *   F1 = F1 + (k * gain) * (obs - q)                      (k == 0: the term is skipped, obs and gain are not read)
+ *   q  = q + (dt / 12) * ((23 * F1 - 16 * F2) + 5 * F3)   (:71; this expression order is the contract of the strict build)
+ * boundary(q), then the slots rotate F1 -> F2 -> F3 -> F1 (:72-73 without the copies): on return F2 holds the newest nudged tendency,
+ * F3 the one before it and F1 the oldest, which the next step overwrites.  dt is the caller's, signed: backward integration passes
+ * dt < 0, direction = -1 and the sign of k it wants.  Time and iteration count of the handle do not change (pystep_bfn leaves them
+ * alone).  nsteps == 0: no-op; nsteps < 0: MSOM_ERR_ARG; no msom_bfn_begin since msom_set_const, or k != 0 with MSOM_BFN_OBS never
+ * set: MSOM_ERR_STATE.  Returns at the first error; the stream is synchronised on return.
+ * msom_bfn_misfit: sqrt(sum gain (obs - q)^2 / sum gain) over every cell-layer of the domain (all tiles; collective there), by the
+ * deterministic two-stage sums; MSOM_ERR_STATE without observations. */
+int msom_bfn_begin(msom_t *m);
+int msom_bfn_steps(msom_t *m, int nsteps, double dt, double direction, double k);
+int msom_bfn_misfit(msom_t *m, double *misfit);
 
 /* ---- time loop of Basilisk predictor-corrector run() as driven by msqg/qg.c
  * msom_step: one RK2 step on the internal state (update, dtnext, advance dt/2, update,

@@ -13,6 +13,9 @@ from .api import (  # noqa: F401
     NODE_FIELDS,
     NodeQG,
     QG,
+    bfn_begin,
+    bfn_misfit,
+    bfn_steps,
     init_grid,
     load_library,
     pyp2q,
@@ -29,5 +32,5 @@ from .api import (  # noqa: F401
 
 __all__ = [
     "QG", "NodeQG", "NODE_FIELDS", "MGStats", "MsomError", "FIELDS", "load_library", "read_params", "init_grid", "set_vars",
-    "set_vars_bfn", "set_const", "pystep_bfn", "pystep_de", "pyq2p", "pyp2q", "trash_vars", "trash_vars_bfn",
+    "set_vars_bfn", "set_const", "pystep_bfn", "bfn_begin", "bfn_steps", "bfn_misfit", "pystep_de", "pyq2p", "pyp2q", "trash_vars", "trash_vars_bfn",
 ]

@@ -10,7 +10,8 @@ _LIBDIR = os.path.join(_HERE, "lib")
 
 FIELDS = dict(PSI=0, Q=1, ZETA=2, PSIPG=3, ZETAPG=4, QFORC=5, TMP=6, FR=7, S=8, DQ=9, RO=10, TOPO=11,
               QPRED=12, NOISE=13, SIGMA=14, PTR=15, PTR_RELAX=16, DPTR=17, PTR_PRED=18, RD=19, QOF=20,
-              DE_BF=21, DE_VD=22, DE_J1=23, DE_J2=24, DE_J3=25, DE_FT=26, TMP2=27, PO_MFT=28)
+              DE_BF=21, DE_VD=22, DE_J1=23, DE_J2=24, DE_J3=25, DE_FT=26, TMP2=27, PO_MFT=28,
+              BFN_F1=29, BFN_F2=30, BFN_F3=31, BFN_OBS=32, BFN_GAIN=33)
 
 
 class MsomError(RuntimeError):
@@ -62,6 +63,9 @@ def load_library(strict=False):
         "pystep_bfn": (ci, [vp, vp, ci, ci, ci, vp, ci, ci, ci, cd, ci]),
         "pyq2p": (ci, [vp, vp, ci, ci, ci, vp, ci, ci, ci]),
         "pyp2q": (ci, [vp, vp, ci, ci, ci, vp, ci, ci, ci]),
+        "msom_bfn_begin": (ci, [vp]),
+        "msom_bfn_steps": (ci, [vp, ci, cd, cd, cd]),
+        "msom_bfn_misfit": (ci, [vp, _dp]),
         "msom_step": (ci, [vp, _dp]),
         "msom_set_tnext": (ci, [vp, cd]),
         "msom_time": (cd, [vp]),
@@ -209,7 +213,10 @@ class QG:
 
     # -- fields (pyset_field / pyget_field, msqg/qg.h:1164-1188)
     def shape(self, field):
-        return (self.L.msom_field_layers(self.h, field), self.ny, self.nx)
+        n = self.L.msom_field_layers(self.h, field)
+        if n < 0 and FIELDS["BFN_F1"] <= field <= FIELDS["BFN_GAIN"]:
+            n = self.nl     # allocated by the first msom_set_field / msom_get_field / msom_bfn_begin
+        return (n, self.ny, self.nx)
 
     def set(self, field, a):
         a = _f64(a, self.shape(field))
@@ -273,6 +280,22 @@ class QG:
         p = _f64(p)
         assert q.dtype == np.float64 and q.flags.c_contiguous
         self._chk(self.L.pyp2q(self.h, _ptr(p), *p.shape, _ptr(q), *q.shape))
+
+    # -- the loop of msqg/qg_bfn.py:47-73 on the device; state Q, observations BFN_OBS, gain BFN_GAIN, history BFN_F1..F3
+    def bfn_begin(self):
+        """zero AB3 history (msqg/qg_bfn.py:49-51)"""
+        self._chk(self.L.msom_bfn_begin(self.h))
+
+    def bfn_steps(self, nsteps, dt, direction=1.0, k=0.0):
+        """nsteps times: F1 = pystep_bfn tendency of Q + (k * gain) * (obs - Q); Q += dt / 12 * (23 F1 - 16 F2 + 5 F3); rotate the history.
+        dt is signed (backward: dt < 0, direction = -1)."""
+        self._chk(self.L.msom_bfn_steps(self.h, int(nsteps), float(dt), float(direction), float(k)))
+
+    def bfn_misfit(self):
+        """sqrt(sum gain (obs - Q)^2 / sum gain)"""
+        out = C.c_double()
+        self._chk(self.L.msom_bfn_misfit(self.h, C.byref(out)))
+        return out.value
 
     # -- time loop
     def step(self):
@@ -442,6 +465,20 @@ def set_const():
 
 def pystep_bfn(var, tend, direction, vartype):
     _state["model"].pystep_bfn(var, tend, direction, vartype)
+
+
+def bfn_begin():
+    _state["model"].bfn_begin()
+
+
+def bfn_steps(nsteps, dt, direction=1.0, k=0.0):
+    """the loop of msqg/qg_bfn.py:62-73 on the device; state and inputs through the model's fields
+    (FIELDS: Q, BFN_OBS, BFN_GAIN, BFN_F1..F3)"""
+    _state["model"].bfn_steps(nsteps, dt, direction, k)
+
+
+def bfn_misfit():
+    return _state["model"].bfn_misfit()
 
 
 def pyq2p(p, q):

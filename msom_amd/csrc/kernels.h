@@ -62,6 +62,12 @@ void launch_forcing(hipStream_t st, const double *zeta, const double *psi, const
                     double D, double dhb);
 void launch_advance(hipStream_t st, double *qo, const double *qi, const double *dq, const double *noise, const NatGeom &g, int nl, double dt,
                     double dts);
+// nudging + AB3 update of msom_bfn_steps; obs == nullptr: no nudging term, gain == nullptr: gain 1
+void launch_bfn_ab3(hipStream_t st, double *q, double *f1, const double *f2, const double *f3, const double *obs, const double *gain,
+                    const NatGeom &g, int nl, double dt12, double k);
+int bfn_misfit_blocks(const NatGeom &g);
+void launch_bfn_misfit(hipStream_t st, const double *q, const double *obs, const double *gain, double *partial, double *out2, const NatGeom &g,
+                       int nl);
 int partial_count(const NatGeom &g);
 void launch_sum_final(hipStream_t st, const double *partial, double *out, int n);
 void launch_ke(hipStream_t st, const double *po, double *partial, double *out, const NatGeom &g, double D);

@@ -450,6 +450,53 @@ void launch_advance(hipStream_t st, double *qo, const double *qi, const double *
   hipLaunchKernelGGL(k_advance, grid2d(g.nx, g.ny), block2d(), 0, st, qo, qi, dq, noise, g, nl, dt, dts);
 }
 
+// nudging + Adams-Bashforth 3 update of msom_bfn_steps (the loop body of msqg/qg_bfn.py:67-71 after pystep_bfn):
+//   f1 = tend + (k gain) (obs - q);  q = q + (dt / 12) ((23 f1 - 16 f2) + 5 f3)
+// f1 holds the tendency on entry and the nudged tendency on exit.  Memory-bound: 6 fields read and 2 written with the nudging
+// term, 4 and 1 without.  One thread owns two x-adjacent interior cells of every layer (row starts are 128-byte aligned and the
+// pair starts on an even cell: 16-byte accesses, 1 KiB per wavefront instruction); a last odd cell goes alone.  Pads and ghost
+// cells are not written.  The strict build keeps the expression order above (-ffp-contract=off), the product build may contract.
+template <bool NUDGE, bool GAIN>
+__device__ __forceinline__ void bfn_cell(double &q, double &f1, double f2, double f3, double obs, double gain, double dt12, double kn) {
+  if (NUDGE) f1 = f1 + (GAIN ? kn * gain : kn) * (obs - q);
+  q = q + dt12 * ((23. * f1 - 16. * f2) + 5. * f3);
+}
+template <bool NUDGE, bool GAIN>
+__global__ void __launch_bounds__(BX *BY) k_bfn_ab3(double *q, double *f1, const double *__restrict__ f2, const double *__restrict__ f3,
+                                                    const double *__restrict__ obs, const double *__restrict__ gain, NatGeom g, int nl,
+                                                    double dt12, double kn) {
+  const int i = 2 * (blockIdx.x * BX + threadIdx.x), j = blockIdx.y * BY + threadIdx.y;
+  if (i >= g.nx || j >= g.ny) return;
+  size_t c = nat_idx(g, 0, j, i);
+  if (i + 1 < g.nx) {
+    for (int l = 0; l < nl; l++, c += g.ls) {
+      double2 vq = *reinterpret_cast<const double2 *>(q + c), v1 = *reinterpret_cast<const double2 *>(f1 + c);
+      const double2 v2 = *reinterpret_cast<const double2 *>(f2 + c), v3 = *reinterpret_cast<const double2 *>(f3 + c);
+      double2 vo = make_double2(0., 0.), vg = make_double2(1., 1.);
+      if (NUDGE) vo = *reinterpret_cast<const double2 *>(obs + c);
+      if (NUDGE && GAIN) vg = *reinterpret_cast<const double2 *>(gain + c);
+      bfn_cell<NUDGE, GAIN>(vq.x, v1.x, v2.x, v3.x, vo.x, vg.x, dt12, kn);
+      bfn_cell<NUDGE, GAIN>(vq.y, v1.y, v2.y, v3.y, vo.y, vg.y, dt12, kn);
+      if (NUDGE) *reinterpret_cast<double2 *>(f1 + c) = v1;
+      *reinterpret_cast<double2 *>(q + c) = vq;
+    }
+  } else {
+    for (int l = 0; l < nl; l++, c += g.ls) {
+      double vq = q[c], v1 = f1[c];
+      bfn_cell<NUDGE, GAIN>(vq, v1, f2[c], f3[c], NUDGE ? obs[c] : 0., (NUDGE && GAIN) ? gain[c] : 1., dt12, kn);
+      if (NUDGE) f1[c] = v1;
+      q[c] = vq;
+    }
+  }
+}
+void launch_bfn_ab3(hipStream_t st, double *q, double *f1, const double *f2, const double *f3, const double *obs, const double *gain,
+                    const NatGeom &g, int nl, double dt12, double k) {
+  const dim3 gr(((g.nx + 1) / 2 + BX - 1) / BX, (g.ny + BY - 1) / BY);
+  if (!obs) hipLaunchKernelGGL((k_bfn_ab3<false, false>), gr, block2d(), 0, st, q, f1, f2, f3, obs, gain, g, nl, dt12, k);
+  else if (!gain) hipLaunchKernelGGL((k_bfn_ab3<true, false>), gr, block2d(), 0, st, q, f1, f2, f3, obs, gain, g, nl, dt12, k);
+  else hipLaunchKernelGGL((k_bfn_ab3<true, true>), gr, block2d(), 0, st, q, f1, f2, f3, obs, gain, g, nl, dt12, k);
+}
+
 // ------------------------------------------------------------------ sums (deterministic two-stage)
 
 // stage 1: one partial per block; stage 2: a single block adds the partials in index order
@@ -534,6 +581,41 @@ void launch_ke(hipStream_t st, const double *po, double *partial, double *out, c
   dim3 gr = grid2d(g.nx, g.ny);
   hipLaunchKernelGGL(k_ke_partial, gr, block2d(), 0, st, po, partial, g, D2, 1. / D2);
   hipLaunchKernelGGL(k_sum_final, dim3(1), dim3(256), 0, st, partial, out, (int)(gr.x * gr.y));
+}
+// msom_bfn_misfit: sum gain (obs - q)^2 and sum gain over the interior cells of every layer (gain == nullptr: 1), same two stages.
+// partial holds two arrays of bfn_misfit_blocks(g) + SUM_CHUNKS entries, out2 the two sums.
+__global__ void k_bfn_misfit_partial(const double *__restrict__ q, const double *__restrict__ obs, const double *__restrict__ gain,
+                                     double *partial, NatGeom g, int nl, int stride) {
+  const int i = blockIdx.x * BX + threadIdx.x, j = blockIdx.y * BY + threadIdx.y;
+  double num = 0., den = 0.;
+  if (i < g.nx && j < g.ny) {
+    size_t c = nat_idx(g, 0, j, i);
+    for (int l = 0; l < nl; l++, c += g.ls) {
+      const double d = obs[c] - q[c], w = gain ? gain[c] : 1.;
+      num += w * (d * d);
+      den += w;
+    }
+  }
+  __shared__ double sm[2][BY];
+  num = wave_sum(num); den = wave_sum(den);
+  if (threadIdx.x == 0) { sm[0][threadIdx.y] = num; sm[1][threadIdx.y] = den; }
+  __syncthreads();
+  if (threadIdx.x == 0 && threadIdx.y == 0) {
+    double s0 = 0., s1 = 0.;
+    for (int k = 0; k < BY; k++) { s0 += sm[0][k]; s1 += sm[1][k]; }
+    const int b = blockIdx.y * gridDim.x + blockIdx.x;
+    partial[b] = s0;
+    partial[stride + b] = s1;
+  }
+}
+int bfn_misfit_blocks(const NatGeom &g) { return partial_count(g); }
+void launch_bfn_misfit(hipStream_t st, const double *q, const double *obs, const double *gain, double *partial, double *out2, const NatGeom &g,
+                       int nl) {
+  const dim3 gr = grid2d(g.nx, g.ny);
+  const int nb = gr.x * gr.y, stride = nb + SUM_CHUNKS;
+  hipLaunchKernelGGL(k_bfn_misfit_partial, gr, block2d(), 0, st, q, obs, gain, partial, g, nl, stride);
+  launch_sum_final(st, partial, out2, nb);
+  launch_sum_final(st, partial + stride, out2 + 1, nb);
 }
 void launch_sum_layers(hipStream_t st, const double *f, double *partial, double *out, const NatGeom &g, int nl) {
   dim3 gr = grid2d(g.nx, g.ny);

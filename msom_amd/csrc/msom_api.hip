@@ -6,7 +6,8 @@
 //   set_vars msqg/qg.h:837-925, set_const :931-1116, invertq :114-163,
 //   poisson_layer msqg/poisson_layer.h:263-306, mg_solve/mg_cycle mspg/elliptic.h:43-99,145-229,
 //   update_qg msqg/qg.h:609-650, advance_qg :594-606, run() of Basilisk predictor-corrector.h
-//   (SURVEY App. B), writestdout/output events msqg/qg.c:101-173, pystep_bfn msqg/qg_bfn.h:21-103.
+//   (SURVEY App. B), writestdout/output events msqg/qg.c:101-173, pystep_bfn msqg/qg_bfn.h:21-103,
+//   its time loop msqg/qg_bfn.py:47-73 (msom_bfn_steps).
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -171,6 +172,10 @@ struct msom {
   int res_ready = -1;  // field id whose first multigrid residual (levels 0, 1; SC_RESF; partial sums) the last tendency pass already produced
   int adv_fused = 1;   // fold q_out = q_in + dt dq into the tendency pass
   int rhs_resid = 0;   // let the fused tendency + advance pass produce it: measured slower (23 spilled VGPRs in the 256-VGPR kernel: 2.21 ms vs 1.63 + 0.50 ms), kept as an option
+  // back-and-forth nudging loop on the device (msom_bfn_*)
+  int bfn_begun = 0;                      // msom_bfn_begin since the last msom_set_const
+  int bfn_obs_set = 0, bfn_gain_set = 0;  // MSOM_BFN_OBS / MSOM_BFN_GAIN came in through msom_set_field (gain never set: 1 everywhere)
+  double *bfn_partial = nullptr;          // per-block partial sums of msom_bfn_misfit
   int s_zero = 0;  // pystep_de(onlyKE = 1) zeroed the stretching field S (msqg/qg_energy.h:319-325); undone by msom_set_const
   std::vector<NatGeom> wv_g;
   std::vector<double *> wv_s, wv_r, wv_sig;
@@ -667,6 +672,7 @@ extern "C" int msom_destroy(msom_t *m) {
   if (m->staging) hipFree(m->staging);
   if (m->partial) hipFree(m->partial);
   if (m->partial_rr) hipFree(m->partial_rr);
+  if (m->bfn_partial) hipFree(m->bfn_partial);
   if (m->d_cargs) hipFree(m->d_cargs);
   if (m->partial_umax) hipFree(m->partial_umax);
   if (m->d_scal) hipFree(m->d_scal);
@@ -829,9 +835,10 @@ static int check_field(msom *m, int field) {
 
 // boundary(): wall BCs + halo exchange with the neighbour tiles.  The ghosts of q, dq and the
 // predictor are never read (b enters the solver at cell centres only), so those fields skip
-// the exchange.
+// the exchange; so do the arrays of the nudging loop (tendency history, observations, gain: read at cell centres only).
 static int fill_bc(msom *m, int field) {
-  if (m->nranks > 1 && field != MSOM_Q && field != MSOM_DQ && field != MSOM_QPRED && field != MSOM_NOISE && field != MSOM_SIGMA) {
+  if (m->nranks > 1 && field != MSOM_Q && field != MSOM_DQ && field != MSOM_QPRED && field != MSOM_NOISE && field != MSOM_SIGMA &&
+      !(field >= MSOM_BFN_F1 && field <= MSOM_BFN_GAIN)) {
     int r = exch_nat(m, m->f[field], m->flayers[field], m->fbc[field], 1);
     if (!r && m->fbc[field] == BC_DIRICHLET_LIN) {  // the wrapped ghosts on the domain edges give way to dirichlet(vpg x - upg y)
       const int sides = (m->ix == 0 ? WALL_W : 0) | (m->ix == m->px - 1 ? WALL_E : 0) | (m->iy == 0 ? WALL_S : 0) | (m->iy == m->py - 1 ? WALL_N : 0);
@@ -883,6 +890,8 @@ extern "C" int msom_set_field(msom_t *m, int field, const double *a) {
   if (field == MSOM_ZETAPG) m->have_zpg = 1;
   if (field == MSOM_QFORC) m->have_qforc = 1;
   if (field == MSOM_TOPO) m->flag_topo = 1;
+  if (field == MSOM_BFN_OBS) m->bfn_obs_set = 1;
+  if (field == MSOM_BFN_GAIN) m->bfn_gain_set = 1;
   return sync_stream(m);
 }
 extern "C" int msom_get_field(msom_t *m, int field, double *a) {
@@ -1122,6 +1131,7 @@ extern "C" int msom_set_const(msom_t *m) {
     for (int l = 0; l < nl; l++) m->umax_pg[l] = m->h_scal[SC_UMAX + l];
   }
   m->const_set = 1;
+  m->bfn_begun = 0;
   return sync_stream(m);
 }
 
@@ -2067,6 +2077,69 @@ extern "C" int pyp2q(msom_t *m, double *po_py, int len13, int len14, int len15, 
   NEED_CONST(m);
   if (check_shape(m, len13, len14, len15) || check_shape(m, len16, len17, len18)) return MSOM_ERR_ARG;
   return msom_comp_q(m, po_py, qo_py);
+}
+
+// ------------------------------------------------------------------ the loop of msqg/qg_bfn.py:47-73 on the device
+
+static int ensure_field(msom *m, int field);
+// msqg/qg_bfn.py:49-51: zero history; the AB3 weights apply from the first step on
+extern "C" int msom_bfn_begin(msom_t *m) {
+  NEED_CONST(m);
+  int r;
+  for (int k = MSOM_BFN_F1; k <= MSOM_BFN_F3; k++) {
+    if ((r = ensure_field(m, k))) return r;
+    HIPCHK(hipMemsetAsync(m->f[k], 0, m->g.ls * m->nl * sizeof(double), m->st));
+  }
+  m->bfn_begun = 1;
+  return sync_stream(m);
+}
+
+// msqg/qg_bfn.py:62-73 with the nudging term of :67-68
+extern "C" int msom_bfn_steps(msom_t *m, int nsteps, double dt, double direction, double k) {
+  if (!m) return MSOM_ERR_ARG;
+  if (nsteps < 0) { msom_set_error("msom_bfn_steps: nsteps = %d", nsteps); return MSOM_ERR_ARG; }
+  if (!m->const_set || !m->bfn_begun) { msom_set_error("msom_bfn_steps before msom_bfn_begin"); return MSOM_ERR_STATE; }
+  if (k != 0 && !m->bfn_obs_set) { msom_set_error("msom_bfn_steps: k != 0 and MSOM_BFN_OBS was never set"); return MSOM_ERR_STATE; }
+  if (nsteps == 0) return MSOM_OK;
+  Params &p = m->p;
+  int r;
+  if (direction > 0) {   // msqg/qg_bfn.h:30-41, as pystep_bfn
+    p.iRe = p.Re == 0 ? 0. : 1 / p.Re;
+    p.iRe4 = p.Re4 == 0 ? 0. : -1 / p.Re4;
+    p.Eks = fabs(p.Eks); p.Ekb = fabs(p.Ekb);
+  } else {
+    p.iRe = p.Re == 0 ? 0. : -1 / p.Re;
+    p.iRe4 = p.Re4 == 0 ? 0. : 1 / p.Re4;
+    p.Eks = -fabs(p.Eks); p.Ekb = -fabs(p.Ekb);
+  }
+  const double dt12 = dt / 12;
+  const double *obs = k != 0 ? m->f[MSOM_BFN_OBS] : nullptr, *gain = (k != 0 && m->bfn_gain_set) ? m->f[MSOM_BFN_GAIN] : nullptr;
+  for (int n = 0; n < nsteps; n++) {
+    if (solve_and_dt(m, MSOM_Q, p.DT) < 0) return m->sticky ? m->sticky : MSOM_ERR_HIP;  // invertq + the dt limiter inside advection_pv
+    if ((r = rhs_terms(m, MSOM_Q, MSOM_BFN_F1, 0, p.iRe, p.iRe4, p.Eks, p.Ekb))) return r;   // the tendency goes straight into the F1 slot
+    launch_bfn_ab3(m->st, m->f[MSOM_Q], m->f[MSOM_BFN_F1], m->f[MSOM_BFN_F2], m->f[MSOM_BFN_F3], obs, gain, m->g, m->nl, dt12, k);
+    fill_bc(m, MSOM_Q);    // boundary(q), as upload does after its pack
+    m->res_ready = -1;     // what the handle caches from q
+    m->umax_ready = 0;
+    m->spec_valid = 0;
+    double *f1 = m->f[MSOM_BFN_F1];   // F3 = F2; F2 = F1 (:72-73) as a rotation of the slots
+    m->f[MSOM_BFN_F1] = m->f[MSOM_BFN_F3];
+    m->f[MSOM_BFN_F3] = m->f[MSOM_BFN_F2];
+    m->f[MSOM_BFN_F2] = f1;
+  }
+  return sync_stream(m);
+}
+
+extern "C" int msom_bfn_misfit(msom_t *m, double *misfit) {
+  if (!m || !misfit) return MSOM_ERR_ARG;
+  if (!m->bfn_obs_set) { msom_set_error("msom_bfn_misfit: MSOM_BFN_OBS was never set"); return MSOM_ERR_STATE; }
+  if (!m->bfn_partial) HIPCHK(hipMalloc(&m->bfn_partial, 2 * ((size_t)bfn_misfit_blocks(m->g) + 64) * sizeof(double)));
+  launch_bfn_misfit(m->st, m->f[MSOM_Q], m->f[MSOM_BFN_OBS], m->bfn_gain_set ? m->f[MSOM_BFN_GAIN] : nullptr, m->bfn_partial,
+                    m->d_scal + SC_LSUM, m->g, m->nl);
+  int r = reduce_scal(m, SC_LSUM, 2, RED_SUM);
+  if (r) return r;
+  *misfit = sqrt(m->h_scal[SC_LSUM] / m->h_scal[SC_LSUM + 1]);
+  return MSOM_OK;
 }
 
 // ------------------------------------------------------------------ time loop
