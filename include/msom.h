@@ -179,6 +179,54 @@ int msom_bfn_begin(msom_t *m);
 int msom_bfn_steps(msom_t *m, int nsteps, double dt, double direction, double k);
 int msom_bfn_misfit(msom_t *m, double *misfit);
 
+/* ---- running time means and eddy statistics on the device, and time_filter (msqg/qg.h:491-507).  The accumulators are no field ids:
+ * they have this enum and the accessors below.  Ids 0 .. MSOM_ST_NACC - 1 are weighted sums kept in device memory, one [nl][ny][nx]
+ * fp64 array each, only those a handle asked for; the ids from 16 on are formed from them on request and never stored. */
+enum { MSOM_ST_PSI = 0,  /* sum w psi            */   MSOM_ST_Q = 1,   /* sum w q   */
+       MSOM_ST_PSI2 = 2, /* sum w psi^2          */   MSOM_ST_Q2 = 3,  /* sum w q^2 */
+       MSOM_ST_KE = 4,   /* sum w (u^2 + v^2)/2  */
+       MSOM_ST_UQ = 5,   /* sum w u q            */   MSOM_ST_VQ = 6,  /* sum w v q */
+       MSOM_ST_NACC = 7,
+       /* derived on the device from the accumulators, never stored */
+       MSOM_ST_EKE = 16,      /* mean KE - KE of the mean psi             */
+       MSOM_ST_UQ_EDDY = 17,  /* mean(uq) - u(mean psi) * mean(q)         */
+       MSOM_ST_VQ_EDDY = 18,
+       MSOM_ST_QME = 32 };    /* qo_me of time_filter, msqg/qg.h:499-503  */
+/* A sample reads the handle's MSOM_PSI (with the ghost values boundary() left in it, the ones the Jacobian reads; on tiles the exchanged
+ * ones) and MSOM_Q, and adds to every selected accumulator, cell by cell,
+ *   acc = acc + w * x,   x = psi, q, psi*psi, q*q, 0.5 * (u*u + v*v), u*q, v*q
+ *   u = (psi[j-1][i] - psi[j+1][i]) / (2 Delta),   v = (psi[j][i+1] - psi[j][i-1]) / (2 Delta)     (2 Delta formed once on the host)
+ * and W = W + w.  This expression order is the contract of the strict build (true divisions); the product build multiplies by
+ * 1 / (2 Delta) and may contract.  No atomics and no reductions: the result is the same on every run.
+ * msom_stats_begin: bit k of mask selects accumulator k; allocates the selected ones, zeroes them and W, restarts the count of
+ *   "stats_every".  May be called again (another mask: the arrays are reallocated).  msom_set_const drops the statistics.
+ * msom_stats_accumulate: one sample of weight w from the psi and q the handle holds now; queued on the library's stream, not synchronised.
+ * msom_stats_weight: W.  msom_stats_get: `which` < MSOM_ST_NACC: S / W (a true division in both builds); MSOM_ST_EKE (needs PSI and KE)
+ *   = S_KE / W - 0.5 * (um*um + vm*vm), MSOM_ST_UQ_EDDY (PSI, Q, UQ) = S_UQ / W - um * (S_Q / W), MSOM_ST_VQ_EDDY (PSI, Q, VQ) likewise
+ *   with vm, where um, vm are the differences above of the mean psi after boundary() on a copy of it in a scratch field (difference
+ *   operator and boundary conditions are linear, so these are the mean velocities); MSOM_ST_QME: qo_me.  out: [nl][ny][nx], host or
+ *   device pointer, the local tile as with msom_get_field; the derived ids are collective on tiles (halo exchange of the mean psi).
+ *   Both calls synchronise the stream.
+ * Option "stats" [0] = 1: every msom_step takes one sample of (q_n, psi_n) with weight dt_n -- q_n the state the step starts from,
+ *   psi_n what the step's first inversion leaves in MSOM_PSI (the pair the output event of msqg/qg.c:115 sees), dt_n the step the
+ *   limiter chose -- before the second stage overwrites psi, with no host synchronisation (a lazy step stays lazy: the weight is read
+ *   from the device scalar the step keeps it in).  "stats_every" [1] = n: only every n-th step since msom_stats_begin, with that
+ *   step's dt.  msom_bfn_steps, msom_update and the pystep_* calls never sample; the option changes nothing in psi, q, dt or mgstats.
+ * msom_time_filter: qo_me = (1 - a) * qo_me + a * q with a = dt / tau_f (option "tau_f" [20]) on the handle's MSOM_Q; qo_me is
+ *   allocated and zeroed by the first call after msom_set_const (the reference's freshly created field) and needs no msom_stats_begin.
+ * Errors: null handle, mask 0 or a bit >= MSOM_ST_NACC, w or dt not finite, `which` unknown or its accumulators not in the mask:
+ *   MSOM_ERR_ARG; msom_stats_begin / msom_time_filter before msom_set_const, any other stats call (or option "stats" = 1, or a
+ *   msom_step with it) with no msom_stats_begin since msom_set_const, msom_stats_get with W == 0 or of MSOM_ST_QME with no
+ *   msom_time_filter since msom_set_const: MSOM_ERR_STATE.
+ * msom_get_param "stats_mask" / "stats_bytes": the mask, and 8 nl ny nx bytes per array held (accumulators, qo_me; the allocations
+ *   carry the pads of a field on top); both 0 on a handle that never called msom_stats_begin or msom_time_filter;
+ *   "stats_dev_samples": automatic samples since msom_stats_begin that read their weight from the device scalar. */
+int msom_stats_begin(msom_t *m, unsigned mask);     /* bit k = accumulator k; allocates those, zeroes them and W */
+int msom_stats_accumulate(msom_t *m, double w);     /* one sample of the handle's MSOM_PSI / MSOM_Q, weight w */
+int msom_stats_weight(msom_t *m, double *W);        /* sum of the weights so far */
+int msom_stats_get(msom_t *m, int which, double *out); /* [nl][ny][nx], host or device pointer: S / W, or a derived quantity */
+int msom_time_filter(msom_t *m, double dt);         /* qo_me = (1 - a) * qo_me + a * q, a = dt / tau_f; option "tau_f" [20] */
+
 /* ---- time loop of Basilisk predictor-corrector run() as driven by msqg/qg.c
  * msom_step: one RK2 step on the internal state (update, dtnext, advance dt/2, update,
  * advance dt).  msom_set_tnext gives the time of the next t-scheduled event (output). */

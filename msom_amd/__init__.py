@@ -13,6 +13,7 @@ from .api import (  # noqa: F401
     NODE_FIELDS,
     NodeQG,
     QG,
+    STATS,
     bfn_begin,
     bfn_misfit,
     bfn_steps,
@@ -31,6 +32,6 @@ from .api import (  # noqa: F401
 )
 
 __all__ = [
-    "QG", "NodeQG", "NODE_FIELDS", "MGStats", "MsomError", "FIELDS", "load_library", "read_params", "init_grid", "set_vars",
+    "QG", "NodeQG", "NODE_FIELDS", "MGStats", "MsomError", "FIELDS", "STATS", "load_library", "read_params", "init_grid", "set_vars",
     "set_vars_bfn", "set_const", "pystep_bfn", "bfn_begin", "bfn_steps", "bfn_misfit", "pystep_de", "pyq2p", "pyp2q", "trash_vars", "trash_vars_bfn",
 ]

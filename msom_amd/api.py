@@ -13,6 +13,9 @@ FIELDS = dict(PSI=0, Q=1, ZETA=2, PSIPG=3, ZETAPG=4, QFORC=5, TMP=6, FR=7, S=8, 
               DE_BF=21, DE_VD=22, DE_J1=23, DE_J2=24, DE_J3=25, DE_FT=26, TMP2=27, PO_MFT=28,
               BFN_F1=29, BFN_F2=30, BFN_F3=31, BFN_OBS=32, BFN_GAIN=33)
 
+# running statistics (msom_stats_*): accumulators 0 .. NACC - 1 (bit k of the mask), derived quantities, qo_me of time_filter
+STATS = dict(PSI=0, Q=1, PSI2=2, Q2=3, KE=4, UQ=5, VQ=6, NACC=7, EKE=16, UQ_EDDY=17, VQ_EDDY=18, QME=32)
+
 
 class MsomError(RuntimeError):
     pass
@@ -66,6 +69,11 @@ def load_library(strict=False):
         "msom_bfn_begin": (ci, [vp]),
         "msom_bfn_steps": (ci, [vp, ci, cd, cd, cd]),
         "msom_bfn_misfit": (ci, [vp, _dp]),
+        "msom_stats_begin": (ci, [vp, C.c_uint]),
+        "msom_stats_accumulate": (ci, [vp, cd]),
+        "msom_stats_weight": (ci, [vp, _dp]),
+        "msom_stats_get": (ci, [vp, ci, vp]),
+        "msom_time_filter": (ci, [vp, cd]),
         "msom_step": (ci, [vp, _dp]),
         "msom_set_tnext": (ci, [vp, cd]),
         "msom_time": (cd, [vp]),
@@ -296,6 +304,32 @@ class QG:
         out = C.c_double()
         self._chk(self.L.msom_bfn_misfit(self.h, C.byref(out)))
         return out.value
+
+    # -- running time means and eddy statistics on the device (STATS), time_filter of msqg/qg.h:491-507
+    def stats_begin(self, mask):
+        """allocate and zero the accumulators of `mask` (bit STATS[name] each) and the weight sum; option("stats", 1) then lets
+        every step() take one sample of (q_n, psi_n) with weight dt_n"""
+        self._chk(self.L.msom_stats_begin(self.h, int(mask)))
+
+    def stats_accumulate(self, w):
+        """one sample of the PSI and Q the model holds now, weight w"""
+        self._chk(self.L.msom_stats_accumulate(self.h, float(w)))
+
+    def stats_weight(self):
+        out = C.c_double()
+        self._chk(self.L.msom_stats_weight(self.h, C.byref(out)))
+        return out.value
+
+    def stats_get(self, which, out=None):
+        """mean of accumulator `which` (sum / weight), a derived quantity (EKE, UQ_EDDY, VQ_EDDY) or QME; [nl][ny][nx] of this tile.
+        out: optional destination, a numpy array or a tensor (host or device)"""
+        a = np.empty((self.nl, self.ny, self.nx)) if out is None else out
+        self._chk(self.L.msom_stats_get(self.h, int(which), _ptr(a)))
+        return a
+
+    def time_filter(self, dt):
+        """qo_me = (1 - a) * qo_me + a * Q, a = dt / tau_f (option "tau_f", 20); read it back with stats_get(STATS["QME"])"""
+        self._chk(self.L.msom_time_filter(self.h, float(dt)))
 
     # -- time loop
     def step(self):

@@ -68,6 +68,18 @@ void launch_bfn_ab3(hipStream_t st, double *q, double *f1, const double *f2, con
 int bfn_misfit_blocks(const NatGeom &g);
 void launch_bfn_misfit(hipStream_t st, const double *q, const double *obs, const double *gain, double *partial, double *out2, const NatGeom &g,
                        int nl);
+// running statistics (msom_stats_*): s[k] = accumulator MSOM_ST_k (natural layout) or null where the mask does not select it
+struct StatsAcc {
+  double *s[MSOM_ST_NACC];
+};
+// one sample of weight *w_dev (w_dev != nullptr) or w into the accumulators of `mask`; *W += the weight.  D2 = 2 Delta
+void launch_stats_acc(hipStream_t st, unsigned mask, const double *psi, const double *q, const StatsAcc &a, const NatGeom &g, int nl,
+                      const double *w_dev, double w, double D2, double *W);
+void launch_stats_mean(hipStream_t st, double *out, const double *s, const double *W, const NatGeom &g, int nl);
+// which = MSOM_ST_EKE / UQ_EDDY / VQ_EDDY from the mean psi pm (ghosts filled), sa = KE / UQ / VQ, sq = Q (eddy fluxes); out: [nl][ny][nx]
+void launch_stats_derive(hipStream_t st, double *out, const double *pm, const double *sa, const double *sq, const double *W, const NatGeom &g,
+                         int nl, int which, double D2);
+void launch_time_filter(hipStream_t st, double *me, const double *q, const NatGeom &g, int nl, double a);
 int partial_count(const NatGeom &g);
 void launch_sum_final(hipStream_t st, const double *partial, double *out, int n);
 void launch_ke(hipStream_t st, const double *po, double *partial, double *out, const NatGeom &g, double D);

@@ -497,6 +497,147 @@ void launch_bfn_ab3(hipStream_t st, double *q, double *f1, const double *f2, con
   else hipLaunchKernelGGL((k_bfn_ab3<true, true>), gr, block2d(), 0, st, q, f1, f2, f3, obs, gain, g, nl, dt12, k);
 }
 
+// one sample of the running statistics (msom_stats_accumulate, the automatic sample of msom_step): for every selected accumulator k
+//   s_k = s_k + w * x_k,   x = psi, q, psi*psi, q*q, 0.5 * (u*u + v*v), u*q, v*q   (MSOM_ST_PSI .. MSOM_ST_VQ)
+// with u = (psi[j-1][i] - psi[j+1][i]) / (2 D), v = (psi[j][i+1] - psi[j][i-1]) / (2 D) from the ghost values boundary() left, the ones
+// the Jacobian reads.  The strict build keeps this expression order with true divisions, the product build multiplies by 1 / (2 D) and
+// may contract.  Shaped like k_bfn_ab3: one thread owns two x-adjacent interior cells of every layer, 16-byte accesses (the rows
+// j - 1, j, j + 1 of psi as aligned double2, its two outer x neighbours as scalar loads), a last odd cell goes alone; pads and ghost
+// cells are not written.  Instantiated on the mask: what is not selected is neither read nor written, and psi / q / the neighbour
+// rows are loaded only where a selected quantity needs them.  Every cell owns its accumulators: no atomics, no reductions, the same
+// bits on every run.  w comes from the device (wp, the dt of k_step_dt) or by value; the thread of cell (0, 0) adds it to *W.
+template <int K, unsigned MASK>
+__device__ __forceinline__ void stats_add2(const StatsAcc &a, size_t c, double w, double x0, double x1) {
+  if constexpr ((MASK >> K) & 1u) {
+    double2 s = *reinterpret_cast<const double2 *>(a.s[K] + c);
+    s.x = s.x + w * x0;
+    s.y = s.y + w * x1;
+    *reinterpret_cast<double2 *>(a.s[K] + c) = s;
+  }
+}
+template <int K, unsigned MASK>
+__device__ __forceinline__ void stats_add1(const StatsAcc &a, size_t c, double w, double x) {
+  if constexpr ((MASK >> K) & 1u) a.s[K][c] = a.s[K][c] + w * x;
+}
+template <unsigned MASK>
+__global__ void __launch_bounds__(BX *BY) k_stats_acc(const double *__restrict__ psi, const double *__restrict__ q, StatsAcc a, NatGeom g, int nl,
+                                                      const double *__restrict__ wp, double wv, double D2, double rD2, double *W) {
+  constexpr unsigned B_PSI = 1u << MSOM_ST_PSI, B_Q = 1u << MSOM_ST_Q, B_PSI2 = 1u << MSOM_ST_PSI2, B_Q2 = 1u << MSOM_ST_Q2,
+                     B_KE = 1u << MSOM_ST_KE, B_UQ = 1u << MSOM_ST_UQ, B_VQ = 1u << MSOM_ST_VQ;
+  constexpr bool NU = (MASK & (B_KE | B_UQ)) != 0, NV = (MASK & (B_KE | B_VQ)) != 0;   // which velocity components are needed
+  constexpr bool NP = (MASK & (B_PSI | B_PSI2)) != 0 || NV, NQ = (MASK & (B_Q | B_Q2 | B_UQ | B_VQ)) != 0;
+  const double w = wp ? *wp : wv;
+  const int i = 2 * (blockIdx.x * BX + threadIdx.x), j = blockIdx.y * BY + threadIdx.y;
+  if (W && i == 0 && j == 0) *W = *W + w;
+  if (i >= g.nx || j >= g.ny) return;
+  size_t c = nat_idx(g, 0, j, i);
+  if (i + 1 < g.nx) {
+    for (int l = 0; l < nl; l++, c += g.ls) {
+      double2 p = make_double2(0., 0.), vq = make_double2(0., 0.), u = make_double2(0., 0.), v = make_double2(0., 0.);
+      if (NP) p = *reinterpret_cast<const double2 *>(psi + c);
+      if (NQ) vq = *reinterpret_cast<const double2 *>(q + c);
+      if (NU) {
+        const double2 s = *reinterpret_cast<const double2 *>(psi + c - g.pitch), n = *reinterpret_cast<const double2 *>(psi + c + g.pitch);
+        u.x = DIVC(s.x - n.x, D2, rD2);
+        u.y = DIVC(s.y - n.y, D2, rD2);
+      }
+      if (NV) {
+        v.x = DIVC(p.y - psi[c - 1], D2, rD2);
+        v.y = DIVC(psi[c + 2] - p.x, D2, rD2);
+      }
+      stats_add2<MSOM_ST_PSI, MASK>(a, c, w, p.x, p.y);
+      stats_add2<MSOM_ST_Q, MASK>(a, c, w, vq.x, vq.y);
+      stats_add2<MSOM_ST_PSI2, MASK>(a, c, w, p.x * p.x, p.y * p.y);
+      stats_add2<MSOM_ST_Q2, MASK>(a, c, w, vq.x * vq.x, vq.y * vq.y);
+      stats_add2<MSOM_ST_KE, MASK>(a, c, w, 0.5 * (u.x * u.x + v.x * v.x), 0.5 * (u.y * u.y + v.y * v.y));
+      stats_add2<MSOM_ST_UQ, MASK>(a, c, w, u.x * vq.x, u.y * vq.y);
+      stats_add2<MSOM_ST_VQ, MASK>(a, c, w, v.x * vq.x, v.y * vq.y);
+    }
+  } else {
+    for (int l = 0; l < nl; l++, c += g.ls) {
+      const double p = NP ? psi[c] : 0., vq = NQ ? q[c] : 0.;
+      const double u = NU ? DIVC(psi[c - g.pitch] - psi[c + g.pitch], D2, rD2) : 0., v = NV ? DIVC(psi[c + 1] - psi[c - 1], D2, rD2) : 0.;
+      stats_add1<MSOM_ST_PSI, MASK>(a, c, w, p);
+      stats_add1<MSOM_ST_Q, MASK>(a, c, w, vq);
+      stats_add1<MSOM_ST_PSI2, MASK>(a, c, w, p * p);
+      stats_add1<MSOM_ST_Q2, MASK>(a, c, w, vq * vq);
+      stats_add1<MSOM_ST_KE, MASK>(a, c, w, 0.5 * (u * u + v * v));
+      stats_add1<MSOM_ST_UQ, MASK>(a, c, w, u * vq);
+      stats_add1<MSOM_ST_VQ, MASK>(a, c, w, v * vq);
+    }
+  }
+}
+template <unsigned M>
+static void stats_acc_dispatch(unsigned mask, hipStream_t st, const double *psi, const double *q, const StatsAcc &a, const NatGeom &g, int nl,
+                               const double *wp, double wv, double D2, double *W) {
+  if (mask == M) {
+    const dim3 gr(((g.nx + 1) / 2 + BX - 1) / BX, (g.ny + BY - 1) / BY);
+    hipLaunchKernelGGL((k_stats_acc<M>), gr, block2d(), 0, st, psi, q, a, g, nl, wp, wv, D2, 1. / D2, W);
+  } else if constexpr (M > 1)
+    stats_acc_dispatch<M - 1>(mask, st, psi, q, a, g, nl, wp, wv, D2, W);
+}
+void launch_stats_acc(hipStream_t st, unsigned mask, const double *psi, const double *q, const StatsAcc &a, const NatGeom &g, int nl,
+                      const double *w_dev, double w, double D2, double *W) {
+  stats_acc_dispatch<(1u << MSOM_ST_NACC) - 1>(mask, st, psi, q, a, g, nl, w_dev, w, D2, W);
+}
+
+// msom_stats_get: mean = s / *W (a true division in both builds) into a natural field, interior cells
+__global__ void __launch_bounds__(BX *BY) k_stats_mean(double *__restrict__ out, const double *__restrict__ s, const double *__restrict__ W,
+                                                       NatGeom g, int nl) {
+  const int i = blockIdx.x * BX + threadIdx.x, j = blockIdx.y * BY + threadIdx.y;
+  if (i >= g.nx || j >= g.ny) return;
+  const double wt = *W;
+  size_t c = nat_idx(g, 0, j, i);
+  for (int l = 0; l < nl; l++, c += g.ls) out[c] = s[c] / wt;
+}
+void launch_stats_mean(hipStream_t st, double *out, const double *s, const double *W, const NatGeom &g, int nl) {
+  hipLaunchKernelGGL(k_stats_mean, grid2d(g.nx, g.ny), block2d(), 0, st, out, s, W, g, nl);
+}
+// the derived statistics, from pm = mean psi with its ghost ring refilled by boundary() (the difference operator and the boundary
+// conditions are linear: u, v of the mean psi are the mean u, v) and the accumulators sa (KE, or UQ / VQ) and sq (Q):
+//   MSOM_ST_EKE     = sa / W - 0.5 * (um * um + vm * vm)
+//   MSOM_ST_UQ_EDDY = sa / W - um * (sq / W),   MSOM_ST_VQ_EDDY = sa / W - vm * (sq / W)
+// written contiguously [nl][ny][nx] (the staging layout msom_get_field copies out)
+__global__ void __launch_bounds__(BX *BY) k_stats_derive(double *__restrict__ out, const double *__restrict__ pm, const double *__restrict__ sa,
+                                                         const double *__restrict__ sq, const double *__restrict__ W, NatGeom g, int nl, int which,
+                                                         double D2, double rD2) {
+  const int i = blockIdx.x * BX + threadIdx.x, j = blockIdx.y * BY + threadIdx.y;
+  if (i >= g.nx || j >= g.ny) return;
+  const double wt = *W;
+  size_t c = nat_idx(g, 0, j, i), o = (size_t)j * g.nx + i;
+  for (int l = 0; l < nl; l++, c += g.ls, o += (size_t)g.nx * g.ny) {
+    const double um = DIVC(pm[c - g.pitch] - pm[c + g.pitch], D2, rD2), vm = DIVC(pm[c + 1] - pm[c - 1], D2, rD2);
+    const double ma = sa[c] / wt;
+    if (which == MSOM_ST_EKE) out[o] = ma - 0.5 * (um * um + vm * vm);
+    else out[o] = ma - (which == MSOM_ST_UQ_EDDY ? um : vm) * (sq[c] / wt);
+  }
+}
+void launch_stats_derive(hipStream_t st, double *out, const double *pm, const double *sa, const double *sq, const double *W, const NatGeom &g,
+                         int nl, int which, double D2) {
+  hipLaunchKernelGGL(k_stats_derive, grid2d(g.nx, g.ny), block2d(), 0, st, out, pm, sa, sq, W, g, nl, which, D2, 1. / D2);
+}
+// time_filter, msqg/qg.h:491-507: qo_me = (1 - alpha_f) * qo_me + alpha_f * qo, pointwise on the interior cells (b = 1 - alpha_f formed once)
+__global__ void __launch_bounds__(BX *BY) k_time_filter(double *me, const double *__restrict__ q, NatGeom g, int nl, double a, double b) {
+  const int i = 2 * (blockIdx.x * BX + threadIdx.x), j = blockIdx.y * BY + threadIdx.y;
+  if (i >= g.nx || j >= g.ny) return;
+  size_t c = nat_idx(g, 0, j, i);
+  if (i + 1 < g.nx) {
+    for (int l = 0; l < nl; l++, c += g.ls) {
+      double2 vm = *reinterpret_cast<const double2 *>(me + c);
+      const double2 vq = *reinterpret_cast<const double2 *>(q + c);
+      vm.x = b * vm.x + a * vq.x;
+      vm.y = b * vm.y + a * vq.y;
+      *reinterpret_cast<double2 *>(me + c) = vm;
+    }
+  } else {
+    for (int l = 0; l < nl; l++, c += g.ls) me[c] = b * me[c] + a * q[c];
+  }
+}
+void launch_time_filter(hipStream_t st, double *me, const double *q, const NatGeom &g, int nl, double a) {
+  const dim3 gr(((g.nx + 1) / 2 + BX - 1) / BX, (g.ny + BY - 1) / BY);
+  hipLaunchKernelGGL(k_time_filter, gr, block2d(), 0, st, me, q, g, nl, a, 1 - a);
+}
+
 // ------------------------------------------------------------------ sums (deterministic two-stage)
 
 // stage 1: one partial per block; stage 2: a single block adds the partials in index order

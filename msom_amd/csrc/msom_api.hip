@@ -7,7 +7,7 @@
 //   poisson_layer msqg/poisson_layer.h:263-306, mg_solve/mg_cycle mspg/elliptic.h:43-99,145-229,
 //   update_qg msqg/qg.h:609-650, advance_qg :594-606, run() of Basilisk predictor-corrector.h
 //   (SURVEY App. B), writestdout/output events msqg/qg.c:101-173, pystep_bfn msqg/qg_bfn.h:21-103,
-//   its time loop msqg/qg_bfn.py:47-73 (msom_bfn_steps).
+//   its time loop msqg/qg_bfn.py:47-73 (msom_bfn_steps), time_filter msqg/qg.h:491-507 (msom_time_filter).
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -17,6 +17,7 @@
 #include <time.h>
 
 #include <algorithm>
+#include <cmath>
 #include <string>
 #include <utility>
 #include <functional>
@@ -176,6 +177,15 @@ struct msom {
   int bfn_begun = 0;                      // msom_bfn_begin since the last msom_set_const
   int bfn_obs_set = 0, bfn_gain_set = 0;  // MSOM_BFN_OBS / MSOM_BFN_GAIN came in through msom_set_field (gain never set: 1 everywhere)
   double *bfn_partial = nullptr;          // per-block partial sums of msom_bfn_misfit
+  // running statistics on the device (msom_stats_*, msom_time_filter); nothing is allocated until one of them is called
+  unsigned stats_mask = 0;                // accumulators selected by the last msom_stats_begin since msom_set_const (0: none)
+  StatsAcc stats = {};                    // the selected accumulators, natural layout, nl layers each
+  double *stats_W = nullptr;              // device scalar: sum of the weights
+  double *stats_qme = nullptr;            // qo_me of time_filter (allocated by the first msom_time_filter after msom_set_const)
+  int stats_on = 0, stats_every = 1;      // options "stats", "stats_every"
+  long stats_count = 0;                   // msom_step calls seen since msom_stats_begin (every stats_every-th one samples)
+  long stats_ndev = 0;                    // ... of whose samples, those that read their weight from the device (tests ask: stats_dev_samples)
+  double tau_f = 20;                      // option "tau_f" (msqg/qg.h:495)
   int s_zero = 0;  // pystep_de(onlyKE = 1) zeroed the stretching field S (msqg/qg_energy.h:319-325); undone by msom_set_const
   std::vector<NatGeom> wv_g;
   std::vector<double *> wv_s, wv_r, wv_sig;
@@ -193,6 +203,7 @@ struct msom {
 };
 
 static void free_agglomeration(msom *m);
+static void stats_drop(msom *m);
 
 extern "C" const char *msom_version(void) {
 #ifdef MSOM_STRICT
@@ -673,6 +684,7 @@ extern "C" int msom_destroy(msom_t *m) {
   if (m->partial) hipFree(m->partial);
   if (m->partial_rr) hipFree(m->partial_rr);
   if (m->bfn_partial) hipFree(m->bfn_partial);
+  stats_drop(m);
   if (m->d_cargs) hipFree(m->d_cargs);
   if (m->partial_umax) hipFree(m->partial_umax);
   if (m->d_scal) hipFree(m->d_scal);
@@ -754,6 +766,18 @@ extern "C" int msom_set_option(msom_t *m, const char *key, double v) {
   else if (!strcmp(key, "seed")) { m->seed = (unsigned)v; srand(m->seed); }
   else if (!strcmp(key, "noise_mode")) m->noise_mode = (int)v;
   else if (!strcmp(key, "stoch_fused")) m->stoch_fused = (int)v;
+  else if (!strcmp(key, "stats")) {
+    if ((int)v && !m->stats_mask) { msom_set_error("option stats = 1 before msom_stats_begin"); return MSOM_ERR_STATE; }
+    m->stats_on = (int)v != 0;
+  }
+  else if (!strcmp(key, "stats_every")) {
+    if (!(v >= 1)) { msom_set_error("option stats_every = %g", v); return MSOM_ERR_ARG; }
+    m->stats_every = (int)v;
+  }
+  else if (!strcmp(key, "tau_f")) {
+    if (!(v > 0) || !std::isfinite(v)) { msom_set_error("option tau_f = %g", v); return MSOM_ERR_ARG; }
+    m->tau_f = v;
+  }
   else if (!strcmp(key, "stochastic")) {
     m->stochastic = (int)v;
     if (m->stochastic && !m->f[MSOM_NOISE]) {
@@ -801,6 +825,13 @@ extern "C" double msom_get_param(msom_t *m, const char *key) {
   if (!strcmp(key, "uniform_S")) return m->uniformS;
   if (!strcmp(key, "agg_level")) return m->agg_level;
   if (!strcmp(key, "overlap")) return m->overlap;
+  if (!strcmp(key, "stats_mask")) return m->stats_mask;
+  if (!strcmp(key, "stats_dev_samples")) return (double)m->stats_ndev;
+  if (!strcmp(key, "stats_bytes")) {   // 8 nl ny nx per array held: the selected accumulators and qo_me
+    int n = m->stats_qme ? 1 : 0;
+    for (int k = 0; k < MSOM_ST_NACC; k++) n += m->stats.s[k] ? 1 : 0;
+    return (double)n * m->nl * m->nx * m->ny * sizeof(double);
+  }
   // which kernels the dispatch picks for this handle (bench.py names what ran from these, not from a table)
   if (!strcmp(key, "resmax_marching")) return m->uniformS && m->nl <= MSOM_FASTNL && m->g.nx >= 64 && m->g.ny >= 16 && m->opt.resmax_rows >= 0;
   // how the wall-ring chunks around the fused visit run (-1: no fused visit on this handle), as launch_relax_visit reads the option
@@ -1132,6 +1163,7 @@ extern "C" int msom_set_const(msom_t *m) {
   }
   m->const_set = 1;
   m->bfn_begun = 0;
+  stats_drop(m);
   return sync_stream(m);
 }
 
@@ -2142,6 +2174,111 @@ extern "C" int msom_bfn_misfit(msom_t *m, double *misfit) {
   return MSOM_OK;
 }
 
+// ------------------------------------------------------------------ running statistics on the device, time_filter (msqg/qg.h:491-507)
+
+static void stats_drop(msom *m) {
+  for (int k = 0; k < MSOM_ST_NACC; k++) {
+    if (m->stats.s[k]) hipFree(m->stats.s[k]);
+    m->stats.s[k] = nullptr;
+  }
+  if (m->stats_W) hipFree(m->stats_W);
+  if (m->stats_qme) hipFree(m->stats_qme);
+  m->stats_W = m->stats_qme = nullptr;
+  m->stats_mask = 0;
+  m->stats_count = m->stats_ndev = 0;
+}
+// one sample of the handle's psi and q: weight *w_dev (device scalar) or w
+static void stats_sample(msom *m, const double *w_dev, double w) {
+  launch_stats_acc(m->st, m->stats_mask, m->f[MSOM_PSI], m->f[MSOM_Q], m->stats, m->g, m->nl, w_dev, w, 2. * (m->p.L0 / m->gnx), m->stats_W);
+}
+#define NEED_STATS(m, fn)                                                                   \
+  do {                                                                                      \
+    if (!(m)->const_set || !(m)->stats_mask) {                                              \
+      msom_set_error(fn ": no msom_stats_begin since msom_set_const");                      \
+      return MSOM_ERR_STATE;                                                                \
+    }                                                                                       \
+  } while (0)
+
+extern "C" int msom_stats_begin(msom_t *m, unsigned mask) {
+  if (!m) return MSOM_ERR_ARG;
+  if (mask == 0 || mask >> MSOM_ST_NACC) { msom_set_error("msom_stats_begin: mask 0x%x", mask); return MSOM_ERR_ARG; }
+  if (!m->const_set) { msom_set_error("msom_stats_begin before msom_set_const"); return MSOM_ERR_STATE; }
+  HIPCHK(hipStreamSynchronize(m->st));   // a sample of an earlier mask may still be running
+  const size_t bytes = m->g.ls * m->nl * sizeof(double);
+  for (int k = 0; k < MSOM_ST_NACC; k++) {
+    const bool want = (mask >> k) & 1u;
+    if (!want && m->stats.s[k]) { HIPCHK(hipFree(m->stats.s[k])); m->stats.s[k] = nullptr; }
+    if (want && !m->stats.s[k]) HIPCHK(hipMalloc(&m->stats.s[k], bytes));
+    if (want) HIPCHK(hipMemsetAsync(m->stats.s[k], 0, bytes, m->st));
+  }
+  if (!m->stats_W) HIPCHK(hipMalloc(&m->stats_W, sizeof(double)));
+  HIPCHK(hipMemsetAsync(m->stats_W, 0, sizeof(double), m->st));
+  m->stats_mask = mask;
+  m->stats_count = m->stats_ndev = 0;
+  return sync_stream(m);
+}
+
+extern "C" int msom_stats_accumulate(msom_t *m, double w) {
+  if (!m) return MSOM_ERR_ARG;
+  if (!std::isfinite(w)) { msom_set_error("msom_stats_accumulate: w = %g", w); return MSOM_ERR_ARG; }
+  NEED_STATS(m, "msom_stats_accumulate");
+  stats_sample(m, nullptr, w);
+  return m->sticky;
+}
+
+extern "C" int msom_stats_weight(msom_t *m, double *W) {
+  if (!m || !W) return MSOM_ERR_ARG;
+  NEED_STATS(m, "msom_stats_weight");
+  HIPCHK(hipMemcpyAsync(W, m->stats_W, sizeof(double), hipMemcpyDeviceToHost, m->st));
+  return sync_stream(m);
+}
+
+extern "C" int msom_stats_get(msom_t *m, int which, double *out) {
+  if (!m || !out) return MSOM_ERR_ARG;
+  const size_t n = (size_t)m->nl * m->nx * m->ny;
+  if (which == MSOM_ST_QME) {
+    if (!m->const_set || !m->stats_qme) { msom_set_error("msom_stats_get: no msom_time_filter since msom_set_const"); return MSOM_ERR_STATE; }
+    launch_unpack(m->st, m->stats_qme, m->staging, m->g, m->nl);
+    HIPCHK(hipMemcpyAsync(out, m->staging, n * sizeof(double), hipMemcpyDefault, m->st));
+    return sync_stream(m);
+  }
+  unsigned need;
+  int sa = -1;
+  if (which >= 0 && which < MSOM_ST_NACC) need = 1u << which;
+  else if (which == MSOM_ST_EKE) need = 1u << MSOM_ST_PSI | 1u << (sa = MSOM_ST_KE);
+  else if (which == MSOM_ST_UQ_EDDY) need = 1u << MSOM_ST_PSI | 1u << MSOM_ST_Q | 1u << (sa = MSOM_ST_UQ);
+  else if (which == MSOM_ST_VQ_EDDY) need = 1u << MSOM_ST_PSI | 1u << MSOM_ST_Q | 1u << (sa = MSOM_ST_VQ);
+  else { msom_set_error("msom_stats_get: unknown id %d", which); return MSOM_ERR_ARG; }
+  NEED_STATS(m, "msom_stats_get");
+  if ((m->stats_mask & need) != need) { msom_set_error("msom_stats_get: id %d needs accumulators 0x%x, the mask is 0x%x", which, need, m->stats_mask); return MSOM_ERR_ARG; }
+  double W = 0;
+  int r = msom_stats_weight(m, &W);
+  if (r) return r;
+  if (W == 0) { msom_set_error("msom_stats_get: the sum of the weights is 0"); return MSOM_ERR_STATE; }
+  // the mean goes into the scratch field MSOM_TMP (layers and boundary condition of psi)
+  launch_stats_mean(m->st, m->f[MSOM_TMP], m->stats.s[sa < 0 ? which : MSOM_ST_PSI], m->stats_W, m->g, m->nl);
+  if (sa < 0) return download(m, MSOM_TMP, out);
+  if ((r = fill_bc(m, MSOM_TMP))) return r;   // boundary() on the copy of the mean psi: collective on tiles
+  launch_stats_derive(m->st, m->staging, m->f[MSOM_TMP], m->stats.s[sa], m->stats.s[MSOM_ST_Q], m->stats_W, m->g, m->nl, which,
+                      2. * (m->p.L0 / m->gnx));
+  HIPCHK(hipMemcpyAsync(out, m->staging, n * sizeof(double), hipMemcpyDefault, m->st));
+  return sync_stream(m);
+}
+
+// time_filter, msqg/qg.h:491-507 (alpha_f = dt / tau_f; qo_me starts from the zeros of a freshly created field)
+extern "C" int msom_time_filter(msom_t *m, double dt) {
+  if (!m) return MSOM_ERR_ARG;
+  if (!std::isfinite(dt)) { msom_set_error("msom_time_filter: dt = %g", dt); return MSOM_ERR_ARG; }
+  if (!m->const_set) { msom_set_error("msom_time_filter before msom_set_const"); return MSOM_ERR_STATE; }
+  if (!m->stats_qme) {
+    const size_t bytes = m->g.ls * m->nl * sizeof(double);
+    HIPCHK(hipMalloc(&m->stats_qme, bytes));
+    HIPCHK(hipMemsetAsync(m->stats_qme, 0, bytes, m->st));
+  }
+  launch_time_filter(m->st, m->stats_qme, m->f[MSOM_Q], m->g, m->nl, dt / m->tau_f);
+  return sync_stream(m);
+}
+
 // ------------------------------------------------------------------ time loop
 
 // dtnext() [Basilisk, SURVEY App. B]
@@ -2190,6 +2327,7 @@ static bool spec_ok(msom *m) {
 
 extern "C" int msom_step(msom_t *m, double *dt_used) {
   NEED_CONST(m);
+  if (m->stats_on && !m->stats_mask) { msom_set_error("msom_step: option stats = 1 and no msom_stats_begin since msom_set_const"); return MSOM_ERR_STATE; }
   const Params &p = m->p;
   double tnext;
   int r, advanced = 0;
@@ -2221,6 +2359,12 @@ extern "C" int msom_step(msom_t *m, double *dt_used) {
     m->dt = dtnext(m, d, &tnext);
     if ((r = rhs_terms(m, MSOM_Q, MSOM_DQ, 1, p.iRe, p.iRe4, p.Eks, p.Ekb, MSOM_QPRED, MSOM_Q, m->dt / 2., &advanced))) return r;
     if (!advanced && (r = advance_qg(m, MSOM_QPRED, MSOM_Q, MSOM_DQ, m->dt / 2.))) return r;
+  }
+  // option "stats": one sample of (q_n, psi_n = what the first inversion left, dt_n) before stage 2 overwrites psi.  Queued behind the
+  // stage's tendency pass; on the speculative path the weight is the device scalar k_step_dt wrote (no host value is waited for)
+  if (m->stats_on && m->stats_count++ % m->stats_every == 0) {
+    stats_sample(m, hit1 ? m->d_scal + SC_SPEC + 1 : nullptr, m->dt);
+    m->stats_ndev += hit1;
   }
   const bool tracers = m->p.nptr > 0;
   if (tracers && ((r = tracer_update(m, MSOM_PTR)) || (r = tracer_advance(m, MSOM_PTR_PRED, MSOM_PTR, m->dt / 2.)))) return r;
