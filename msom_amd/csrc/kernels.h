@@ -2,7 +2,35 @@
 #ifndef MSOM_KERNELS_H
 #define MSOM_KERNELS_H
 
+#include <stdio.h>
+#include <stdlib.h>
+
+#include <type_traits>
+#include <utility>
+
 #include "msom_internal.h"
+
+// Run-time value -> template argument.  with_int<LO, HI>(v, f) calls f(std::integral_constant<int, v>{}) and returns true when
+// LO <= v <= HI; otherwise it calls nothing and returns false.  The range is the list of instantiations a launcher has: a launcher
+// that returns int answers false with -1, a void one with no_kernel() -- never with a silent skip.
+template <int LO, int HI, class F>
+static inline bool with_int(int v, F &&f) {
+  if constexpr (LO > HI) return false;
+  else {
+    if (v == LO) { f(std::integral_constant<int, LO>{}); return true; }
+    return with_int<LO + 1, HI>(v, std::forward<F>(f));
+  }
+}
+// f(std::true_type{}) or f(std::false_type{})
+template <class F>
+static inline void with_bool(bool b, F &&f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+[[noreturn]] static inline void no_kernel(const char *launcher, int nl) {
+  fprintf(stderr, "msom: %s: no kernel for nl = %d\n", launcher, nl);
+  abort();
+}
 
 // layer metrics idh0/idh1 (msqg/qg.h:1017-1027), passed by value to kernels
 struct LayerCoef {

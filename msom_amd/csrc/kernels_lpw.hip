@@ -395,25 +395,16 @@ void launch_rhs_lpw(hipStream_t st, const KernelOpts &o, const double *psi, cons
   if (H < 8) H = 8;
   a.H = H;
   const dim3 gr((strips + a.NS - 1) / a.NS, (g.ny + H - 1) / H), bl(64 * nl * a.NS);
-  const int sel = (uniformS ? 4 : 0) | (have_qforc ? 2 : 0) | (q_out ? 1 : 0);
-  if (stoch) {  // only with the advance fused (the caller folds -q/tau and the noise into q_in)
-    switch (sel) {
-      case 1: hipLaunchKernelGGL((k_rhs_lpw<LPW_R, false, false, true, true>), gr, bl, 0, st, a); break;
-      case 3: hipLaunchKernelGGL((k_rhs_lpw<LPW_R, false, true, true, true>), gr, bl, 0, st, a); break;
-      case 5: hipLaunchKernelGGL((k_rhs_lpw<LPW_R, true, false, true, true>), gr, bl, 0, st, a); break;
-      case 7: hipLaunchKernelGGL((k_rhs_lpw<LPW_R, true, true, true, true>), gr, bl, 0, st, a); break;
-      default: fprintf(stderr, "msom: launch_rhs_lpw: stochastic variant needs q_out\n"); abort();
-    }
-    return;
+  if (stoch && !q_out) {  // only with the advance fused (the caller folds -q/tau and the noise into q_in)
+    fprintf(stderr, "msom: launch_rhs_lpw: stochastic variant needs q_out\n");
+    abort();
   }
-  switch (sel) {
-    case 0: hipLaunchKernelGGL((k_rhs_lpw<LPW_R, false, false, false>), gr, bl, 0, st, a); break;
-    case 1: hipLaunchKernelGGL((k_rhs_lpw<LPW_R, false, false, true>), gr, bl, 0, st, a); break;
-    case 2: hipLaunchKernelGGL((k_rhs_lpw<LPW_R, false, true, false>), gr, bl, 0, st, a); break;
-    case 3: hipLaunchKernelGGL((k_rhs_lpw<LPW_R, false, true, true>), gr, bl, 0, st, a); break;
-    case 4: hipLaunchKernelGGL((k_rhs_lpw<LPW_R, true, false, false>), gr, bl, 0, st, a); break;
-    case 5: hipLaunchKernelGGL((k_rhs_lpw<LPW_R, true, false, true>), gr, bl, 0, st, a); break;
-    case 6: hipLaunchKernelGGL((k_rhs_lpw<LPW_R, true, true, false>), gr, bl, 0, st, a); break;
-    default: hipLaunchKernelGGL((k_rhs_lpw<LPW_R, true, true, true>), gr, bl, 0, st, a); break;
-  }
+  with_bool(uniformS, [&](auto U) {
+    with_bool(have_qforc, [&](auto Q) {
+      constexpr bool UNI = decltype(U)::value, QF = decltype(Q)::value;
+      if (stoch) hipLaunchKernelGGL((k_rhs_lpw<LPW_R, UNI, QF, true, true>), gr, bl, 0, st, a);
+      else if (q_out) hipLaunchKernelGGL((k_rhs_lpw<LPW_R, UNI, QF, true>), gr, bl, 0, st, a);
+      else hipLaunchKernelGGL((k_rhs_lpw<LPW_R, UNI, QF, false>), gr, bl, 0, st, a);
+    });
+  });
 }

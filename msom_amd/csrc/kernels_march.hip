@@ -1214,52 +1214,39 @@ static void march_launch(hipStream_t st, Kern kern, MarchArgs a, int ow, int chu
 // dma: option march_dma
 template <int NL>
 static int march_dispatch(hipStream_t st, const MarchArgs &a, int K, int rows, int dma) {
-  if (dma && !(K == 4 && NL > 6) && !((a.coarse || a.psi_out) && NL > 6)) {
+  const bool pl = a.coarse != nullptr, corr = a.psi_out != nullptr;
+  // LDS-DMA forms: K = 2 .. 4 up to 6 layers, K = 2, 3 above (no K = 4 for NL > 6).  The prolongation (PL) runs for K >= 3, and neither
+  // PL nor the correction (CORR) runs for NL > 6: the register-window kernels below take those.  (Run-time tests: the PL and CORR
+  // forms are instantiated for every (NL, K) of the range)
+  if (dma && !(pl && K < 3) && !((pl || corr) && NL > 6)) {
     // 1: one strip per workgroup; 2 (default): four adjacent strips per workgroup, marching in step, for the plain pass
     // (the pass with the prolongation measured faster with one: 7.09 vs 7.25 ms per RK2 step); 3: four for both
-    constexpr int NLS = NL;
-    const bool four = a.rb.n ? false : (a.coarse ? dma >= 3 : dma >= 2);   // compact ring grid: one chunk per workgroup
-#define MARCH_DMA_K(KK)                                                                                                      \
-    if constexpr (NL <= 6) {   /* four strips per workgroup: 4 x the LDS ring; at nl = 7, 8 that leaves one workgroup per CU */   \
-      if (a.coarse && four) { march_launch(st, k_relax_march_dma<NLS, KK, 4, 4, true>, a, 56 * 4, rows, 256); return 0; }        \
-      if (a.psi_out && four) { march_launch(st, k_relax_march_dma<NLS, KK, 2, 4, false, true>, a, 60 * 4, rows, 256); return 0; } \
-      if (!a.coarse && !a.psi_out && four) { march_launch(st, k_relax_march_dma<NLS, KK, 2, 4, false>, a, 60 * 4, rows, 256); return 0; } \
-    }                                                                                                                        \
-    if (a.coarse) march_launch(st, k_relax_march_dma<NLS, KK, 4, 1, true>, a, 56, rows, 64);                                   \
-    else if (a.psi_out) march_launch(st, k_relax_march_dma<NLS, KK, 2, 1, false, true>, a, 60, rows, 64);                      \
-    else march_launch(st, k_relax_march_dma<NLS, KK, 2, 1, false>, a, 60, rows, 64);                                           \
-    return 0;
-    if constexpr (NL <= 6) {
-      switch (K) {
-        case 2: if (!a.coarse) { MARCH_DMA_K(2) } break;
-        case 3: { MARCH_DMA_K(3) }
-        case 4: { MARCH_DMA_K(4) }
+    const bool four = a.rb.n ? false : (pl ? dma >= 3 : dma >= 2);   // compact ring grid: one chunk per workgroup
+    const bool done = with_int<2, NL <= 6 ? 4 : 3>(K, [&](auto Kc) {
+      constexpr int KK = decltype(Kc)::value;
+      if constexpr (NL <= 6) {   // four strips per workgroup: 4 x the LDS ring; at nl = 7, 8 that leaves one workgroup per CU
+        if (four) {
+          if (pl) march_launch(st, k_relax_march_dma<NL, KK, 4, 4, true>, a, 56 * 4, rows, 256);
+          else if (corr) march_launch(st, k_relax_march_dma<NL, KK, 2, 4, false, true>, a, 60 * 4, rows, 256);
+          else march_launch(st, k_relax_march_dma<NL, KK, 2, 4, false>, a, 60 * 4, rows, 256);
+          return;
+        }
       }
-    } else {
-      switch (K) {
-        case 2: if (!a.coarse) { MARCH_DMA_K(2) } break;
-        case 3: { MARCH_DMA_K(3) }
-      }
+      if (pl) march_launch(st, k_relax_march_dma<NL, KK, 4, 1, true>, a, 56, rows, 64);
+      else if (corr) march_launch(st, k_relax_march_dma<NL, KK, 2, 1, false, true>, a, 60, rows, 64);
+      else march_launch(st, k_relax_march_dma<NL, KK, 2, 1, false>, a, 60, rows, 64);
+    });
+    if (done) return 0;
+  }
+  // register-window kernels
+  return with_int<2, 4>(K, [&](auto Kc) {
+    constexpr int KK = decltype(Kc)::value;
+    if constexpr (KK >= 3) {   // PL exists for K = 3, 4
+      if (pl) { march_launch(st, k_relax_march<NL, KK, true, false>, a, KK == 4 ? 58 : 60, rows); return; }
     }
-#undef MARCH_DMA_K
-  }
-  switch (K) {
-    case 2:
-      if (a.psi_out) march_launch(st, k_relax_march<NL, 2, false, true>, a, 62, rows);
-      else march_launch(st, k_relax_march<NL, 2, false, false>, a, 62, rows);
-      return 0;
-    case 3:
-      if (a.coarse) march_launch(st, k_relax_march<NL, 3, true, false>, a, 60, rows);
-      else if (a.psi_out) march_launch(st, k_relax_march<NL, 3, false, true>, a, 60, rows);
-      else march_launch(st, k_relax_march<NL, 3, false, false>, a, 60, rows);
-      return 0;
-    case 4:
-      if (a.coarse) march_launch(st, k_relax_march<NL, 4, true, false>, a, 58, rows);
-      else if (a.psi_out) march_launch(st, k_relax_march<NL, 4, false, true>, a, 60, rows);
-      else march_launch(st, k_relax_march<NL, 4, false, false>, a, 60, rows);
-      return 0;
-  }
-  return -1;
+    if (corr) march_launch(st, k_relax_march<NL, KK, false, true>, a, KK == 2 ? 62 : 60, rows);
+    else march_launch(st, k_relax_march<NL, KK, false, false>, a, KK == 2 ? 62 : 60, rows);
+  }) ? 0 : -1;
 }
 
 // the lean body addresses all layers of a field through 32-bit unsigned per-lane byte offsets (voffL, voffC): admitted while
@@ -1293,17 +1280,9 @@ int launch_relax_march(hipStream_t st, const KernelOpts &o, const double *in, do
   a.lean = !o.march_lean ? 0 : o.march_lean * (int)(march_lean_fits(nl, sg, mc ? &mc->g : nullptr) && (!coarse || c1 == 0));
   a.in = in; a.out = out; a.res = res; a.g = sg; a.c1 = c1; a.walls = walls; a.rc = rc; a.remap = o.march_xcd; a.flip = o.march_flip; a.dbg = o.march_dbg;
   if (nl >= 7 && K > 3) return -1;  // 4 windows of 7 or 8 layers do not fit 256 VGPRs
-  switch (nl) {
-    case 1: return march_dispatch<1>(st, a, K, chunk_rows, o.march_dma);
-    case 2: return march_dispatch<2>(st, a, K, chunk_rows, o.march_dma);
-    case 3: return march_dispatch<3>(st, a, K, chunk_rows, o.march_dma);
-    case 4: return march_dispatch<4>(st, a, K, chunk_rows, o.march_dma);
-    case 5: return march_dispatch<5>(st, a, K, chunk_rows, o.march_dma);
-    case 6: return march_dispatch<6>(st, a, K, chunk_rows, o.march_dma);
-    case 7: return march_dispatch<7>(st, a, K, chunk_rows, o.march_dma);
-    case 8: return march_dispatch<8>(st, a, K, chunk_rows, o.march_dma);
-  }
-  return -1;
+  int r = -1;
+  with_int<1, MSOM_FASTNL>(nl, [&](auto N) { r = march_dispatch<N()>(st, a, K, chunk_rows, o.march_dma); });
+  return r;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1456,22 +1435,17 @@ template <int NL>
 static void visit_dispatch(hipStream_t st, const MarchArgs &a, const VisitGeom &v, int pairs) {
   // mixed launch (ring_kind): a 1-D grid, the ring workgroups first so that their latency-bound chains start with the launch
   const dim3 grid = a.ring_kind ? dim3(a.ring_wg + a.fnbx * a.fnby) : dim3(v.ns / pairs, v.nc);
-#define VISIT_KIND(KIND)                                                                            \
-  if (pairs == 2) hipLaunchKernelGGL((k_relax_visit<NL, 2, KIND>), grid, dim3(256), 0, st, a); \
-  else hipLaunchKernelGGL((k_relax_visit<NL, 1, KIND>), grid, dim3(128), 0, st, a);
-  if (a.ring_kind == 1) { VISIT_KIND(1) }
-  else if (a.ring_kind == 2) { VISIT_KIND(2) }
-  else { VISIT_KIND(0) }
-#undef VISIT_KIND
+  // ring_kind is 0, 1 or 2 (launch_relax_visit), pairs 1 or 2 (relax_visit_fits)
+  with_int<0, 2>(a.ring_kind, [&](auto R) {
+    with_int<1, 2>(pairs, [&](auto P) {
+      constexpr int PAIRS = decltype(P)::value;
+      hipLaunchKernelGGL((k_relax_visit<NL, PAIRS, decltype(R)::value>), grid, dim3(128 * PAIRS), 0, st, a);
+    });
+  });
 }
 static void visit_dispatch_nl(hipStream_t st, const MarchArgs &a, const VisitGeom &v, int pairs, int nl) {
-  switch (nl) {
-    case 2: visit_dispatch<2>(st, a, v, pairs); break;
-    case 3: visit_dispatch<3>(st, a, v, pairs); break;
-    case 4: visit_dispatch<4>(st, a, v, pairs); break;
-    case 5: visit_dispatch<5>(st, a, v, pairs); break;
-    case 6: visit_dispatch<6>(st, a, v, pairs); break;
-  }
+  // 2 .. 6: the visit is made of the K = 4 lean PL and CORR bodies, which exist up to 6 layers; relax_visit_fits admits this range
+  if (!with_int<2, 6>(nl, [&](auto N) { visit_dispatch<N()>(st, a, v, pairs); })) no_kernel("launch_relax_visit", nl);
 }
 
 // PL + 4 half-sweeps (colour 0 first) and 4 + correction, the prolongation from `coarse`; da_alt receives the first pass's values

@@ -547,16 +547,9 @@ static dim3 resmax_march_launch(hipStream_t st, const Res2Args &p, int H) {
   return gr;
 }
 static dim3 launch_resmax_march(hipStream_t st, const Res2Args &p, int H) {
-  switch (p.nl) {
-    case 1: return resmax_march_launch<1>(st, p, H);
-    case 2: return resmax_march_launch<2>(st, p, H);
-    case 3: return resmax_march_launch<3>(st, p, H);
-    case 4: return resmax_march_launch<4>(st, p, H);
-    case 5: return resmax_march_launch<5>(st, p, H);
-    case 6: return resmax_march_launch<6>(st, p, H);
-    case 7: return resmax_march_launch<7>(st, p, H);
-    default: return resmax_march_launch<8>(st, p, H);
-  }
+  dim3 gr;
+  if (!with_int<1, MSOM_FASTNL>(p.nl, [&](auto N) { gr = resmax_march_launch<N()>(st, p, H); })) no_kernel("launch_resmax_march", p.nl);
+  return gr;
 }
 
 // out[l] = max_b partial[b][l]
@@ -1616,23 +1609,12 @@ __global__ void __launch_bounds__(MGC_NT) k_mg_coarse_lean(const CoarseArgs *pa,
 template <int NL>
 static void mg_coarse_dispatch(hipStream_t st, const CoarseArgs *d_args, int nrelax, int uniformS, int lean) {
   if (lean) { hipLaunchKernelGGL((k_mg_coarse_lean<NL>), dim3(1), dim3(MGC_NT), 0, st, d_args, nrelax); return; }
-  if (uniformS) hipLaunchKernelGGL((k_mg_coarse<NL, true>), dim3(1), dim3(MGC_NT), 0, st, d_args, nrelax);
-  else hipLaunchKernelGGL((k_mg_coarse<NL, false>), dim3(1), dim3(MGC_NT), 0, st, d_args, nrelax);
+  with_bool(uniformS, [&](auto U) { hipLaunchKernelGGL((k_mg_coarse<NL, U()>), dim3(1), dim3(MGC_NT), 0, st, d_args, nrelax); });
 }
 size_t mg_coarse_static_lds() { return sizeof(double) * MGC_POOL + sizeof(MgcShared); }
 
 void launch_mg_coarse(hipStream_t st, const CoarseArgs *d_args, int nrelax, int nl, int uniformS, int lean) {
-  switch (nl) {
-    case 1: mg_coarse_dispatch<1>(st, d_args, nrelax, uniformS, lean); break;
-    case 2: mg_coarse_dispatch<2>(st, d_args, nrelax, uniformS, lean); break;
-    case 3: mg_coarse_dispatch<3>(st, d_args, nrelax, uniformS, lean); break;
-    case 4: mg_coarse_dispatch<4>(st, d_args, nrelax, uniformS, lean); break;
-    case 5: mg_coarse_dispatch<5>(st, d_args, nrelax, uniformS, lean); break;
-    case 6: mg_coarse_dispatch<6>(st, d_args, nrelax, uniformS, lean); break;
-    case 7: mg_coarse_dispatch<7>(st, d_args, nrelax, uniformS, lean); break;
-    case 8: mg_coarse_dispatch<8>(st, d_args, nrelax, uniformS, lean); break;
-    default: break;
-  }
+  if (!with_int<1, MSOM_FASTNL>(nl, [&](auto N) { mg_coarse_dispatch<N()>(st, d_args, nrelax, uniformS, lean); })) no_kernel("launch_mg_coarse", nl);
 }
 
 
@@ -1644,119 +1626,60 @@ __global__ void __launch_bounds__(BX *BY) k_relax_red_prolong(RelaxPArgs p) {
 template <int NL>
 static void relax_red_prolong_dispatch(hipStream_t st, const RelaxPArgs &p, int uniformS, int dbg) {   // dbg: option rhs_dbg
   dim3 gr = grid2d(p.g.hk, (p.g.ny + 1) / 2);
-  if (!(dbg & 256) && p.g.hk >= 128 && !(dbg & 512)) {  // wide levels: coarse windows through LDS
-    if (uniformS) hipLaunchKernelGGL((k_relax_red_prolong3<NL, true>), gr, block2d(), 0, st, p);
-    else hipLaunchKernelGGL((k_relax_red_prolong3<NL, false>), gr, block2d(), 0, st, p);
-    return;
-  }
-  if (!(dbg & 256)) {  // both row parities per thread
-    if (uniformS) hipLaunchKernelGGL((k_relax_red_prolong2<NL, true>), gr, block2d(), 0, st, p);
-    else hipLaunchKernelGGL((k_relax_red_prolong2<NL, false>), gr, block2d(), 0, st, p);
-    return;
-  }
-  gr.z = 2;
-  if (uniformS) hipLaunchKernelGGL((k_relax_red_prolong<NL, true>), gr, block2d(), 0, st, p);
-  else hipLaunchKernelGGL((k_relax_red_prolong<NL, false>), gr, block2d(), 0, st, p);
+  with_bool(uniformS, [&](auto U) {
+    if (!(dbg & 256) && p.g.hk >= 128 && !(dbg & 512))  // wide levels: coarse windows through LDS
+      hipLaunchKernelGGL((k_relax_red_prolong3<NL, U()>), gr, block2d(), 0, st, p);
+    else if (!(dbg & 256))  // both row parities per thread
+      hipLaunchKernelGGL((k_relax_red_prolong2<NL, U()>), gr, block2d(), 0, st, p);
+    else {
+      gr.z = 2;
+      hipLaunchKernelGGL((k_relax_red_prolong<NL, U()>), gr, block2d(), 0, st, p);
+    }
+  });
 }
 void launch_relax_red_prolong(hipStream_t st, const KernelOpts &o, double *da, const double *coarse, const SplitGeom &cg, const double *res, const double *S,
                               const SplitGeom &sg, int nl, const RelaxCoef &rc, int uniformS, int walls) {
   RelaxPArgs p;
   p.da = da; p.res = res; p.S = S; p.coarse = coarse; p.g = sg; p.cg = cg; p.walls = walls; p.rc = rc;
-  switch (nl) {
-    case 1: relax_red_prolong_dispatch<1>(st, p, uniformS, o.rhs_dbg); break;
-    case 2: relax_red_prolong_dispatch<2>(st, p, uniformS, o.rhs_dbg); break;
-    case 3: relax_red_prolong_dispatch<3>(st, p, uniformS, o.rhs_dbg); break;
-    case 4: relax_red_prolong_dispatch<4>(st, p, uniformS, o.rhs_dbg); break;
-    case 5: relax_red_prolong_dispatch<5>(st, p, uniformS, o.rhs_dbg); break;
-    case 6: relax_red_prolong_dispatch<6>(st, p, uniformS, o.rhs_dbg); break;
-    case 7: relax_red_prolong_dispatch<7>(st, p, uniformS, o.rhs_dbg); break;
-    case 8: relax_red_prolong_dispatch<8>(st, p, uniformS, o.rhs_dbg); break;
-    default: break;
-  }
+  if (!with_int<1, MSOM_FASTNL>(nl, [&](auto N) { relax_red_prolong_dispatch<N()>(st, p, uniformS, o.rhs_dbg); }))
+    no_kernel("launch_relax_red_prolong", nl);
 }
 
 template <int NL>
 static void relax_dispatch(hipStream_t st, const RelaxArgs &p, int uniformS, int fine) {
-  if (p.g.hk % 2 == 0 && p.g.hk >= 128) {  // wide levels: two points per thread, 16-byte accesses
-    dim3 g2 = grid2d(p.g.hk / 2, p.g.ny);
-    if (uniformS) {
-      if (fine) hipLaunchKernelGGL((k_relax_color_x2<NL, true, true>), g2, block2d(), 0, st, p);
-      else hipLaunchKernelGGL((k_relax_color_x2<NL, true, false>), g2, block2d(), 0, st, p);
-    } else {
-      if (fine) hipLaunchKernelGGL((k_relax_color_x2<NL, false, true>), g2, block2d(), 0, st, p);
-      else hipLaunchKernelGGL((k_relax_color_x2<NL, false, false>), g2, block2d(), 0, st, p);
-    }
-    return;
-  }
-  dim3 gr = grid2d(p.g.hk, p.g.ny);
-  if (uniformS) {
-    if (fine) hipLaunchKernelGGL((k_relax_color<NL, true, true>), gr, block2d(), 0, st, p);
-    else hipLaunchKernelGGL((k_relax_color<NL, true, false>), gr, block2d(), 0, st, p);
-  } else {
-    if (fine) hipLaunchKernelGGL((k_relax_color<NL, false, true>), gr, block2d(), 0, st, p);
-    else hipLaunchKernelGGL((k_relax_color<NL, false, false>), gr, block2d(), 0, st, p);
-  }
+  with_bool(uniformS, [&](auto U) {
+    with_bool(fine, [&](auto F) {
+      constexpr bool UNIFORM = decltype(U)::value, FINE = decltype(F)::value;
+      if (p.g.hk % 2 == 0 && p.g.hk >= 128)  // wide levels: two points per thread, 16-byte accesses
+        hipLaunchKernelGGL((k_relax_color_x2<NL, UNIFORM, FINE>), grid2d(p.g.hk / 2, p.g.ny), block2d(), 0, st, p);
+      else
+        hipLaunchKernelGGL((k_relax_color<NL, UNIFORM, FINE>), grid2d(p.g.hk, p.g.ny), block2d(), 0, st, p);
+    });
+  });
 }
 template <int NL>
 static void relax_dispatch_wide(hipStream_t st, const RelaxArgs &p, int uniformS) {
-  dim3 gr = grid2d(p.g.hk, p.g.ny);
-  if (uniformS) hipLaunchKernelGGL((k_relax_color<NL, true, false>), gr, block2d(), 0, st, p);
-  else hipLaunchKernelGGL((k_relax_color<NL, false, false>), gr, block2d(), 0, st, p);
+  with_bool(uniformS, [&](auto U) { hipLaunchKernelGGL((k_relax_color<NL, U(), false>), grid2d(p.g.hk, p.g.ny), block2d(), 0, st, p); });
 }
 template <int NL>
 static void relax_ring_dispatch(hipStream_t st, const RelaxArgs &p, int uniformS) {
   const int n = 2 * p.g.hk + p.g.ny - 2;
-  if (uniformS) hipLaunchKernelGGL((k_relax_ring<NL, true>), dim3((n + 255) / 256), dim3(256), 0, st, p);
-  else hipLaunchKernelGGL((k_relax_ring<NL, false>), dim3((n + 255) / 256), dim3(256), 0, st, p);
+  with_bool(uniformS, [&](auto U) { hipLaunchKernelGGL((k_relax_ring<NL, U()>), dim3((n + 255) / 256), dim3(256), 0, st, p); });
 }
 void launch_relax_ring(hipStream_t st, double *da, const double *res, const double *S, const SplitGeom &sg, int nl, const RelaxCoef &rc,
                        int uniformS, int color, int walls) {
   RelaxArgs p;
   p.da = da; p.res = res; p.S = S; p.g = sg; p.color = color; p.walls = walls; p.rc = rc; p.region = 0;
-  switch (nl) {
-    case 1: relax_ring_dispatch<1>(st, p, uniformS); break;
-    case 2: relax_ring_dispatch<2>(st, p, uniformS); break;
-    case 3: relax_ring_dispatch<3>(st, p, uniformS); break;
-    case 4: relax_ring_dispatch<4>(st, p, uniformS); break;
-    case 5: relax_ring_dispatch<5>(st, p, uniformS); break;
-    case 6: relax_ring_dispatch<6>(st, p, uniformS); break;
-    case 7: relax_ring_dispatch<7>(st, p, uniformS); break;
-    case 8: relax_ring_dispatch<8>(st, p, uniformS); break;
-    case 9: relax_ring_dispatch<9>(st, p, uniformS); break;
-    case 10: relax_ring_dispatch<10>(st, p, uniformS); break;
-    case 11: relax_ring_dispatch<11>(st, p, uniformS); break;
-    case 12: relax_ring_dispatch<12>(st, p, uniformS); break;
-    case 13: relax_ring_dispatch<13>(st, p, uniformS); break;
-    case 14: relax_ring_dispatch<14>(st, p, uniformS); break;
-    case 15: relax_ring_dispatch<15>(st, p, uniformS); break;
-    case 16: relax_ring_dispatch<16>(st, p, uniformS); break;
-    default: break;
-  }
+  if (!with_int<1, MSOM_MAXNL>(nl, [&](auto N) { relax_ring_dispatch<N()>(st, p, uniformS); })) no_kernel("launch_relax_ring", nl);
 }
 void launch_relax_color(hipStream_t st, double *da, const double *res, const double *S, const SplitGeom &sg, int nl, const RelaxCoef &rc,
                         int uniformS, int color, int walls, int fine, int region) {
   RelaxArgs p;
   p.da = da; p.res = res; p.S = S; p.g = sg; p.color = color; p.walls = walls; p.rc = rc; p.region = region;
-  switch (nl) {
-    case 1: relax_dispatch<1>(st, p, uniformS, fine); break;
-    case 2: relax_dispatch<2>(st, p, uniformS, fine); break;
-    case 3: relax_dispatch<3>(st, p, uniformS, fine); break;
-    case 4: relax_dispatch<4>(st, p, uniformS, fine); break;
-    case 5: relax_dispatch<5>(st, p, uniformS, fine); break;
-    case 6: relax_dispatch<6>(st, p, uniformS, fine); break;
-    case 7: relax_dispatch<7>(st, p, uniformS, fine); break;
-    case 8: relax_dispatch<8>(st, p, uniformS, fine); break;
-    // nl > MSOM_FASTNL (round 3): the one-column-per-thread kernel only, column systems of up to MSOM_MAXNL layers in registers
-    case 9: relax_dispatch_wide<9>(st, p, uniformS); break;
-    case 10: relax_dispatch_wide<10>(st, p, uniformS); break;
-    case 11: relax_dispatch_wide<11>(st, p, uniformS); break;
-    case 12: relax_dispatch_wide<12>(st, p, uniformS); break;
-    case 13: relax_dispatch_wide<13>(st, p, uniformS); break;
-    case 14: relax_dispatch_wide<14>(st, p, uniformS); break;
-    case 15: relax_dispatch_wide<15>(st, p, uniformS); break;
-    case 16: relax_dispatch_wide<16>(st, p, uniformS); break;
-    default: break;  // rejected at create time (MSOM_MAXNL)
-  }
+  // nl > MSOM_FASTNL: the one-column-per-thread kernel only, column systems of up to MSOM_MAXNL layers in registers
+  if (!with_int<1, MSOM_FASTNL>(nl, [&](auto N) { relax_dispatch<N()>(st, p, uniformS, fine); }) &&
+      !with_int<MSOM_FASTNL + 1, MSOM_MAXNL>(nl, [&](auto N) { relax_dispatch_wide<N()>(st, p, uniformS); }))
+    no_kernel("launch_relax_color", nl);   // (create_common admits nl <= MSOM_MAXNL)
 }
 
 // ------------------------------------------------------------------ temporally blocked smoother
@@ -1952,13 +1875,9 @@ __global__ void __launch_bounds__(BNT) k_relax_block(BlockArgs p) {
 template <int NL, int BTY, int BNT>
 static void block_launch(hipStream_t st, const BlockArgs &p, int prolong, int fine) {
   dim3 gr((p.g.nx + BTX - 1) / BTX, (p.g.ny + BTY - 1) / BTY);
-  if (prolong) {
-    if (fine) hipLaunchKernelGGL((k_relax_block<NL, BTY, BNT, true, true>), gr, dim3(BNT), 0, st, p);
-    else hipLaunchKernelGGL((k_relax_block<NL, BTY, BNT, true, false>), gr, dim3(BNT), 0, st, p);
-  } else {
-    if (fine) hipLaunchKernelGGL((k_relax_block<NL, BTY, BNT, false, true>), gr, dim3(BNT), 0, st, p);
-    else hipLaunchKernelGGL((k_relax_block<NL, BTY, BNT, false, false>), gr, dim3(BNT), 0, st, p);
-  }
+  with_bool(prolong, [&](auto P) {
+    with_bool(fine, [&](auto F) { hipLaunchKernelGGL((k_relax_block<NL, BTY, BNT, decltype(P)::value, F()>), gr, dim3(BNT), 0, st, p); });
+  });
 }
 template <int NL>
 static void block_dispatch(hipStream_t st, const BlockArgs &p, int prolong, int fine, int variant) {   // variant: option block_variant
@@ -1982,17 +1901,7 @@ void launch_relax_block2(hipStream_t st, const KernelOpts &o, const double *da_i
   p.da_in = da_in; p.res = res; p.coarse = coarse; p.da_out = da_out; p.g = sg; p.cg = cg; p.walls = walls; p.rc = rc;
   p.nh = 4; p.c0 = 0; p.S = nullptr;
   const int prolong = coarse != nullptr;
-  switch (nl) {
-    case 1: block_dispatch<1>(st, p, prolong, fine, o.block_variant); break;
-    case 2: block_dispatch<2>(st, p, prolong, fine, o.block_variant); break;
-    case 3: block_dispatch<3>(st, p, prolong, fine, o.block_variant); break;
-    case 4: block_dispatch<4>(st, p, prolong, fine, o.block_variant); break;
-    case 5: block_dispatch<5>(st, p, prolong, fine, o.block_variant); break;
-    case 6: block_dispatch<6>(st, p, prolong, fine, o.block_variant); break;
-    case 7: block_dispatch<7>(st, p, prolong, fine, o.block_variant); break;
-    case 8: block_dispatch<8>(st, p, prolong, fine, o.block_variant); break;
-    default: break;
-  }
+  if (!with_int<1, MSOM_FASTNL>(nl, [&](auto N) { block_dispatch<N()>(st, p, prolong, fine, o.block_variant); })) no_kernel("launch_relax_block2", nl);
 }
 
 // up to 8 half-sweeps starting with colour c0 (+ the prolongation from `coarse` when given): 64 x 16 tile, halo 8, 640 threads
@@ -2000,8 +1909,7 @@ void launch_relax_block2(hipStream_t st, const KernelOpts &o, const double *da_i
 template <int NL, int TX, int TY, int NT, bool GEN = false>
 static void block8_launch_t(hipStream_t st, const BlockArgs &p, int prolong) {
   dim3 gr((p.g.nx + TX - 1) / TX, (p.g.ny + TY - 1) / TY);
-  if (prolong) hipLaunchKernelGGL((k_relax_block<NL, TY, NT, true, false, 8, TX, GEN>), gr, dim3(NT), 0, st, p);
-  else hipLaunchKernelGGL((k_relax_block<NL, TY, NT, false, false, 8, TX, GEN>), gr, dim3(NT), 0, st, p);
+  with_bool(prolong, [&](auto P) { hipLaunchKernelGGL((k_relax_block<NL, TY, NT, P(), false, 8, TX, GEN>), gr, dim3(NT), 0, st, p); });
 }
 // tile shape: the launch-bound levels have few tiles and the pass lasts as long as ONE workgroup does, so small tiles (16 x 16: four
 // times the half-sweep work of the level in halo cells, but a quarter of the serial work per workgroup) win up to 256^2; wider levels
@@ -2036,18 +1944,7 @@ int launch_relax_block8(hipStream_t st, const KernelOpts &o, const double *da_in
   p.da_in = da_in; p.res = res; p.coarse = coarse; p.da_out = da_out; p.g = sg; p.cg = cg; p.walls = walls; p.rc = rc;
   p.nh = nh; p.c0 = c0;
   const int prolong = coarse != nullptr;
-  switch (nl) {
-    case 1: block8_launch<1>(st, p, prolong, o.block_variant); break;
-    case 2: block8_launch<2>(st, p, prolong, o.block_variant); break;
-    case 3: block8_launch<3>(st, p, prolong, o.block_variant); break;
-    case 4: block8_launch<4>(st, p, prolong, o.block_variant); break;
-    case 5: block8_launch<5>(st, p, prolong, o.block_variant); break;
-    case 6: block8_launch<6>(st, p, prolong, o.block_variant); break;
-    case 7: block8_launch<7>(st, p, prolong, o.block_variant); break;
-    case 8: block8_launch<8>(st, p, prolong, o.block_variant); break;
-    default: return -1;
-  }
-  return 0;
+  return with_int<1, MSOM_FASTNL>(nl, [&](auto N) { block8_launch<N()>(st, p, prolong, o.block_variant); }) ? 0 : -1;
 }
 
 // ------------------------------------------------------------------ K12 correction a += da (+ boundary(a))

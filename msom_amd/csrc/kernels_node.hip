@@ -609,17 +609,8 @@ void launch_n_relax_prolong(hipStream_t st, double *a, const double *b, const do
   p.a = a; p.b = b; p.mk = mk; p.S2 = S2; p.g = g; p.color = 0; p.sqD = D * D; p.iRd2 = iRd2; p.lc = lc; p.S2row = S2row;
   const int n = g.nx - 1;
   dim3 gr = grid2d(n / 2 + 1, n + 1);
-  switch (nl) {
-    case 1: hipLaunchKernelGGL(k_n_relax_prolong_s<1>, gr, block2d(), 0, st, p, coarse, cg, csp); break;
-    case 2: hipLaunchKernelGGL(k_n_relax_prolong_s<2>, gr, block2d(), 0, st, p, coarse, cg, csp); break;
-    case 3: hipLaunchKernelGGL(k_n_relax_prolong_s<3>, gr, block2d(), 0, st, p, coarse, cg, csp); break;
-    case 4: hipLaunchKernelGGL(k_n_relax_prolong_s<4>, gr, block2d(), 0, st, p, coarse, cg, csp); break;
-    case 5: hipLaunchKernelGGL(k_n_relax_prolong_s<5>, gr, block2d(), 0, st, p, coarse, cg, csp); break;
-    case 6: hipLaunchKernelGGL(k_n_relax_prolong_s<6>, gr, block2d(), 0, st, p, coarse, cg, csp); break;
-    case 7: hipLaunchKernelGGL(k_n_relax_prolong_s<7>, gr, block2d(), 0, st, p, coarse, cg, csp); break;
-    case 8: hipLaunchKernelGGL(k_n_relax_prolong_s<8>, gr, block2d(), 0, st, p, coarse, cg, csp); break;
-    default: break;
-  }
+  if (!with_int<1, MSOM_FASTNL>(nl, [&](auto N) { hipLaunchKernelGGL(k_n_relax_prolong_s<N()>, gr, block2d(), 0, st, p, coarse, cg, csp); }))
+    no_kernel("launch_n_relax_prolong", nl);
 }
 // ---- K consecutive colour half-sweeps of the vertex smoother in ONE pass (round 2), the marching scheme of kernels_march.hip in
 // the natural layout.  A colour pass of k_n_relax touches every cache line of `a` twice (it reads the other colour and writes
@@ -723,12 +714,7 @@ static int n_relax_march_dispatch(hipStream_t st, const NRelaxArgs &p, const dou
     if (rows > 0) H = rows;
     hipLaunchKernelGGL(kern, dim3(strips, (n1 + H - 1) / H), dim3(64), 0, st, p, a_in, H);
   };
-  switch (K) {
-    case 2: launch(k_n_relax_march<NL, 2>, 60); return 0;
-    case 3: launch(k_n_relax_march<NL, 3>, 58); return 0;
-    case 4: launch(k_n_relax_march<NL, 4>, 56); return 0;
-  }
-  return -1;
+  return with_int<2, 4>(K, [&](auto Kc) { launch(k_n_relax_march<NL, Kc()>, 64 - 2 * Kc()); }) ? 0 : -1;   // the kernel's OW
 }
 // ---------------------------------------------------------------------------------------------------------------------
 // k_n_relax_march_s (round 3): K colour half-sweeps of a SPLIT level chained in one pass, the scheme of kernels_march.hip on
@@ -849,12 +835,7 @@ template <int NL>
 static int n_relax_march_s_dispatch(hipStream_t st, const NRelaxArgs &p, const double *a_in, int K, int partial, int rows) {
   const int n = p.g.nx - 1, H = rows > 0 ? rows : 12;
   auto launch = [&](auto kern, int ow) { hipLaunchKernelGGL(kern, dim3(((n >> 1) + 1 + ow - 1) / ow, (n + 1 + H - 1) / H), dim3(64), 0, st, p, a_in, H, partial); };
-  switch (K) {
-    case 2: launch(k_n_relax_march_s<NL, 2>, 62); return 0;
-    case 3: launch(k_n_relax_march_s<NL, 3>, 60); return 0;
-    case 4: launch(k_n_relax_march_s<NL, 4>, 60); return 0;
-  }
-  return -1;
+  return with_int<2, 4>(K, [&](auto Kc) { launch(k_n_relax_march_s<NL, Kc()>, 64 - 2 * ((Kc() + 1) / 2)); }) ? 0 : -1;   // the kernel's OW
 }
 // K (2..4) half-sweeps of a split level starting with colour `color`, a_in -> a_out (both in the split layout g); S2 by row tables;
 // chunks of `rows` rows (0: 12)
@@ -863,15 +844,10 @@ int launch_n_relax_march_s(hipStream_t st, const double *a_in, double *a_out, co
   NRelaxArgs p;
   p.a = a_out; p.b = b; p.mk = mk; p.S2 = nullptr; p.g = g; p.color = color; p.sqD = D * D; p.iRd2 = iRd2; p.lc = lc; p.S2row = S2row;
   if (nl > 1 && !S2row) return -1;
-  switch (nl) {
-    case 1: return n_relax_march_s_dispatch<1>(st, p, a_in, K, partial, rows);
-    case 2: return n_relax_march_s_dispatch<2>(st, p, a_in, K, partial, rows);
-    case 3: return n_relax_march_s_dispatch<3>(st, p, a_in, K, partial, rows);
-    case 4: return n_relax_march_s_dispatch<4>(st, p, a_in, K, partial, rows);
-    case 5: return n_relax_march_s_dispatch<5>(st, p, a_in, K, partial, rows);
-    case 6: return n_relax_march_s_dispatch<6>(st, p, a_in, K, partial, rows);
-  }
-  return -1;
+  int r = -1;
+  // 1 .. 6: K windows of 3 rows x nl layers, the residual and the mask delay lines stay in registers (node_march_kmax)
+  with_int<1, 6>(nl, [&](auto N) { r = n_relax_march_s_dispatch<N()>(st, p, a_in, K, partial, rows); });
+  return r;
 }
 
 // K (2..4) half-sweeps starting with colour `color`, a_in -> a_out, chunks of `rows` rows (0: automatic); returns -1 if K is not supported
@@ -879,17 +855,9 @@ int launch_n_relax_march(hipStream_t st, const double *a_in, double *a_out, cons
                          int color, int K, double D, double iRd2, const LayerCoef &lc, int rows) {
   NRelaxArgs p;
   p.a = a_out; p.b = b; p.mk = mk; p.S2 = S2; p.g = g; p.color = color; p.sqD = D * D; p.iRd2 = iRd2; p.lc = lc;
-  switch (nl) {
-    case 1: return n_relax_march_dispatch<1>(st, p, a_in, K, rows);
-    case 2: return n_relax_march_dispatch<2>(st, p, a_in, K, rows);
-    case 3: return n_relax_march_dispatch<3>(st, p, a_in, K, rows);
-    case 4: return n_relax_march_dispatch<4>(st, p, a_in, K, rows);
-    case 5: return n_relax_march_dispatch<5>(st, p, a_in, K, rows);
-    case 6: return n_relax_march_dispatch<6>(st, p, a_in, K, rows);
-    case 7: return n_relax_march_dispatch<7>(st, p, a_in, K, rows);
-    case 8: return n_relax_march_dispatch<8>(st, p, a_in, K, rows);
-  }
-  return -1;
+  int r = -1;
+  with_int<1, MSOM_FASTNL>(nl, [&](auto N) { r = n_relax_march_dispatch<N()>(st, p, a_in, K, rows); });
+  return r;
 }
 
 // K (2..8) colour half-sweeps of a split level in one launch, for the levels whose colour passes are launch-bound (65 .. 1025 vertices
@@ -964,13 +932,8 @@ int launch_n_relax_tile_s(hipStream_t st, const double *a_in, double *a_out, con
   NRelaxArgs p;
   p.a = a_out; p.b = b; p.mk = mk; p.S2 = nullptr; p.g = g; p.color = color; p.sqD = D * D; p.iRd2 = iRd2; p.lc = lc; p.S2row = S2row;
   const dim3 grid((g.nx + NTS_T - 1) / NTS_T, (g.ny + NTS_T - 1) / NTS_T);
-  switch (nl) {
-    case 1: hipLaunchKernelGGL(k_n_relax_tile_s<1>, grid, dim3(NTS_NT), 0, st, p, a_in, K); return 0;
-    case 2: hipLaunchKernelGGL(k_n_relax_tile_s<2>, grid, dim3(NTS_NT), 0, st, p, a_in, K); return 0;
-    case 3: hipLaunchKernelGGL(k_n_relax_tile_s<3>, grid, dim3(NTS_NT), 0, st, p, a_in, K); return 0;
-    case 4: hipLaunchKernelGGL(k_n_relax_tile_s<4>, grid, dim3(NTS_NT), 0, st, p, a_in, K); return 0;
-  }
-  return -1;
+  // 1 .. 4: the kernel's static LDS array is nl x 40 x 41 doubles, 52 KB at nl = 4 and past the 64 KB a static array may have at 5
+  return with_int<1, 4>(nl, [&](auto N) { hipLaunchKernelGGL(k_n_relax_tile_s<N()>, grid, dim3(NTS_NT), 0, st, p, a_in, K); }) ? 0 : -1;
 }
 
 // NS full red-black sweeps in ONE pass over HBM, out of place (a_in -> a_out; neighbouring workgroups read each
@@ -1036,17 +999,7 @@ int launch_n_relax_tile(hipStream_t st, const double *a_in, double *a_out, const
   NRelaxArgs p;
   p.a = a_out; p.b = b; p.mk = mk; p.S2 = S2; p.g = g; p.color = 0; p.sqD = D * D; p.iRd2 = iRd2; p.lc = lc;
   if (ns == 2 && nl > 6) ns = 1;
-  switch (nl) {
-    case 1: n_relax_tile_dispatch<1>(st, p, a_in, ns); break;
-    case 2: n_relax_tile_dispatch<2>(st, p, a_in, ns); break;
-    case 3: n_relax_tile_dispatch<3>(st, p, a_in, ns); break;
-    case 4: n_relax_tile_dispatch<4>(st, p, a_in, ns); break;
-    case 5: n_relax_tile_dispatch<5>(st, p, a_in, ns); break;
-    case 6: n_relax_tile_dispatch<6>(st, p, a_in, ns); break;
-    case 7: n_relax_tile_dispatch<7>(st, p, a_in, ns); break;
-    case 8: n_relax_tile_dispatch<8>(st, p, a_in, ns); break;
-    default: break;
-  }
+  if (!with_int<1, MSOM_FASTNL>(nl, [&](auto N) { n_relax_tile_dispatch<N()>(st, p, a_in, ns); })) no_kernel("launch_n_relax_tile", nl);
   return ns;
 }
 void launch_n_relax(hipStream_t st, double *a, const double *b, const double *mk, const double *S2, const NatGeom &g, int nl, int color, double D,
@@ -1055,31 +1008,11 @@ void launch_n_relax(hipStream_t st, double *a, const double *b, const double *mk
   p.a = a; p.b = b; p.mk = mk; p.S2 = S2; p.g = g; p.color = color; p.sqD = D * D; p.iRd2 = iRd2; p.lc = lc; p.S2row = S2row;
   const int n = g.nx - 1;
   dim3 gr = grid2d((n + 1) / 2, n - 1);
-  if (sp) {
-    switch (nl) {
-      case 1: hipLaunchKernelGGL(k_n_relax_s<1>, gr, block2d(), 0, st, p); break;
-      case 2: hipLaunchKernelGGL(k_n_relax_s<2>, gr, block2d(), 0, st, p); break;
-      case 3: hipLaunchKernelGGL(k_n_relax_s<3>, gr, block2d(), 0, st, p); break;
-      case 4: hipLaunchKernelGGL(k_n_relax_s<4>, gr, block2d(), 0, st, p); break;
-      case 5: hipLaunchKernelGGL(k_n_relax_s<5>, gr, block2d(), 0, st, p); break;
-      case 6: hipLaunchKernelGGL(k_n_relax_s<6>, gr, block2d(), 0, st, p); break;
-      case 7: hipLaunchKernelGGL(k_n_relax_s<7>, gr, block2d(), 0, st, p); break;
-      case 8: hipLaunchKernelGGL(k_n_relax_s<8>, gr, block2d(), 0, st, p); break;
-      default: break;
-    }
-    return;
-  }
-  switch (nl) {
-    case 1: hipLaunchKernelGGL(k_n_relax<1>, gr, block2d(), 0, st, p); break;
-    case 2: hipLaunchKernelGGL(k_n_relax<2>, gr, block2d(), 0, st, p); break;
-    case 3: hipLaunchKernelGGL(k_n_relax<3>, gr, block2d(), 0, st, p); break;
-    case 4: hipLaunchKernelGGL(k_n_relax<4>, gr, block2d(), 0, st, p); break;
-    case 5: hipLaunchKernelGGL(k_n_relax<5>, gr, block2d(), 0, st, p); break;
-    case 6: hipLaunchKernelGGL(k_n_relax<6>, gr, block2d(), 0, st, p); break;
-    case 7: hipLaunchKernelGGL(k_n_relax<7>, gr, block2d(), 0, st, p); break;
-    case 8: hipLaunchKernelGGL(k_n_relax<8>, gr, block2d(), 0, st, p); break;
-    default: break;
-  }
+  const bool ok = with_int<1, MSOM_FASTNL>(nl, [&](auto N) {
+    if (sp) hipLaunchKernelGGL(k_n_relax_s<N()>, gr, block2d(), 0, st, p);
+    else hipLaunchKernelGGL(k_n_relax<N()>, gr, block2d(), 0, st, p);
+  });
+  if (!ok) no_kernel("launch_n_relax", nl);
 }
 // residual_baroclinic qg_baroclinic_ms.h:295-341 / residual_barotropic qg_barotropic.h:78-97; max -> *maxres
 struct NResArgs {
@@ -1272,17 +1205,9 @@ void launch_n_correct_residual(hipStream_t st, const double *a, double *a_out, c
   p.sp = gres != nullptr; p.gr = gres ? *gres : g;
   const NatGeom gd = gda ? *gda : g;
   const int dsp = gda != nullptr;
-  switch (march ? nl : 0) {
-    case 1: ncr_launch<1>(st, p, da, gd, dsp, a_out, bcv); break;
-    case 2: ncr_launch<2>(st, p, da, gd, dsp, a_out, bcv); break;
-    case 3: ncr_launch<3>(st, p, da, gd, dsp, a_out, bcv); break;
-    case 4: ncr_launch<4>(st, p, da, gd, dsp, a_out, bcv); break;
-    case 5: ncr_launch<5>(st, p, da, gd, dsp, a_out, bcv); break;
-    case 6: ncr_launch<6>(st, p, da, gd, dsp, a_out, bcv); break;
-    case 7: ncr_launch<7>(st, p, da, gd, dsp, a_out, bcv); break;
-    case 8: ncr_launch<8>(st, p, da, gd, dsp, a_out, bcv); break;
-    default: hipLaunchKernelGGL(k_n_correct_residual, grid_capped(g.nx, g.ny), block2d(), 0, st, p, da, gd, dsp, a_out, bcv);
-  }
+  // the marched form where it is asked for and exists, else one thread per vertex
+  if (!(march && with_int<1, MSOM_FASTNL>(nl, [&](auto N) { ncr_launch<N()>(st, p, da, gd, dsp, a_out, bcv); })))
+    hipLaunchKernelGGL(k_n_correct_residual, grid_capped(g.nx, g.ny), block2d(), 0, st, p, da, gd, dsp, a_out, bcv);
 }
 // restriction_coarsen_vert (residual), restriction_coarsen_vert2 (mask), restriction_vert (injection), my_vertex.h:49-75
 __device__ __forceinline__ void n_restrict_pt(const double *__restrict__ f, const NatGeom &fg, double *c, const NatGeom &cg, int nl, int kind, int I, int J) {
@@ -1427,17 +1352,8 @@ __global__ void __launch_bounds__(NMGC_NT) k_n_mg_coarse(NCoarseArgs a, int nrel
   }
 }
 void launch_n_mg_coarse(hipStream_t st, const NCoarseArgs &a, int nrelax, int nl) {
-  switch (nl) {
-    case 1: hipLaunchKernelGGL(k_n_mg_coarse<1>, dim3(1), dim3(NMGC_NT), 0, st, a, nrelax); break;
-    case 2: hipLaunchKernelGGL(k_n_mg_coarse<2>, dim3(1), dim3(NMGC_NT), 0, st, a, nrelax); break;
-    case 3: hipLaunchKernelGGL(k_n_mg_coarse<3>, dim3(1), dim3(NMGC_NT), 0, st, a, nrelax); break;
-    case 4: hipLaunchKernelGGL(k_n_mg_coarse<4>, dim3(1), dim3(NMGC_NT), 0, st, a, nrelax); break;
-    case 5: hipLaunchKernelGGL(k_n_mg_coarse<5>, dim3(1), dim3(NMGC_NT), 0, st, a, nrelax); break;
-    case 6: hipLaunchKernelGGL(k_n_mg_coarse<6>, dim3(1), dim3(NMGC_NT), 0, st, a, nrelax); break;
-    case 7: hipLaunchKernelGGL(k_n_mg_coarse<7>, dim3(1), dim3(NMGC_NT), 0, st, a, nrelax); break;
-    case 8: hipLaunchKernelGGL(k_n_mg_coarse<8>, dim3(1), dim3(NMGC_NT), 0, st, a, nrelax); break;
-    default: break;
-  }
+  if (!with_int<1, MSOM_FASTNL>(nl, [&](auto N) { hipLaunchKernelGGL(k_n_mg_coarse<N()>, dim3(1), dim3(NMGC_NT), 0, st, a, nrelax); }))
+    no_kernel("launch_n_mg_coarse", nl);
 }
 void launch_n_prolong(hipStream_t st, const double *c, const NatGeom &cg, double *f, const NatGeom &fg, int nl, int csp, int fsp) {
   if (csp || fsp) hipLaunchKernelGGL(k_n_prolong_s, grid2d(fg.nx, fg.ny), block2d(), 0, st, c, cg, csp, f, fg, fsp, nl);

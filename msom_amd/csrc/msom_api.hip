@@ -3235,6 +3235,11 @@ extern "C" int msom_bench_kernel(msom_t *m, const char *kernel, int reps, double
   if (m) m->res_ready = -1;
   NEED_CONST(m);
   if (!kernel || reps < 1 || !avg_ms) return MSOM_ERR_ARG;
+  // the solver's guard for these launchers is sweep_path / fuse_prolong; here the caller names them
+  if (m->nl > MSOM_FASTNL && (!strncmp(kernel, "block2", 6) || !strcmp(kernel, "red_prolong"))) {
+    msom_set_error("kernel %s has no instantiation for nl = %d (1..%d)", kernel, m->nl, MSOM_FASTNL);
+    return MSOM_ERR_ARG;
+  }
   hipEvent_t a, b;
   HIPCHK(hipEventCreate(&a));
   HIPCHK(hipEventCreate(&b));
