@@ -227,6 +227,49 @@ int msom_stats_weight(msom_t *m, double *W);        /* sum of the weights so far
 int msom_stats_get(msom_t *m, int which, double *out); /* [nl][ny][nx], host or device pointer: S / W, or a derived quantity */
 int msom_time_filter(msom_t *m, double dt);         /* qo_me = (1 - a) * qo_me + a * q, a = dt / tau_f; option "tau_f" [20] */
 
+/* ---- vertical normal modes of the stretching operator on the device: eigmod of msqg/eigmode.h (compiled out in the reference by
+ * MODE_PV_INVERT 0) and the layer <-> mode products of msqg/qg.h:117-131,143-157.  The mode arrays are no field ids: they have this enum
+ * and the accessors below.  Only M2L and IBU are stored; L2M and RD are formed from them on request. */
+enum { MSOM_MD_IBU = 0,  /* iBu_m = -lambda_m, iBu_0 = 0 exactly (eigmode.h:256-266); nl arrays [ny][nx]          */
+       MSOM_MD_RD  = 1,  /* sqrt(-1 / iBu_m), 0 for m = 0 (eigmode.h:284); nl arrays                               */
+       MSOM_MD_M2L = 2,  /* cm2l: array k*nl+m = vr[k][m], layer k from mode m (eigmode.h:246-248); nl*nl arrays   */
+       MSOM_MD_L2M = 3,  /* cl2m: array m*nl+k, mode m from layer k (eigmode.h:245-247); nl*nl arrays              */
+       MSOM_MD_N   = 4 };
+/* msom_modes_compute (after msom_set_const): per column, from the handle's MSOM_S and the layer thicknesses, the eigenproblem of the
+ *   tridiagonal amat of eigmode.h:86-109 (amat[l][l+1] = -S_l / (dhc_l dhf_l), amat[l][l-1] = -S_l-1 / (dhc_l-1 dhf_l), diagonal = minus
+ *   the row's off-diagonals; nl = 1: the 1 x 1 zero matrix), solved as the symmetric tridiagonal D^1/2 amat D^-1/2, D = diag(dhf), by
+ *   cyclic Jacobi rotations with a fixed cap of sweeps.  Modes in ascending order of the eigenvalue, mode 0 the barotropic one; right
+ *   vectors with Flierl's normalisation sum_k dhf_k vr_km^2 = htotal (= 1, eigmode.h:70) and positive at the surface (sign(x) = x > 0 ?
+ *   1 : -1); iBu_m = -lambda_m with iBu_0 = 0; left vectors l2m[m][k] = dhf[k] * m2l[k][m] (that product, htotal = 1 dropped), which is
+ *   what the normalisation of eigmode.h:223-231 gives; Rd_m = sqrt(-1. / iBu_m).
+ *   Storage: a stratification that is the same in every column (no MSOM_FR / MSOM_RO / MSOM_S set, no varRo) is solved once, by the same
+ *   kernel on cell (0, 0), and kept as nl*nl + nl doubles in the handle; otherwise nl*nl + nl arrays of one layer each are allocated on
+ *   the first compute and freed by msom_destroy.  Option "modes_compact" [-1: automatic; 0: always per column].
+ *   An interface whose S is not positive and finite (the spectrum is degenerate, the vectors are not unique), or an iteration that hits
+ *   the cap: MSOM_ERR_CONFIG, no modes; the handle stays usable.  msom_set_const drops the modes.
+ * msom_modes_layers: arrays of `which` (nl or nl*nl).  msom_modes_get: those arrays, [layers][ny][nx], the local tile; the compact
+ *   form is broadcast.
+ * msom_modes_project: to_modes != 0: out_m = sum_k l2m[m][k] * in_k, else out_k = sum_m m2l[k][m] * in_m, accumulated as acc = 0;
+ *   acc = acc + c * x with the inner index ascending (the contract of the strict build; the product build fuses each step).  Pointwise,
+ *   so it works on tiles; in == out is allowed.
+ * msom_modes_energy: from the handle's MSOM_PSI with the ghost values boundary() left there and u, v as the msom_stats_* block defines
+ *   them: x_m = sum_k l2m[m][k] x_k for u, v, psi; ke[m] = sum_cells 0.5 * (u_m^2 + v_m^2) * Delta^2, pe[m] = sum_cells 0.5 * (-iBu_m) *
+ *   psi_m^2 * Delta^2, one pass over psi, deterministic two-stage sums; over all tiles (collective there, like msom_bfn_misfit).
+ *   Pointwise sum_m u_m^2 = sum_k dhf_k u_k^2 and sum_m (-iBu_m) psi_m^2 = sum_l S_l (psi_l - psi_l+1)^2 / dhc_l.
+ * msom_modes_set_rd: MSOM_RD = MSOM_MD_RD of `mode` with the boundary condition of msom_set_field(MSOM_RD); the next msom_wavelet_filter
+ *   builds sig_filt = min(afilt * Rd, Lfmax) from it.  mode = 1 is the reference's MODE_PV_INVERT branch, msqg/qg.h:1055-1057.
+ * Errors: null handle, `which` out of range, null in / out (msom_modes_energy: both null), mode outside 1 .. nl-1: MSOM_ERR_ARG; any call
+ *   but msom_modes_compute with no successful msom_modes_compute since msom_set_const: MSOM_ERR_STATE.  The stream is synchronised on
+ *   return of every call except msom_modes_project with two device pointers.
+ * msom_get_param "modes_ready", "modes_compact" (the form held, or that the next compute will take), "modes_bytes" (8 ny nx per stored
+ *   array, 0 in the compact form).  msom_bench_kernel names "modes_project" and "modes_energy". */
+int msom_modes_compute(msom_t *m);
+int msom_modes_layers(msom_t *m, int which);                       /* nl or nl*nl */
+int msom_modes_get(msom_t *m, int which, double *out);             /* [layers][ny][nx], host or device pointer, local tile */
+int msom_modes_project(msom_t *m, int to_modes, const double *in, double *out);  /* [nl][ny][nx] each, host or device */
+int msom_modes_energy(msom_t *m, double *ke, double *pe);          /* [nl] each, host pointers; either may be NULL */
+int msom_modes_set_rd(msom_t *m, int mode);                        /* MSOM_RD = MSOM_MD_RD of `mode` */
+
 /* ---- time loop of Basilisk predictor-corrector run() as driven by msqg/qg.c
  * msom_step: one RK2 step on the internal state (update, dtnext, advance dt/2, update,
  * advance dt).  msom_set_tnext gives the time of the next t-scheduled event (output). */

@@ -16,6 +16,10 @@ FIELDS = dict(PSI=0, Q=1, ZETA=2, PSIPG=3, ZETAPG=4, QFORC=5, TMP=6, FR=7, S=8, 
 # running statistics (msom_stats_*): accumulators 0 .. NACC - 1 (bit k of the mask), derived quantities, qo_me of time_filter
 STATS = dict(PSI=0, Q=1, PSI2=2, Q2=3, KE=4, UQ=5, VQ=6, NACC=7, EKE=16, UQ_EDDY=17, VQ_EDDY=18, QME=32)
 
+# vertical normal modes (msom_modes_*): what modes_get returns -- IBU and RD nl arrays, M2L (array k*nl + m: layer k from mode m) and
+# L2M (array m*nl + k: mode m from layer k) nl*nl arrays
+MODES = dict(IBU=0, RD=1, M2L=2, L2M=3, N=4)
+
 
 class MsomError(RuntimeError):
     pass
@@ -74,6 +78,12 @@ def load_library(strict=False):
         "msom_stats_weight": (ci, [vp, _dp]),
         "msom_stats_get": (ci, [vp, ci, vp]),
         "msom_time_filter": (ci, [vp, cd]),
+        "msom_modes_compute": (ci, [vp]),
+        "msom_modes_layers": (ci, [vp, ci]),
+        "msom_modes_get": (ci, [vp, ci, vp]),
+        "msom_modes_project": (ci, [vp, ci, vp, vp]),
+        "msom_modes_energy": (ci, [vp, _dp, _dp]),
+        "msom_modes_set_rd": (ci, [vp, ci]),
         "msom_step": (ci, [vp, _dp]),
         "msom_set_tnext": (ci, [vp, cd]),
         "msom_time": (cd, [vp]),
@@ -330,6 +340,40 @@ class QG:
     def time_filter(self, dt):
         """qo_me = (1 - a) * qo_me + a * Q, a = dt / tau_f (option "tau_f", 20); read it back with stats_get(STATS["QME"])"""
         self._chk(self.L.msom_time_filter(self.h, float(dt)))
+
+    # -- vertical normal modes of the stretching operator on the device (MODES), msqg/eigmode.h
+    def modes_compute(self):
+        """eigen-decomposition of the stretching matrix of every column (once, where the stratification is uniform); after set_const"""
+        self._chk(self.L.msom_modes_compute(self.h))
+
+    def modes_get(self, which, out=None):
+        """the arrays of MODES[name]: [nl or nl*nl][ny][nx] of this tile.  out: optional destination (numpy array or tensor)"""
+        n = self.L.msom_modes_layers(self.h, int(which))
+        if n < 0:
+            self._chk(n)
+        a = np.empty((n, self.ny, self.nx)) if out is None else out
+        self._chk(self.L.msom_modes_get(self.h, int(which), _ptr(a)))
+        return a
+
+    def modes_project(self, a, to_modes, out=None):
+        """layers -> modes (to_modes true: sum_k l2m[m][k] a_k) or modes -> layers (sum_m m2l[k][m] a_m) of a [nl][ny][nx] array, host
+        or device.  out: optional destination, may be `a` itself; two device arrays are not waited for"""
+        a = _f64(a, (self.nl, self.ny, self.nx))
+        if out is None:
+            out = np.empty((self.nl, self.ny, self.nx))
+        self._chk(self.L.msom_modes_project(self.h, 1 if to_modes else 0, _ptr(a), _ptr(out)))
+        return out
+
+    def modes_energy(self):
+        """(ke, pe): kinetic and potential energy of every mode from the PSI the model holds, summed over the domain (all tiles)"""
+        ke, pe = np.empty(self.nl), np.empty(self.nl)
+        self._chk(self.L.msom_modes_energy(self.h, ke.ctypes.data_as(_dp), pe.ctypes.data_as(_dp)))
+        return ke, pe
+
+    def modes_set_rd(self, mode=1):
+        """RD = deformation radius of `mode`, so that the next wavelet_filter builds sig_filt = min(afilt * Rd, Lfmax) from the
+        stratification (mode 1: the reference's MODE_PV_INVERT branch, msqg/qg.h:1055-1057)"""
+        self._chk(self.L.msom_modes_set_rd(self.h, int(mode)))
 
     # -- time loop
     def step(self):

@@ -9,6 +9,7 @@
 #include <utility>
 
 #include "msom_internal.h"
+#include "modes_inl.h"   // ModesLayers, the per-column eigen routine
 
 // Run-time value -> template argument.  with_int<LO, HI>(v, f) calls f(std::integral_constant<int, v>{}) and returns true when
 // LO <= v <= HI; otherwise it calls nothing and returns false.  The range is the list of instantiations a launcher has: a launcher
@@ -214,6 +215,29 @@ bool relax_visit_fits(int nl, const SplitGeom &sg, int rows, int pairs);
 extern "C" int msom_visit_ring(int hk, int ny, int march_rows, int visit_rows, int pairs, int corr, int *geom, int *bands);
 // can the lean interior body of the pass address every layer of the level (sg) and, with the correction, of psi (ng)?
 bool march_lean_fits(int nl, const SplitGeom &sg, const NatGeom *ng);
+
+// ---- kernels_modes.hip: vertical normal modes (msom_modes_*, msqg/eigmode.h).  One decomposition is nl*nl + nl numbers per column:
+// M2L array k*nl + m (layer k from mode m), then iBu_m; `md` holds them as one natural padded layer each (general form), a ModeCoef
+// by value (compact form: the same stratification in every column).  mc != nullptr selects the compact instantiation.
+struct ModeCoef {
+  double m2l[MSOM_MAXNL * MSOM_MAXNL], ibu[MSOM_MAXNL];   // m2l[k * nl + m]
+};
+// eigenproblem of every column of an ncx x ncy grid from S (geometry g); output array a at out[a * ols + (per_column ? cell : 0)];
+// *flag |= MODES_BAD_S / MODES_NOCONV.  -1: no kernel for nl
+int launch_modes_eig(hipStream_t st, const double *S, const NatGeom &g, int nl, int ncx, int ncy, double *out, size_t ols, int per_column,
+                     const ModesLayers &l, int *flag);
+// arrays first .. first + cnt - 1 of MSOM_MD_`which` into out, contiguous [cnt][ny][nx]
+int launch_modes_get(hipStream_t st, double *out, const double *md, const ModeCoef *mc, const NatGeom &g, int nl, const ModesLayers &l, int which,
+                     int first, int cnt);
+int launch_modes_rd(hipStream_t st, double *rd, const double *md, const ModeCoef *mc, const NatGeom &g, int nl, int mode);   // interior of MSOM_RD
+// in, out: contiguous [nl][ny][nx], may be the same array
+int launch_modes_project(hipStream_t st, const double *in, double *out, const double *md, const ModeCoef *mc, const NatGeom &g, int nl,
+                         const ModesLayers &l, int to_modes);
+// out[0 .. nl) = ke[m], out[nl .. 2 nl) = pe[m] of this tile; partial: 2 nl * modes_energy_stride(g) doubles
+int modes_energy_blocks(const NatGeom &g);
+int modes_energy_stride(const NatGeom &g);
+int launch_modes_energy(hipStream_t st, const double *psi, const double *md, const ModeCoef *mc, const NatGeom &g, int nl, const ModesLayers &l,
+                        double *partial, double *out, double D);
 
 // ---- kernels_wavelet.hip
 void launch_wv_restrict(hipStream_t st, const double *f, const NatGeom &fg, double *c, const NatGeom &cg, int nl);

@@ -186,6 +186,15 @@ struct msom {
   long stats_count = 0;                   // msom_step calls seen since msom_stats_begin (every stats_every-th one samples)
   long stats_ndev = 0;                    // ... of whose samples, those that read their weight from the device (tests ask: stats_dev_samples)
   double tau_f = 20;                      // option "tau_f" (msqg/qg.h:495)
+  // vertical normal modes (msom_modes_*, msqg/eigmode.h); nothing is allocated until msom_modes_compute
+  int modes_ready = 0;                    // a successful msom_modes_compute since the last msom_set_const
+  int modes_compact = 0;                  // ... which left the compact form (modes_mc) rather than one array per number (modes_md)
+  int modes_compact_opt = -1;             // option "modes_compact": -1 compact where the stratification is uniform, 0 always per column
+  ModeCoef modes_mc = {};                 // compact form: M2L[k * nl + m] and iBu_m, passed to the kernels by value
+  double *modes_md = nullptr;             // general form: nl*nl + nl natural layers (M2L arrays, then iBu)
+  double *modes_dev = nullptr;            // device scratch: the numbers of the compact solve, then the 2 nl sums of msom_modes_energy
+  int *modes_flag = nullptr;              // device word the eigen kernel ORs its failures into
+  double *modes_partial = nullptr;        // per-block partial sums of msom_modes_energy
   int s_zero = 0;  // pystep_de(onlyKE = 1) zeroed the stretching field S (msqg/qg_energy.h:319-325); undone by msom_set_const
   std::vector<NatGeom> wv_g;
   std::vector<double *> wv_s, wv_r, wv_sig;
@@ -204,6 +213,7 @@ struct msom {
 
 static void free_agglomeration(msom *m);
 static void stats_drop(msom *m);
+static void modes_drop(msom *m);
 
 extern "C" const char *msom_version(void) {
 #ifdef MSOM_STRICT
@@ -685,6 +695,10 @@ extern "C" int msom_destroy(msom_t *m) {
   if (m->partial_rr) hipFree(m->partial_rr);
   if (m->bfn_partial) hipFree(m->bfn_partial);
   stats_drop(m);
+  modes_drop(m);
+  if (m->modes_dev) hipFree(m->modes_dev);
+  if (m->modes_flag) hipFree(m->modes_flag);
+  if (m->modes_partial) hipFree(m->modes_partial);
   if (m->d_cargs) hipFree(m->d_cargs);
   if (m->partial_umax) hipFree(m->partial_umax);
   if (m->d_scal) hipFree(m->d_scal);
@@ -778,6 +792,10 @@ extern "C" int msom_set_option(msom_t *m, const char *key, double v) {
     if (!(v > 0) || !std::isfinite(v)) { msom_set_error("option tau_f = %g", v); return MSOM_ERR_ARG; }
     m->tau_f = v;
   }
+  else if (!strcmp(key, "modes_compact")) {
+    if ((int)v != -1 && (int)v != 0) { msom_set_error("option modes_compact = %g (-1 or 0)", v); return MSOM_ERR_ARG; }
+    m->modes_compact_opt = (int)v;
+  }
   else if (!strcmp(key, "stochastic")) {
     m->stochastic = (int)v;
     if (m->stochastic && !m->f[MSOM_NOISE]) {
@@ -832,6 +850,10 @@ extern "C" double msom_get_param(msom_t *m, const char *key) {
     for (int k = 0; k < MSOM_ST_NACC; k++) n += m->stats.s[k] ? 1 : 0;
     return (double)n * m->nl * m->nx * m->ny * sizeof(double);
   }
+  if (!strcmp(key, "modes_ready")) return m->const_set && m->modes_ready;
+  if (!strcmp(key, "modes_compact")) return m->const_set && m->modes_ready ? m->modes_compact : (m->modes_compact_opt != 0 && m->fr_uniform);
+  if (!strcmp(key, "modes_bytes"))   // 8 ny nx per stored array: nl*nl + nl of them in the general form, none in the compact one
+    return m->modes_md ? (double)(m->nl * m->nl + m->nl) * m->nx * m->ny * sizeof(double) : 0.;
   // which kernels the dispatch picks for this handle (bench.py names what ran from these, not from a table)
   if (!strcmp(key, "resmax_marching")) return m->uniformS && m->nl <= MSOM_FASTNL && m->g.nx >= 64 && m->g.ny >= 16 && m->opt.resmax_rows >= 0;
   // how the wall-ring chunks around the fused visit run (-1: no fused visit on this handle), as launch_relax_visit reads the option
@@ -1164,6 +1186,7 @@ extern "C" int msom_set_const(msom_t *m) {
   m->const_set = 1;
   m->bfn_begun = 0;
   stats_drop(m);
+  modes_drop(m);
   return sync_stream(m);
 }
 
@@ -2279,6 +2302,137 @@ extern "C" int msom_time_filter(msom_t *m, double dt) {
   return sync_stream(m);
 }
 
+// ------------------------------------------------------------------ vertical normal modes (msqg/eigmode.h; products of msqg/qg.h:117-157)
+
+static void modes_drop(msom *m) {
+  if (m->modes_md) hipFree(m->modes_md);
+  m->modes_md = nullptr;
+  m->modes_ready = m->modes_compact = 0;
+}
+static ModesLayers modes_layers(const msom *m) {
+  ModesLayers l = {};
+  for (int k = 0; k < m->nl; k++) l.dhf[k] = m->dhf[k];
+  for (int k = 0; k < m->nl - 1; k++) l.dhc[k] = m->dhc[k];
+  return l;
+}
+static const ModeCoef *modes_mc(const msom *m) { return m->modes_compact ? &m->modes_mc : nullptr; }
+static bool is_device_ptr(const void *p) {
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // an address the runtime does not know: host
+  return a.type == hipMemoryTypeDevice;
+}
+#define NEED_MODES(m, fn)                                                                   \
+  do {                                                                                      \
+    if (!(m)->const_set || !(m)->modes_ready) {                                             \
+      msom_set_error(fn ": no successful msom_modes_compute since msom_set_const");         \
+      return MSOM_ERR_STATE;                                                                \
+    }                                                                                       \
+  } while (0)
+
+extern "C" int msom_modes_compute(msom_t *m) {
+  NEED_CONST(m);
+  const int nl = m->nl, na = nl * nl + nl;
+  const int compact = m->modes_compact_opt != 0 && m->fr_uniform;
+  modes_drop(m);
+  if (!m->modes_flag) HIPCHK(hipMalloc(&m->modes_flag, sizeof(int)));
+  if (!m->modes_dev) HIPCHK(hipMalloc(&m->modes_dev, sizeof(ModeCoef)));
+  HIPCHK(hipMemsetAsync(m->modes_flag, 0, sizeof(int), m->st));
+  int r;
+  if (compact) {   // the same kernel on a one-column grid: cell (0, 0) of S
+    r = launch_modes_eig(m->st, m->f[MSOM_S], m->g, nl, 1, 1, m->modes_dev, 1, 0, modes_layers(m), m->modes_flag);
+  } else {
+    const size_t bytes = (size_t)na * m->g.ls * sizeof(double);
+    HIPCHK(hipMalloc(&m->modes_md, bytes));
+    HIPCHK(hipMemsetAsync(m->modes_md, 0, bytes, m->st));
+    r = launch_modes_eig(m->st, m->f[MSOM_S], m->g, nl, m->nx, m->ny, m->modes_md, m->g.ls, 1, modes_layers(m), m->modes_flag);
+  }
+  if (r) { modes_drop(m); msom_set_error("msom_modes_compute: no kernel for nl = %d", nl); return MSOM_ERR_CONFIG; }
+  int flag = 0;
+  double h[MSOM_MAXNL * MSOM_MAXNL + MSOM_MAXNL];
+  HIPCHK(hipMemcpyAsync(&flag, m->modes_flag, sizeof(int), hipMemcpyDeviceToHost, m->st));
+  if (compact) HIPCHK(hipMemcpyAsync(h, m->modes_dev, na * sizeof(double), hipMemcpyDeviceToHost, m->st));
+  if ((r = sync_stream(m))) { modes_drop(m); return r; }
+  if (flag) {
+    modes_drop(m);
+    if (flag & MODES_BAD_S) msom_set_error("msom_modes_compute: S = (Fr/Ro)^2 is not positive and finite on every interface: the spectrum is degenerate");
+    else msom_set_error("msom_modes_compute: the Jacobi iteration did not converge within %d sweeps", MODES_MAXSWEEP);
+    return MSOM_ERR_CONFIG;
+  }
+  if (compact) {
+    memset(&m->modes_mc, 0, sizeof m->modes_mc);
+    for (int k = 0; k < nl * nl; k++) m->modes_mc.m2l[k] = h[k];
+    for (int k = 0; k < nl; k++) m->modes_mc.ibu[k] = h[nl * nl + k];
+  }
+  m->modes_compact = compact;
+  m->modes_ready = 1;
+  return MSOM_OK;
+}
+
+extern "C" int msom_modes_layers(msom_t *m, int which) {
+  if (!m || which < 0 || which >= MSOM_MD_N) return MSOM_ERR_ARG;
+  NEED_MODES(m, "msom_modes_layers");
+  return which == MSOM_MD_IBU || which == MSOM_MD_RD ? m->nl : m->nl * m->nl;
+}
+
+extern "C" int msom_modes_get(msom_t *m, int which, double *out) {
+  if (!m || which < 0 || which >= MSOM_MD_N || !out) return MSOM_ERR_ARG;
+  NEED_MODES(m, "msom_modes_get");
+  const int nl = m->nl, n = which == MSOM_MD_IBU || which == MSOM_MD_RD ? nl : nl * nl;
+  const size_t cells = (size_t)m->nx * m->ny;
+  for (int first = 0; first < n; first += nl) {   // the staging buffer holds nl arrays
+    const int cnt = std::min(nl, n - first);
+    if (launch_modes_get(m->st, m->staging, m->modes_md, modes_mc(m), m->g, nl, modes_layers(m), which, first, cnt)) return MSOM_ERR_CONFIG;
+    HIPCHK(hipMemcpyAsync(out + first * cells, m->staging, cnt * cells * sizeof(double), hipMemcpyDefault, m->st));
+  }
+  return sync_stream(m);
+}
+
+extern "C" int msom_modes_project(msom_t *m, int to_modes, const double *in, double *out) {
+  if (!m || !in || !out) return MSOM_ERR_ARG;
+  NEED_MODES(m, "msom_modes_project");
+  const size_t bytes = (size_t)m->nl * m->nx * m->ny * sizeof(double);
+  if (is_device_ptr(in) && is_device_ptr(out)) {   // in place on the caller's arrays, queued on the stream and not waited for
+    if (launch_modes_project(m->st, in, out, m->modes_md, modes_mc(m), m->g, m->nl, modes_layers(m), to_modes != 0)) return MSOM_ERR_CONFIG;
+    return m->sticky;
+  }
+  HIPCHK(hipMemcpyAsync(m->staging, in, bytes, hipMemcpyDefault, m->st));
+  if (launch_modes_project(m->st, m->staging, m->staging, m->modes_md, modes_mc(m), m->g, m->nl, modes_layers(m), to_modes != 0)) return MSOM_ERR_CONFIG;
+  HIPCHK(hipMemcpyAsync(out, m->staging, bytes, hipMemcpyDefault, m->st));
+  return sync_stream(m);
+}
+
+// the launch of msom_modes_energy: the 2 nl sums of this tile into modes_dev
+static int modes_energy_launch(msom *m) {
+  if (!m->modes_partial) HIPCHK(hipMalloc(&m->modes_partial, (size_t)2 * MSOM_MAXNL * modes_energy_stride(m->g) * sizeof(double)));
+  if (launch_modes_energy(m->st, m->f[MSOM_PSI], m->modes_md, modes_mc(m), m->g, m->nl, modes_layers(m), m->modes_partial, m->modes_dev,
+                          m->p.L0 / m->gnx))
+    return MSOM_ERR_CONFIG;
+  return MSOM_OK;
+}
+extern "C" int msom_modes_energy(msom_t *m, double *ke, double *pe) {
+  if (!m || (!ke && !pe)) return MSOM_ERR_ARG;
+  NEED_MODES(m, "msom_modes_energy");
+  const int nl = m->nl;
+  int r = modes_energy_launch(m);
+  if (r) return r;
+  double *dst[2] = {ke, pe};
+  for (int part = 0; part < 2; part++) {   // nl sums at a time through the scalar slots (summed over the tiles there)
+    HIPCHK(hipMemcpyAsync(m->d_scal + SC_LSUM, m->modes_dev + part * nl, nl * sizeof(double), hipMemcpyDeviceToDevice, m->st));
+    if ((r = reduce_scal(m, SC_LSUM, nl, RED_SUM))) return r;
+    if (dst[part]) for (int k = 0; k < nl; k++) dst[part][k] = m->h_scal[SC_LSUM + k];
+  }
+  return sync_stream(m);
+}
+
+extern "C" int msom_modes_set_rd(msom_t *m, int mode) {
+  if (!m || mode < 1 || mode > m->nl - 1) return MSOM_ERR_ARG;
+  NEED_MODES(m, "msom_modes_set_rd");
+  if (launch_modes_rd(m->st, m->f[MSOM_RD], m->modes_md, modes_mc(m), m->g, m->nl, mode)) return MSOM_ERR_CONFIG;
+  fill_bc(m, MSOM_RD);   // what msom_set_field(MSOM_RD) does after its pack
+  m->wv_ready = 0;
+  return sync_stream(m);
+}
+
 // ------------------------------------------------------------------ time loop
 
 // dtnext() [Basilisk, SURVEY App. B]
@@ -3240,6 +3394,11 @@ extern "C" int msom_bench_kernel(msom_t *m, const char *kernel, int reps, double
     msom_set_error("kernel %s has no instantiation for nl = %d (1..%d)", kernel, m->nl, MSOM_FASTNL);
     return MSOM_ERR_ARG;
   }
+  if (!strncmp(kernel, "modes_", 6)) {
+    if (strcmp(kernel, "modes_project") && strcmp(kernel, "modes_energy")) { msom_set_error("unknown kernel %s", kernel); return MSOM_ERR_ARG; }
+    NEED_MODES(m, "msom_bench_kernel");
+    if (!m->modes_partial) HIPCHK(hipMalloc(&m->modes_partial, (size_t)2 * MSOM_MAXNL * modes_energy_stride(m->g) * sizeof(double)));
+  }
   hipEvent_t a, b;
   HIPCHK(hipEventCreate(&a));
   HIPCHK(hipEventCreate(&b));
@@ -3276,6 +3435,10 @@ extern "C" int msom_bench_kernel(msom_t *m, const char *kernel, int reps, double
       rhs_terms(m, MSOM_Q, MSOM_DQ, 1, m->p.iRe, m->p.iRe4, m->p.Eks, m->p.Ekb, MSOM_QPRED, MSOM_Q, 1e-9, &adv);
     } else if (!strcmp(kernel, "advance")) {
       launch_advance(m->st, m->f[MSOM_QPRED], m->f[MSOM_Q], m->f[MSOM_DQ], nullptr, m->g, m->nl, 1e-9, 0.);
+    } else if (!strcmp(kernel, "modes_project")) {   // in place on the staging buffer, in the form the handle holds
+      launch_modes_project(m->st, m->staging, m->staging, m->modes_md, modes_mc(m), m->g, m->nl, modes_layers(m), 1);
+    } else if (!strcmp(kernel, "modes_energy")) {
+      modes_energy_launch(m);
     }
   };
   for (int k = 0; k < 3; k++) one();
