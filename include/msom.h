@@ -97,7 +97,8 @@ int msom_destroy(msom_t *m);
  * "TOLERANCE" "NITERMAX" "NITERMIN" (mspg/elliptic.h:111-112, qg.h:159), "DT", "quiet",
  * "stochastic" (-D_STOCHASTIC), "seed", "noise_mode" (0: the reference's serial rand() stream generated on
  * the host, 1: counter-based Philox on the device), "flag_topo", "uniform_S" (0 forces the general
- * S-field kernels), "profile" (HIP-event timing of the finest-level launches: 1 every kernel, 2 only the chained smoother passes;
+ * S-field kernels), "mode_pv_invert" [0] (MODE_PV_INVERT, msqg/qg.h:116: the inversion goes through the vertical modes, one tile only;
+ * see msom_modes_mgstats), "profile" (HIP-event timing of the finest-level launches: 1 every kernel, 2 only the chained smoother passes;
  * an event pair costs ~10 us of stream time).
  * Implementation switches, all result-preserving in the strict build (defaults in brackets):
  * "fused" [1] one-pass tendency kernel, "adv_fused" [1] advance folded into it, "stoch_fused" [1] (product build only) the
@@ -270,6 +271,34 @@ int msom_modes_project(msom_t *m, int to_modes, const double *in, double *out); 
 int msom_modes_energy(msom_t *m, double *ke, double *pe);          /* [nl] each, host pointers; either may be NULL */
 int msom_modes_set_rd(msom_t *m, int mode);                        /* MSOM_RD = MSOM_MD_RD of `mode` */
 
+/* ---- modal PV inversion: the MODE_PV_INVERT 1 body of invertq, msqg/qg.h:116-157, as a run-time option.
+ * msom_set_option("mode_pv_invert", 1) [0]: the one place that inverts (msom_invertq, pyq2p, msom_update, msom_step, msom_run,
+ *   pystep_bfn, msom_bfn_steps, pystep_de) computes the modes if they are not ready (as msom_modes_compute does, its errors pass
+ *   through), projects q_m = sum_k l2m[m][k] q_k, solves the nl independent problems  lap(p_m) + iBu_m p_m = q_m  by the multigrid cycle
+ *   of mspg/elliptic.h (minlevel = 1, red-black Jacobi half-sweeps starting with the colour (i + j) even, mean-of-4 restriction, bilinear
+ *   prolongation), then psi_k = sum_m m2l[k][m] p_m into MSOM_PSI with its boundary fill.  The warm start is the persistent mode-space
+ *   field p_m (the reference's pom), zero after msom_set_const; MSOM_PSI is not read.  msom_comp_q / pyp2q stay layered (:397-403).
+ *   Every mode has its own mgstats: i, nrelax (4 at the start, +1 where resb / resa < 1.2, -1 where > 10, as mg_solve), resb, resa,
+ *   sum.  All modes of a level share a launch; the host reads the nl maxima once per cycle.  Freeze rule: a mode that has met TOLERANCE
+ *   after NITERMIN cycles (or has done NITERMAX) is frozen -- it takes no more sweeps, its correction is zero on every level and its p_m
+ *   keeps its bits -- while the others go on, each with its own nrelax (a launch runs max nrelax sweeps, a mode stops at its count).
+ *   msom_last_mgstats / the mgstats of msom_invertq are the LAST mode's (the reference overwrites mgpsi per poisson() call);
+ *   msom_modes_mgstats gives any mode's: MSOM_ERR_STATE before the first modal solve since msom_set_const, MSOM_ERR_ARG for a mode
+ *   outside 0 .. nl-1.  With the option on, msom_set_const also computes the modes and sets MSOM_RD from mode 1 (msom_modes_set_rd(m, 1),
+ *   msqg/qg.h:1055-1057; skipped for nl = 1).  The fused paths of the layered solver (rhs_resid, residual2, the speculative tendency
+ *   launch, the marched and fused visits) are off in modal mode; max|u| of the dt limiter comes from its own pass over psi.
+ *   Scope: one tile, walls or sbc = -1.  A handle of msom_create_tiled with more than one rank answers the option with MSOM_ERR_CONFIG.
+ *   Doubly periodic: the barotropic mode (iBu_0 = 0) is singular as the layered problem's barotropic part is: zero-mean q needed.
+ * Expression order (the contract of the strict build; E, W, N, S the four neighbours, D = Delta):
+ *   relax:    n = -(D*D) * b;  n = n + (a[E] + a[W]);  n = n + (a[N] + a[S]);  d = (-(iBu * (D*D)) + 2) + 2;  a = n / d
+ *             product build: n = fma(-(D*D), b, a[E] + a[W]);  n = n + (a[N] + a[S]);  a = n * (1 / fma(-iBu, D*D, 4))
+ *   residual: r = b - iBu * a;  r = r + ((a - a[W]) / D - (a[E] - a) / D) / D;  r = r + ((a - a[S]) / D - (a[N] - a) / D) / D
+ *             product build: r = fma(-iBu, a, b) and multiplications by 1 / D for the divisions
+ *   A stratification that varies from column to column reads iBu per cell; on the coarse levels it is the mean of the 4 children, level
+ *   by level (poisson()'s restriction({alpha, lambda})), built by the first modal solve after a msom_modes_compute (a handle
+ *   that only decomposes does not hold it; "modes_bytes" does not count it: 4/3 * 8 nl ny nx more) and dropped with the modes. */
+int msom_modes_mgstats(msom_t *m, int mode, msom_mgstats *st);
+
 /* ---- time loop of Basilisk predictor-corrector run() as driven by msqg/qg.c
  * msom_step: one RK2 step on the internal state (update, dtnext, advance dt/2, update,
  * advance dt).  msom_set_tnext gives the time of the next t-scheduled event (output). */
@@ -342,6 +371,11 @@ int msom_dbg_nlevels(msom_t *m);
 int msom_dbg_level_dims(msom_t *m, int lev, int *nx, int *ny);
 int msom_dbg_relax(msom_t *m, int lev, double *da, const double *res, int nsweeps);
 int msom_dbg_residual(msom_t *m, const double *a, const double *b, double *res, double *maxres);
+/* the modal solver's kernels (need the modes: computed if not ready).  da, res: [mode][y][x] of level `lev`; nhalf half-sweeps starting
+ * with colour 0 (half-sweep h is sweep h / 2); count_per_mode[m] = sweeps mode m takes (NULL: every mode takes all), a mode whose
+ * count is used up keeps its da.  a, b, res: [mode][ny][nx]; maxres_per_mode: nl maxima of |res_m| */
+int msom_dbg_helm_relax(msom_t *m, int lev, double *da, const double *res, int nhalf, const int *count_per_mode);
+int msom_dbg_helm_residual(msom_t *m, const double *a, const double *b, double *res, double *maxres_per_mode);
 int msom_dbg_restrict(msom_t *m, int lev_fine, const double *fine, double *coarse);
 int msom_dbg_prolong(msom_t *m, int lev_coarse, const double *coarse, double *fine);
 int msom_dbg_op(msom_t *m, const char *op, int f_in, int f_out, double add, double fac);

@@ -84,6 +84,9 @@ def load_library(strict=False):
         "msom_modes_project": (ci, [vp, ci, vp, vp]),
         "msom_modes_energy": (ci, [vp, _dp, _dp]),
         "msom_modes_set_rd": (ci, [vp, ci]),
+        "msom_modes_mgstats": (ci, [vp, ci, C.POINTER(MGStats)]),
+        "msom_dbg_helm_relax": (ci, [vp, ci, vp, vp, ci, C.POINTER(ci)]),
+        "msom_dbg_helm_residual": (ci, [vp, vp, vp, vp, _dp]),
         "msom_step": (ci, [vp, _dp]),
         "msom_set_tnext": (ci, [vp, cd]),
         "msom_time": (cd, [vp]),
@@ -374,6 +377,30 @@ class QG:
         """RD = deformation radius of `mode`, so that the next wavelet_filter builds sig_filt = min(afilt * Rd, Lfmax) from the
         stratification (mode 1: the reference's MODE_PV_INVERT branch, msqg/qg.h:1055-1057)"""
         self._chk(self.L.msom_modes_set_rd(self.h, int(mode)))
+
+    # -- modal PV inversion: option("mode_pv_invert", 1) sends every inversion through the modes (MODE_PV_INVERT, msqg/qg.h:116-157)
+    def modes_mgstats(self, mode):
+        """mgstats of `mode` in the last modal solve (mgstats() gives the last mode's, as the reference's mgpsi)"""
+        st = MGStats()
+        self._chk(self.L.msom_modes_mgstats(self.h, int(mode), C.byref(st)))
+        return st
+
+    def helm_relax(self, lev, da, res, nhalf=2, count_per_mode=None):
+        """nhalf red-black half-sweeps (colour 0 first) of a = (sum of the 4 neighbours - D^2 b) / (4 - D^2 iBu_m) on level `lev`, every mode
+        in one launch; da, res: [mode][y][x] of that level.  count_per_mode[m]: sweeps mode m takes (None: all; 0: the mode keeps its da)"""
+        da = np.array(da, dtype=np.float64, order="C")
+        res = _f64(res)
+        cnt = None if count_per_mode is None else (C.c_int * self.nl)(*[int(c) for c in count_per_mode])
+        self._chk(self.L.msom_dbg_helm_relax(self.h, lev, _ptr(da), _ptr(res), int(nhalf), cnt))
+        return da
+
+    def helm_residual(self, a, b):
+        """(res, maxres): res_m = b_m - lap(a_m) - iBu_m a_m on the finest level and max |res_m| per mode; a, b: [mode][ny][nx]"""
+        a, b = _f64(a, (self.nl, self.ny, self.nx)), _f64(b, (self.nl, self.ny, self.nx))
+        res = np.empty_like(a)
+        mx = np.empty(self.nl)
+        self._chk(self.L.msom_dbg_helm_residual(self.h, _ptr(a), _ptr(b), _ptr(res), mx.ctypes.data_as(_dp)))
+        return res, mx
 
     # -- time loop
     def step(self):

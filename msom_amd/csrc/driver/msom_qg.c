@@ -3,6 +3,10 @@
  * printing the per-step line and writing po/qo .bas files.  Everything numerical happens in
  * libmsomhip through the C ABI (include/msom.h).
  *
+ *   msom_qg [params.in [nsteps [key=value ...]]]
+ * nsteps < 0: run to tend.  Every key=value goes to msom_set_option before the inputs are read -- the run-time counterparts of the
+ * reference's compile-time flags, e.g. mode_pv_invert=1 for a run built with MODE_PV_INVERT 1, stochastic=1 for -D_STOCHASTIC.
+ *
  * Multi-GPU (the reference's `mpirun -np 16 ./qg.e`): start one process per GPU with
  *   MSOM_NRANKS (or WORLD_SIZE), MSOM_RANK (or RANK), MSOM_LOCAL_RANK (or LOCAL_RANK, default = rank),
  *   optional MSOM_PX / MSOM_PY (default 1x1, 2x1, 2x2, 2x4) and MSOM_ID_FILE (default ./.msom_comm_id.<MSOM_JOB or MASTER_PORT>)
@@ -79,7 +83,16 @@ int main(int argc, char *argv[]) {
   }
   if (rank == 0)
     fprintf(stdout, "Config: N = %d, nl = %d, L0 = %g\n", (int)msom_get_param(m, "N"), (int)msom_get_param(m, "nl"), msom_get_param(m, "L0"));
-  int r = msom_read_inputs(m, ".");
+  int r = 0;
+  for (int k = 3; k < argc && !r; k++) {
+    char key[64];
+    const char *eq = strchr(argv[k], '=');
+    if (!eq || eq == argv[k] || (size_t)(eq - argv[k]) >= sizeof key) { fprintf(stdout, "argument %s is not key=value\n", argv[k]); msom_destroy(m); return 1; }
+    memcpy(key, argv[k], eq - argv[k]);
+    key[eq - argv[k]] = 0;
+    r = msom_set_option(m, key, atof(eq + 1));
+  }
+  if (!r) r = msom_read_inputs(m, ".");
   if (!r) r = msom_remove_mean(m, MSOM_PSI); /* msqg/qg.c:65-70 */
   if (!r) r = msom_set_const(m);
   if (!r) r = msom_run(m, ".", nsteps);

@@ -239,6 +239,34 @@ int modes_energy_stride(const NatGeom &g);
 int launch_modes_energy(hipStream_t st, const double *psi, const double *md, const ModeCoef *mc, const NatGeom &g, int nl, const ModesLayers &l,
                         double *partial, double *out, double D);
 
+// ---- kernels_helm.hip: the nl independent Helmholtz problems lap(p_m) + iBu_m p_m = q_m of the modal PV inversion (msqg/qg.h:136-141),
+// every mode of a level in one launch.  Fields are laid out as the layered solver's (mode = layer).  Compact form (hc != nullptr): iBu_m
+// by value; general form: iBu per cell from a split-layout array of the level (nl layers).
+struct HelmCoef {
+  double ibu[MSOM_MAXNL];   // iBu_m
+  double rd[MSOM_MAXNL];    // 1 / helm_diag(iBu_m, Delta^2) of the level (product build)
+};
+struct HelmCount {
+  int n[MSOM_MAXNL];        // sweeps mode m takes (0: frozen)
+};
+// the diagonal 4 - Delta^2 iBu in the documented order (include/msom.h); host and device round alike
+MSOM_HD double helm_diag(double ibu, double sqD) {
+#ifdef MSOM_STRICT
+  return (-(ibu * sqD) + 2.) + 2.;
+#else
+  return fma(-ibu, sqD, 4.);
+#endif
+}
+HelmCoef helm_coef(const double *ibu, int nl, double sqD);
+// one half-sweep of colour `color`, sweep number `sweep`: mode m takes part while cnt.n[m] > sweep.  -1: no kernel for nl
+int launch_helm_relax(hipStream_t st, double *da, const double *res, const double *ibu_sp, const HelmCoef *hc, const SplitGeom &sg, int nl,
+                      double sqD, int color, int sweep, const HelmCount &cnt, int walls);
+// res_m = b_m - lap(a_m) - iBu_m a_m (a, b natural, res split); maxres[m] = max(maxres[m], max |res_m|); want_sum: sum_partial[m * stride + block]
+// = sums of b_m per workgroup, helm_residual_blocks(g) of them per mode (second stage: launch_sum_final)
+int helm_residual_blocks(const NatGeom &g);
+int launch_helm_residual(hipStream_t st, const double *a, const double *b, const double *ibu_sp, const HelmCoef *hc, const NatGeom &g, double *res,
+                         const SplitGeom &sg, int nl, double D, double *maxres, double *sum_partial, int stride, int want_sum);
+
 // ---- kernels_wavelet.hip
 void launch_wv_restrict(hipStream_t st, const double *f, const NatGeom &fg, double *c, const NatGeom &cg, int nl);
 void launch_wv_recon(hipStream_t st, const double *s, const double *sc, const double *rc, const double *sig, double *out, const NatGeom &fg,

@@ -26,6 +26,7 @@
 
 #include "comm.h"
 #include "kernels.h"
+#include "helm_inl.h"
 
 #define HIPCHK(x)                                                                          \
   do {                                                                                     \
@@ -195,6 +196,15 @@ struct msom {
   double *modes_dev = nullptr;            // device scratch: the numbers of the compact solve, then the 2 nl sums of msom_modes_energy
   int *modes_flag = nullptr;              // device word the eigen kernel ORs its failures into
   double *modes_partial = nullptr;        // per-block partial sums of msom_modes_energy
+  // modal PV inversion (option mode_pv_invert, msqg/qg.h:116-157); nothing is allocated until the first modal solve
+  int mode_pv_invert = 0;                 // option: invertq goes through the modes (one tile only)
+  std::vector<double *> helm_ibu;         // general form: iBu_m per cell on every level, split layout (built by the first modal solve after msom_modes_compute, dropped with the modes)
+  double *helm_pm = nullptr, *helm_qm = nullptr;   // mode-space natural fields: p_m (warm start, the reference's pom; valid ghosts) and q_m
+  double *helm_scal = nullptr;            // device scalar block of the modal solve: HS_* below, MSOM_MAXNL each
+  double *helm_partial = nullptr;         // per-workgroup sums of q_m (mgstats.sum per mode)
+  HelmSolve helm = {};                    // per-mode mg_solve state (helm_inl.h)
+  int helm_solved = 0;                    // a modal solve since the last msom_set_const (msom_modes_mgstats)
+  ProfSlot prof_helm_relax, prof_helm_resid, prof_helm_coarse;   // finest-level sweeps, residual passes, levels of <= 64 cells a side
   int s_zero = 0;  // pystep_de(onlyKE = 1) zeroed the stretching field S (msqg/qg_energy.h:319-325); undone by msom_set_const
   std::vector<NatGeom> wv_g;
   std::vector<double *> wv_s, wv_r, wv_sig;
@@ -214,6 +224,11 @@ struct msom {
 static void free_agglomeration(msom *m);
 static void stats_drop(msom *m);
 static void modes_drop(msom *m);
+static void helm_drop_pyramid(msom *m) {   // the iBu pyramid of the modal inversion (general form)
+  for (double *p : m->helm_ibu)
+    if (p) hipFree(p);
+  m->helm_ibu.clear();
+}
 
 extern "C" const char *msom_version(void) {
 #ifdef MSOM_STRICT
@@ -699,12 +714,14 @@ extern "C" int msom_destroy(msom_t *m) {
   if (m->modes_dev) hipFree(m->modes_dev);
   if (m->modes_flag) hipFree(m->modes_flag);
   if (m->modes_partial) hipFree(m->modes_partial);
+  for (double *p : {m->helm_pm, m->helm_qm, m->helm_scal, m->helm_partial})
+    if (p) hipFree(p);
   if (m->d_cargs) hipFree(m->d_cargs);
   if (m->partial_umax) hipFree(m->partial_umax);
   if (m->d_scal) hipFree(m->d_scal);
   if (m->h_scal) hipHostFree(m->h_scal);
   if (m->d_wind) hipFree(m->d_wind);
-  for (auto *ps : {&m->prof_sweep, &m->prof_resid, &m->prof_block, &m->prof_march[2], &m->prof_march[3], &m->prof_march[4], &m->prof_rhs, &m->prof_redprol, &m->prof_rescorr, &m->prof_respre, &m->prof_march_pl, &m->prof_march_corr, &m->prof_march_visit, &m->prof_resmax})
+  for (auto *ps : {&m->prof_sweep, &m->prof_resid, &m->prof_block, &m->prof_march[2], &m->prof_march[3], &m->prof_march[4], &m->prof_rhs, &m->prof_redprol, &m->prof_rescorr, &m->prof_respre, &m->prof_march_pl, &m->prof_march_corr, &m->prof_march_visit, &m->prof_resmax, &m->prof_helm_relax, &m->prof_helm_resid, &m->prof_helm_coarse})
     for (auto e : ps->ev) hipEventDestroy(e);
   if (m->comm) comm_destroy(m->comm);
   if (m->ev_c2x) hipEventDestroy(m->ev_c2x);
@@ -796,6 +813,15 @@ extern "C" int msom_set_option(msom_t *m, const char *key, double v) {
     if ((int)v != -1 && (int)v != 0) { msom_set_error("option modes_compact = %g (-1 or 0)", v); return MSOM_ERR_ARG; }
     m->modes_compact_opt = (int)v;
   }
+  else if (!strcmp(key, "mode_pv_invert")) {
+    if ((int)v != 0 && (int)v != 1) { msom_set_error("option mode_pv_invert = %g (0 or 1)", v); return MSOM_ERR_ARG; }
+    if ((int)v && m->nranks > 1) {
+      msom_set_error("option mode_pv_invert: the modal inversion runs on a single tile, this handle is one of %d", m->nranks);
+      return MSOM_ERR_CONFIG;
+    }
+    m->mode_pv_invert = (int)v;
+    m->res_ready = -1;
+  }
   else if (!strcmp(key, "stochastic")) {
     m->stochastic = (int)v;
     if (m->stochastic && !m->f[MSOM_NOISE]) {
@@ -850,6 +876,7 @@ extern "C" double msom_get_param(msom_t *m, const char *key) {
     for (int k = 0; k < MSOM_ST_NACC; k++) n += m->stats.s[k] ? 1 : 0;
     return (double)n * m->nl * m->nx * m->ny * sizeof(double);
   }
+  if (!strcmp(key, "mode_pv_invert")) return m->mode_pv_invert;
   if (!strcmp(key, "modes_ready")) return m->const_set && m->modes_ready;
   if (!strcmp(key, "modes_compact")) return m->const_set && m->modes_ready ? m->modes_compact : (m->modes_compact_opt != 0 && m->fr_uniform);
   if (!strcmp(key, "modes_bytes"))   // 8 ny nx per stored array: nl*nl + nl of them in the general form, none in the compact one
@@ -1187,6 +1214,12 @@ extern "C" int msom_set_const(msom_t *m) {
   m->bfn_begun = 0;
   stats_drop(m);
   modes_drop(m);
+  m->helm_solved = 0;
+  if (m->helm_pm) HIPCHK(hipMemsetAsync(m->helm_pm, 0, m->g.ls * nl * sizeof(double), m->st));   // the reference's freshly created pom
+  if (m->mode_pv_invert) {   // eigmod and sig_filt from mode 1, msqg/qg.h:1053-1057
+    if ((rr = msom_modes_compute(m))) return rr;
+    if (nl > 1 && (rr = msom_modes_set_rd(m, 1))) return rr;
+  }
   return sync_stream(m);
 }
 
@@ -1217,8 +1250,15 @@ static Lev glob_lev(const msom *m, int k) {
 // which smoother a level visit takes -- the one statement of that choice: relax_sweeps, fuse_prolong, mg_cycle, march_levels and
 // msom_get_param("relax_path_<k>") all read it.  Precedence march > block8 > block2 > per-colour launches
 enum { RP_COLOUR = 0, RP_BLOCK2 = 1, RP_BLOCK8 = 2, RP_MARCH = 3, RP_COARSE = 4, RP_GATHERED = 8 };
+// Modal mode (option mode_pv_invert): the solve is helm_solve's, per-colour launches of k_helm_relax on every level, and what the
+// layered solver fuses around its own passes does not apply.  One predicate says so.  rhs_terms asks it before it lets the tendency
+// pass produce the first residual (rhs_resid) and spec_ok before the speculative tendency launch; sweep_path answers RP_COLOUR (the
+// relax_path_<k> report, msom_dbg_relax); residual2 with its max|u| by-product and the marched / fused visits are never reached,
+// because helm_solve does not enter mg_solve.
+static bool layered_fusions(const msom *m) { return !m->mode_pv_invert; }
 static int sweep_path(const msom *m, const Lev &L) {
   const SplitGeom &g = *L.sg;
+  if (!layered_fusions(m)) return RP_COLOUR;
   // chained half-sweeps in registers (k_relax_march).  One GPU (no halo exchange between half-sweeps) or tiles with deep halos,
   // walls or the doubly periodic single tile (deep halo = the field's own other side, launch_split_wrap), uniform S or one layer
   // (no vertical coupling: the column system is x = rhs / 4), and a level big enough to be HBM-bound: a marching wavefront pays one
@@ -1747,8 +1787,175 @@ static int mg_solve(msom *m, const double *b, msom_mgstats *s) {
   return MSOM_OK;
 }
 
+// ------------------------------------------------------------------ modal PV inversion (MODE_PV_INVERT, msqg/qg.h:116-157)
+
+// slots of the modal solve's device scalar block (helm_scal): max |res_m| before the first cycle, after the last one, sum of q_m
+enum { HS_RES0 = 0, HS_RES1 = MSOM_MAXNL, HS_BSUM = 2 * MSOM_MAXNL, HS_COUNT = 3 * MSOM_MAXNL };
+static ModesLayers modes_layers(const msom *m);
+static const ModeCoef *modes_mc(const msom *m);
+static int helm_partial_stride(const msom *m) { return helm_residual_blocks(m->g) + 64; }   // room for the chunk sums of launch_sum_final
+
+// General form: iBu_m per cell on every multigrid level, the mean of the 4 children level by level (poisson()'s
+// restriction({alpha, lambda})), in the split layout of the level.  Built at the first modal solve (or helm hook) after a
+// msom_modes_compute -- a handle that only decomposes never pays its 4/3 nl layers -- and dropped with the modes.
+static int helm_build_pyramid(msom *m) {
+  const int nl = m->nl;
+  m->helm_ibu.assign(m->nlev, nullptr);
+  for (int k = 0; k < m->nlev; k++) {
+    HIPCHK(hipMalloc(&m->helm_ibu[k], m->sg[k].ls * nl * sizeof(double)));
+    HIPCHK(hipMemsetAsync(m->helm_ibu[k], 0, m->sg[k].ls * nl * sizeof(double), m->st));
+  }
+  if (m->nlev > 0) launch_nat_to_split(m->st, m->modes_md + (size_t)nl * nl * m->g.ls, m->g, m->helm_ibu[0], m->sg[0], nl);
+  for (int k = 1; k < m->nlev; k++) launch_restrict(m->st, m->helm_ibu[k - 1], m->sg[k - 1], m->helm_ibu[k], m->sg[k], nl);
+  return MSOM_OK;
+}
+// the modes (computed if they are not ready: the effect and the errors of msom_modes_compute) and the buffers of the modal solve
+static int helm_ensure(msom *m) {
+  if (m->nranks > 1) { msom_set_error("the modal inversion runs on a single tile"); return MSOM_ERR_CONFIG; }
+  if (!m->modes_ready) {
+    int r = msom_modes_compute(m);
+    if (r) return r;
+  }
+  if (!m->modes_compact && m->helm_ibu.empty()) {
+    int r = helm_build_pyramid(m);
+    if (r) { helm_drop_pyramid(m); return r; }
+  }
+  const size_t bytes = m->g.ls * m->nl * sizeof(double);
+  if (!m->helm_pm) {
+    HIPCHK(hipMalloc(&m->helm_pm, bytes));
+    HIPCHK(hipMemsetAsync(m->helm_pm, 0, bytes, m->st));
+  }
+  if (!m->helm_qm) {
+    HIPCHK(hipMalloc(&m->helm_qm, bytes));
+    HIPCHK(hipMemsetAsync(m->helm_qm, 0, bytes, m->st));
+  }
+  if (!m->helm_scal) HIPCHK(hipMalloc(&m->helm_scal, HS_COUNT * sizeof(double)));
+  if (!m->helm_partial) HIPCHK(hipMalloc(&m->helm_partial, (size_t)MSOM_MAXNL * helm_partial_stride(m) * sizeof(double)));
+  return MSOM_OK;
+}
+// coefficient source of level k: iBu_m by value (compact form; *hc filled) or the level's array of the pyramid
+static const HelmCoef *helm_level_coef(const msom *m, int k, HelmCoef *hc, const double **ibu_sp) {
+  if (m->modes_compact) {
+    *hc = helm_coef(m->modes_mc.ibu, m->nl, m->rc[k].sqD);
+    *ibu_sp = nullptr;
+    return hc;
+  }
+  *ibu_sp = m->helm_ibu[k];
+  return nullptr;
+}
+// nhalf half-sweeps of level k starting with colour 0; half-sweep h is sweep h / 2 of the per-mode counts
+static int helm_relax_level(msom *m, int k, int nhalf, const HelmCount &cnt, ProfSlot *ps) {
+  HelmCoef hc;
+  const double *ibu_sp;
+  const HelmCoef *phc = helm_level_coef(m, k, &hc, &ibu_sp);
+  for (int h = 0; h < nhalf; h++) {
+    if (ps && !(h & 1)) prof_begin(m, *ps);
+    if (launch_helm_relax(m->st, m->da[k], m->res[k], ibu_sp, phc, m->sg[k], m->nl, m->rc[k].sqD, h & 1, h >> 1, cnt, m->walls)) {
+      msom_set_error("modal inversion: no kernel for nl = %d", m->nl);
+      return MSOM_ERR_CONFIG;
+    }
+    if (ps && ((h & 1) || h == nhalf - 1)) prof_end(m, *ps);
+  }
+  return MSOM_OK;
+}
+static int helm_residual(msom *m, const double *a, const double *b, int slot, int want_sum) {
+  HelmCoef hc;
+  const double *ibu_sp;
+  const HelmCoef *phc = helm_level_coef(m, 0, &hc, &ibu_sp);
+  if (m->profile) prof_begin(m, m->prof_helm_resid);
+  const int r = launch_helm_residual(m->st, a, b, ibu_sp, phc, m->g, m->res[0], m->sg[0], m->nl, m->rc[0].D, m->helm_scal + slot, m->helm_partial,
+                                     helm_partial_stride(m), want_sum);
+  if (m->profile) prof_end(m, m->prof_helm_resid);
+  if (r) { msom_set_error("modal inversion: no kernel for nl = %d", m->nl); return MSOM_ERR_CONFIG; }
+  return MSOM_OK;
+}
+// one cycle of mspg/elliptic.h:53-89 (minlevel = 1) for every mode at once, level by level: the residual restricted to all levels,
+// then from the coarsest level up prolongation (zero on the coarsest) and max-count sweeps, each mode stopping at its own count.
+// A frozen mode (count 0) is swept nowhere: its correction stays the zero the coarsest level starts from.
+static int helm_cycle(msom *m, const HelmCount &cnt, int nrelax) {
+  const int nl = m->nl;
+  for (int k = 1; k < m->nlev; k++) launch_restrict(m->st, m->res[k - 1], m->sg[k - 1], m->res[k], m->sg[k], nl);
+  int kc = m->nlev;   // finest of the launch-bound levels (<= 64 cells a side); profile slot "helm_coarse" times them as one span
+  for (int k = m->nlev - 1; k >= 1 && m->sg[k].nx <= 64 && m->sg[k].ny <= 64; k--) kc = k;
+  for (int k = m->nlev - 1; k >= 0; k--) {
+    if (m->profile && k == m->nlev - 1 && kc < m->nlev) prof_begin(m, m->prof_helm_coarse);
+    if (k == m->nlev - 1) HIPCHK(hipMemsetAsync(m->da[k], 0, m->sg[k].ls * nl * sizeof(double), m->st));
+    else launch_prolong(m->st, m->da[k + 1], m->sg[k + 1], m->da[k], m->sg[k], nl, m->walls);
+    int r = helm_relax_level(m, k, 2 * nrelax, cnt, m->profile && k == 0 ? &m->prof_helm_relax : nullptr);
+    if (r) return r;
+    if (m->profile && k == kc) prof_end(m, m->prof_helm_coarse);
+  }
+  return MSOM_OK;
+}
+static int helm_read(msom *m, double *h) {
+  HIPCHK(hipMemcpyAsync(h, m->helm_scal, HS_COUNT * sizeof(double), hipMemcpyDeviceToHost, m->st));
+  HIPCHK(hipStreamSynchronize(m->st));
+  return m->sticky;
+}
+// natural [nl] field <-> the other space, through the staging buffer (k_modes_project works on contiguous arrays)
+static int helm_project(msom *m, const double *in, double *out, int to_modes) {
+  launch_unpack(m->st, in, m->staging, m->g, m->nl);
+  if (launch_modes_project(m->st, m->staging, m->staging, m->modes_md, modes_mc(m), m->g, m->nl, modes_layers(m), to_modes)) return MSOM_ERR_CONFIG;
+  launch_pack(m->st, m->staging, out, m->g, m->nl);
+  return MSOM_OK;
+}
+// ghosts of a mode-space field: homogeneous Dirichlet at the faces, or wrapped
+static void helm_fill(msom *m, double *f) {
+  if (m->walls & WALL_PER) launch_fill_periodic(m->st, f, m->g, m->nl, 1);
+  else launch_fill_ghost(m->st, f, m->g, m->nl, BC_DIRICHLET0, m->walls);
+}
+
+// nl times mg_solve(pm, qm, lambda = iBu_m), run side by side: a cycle of the batch is a cycle of every mode that still wants one
+// (helm_inl.h has the bookkeeping).  The host reads the nl maxima once per cycle.
+static int helm_solve(msom *m, const double *q) {
+  const Params &p = m->p;
+  const int nl = m->nl;
+  int r = helm_ensure(m);
+  if (r) return r;
+  m->res_ready = -1;
+  m->umax_ready = 0;
+  m->spec_valid = 0;
+  if ((r = helm_project(m, q, m->helm_qm, 1))) return r;
+  HIPCHK(hipMemsetAsync(m->helm_scal, 0, HS_COUNT * sizeof(double), m->st));
+  HelmSolve &h = m->helm;
+  helm_begin(h, nl, p.nitermin, p.nitermax, p.tolerance);
+  double hs[HS_COUNT];
+  if ((r = helm_residual(m, m->helm_pm, m->helm_qm, HS_RES0, 1))) return r;
+  for (int k = 0; k < nl; k++)
+    launch_sum_final(m->st, m->helm_partial + (size_t)k * helm_partial_stride(m), m->helm_scal + HS_BSUM + k, helm_residual_blocks(m->g));
+  if (p.nitermin < 1) {   // the first cycle depends on the warm start's residual
+    if ((r = helm_read(m, hs))) return r;
+    helm_first(h, hs + HS_RES0, hs + HS_BSUM);
+  }
+  HelmCount cnt = {};
+  int nrelax;
+  while ((nrelax = helm_counts(h, cnt.n)) > 0) {
+    if ((r = helm_cycle(m, cnt, nrelax))) return r;
+    launch_correct(m->st, m->helm_pm, m->g, m->da[0], m->sg[0], nl, m->walls);   // a frozen mode adds its zero correction
+    HIPCHK(hipMemsetAsync(m->helm_scal + HS_RES1, 0, MSOM_MAXNL * sizeof(double), m->st));
+    if ((r = helm_residual(m, m->helm_pm, m->helm_qm, HS_RES1, 0))) return r;
+    if ((r = helm_read(m, hs))) return r;
+    helm_first(h, hs + HS_RES0, hs + HS_BSUM);
+    helm_cycle_done(h, cnt.n, hs + HS_RES1);
+  }
+  if (!h.have_first) {   // NITERMAX == 0
+    if ((r = helm_read(m, hs))) return r;
+    helm_first(h, hs + HS_RES0, hs + HS_BSUM);
+  }
+  for (int k = 0; k < nl; k++)
+    if (h.s[k].resa > p.tolerance && !m->quiet)
+      fprintf(stderr, "WARNING: convergence not reached after %d iterations\n  mode: %d res: %g sum: %g nrelax: %d\n", h.s[k].i, k, h.s[k].resa,
+              h.s[k].sum, h.s[k].nrelax);
+  m->mg = h.s[nl - 1];   // the reference's mgpsi is overwritten by every poisson() call: the last mode's stay
+  m->helm_solved = 1;
+  if ((r = helm_project(m, m->helm_pm, m->f[MSOM_PSI], 0))) return r;
+  fill_bc(m, MSOM_PSI);
+  return m->sticky;
+}
+
 // invertq, msqg/qg.h:114-163 (the trailing boundary(pol) is already done by the correction)
 static int invertq(msom *m, const double *q) {
+  if (m->mode_pv_invert) return helm_solve(m, q);
   return mg_solve(m, q, &m->mg);
 }
 
@@ -1808,7 +2015,7 @@ static int rhs_terms(msom *m, int qfield, int dqfield, int with_qforcing, double
     // the advance rides along: the pass can also emit the first residual of the inversion of q[adv_out]
     // the residual by-product exists only in the LDS-tile kernel: asking for it selects that kernel
     const int variant = (m->rhs_resid && m->rhs_variant == 6) ? 1 : m->rhs_variant;
-    const bool use_rr = adv_out >= 0 && m->rhs_resid && variant == 1 && m->mg_fused && m->nlev > 1 && m->bc != BC_PERIODIC;
+    const bool use_rr = adv_out >= 0 && layered_fusions(m) && m->rhs_resid && variant == 1 && m->mg_fused && m->nlev > 1 && m->bc != BC_PERIODIC;
     RhsResid rr;
     if (use_rr) {
       rr.res = m->res[0]; rr.res_c = m->res[1]; rr.res_max = m->d_scal + SC_RESF; rr.bsum_partial = m->partial_rr;
@@ -2082,6 +2289,14 @@ extern "C" int msom_last_mgstats(msom_t *m, msom_mgstats *st) {
   return MSOM_OK;
 }
 
+extern "C" int msom_modes_mgstats(msom_t *m, int mode, msom_mgstats *st) {
+  if (!m || !st) return MSOM_ERR_ARG;
+  if (!m->const_set || !m->helm_solved) { msom_set_error("msom_modes_mgstats: no modal solve since msom_set_const"); return MSOM_ERR_STATE; }
+  if (mode < 0 || mode >= m->nl) { msom_set_error("msom_modes_mgstats: mode %d outside 0 .. %d", mode, m->nl - 1); return MSOM_ERR_ARG; }
+  *st = m->helm.s[mode];
+  return MSOM_OK;
+}
+
 // ------------------------------------------------------------------ pystep_bfn & co
 
 static int check_shape(msom *m, int a, int b, int c) {
@@ -2307,6 +2522,7 @@ extern "C" int msom_time_filter(msom_t *m, double dt) {
 static void modes_drop(msom *m) {
   if (m->modes_md) hipFree(m->modes_md);
   m->modes_md = nullptr;
+  helm_drop_pyramid(m);
   m->modes_ready = m->modes_compact = 0;
 }
 static ModesLayers modes_layers(const msom *m) {
@@ -2475,7 +2691,7 @@ static int tracer_advance(msom *m, int out, int in, double dt) {
 // can a stage's tendency pass be queued speculatively?  One tile, the fused one-layer-per-wavefront kernel with the advance
 // folded in, max|u| out of the solver's last pass, nothing with side effects in the pass (noise draws, tracers)
 static bool spec_ok(msom *m) {
-  return m->async_solve && m->nranks == 1 && m->fused && m->adv_fused && m->rhs_variant == 6 && !m->rhs_resid && m->mg_fused && m->nlev > 1 &&
+  return layered_fusions(m) && m->async_solve && m->nranks == 1 && m->fused && m->adv_fused && m->rhs_variant == 6 && !m->rhs_resid && m->mg_fused && m->nlev > 1 &&
          m->nl <= MSOM_FASTNL && !m->have_pg && !m->have_zpg && !m->flag_topo && !m->stochastic && m->p.nptr == 0 && m->p.nitermin >= 1 && !m->dbg_nosync;
 }
 
@@ -3327,6 +3543,39 @@ extern "C" int msom_dbg_residual(msom_t *m, const double *a, const double *b, do
   if (maxres) *maxres = m->h_scal[SC_RES0];
   return MSOM_OK;
 }
+extern "C" int msom_dbg_helm_relax(msom_t *m, int lev, double *da, const double *res, int nhalf, const int *count_per_mode) {
+  if (m) m->res_ready = -1;
+  NEED_CONST(m);
+  if (lev < 0 || lev >= m->nlev || !da || !res || nhalf < 0) return MSOM_ERR_ARG;
+  int r;
+  if ((r = helm_ensure(m))) return r;
+  if ((r = split_upload(m, m->da[lev], m->sg[lev], da, m->nl, BC_DIRICHLET0))) return r;
+  if ((r = split_upload(m, m->res[lev], m->sg[lev], res, m->nl, BC_NEUMANN))) return r;
+  HelmCount cnt = {};
+  for (int k = 0; k < m->nl; k++) cnt.n[k] = count_per_mode ? count_per_mode[k] : (nhalf + 1) / 2;
+  if ((r = helm_relax_level(m, lev, nhalf, cnt, nullptr))) return r;
+  return split_download(m, m->da[lev], m->sg[lev], da, m->nl);
+}
+extern "C" int msom_dbg_helm_residual(msom_t *m, const double *a, const double *b, double *res, double *maxres_per_mode) {
+  if (m) m->res_ready = -1;
+  NEED_CONST(m);
+  if (!a || !b || !res) return MSOM_ERR_ARG;
+  int r;
+  if ((r = helm_ensure(m))) return r;
+  const size_t n = (size_t)m->nl * m->nx * m->ny * sizeof(double);
+  HIPCHK(hipMemcpyAsync(m->staging, a, n, hipMemcpyDefault, m->st));
+  launch_pack(m->st, m->staging, m->f[MSOM_TMP], m->g, m->nl);
+  helm_fill(m, m->f[MSOM_TMP]);
+  HIPCHK(hipMemcpyAsync(m->staging, b, n, hipMemcpyDefault, m->st));
+  launch_pack(m->st, m->staging, m->helm_qm, m->g, m->nl);
+  HIPCHK(hipMemsetAsync(m->helm_scal, 0, HS_COUNT * sizeof(double), m->st));
+  if ((r = helm_residual(m, m->f[MSOM_TMP], m->helm_qm, HS_RES0, 0))) return r;
+  double hs[HS_COUNT];
+  if ((r = helm_read(m, hs))) return r;
+  if ((r = split_download(m, m->res[0], m->sg[0], res, m->nl))) return r;
+  if (maxres_per_mode) for (int k = 0; k < m->nl; k++) maxres_per_mode[k] = hs[HS_RES0 + k];
+  return MSOM_OK;
+}
 extern "C" int msom_dbg_restrict(msom_t *m, int lev_fine, const double *fine, double *coarse) {
   if (m) m->res_ready = -1;
   NEED_CONST(m);
@@ -3369,7 +3618,7 @@ extern "C" int msom_dbg_op(msom_t *m, const char *op, int f_in, int f_out, doubl
 
 extern "C" int msom_profile_reset(msom_t *m) {
   if (!m) return MSOM_ERR_ARG;
-  for (auto *ps : {&m->prof_sweep, &m->prof_resid, &m->prof_block, &m->prof_march[2], &m->prof_march[3], &m->prof_march[4], &m->prof_rhs, &m->prof_redprol, &m->prof_rescorr, &m->prof_respre, &m->prof_march_pl, &m->prof_march_corr, &m->prof_march_visit, &m->prof_resmax}) { ps->used = 0; ps->total_ms = 0; ps->launches = 0; }
+  for (auto *ps : {&m->prof_sweep, &m->prof_resid, &m->prof_block, &m->prof_march[2], &m->prof_march[3], &m->prof_march[4], &m->prof_rhs, &m->prof_redprol, &m->prof_rescorr, &m->prof_respre, &m->prof_march_pl, &m->prof_march_corr, &m->prof_march_visit, &m->prof_resmax, &m->prof_helm_relax, &m->prof_helm_resid, &m->prof_helm_coarse}) { ps->used = 0; ps->total_ms = 0; ps->launches = 0; }
   return MSOM_OK;
 }
 extern "C" int msom_profile_read(msom_t *m, const char *kernel, double *avg_ms, long *launches) {
@@ -3377,7 +3626,8 @@ extern "C" int msom_profile_read(msom_t *m, const char *kernel, double *avg_ms, 
   ProfSlot *ps = !strcmp(kernel, "sweep") ? &m->prof_sweep : !strcmp(kernel, "residual") ? &m->prof_resid : !strcmp(kernel, "block2") ? &m->prof_block :
                  !strcmp(kernel, "march2") ? &m->prof_march[2] : !strcmp(kernel, "march3") ? &m->prof_march[3] : !strcmp(kernel, "march4") ? &m->prof_march[4] :
                  !strcmp(kernel, "march_pl") ? &m->prof_march_pl : !strcmp(kernel, "march_corr") ? &m->prof_march_corr : !strcmp(kernel, "march_visit") ? &m->prof_march_visit : !strcmp(kernel, "resid_max") ? &m->prof_resmax : !strcmp(kernel, "rhs") ? &m->prof_rhs : !strcmp(kernel, "red_prolong") ? &m->prof_redprol : !strcmp(kernel, "resid_correct") ? &m->prof_rescorr :
-                 !strcmp(kernel, "resid_restrict") ? &m->prof_respre : nullptr;
+                 !strcmp(kernel, "resid_restrict") ? &m->prof_respre : !strcmp(kernel, "helm_relax") ? &m->prof_helm_relax :
+                 !strcmp(kernel, "helm_residual") ? &m->prof_helm_resid : !strcmp(kernel, "helm_coarse") ? &m->prof_helm_coarse : nullptr;
   if (!ps) { msom_set_error("unknown kernel %s", kernel); return MSOM_ERR_ARG; }
   prof_collect(m, *ps);
   if (avg_ms) *avg_ms = ps->launches ? ps->total_ms / ps->launches : 0.;
@@ -3399,12 +3649,23 @@ extern "C" int msom_bench_kernel(msom_t *m, const char *kernel, int reps, double
     NEED_MODES(m, "msom_bench_kernel");
     if (!m->modes_partial) HIPCHK(hipMalloc(&m->modes_partial, (size_t)2 * MSOM_MAXNL * modes_energy_stride(m->g) * sizeof(double)));
   }
+  HelmCount helm_all = {};
+  if (!strncmp(kernel, "helm_", 5)) {   // "helm_sweep": both half-sweeps of the finest level, every mode; "helm_residual"
+    if (strcmp(kernel, "helm_sweep") && strcmp(kernel, "helm_residual")) { msom_set_error("unknown kernel %s", kernel); return MSOM_ERR_ARG; }
+    int r = helm_ensure(m);
+    if (r) return r;
+    for (int k = 0; k < m->nl; k++) helm_all.n[k] = 1;
+  }
   hipEvent_t a, b;
   HIPCHK(hipEventCreate(&a));
   HIPCHK(hipEventCreate(&b));
   const double D = m->p.L0 / m->gnx;
   auto one = [&](void) {
-    if (!strcmp(kernel, "sweep")) {
+    if (!strcmp(kernel, "helm_sweep")) {
+      helm_relax_level(m, 0, 2, helm_all, nullptr);
+    } else if (!strcmp(kernel, "helm_residual")) {
+      helm_residual(m, m->helm_pm, m->helm_qm, HS_RES1, 0);
+    } else if (!strcmp(kernel, "sweep")) {
       for (int c = 0; c < 2; c++) launch_relax_color(m->st, m->da[0], m->res[0], m->S[0], m->sg[0], m->nl, m->rc[0], m->uniformS, c, m->walls, 1);
     } else if (!strcmp(kernel, "residual")) {
       launch_residual(m->st, m->f[MSOM_PSI], m->f[MSOM_Q], m->f[MSOM_S], m->g, m->res[0], m->sg[0], m->nl, m->rc[0], m->uniformS, m->d_scal + SC_RES1, m->partial, 0);
