@@ -354,6 +354,68 @@ int msom_dbg_wavelet_levels(msom_t *m);
 int msom_dbg_siglev(msom_t *m, int level, double *out);
 int msom_dbg_wavelet_apply(msom_t *m, int field);
 
+/* ---- the newqg dialect: the cell-centred, dimensional one-layer model of newqg/qg.h with the optional Helmholtz ("1.5-layer")
+ * inversion, on a msom_t.  msom_create_newqg parses a params.in of that model, msom_create_newqg_str the same text from memory; NULL on
+ * error.  One tile, one layer.
+ * Keys (newqg/extra.h:42-58): N nl L0 DT CFL TOLERANCE f0 beta hEkb tau0 nu gp_low sbc tend dtout dh; extension keys Ny NITERMAX NITERMIN
+ *   as in msom_create.  Defaults newqg/qg.h:85-94 and the Basilisk globals: f0 = 1, dh = [1], tend = dtout = 1, N = 64, L0 = 1, DT = 1e10,
+ *   CFL = 0.5, TOLERANCE = 1e-3, everything else 0.  Line rules as msom_create.  Derived: nu != 0: DT = 0.5 * min(DT, sq(L0/N) / nu / 4)
+ *   (extra.h:71); bc_fac = sbc / ((0.5*sbc + 1) * sq(L0/N)) (qg.h:295); iRd2_low = gp_low != 0 ? -(f0*f0) / (gp_low * dh[0]) : 0
+ *   (qg.h:348-354, a uniform field there).  nl != 1 ("to be updated for multi layer", qg.h:347), N or Ny not a power of two >= 2,
+ *   dh[0] == 0, sbc < 0 other than -1 (the reference installs its wall conditions for sbc >= 0 only, qg.h:303): MSOM_ERR_CONFIG (NULL,
+ *   message in msom_last_error).  tau0 is parsed and reported only: the reference uses it in the
+ *   driver's sample forcing alone (newqg/qg.c:69-75).
+ * msom_get_param: model (1 on such a handle, 0 on every other), N nx ny nl L0 DT CFL TOLERANCE tend dtout f0 beta nu hEkb tau0 gp_low sbc
+ *   bc_fac iRd2_low dh_0 nlevels, and the options nq_fused nq_adv_fused nq_rows (nq_rows: the chunk height a launch takes).
+ * Fields: MSOM_PSI, MSOM_Q, MSOM_ZETA, MSOM_DQ, MSOM_QPRED, MSOM_QFORC, one layer each; every other id: MSOM_ERR_ARG from
+ *   msom_set_field / msom_get_field, 0 from msom_field_layers.
+ * Boundary conditions (qg.h:303-319; sbc = -1: periodic(right), periodic(top), newqg/qg.c:33-36): psi dirichlet(0), ghost = -interior,
+ *   corners by the y rule over the x-ghost column; zeta and q ghosts bc_fac * (psi[interior] - psi[ghost]) -- 0 with sbc = 0 -- and a
+ *   corner ghost is that y rule on the x-ghost column, bc_fac * (psi[x-ghost, interior row] - psi[corner ghost]); sbc = -1: wrapped copies.
+ * Calls:
+ *   msom_set_const (qg.h:345-358): q = comp_q(psi), boundary fill; time = 0, iteration = 0, the limiter's previous = 0 (the static of
+ *     qg.h:203 at the start of a run).  Every call below needs it first: MSOM_ERR_STATE otherwise (msom_update: that code as its value).
+ *   msom_comp_q (:184-189): q = lap(psi); gp_low != 0: q = q + iRd2_low * psi.
+ *   msom_invertq (:148-157): poisson(psi, q, lambda = iRd2_low): the multigrid of the modal inversion above with ONE problem,
+ *     iBu := iRd2_low, a = MSOM_PSI in place (warm start and result; there is no mode-space field), b = q, no projections, psi's boundary
+ *     fill after the last correction; relax / residual expression orders as documented there (Basilisk's poisson() relax and residual,
+ *     text mspg/elliptic.h:262-350).  mgstats of the one problem: i, nrelax from 4 by the 1.2 / 10 rule, resb, resa, sum.  gp_low = 0 is
+ *     plain Poisson; doubly periodic with gp_low = 0 needs zero-mean q.
+ *   msom_update (:264-284): solve, tendency into MSOM_ZETA (always stored: update_qg leaves lap(psi) there) and MSOM_DQ, and the
+ *     limiter of advection_pv :202-219, applied ONCE per update with one `previous` (max|u| over the faces from a pass over psi:
+ *     D / max|u| is the minimum over the faces of D / |u| exactly).  Returns the new dtmax.
+ *   msom_advance (:249-261): qo = qi + dq * dt.
+ *   msom_step, msom_set_tnext, msom_time, msom_iter: one iteration of the predictor-corrector run() as msom_step above (dtnext, update,
+ *     advance dt/2, update, advance dt); `previous` moves in the second update too; synchronous.
+ *   msom_ke: sum -0.5 * psi * lap(psi) * Delta^2 (newqg/qg.c:89-91), deterministic two-stage sums.
+ *   msom_last_mgstats, msom_write_nc / msom_read_nc (the format is newqg/netcdf_bas.h), msom_profile_read ("rhs", "helm_relax",
+ *     "helm_residual", "helm_coarse") / msom_profile_reset, msom_sync, msom_dbg_nlevels / msom_dbg_level_dims, msom_destroy;
+ *     msom_bench_kernel: "nq_rhs" (tendency + advance), "nq_rhs_dq", "helm_sweep", "helm_residual"; a measurement, not an operator: it
+ *     overwrites MSOM_ZETA, MSOM_DQ and MSOM_QPRED of the handle and the solver's work arrays (psi and q stay).
+ *   Forcing: surface_forcing is a prototype the driver fills in (:246); here it is the handle's MSOM_QFORC: once set, dq = dq + qforc as
+ *     the last term.  The driver's time-dependent sample expression and its noise() start are the caller's.
+ * Options: TOLERANCE NITERMAX NITERMIN DT quiet profile; nq_fused [1] (0: the tendency as one launch per reference loop, the validation
+ *   chain; same bits in the strict build), nq_adv_fused [1] (the advance folded into the tendency pass, dq then not stored by
+ *   msom_step), nq_rows [0 = automatic] chunk height of the fused kernel.  Any other key: MSOM_ERR_ARG.
+ * Every other entry point of this header that takes a msom_t * (msom_run, pystep_*, pyq2p / pyp2q, msom_bfn_*, msom_stats_*,
+ *   msom_time_filter, msom_modes_*, msom_wavelet_filter, the energy budgets, .bas IO, msom_read_inputs, msom_remove_mean, msom_tile_info,
+ *   msom_dbg_relax / _residual / _helm_* / _restrict / _prolong / _op / _wavelet_* / _siglev) is an msqg operator and answers such a handle
+ *   with MSOM_ERR_CONFIG, a message naming the call, and no change to its fields.  msom_create_tiled has no newqg form.
+ * Expression order of the tendency (the contract of the strict build: true divisions, no contraction; it is how the C of
+ *   newqg/qg.h:125-141,164,200,229,240,258 parses; E / W = x +- 1, N / S = y +- 1, D = Delta):
+ *   z    = ((((pE + pW) + pN) + pS) - 4*p) / (D*D)                       (the 0*zeta_old of comp_del2(.., 0., 1.) is dropped)
+ *   J    = ((pE-pW)*(zN-zS) + (pS-pN)*(zE-zW) + pE*(zNE-zSE) - pW*(zNW-zSW) - pN*(zNE-zNW) + pS*(zSE-zSW)
+ *           + zN*(pNE-pNW) - zS*(pSE-pSW) - zE*(pNE-pSE) + zW*(pNW-pSW)) / ((12.*D)*D)      summed left to right
+ *   dq   = 0 + ((-J) - (beta*(pE - pW)) / (2*D))                         (the += on the zeroed updates, :267-270,200)
+ *   dq   = dq + nu * (((((zE + zW) + zN) + zS) - 4*z) / (D*D))
+ *   dq   = dq - ((hEkb*f0) / (2*dh0)) * z                                (coefficient formed once on the host)
+ *   dq   = dq + qforc                                                    (only if MSOM_QFORC was set)
+ *   qout = qin + dq*dt
+ *   Product build: reciprocals of D*D, (12 D) D and 2 D formed once on the host; the Jacobian one chain of fused multiply-adds in the
+ *   order above, z and lap(z) as fma(-4, c, sum) * (1 / (D*D)), and dq = fma(nu, lap z, dq), fma(-cek, z, dq), qout = fma(dq, dt, qin). */
+msom_t *msom_create_newqg(const char *params_path);
+msom_t *msom_create_newqg_str(const char *params_text);
+
 /* select the HIP device of the calling thread before msom_create* (one process per GPU:
  * device = LOCAL_RANK) */
 int msom_set_device(int device);

@@ -12,6 +12,7 @@ from .api import (  # noqa: F401
     MODES,
     MsomError,
     NODE_FIELDS,
+    NewQG,
     NodeQG,
     QG,
     STATS,
@@ -33,6 +34,6 @@ from .api import (  # noqa: F401
 )
 
 __all__ = [
-    "QG", "NodeQG", "NODE_FIELDS", "MGStats", "MsomError", "FIELDS", "STATS", "MODES", "load_library", "read_params", "init_grid", "set_vars",
+    "QG", "NodeQG", "NewQG", "NODE_FIELDS", "MGStats", "MsomError", "FIELDS", "STATS", "MODES", "load_library", "read_params", "init_grid", "set_vars",
     "set_vars_bfn", "set_const", "pystep_bfn", "bfn_begin", "bfn_steps", "bfn_misfit", "pystep_de", "pyq2p", "pyp2q", "trash_vars", "trash_vars_bfn",
 ]

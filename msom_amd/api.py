@@ -54,6 +54,8 @@ def load_library(strict=False):
         "msom_version": (cs, []),
         "msom_create": (vp, [cs]),
         "msom_create_str": (vp, [cs]),
+        "msom_create_newqg": (vp, [cs]),
+        "msom_create_newqg_str": (vp, [cs]),
         "msom_destroy": (ci, [vp]),
         "msom_set_option": (ci, [vp, cs, cd]),
         "msom_get_param": (cd, [vp, cs]),
@@ -534,6 +536,46 @@ class QG:
         ms = C.c_double()
         self._chk(self.L.msom_bench_kernel(self.h, kernel.encode(), reps, C.byref(ms)))
         return ms.value
+
+
+class NewQG:
+    """The cell-centred one-layer model with the optional Helmholtz ("1.5-layer", gp_low) inversion: one `qg.e` process of newqg/qg.c
+    without its driver's sample forcing (set QFORC instead).  Fields PSI, Q, ZETA, DQ, QPRED, QFORC, arrays [1][ny][nx].  Only the
+    calls the dialect has are defined here; the handle answers every other entry point of msom.h with MSOM_ERR_CONFIG."""
+
+    FIELD_IDS = tuple(FIELDS[k] for k in ("PSI", "Q", "ZETA", "DQ", "QPRED", "QFORC"))
+
+    def __init__(self, params=None, path=None, strict=False):
+        self.L = load_library(strict)
+        self.h = self.L.msom_create_newqg(path.encode()) if path is not None else self.L.msom_create_newqg_str(params.encode())
+        if not self.h:
+            raise MsomError(self.L.msom_last_error().decode())
+        self.nl = 1
+        self.nx, self.ny = int(self.param("nx")), int(self.param("ny"))
+
+    close, __del__, _chk = QG.close, QG.__del__, QG._chk
+    param, option = QG.param, QG.option
+    set_const = QG.set_const
+    update, advance, invertq, comp_q = QG.update, QG.advance, QG.invertq, QG.comp_q
+    step, set_tnext, t, iter, ke, mgstats = QG.step, QG.set_tnext, QG.t, QG.iter, QG.ke, QG.mgstats
+    write_nc, read_nc = QG.write_nc, QG.read_nc
+    profile_read, profile_reset, sync, bench_kernel = QG.profile_read, QG.profile_reset, QG.sync, QG.bench_kernel
+
+    def shape(self, field):
+        return (self.L.msom_field_layers(self.h, field), self.ny, self.nx)
+
+    def set(self, field, a):
+        a = _f64(a, (1, self.ny, self.nx))
+        self._chk(self.L.msom_set_field(self.h, field, _ptr(a)))
+
+    def get(self, field):
+        a = np.empty((1, self.ny, self.nx))
+        self._chk(self.L.msom_get_field(self.h, field, _ptr(a)))
+        return a
+
+    def level_dims(self):
+        """(nx, ny) of every multigrid level, finest first"""
+        return [(self.nx >> k, self.ny >> k) for k in range(int(self.param("nlevels")))]
 
 
 # ---------------------------------------------------------------------------

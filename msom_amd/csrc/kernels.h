@@ -267,6 +267,18 @@ int helm_residual_blocks(const NatGeom &g);
 int launch_helm_residual(hipStream_t st, const double *a, const double *b, const double *ibu_sp, const HelmCoef *hc, const NatGeom &g, double *res,
                          const SplitGeom &sg, int nl, double D, double *maxres, double *sum_partial, int stride, int want_sum);
 
+// ---- kernels_newqg.hip: tendency of the cell-centred one-layer model (newqg/qg.h:264-284), one layer, one tile.
+// One pass psi -> zeta (always stored) and dq, or q_out = q_in + dt * dq when q_out != nullptr (dq then not stored).  psi carries its
+// ghost ring (walls) or wrapped copies two cells deep (walls & WALL_PER).  qforc == nullptr: no forcing term.  cek = (hEkb f0) / (2 dh0).
+// rows: chunk height (0: automatic); nq_rhs_rows gives the height a launch takes.
+int nq_rhs_rows(const NatGeom &g, int rows);
+void launch_nq_rhs(hipStream_t st, const double *psi, const double *qforc, double *zeta, double *dq, const NatGeom &g, int walls, double D,
+                   double beta, double nu, double cek, double bc_fac, const double *q_in, double *q_out, double dt, int rows);
+// the validation chain: ghost ring f[ghost] = bc_fac * (psi[interior] - psi[ghost]) of zeta / q (newqg/qg.h:310-318, corners by the
+// y rule), and dq = 0 + ((-J(psi, zeta)) - beta_effect(psi)) (:199-200) from fields with their ghost rings
+void launch_nq_ghost(hipStream_t st, const double *psi, double *f, const NatGeom &g, double bc_fac);
+void launch_nq_adv(hipStream_t st, const double *psi, const double *zeta, double *dq, const NatGeom &g, double D, double beta);
+
 // ---- kernels_wavelet.hip
 void launch_wv_restrict(hipStream_t st, const double *f, const NatGeom &fg, double *c, const NatGeom &cg, int nl);
 void launch_wv_recon(hipStream_t st, const double *s, const double *sc, const double *rc, const double *sig, double *out, const NatGeom &fg,

@@ -208,6 +208,12 @@ struct msom {
   int s_zero = 0;  // pystep_de(onlyKE = 1) zeroed the stretching field S (msqg/qg_energy.h:319-325); undone by msom_set_const
   std::vector<NatGeom> wv_g;
   std::vector<double *> wv_s, wv_r, wv_sig;
+  // newqg dialect (msom_create_newqg): the cell-centred one-layer model of newqg/qg.h runs on this handle; 0 on every other
+  int model = 0;
+  NewqgParams nq = {};
+  int nq_fused = 1;      // option: the tendency in one pass (k_nq_rhs); 0: one launch per reference loop (validation chain)
+  int nq_adv_fused = 1;  // option: q_out = q_in + dt dq folded into that pass
+  int nq_rows = 0;       // option: chunk height of k_nq_rhs (0: automatic)
   // time loop
   double t = 0, dt = 1., tnext = HUGE_VAL, previous = 0;
   int iter = 0;
@@ -229,6 +235,30 @@ static void helm_drop_pyramid(msom *m) {   // the iBu pyramid of the modal inver
     if (p) hipFree(p);
   m->helm_ibu.clear();
 }
+
+// ---- the two dialects of a msom_t.  An entry point of the msqg dialect answers a newqg handle with MSOM_ERR_CONFIG: this one guard,
+// first statement of each of them; the calls both dialects have dispatch to the nq_* functions of the newqg section below.
+static int nq_refuse(const char *fn) {
+  msom_set_error("%s: not available on a newqg handle (msom_create_newqg)", fn);
+  return MSOM_ERR_CONFIG;
+}
+#define MSQG_ONLY(m)                                  \
+  do {                                                \
+    if ((m) && (m)->model) return nq_refuse(__func__); \
+  } while (0)
+static bool nq_has_field(int field) {
+  return field == MSOM_PSI || field == MSOM_Q || field == MSOM_ZETA || field == MSOM_DQ || field == MSOM_QPRED || field == MSOM_QFORC;
+}
+static int nq_set_option(msom *m, const char *key, double v);
+static double nq_get_param(msom *m, const char *key);
+static int nq_after_upload(msom *m, int field);
+static int nq_set_const(msom *m);
+static double nq_update(msom *m, const double *q, double *dqdt, double dtmax);
+static int nq_advance(msom *m, double *qout, const double *qin, const double *dqdt, double dt);
+static int nq_invertq(msom *m, const double *q, double *psi, msom_mgstats *st);
+static int nq_comp_q_api(msom *m, const double *psi, double *q);
+static int nq_step(msom *m, double *dt_used);
+static int nq_bench_kernel(msom *m, const char *kernel, int reps, double *avg_ms);
 
 extern "C" const char *msom_version(void) {
 #ifdef MSOM_STRICT
@@ -517,6 +547,7 @@ static int alloc_all(msom *m) {
   for (int k = 0; k < MSOM_NFIELDS; k++) {
     if (k == MSOM_NOISE || k == MSOM_SIGMA || k == MSOM_QOF || k >= MSOM_DE_BF) continue;  // allocated when "stochastic" is switched on / on the first filter call
     if (k >= MSOM_PTR && k <= MSOM_PTR_PRED && m->p.nptr <= 0) continue;
+    if (m->model && !nq_has_field(k)) continue;   // newqg dialect: its six fields, every other id stays unallocated (MSOM_ERR_ARG)
     size_t bytes = m->g.ls * m->flayers[k] * sizeof(double);
     HIPCHK(hipMalloc(&m->f[k], bytes));
     HIPCHK(hipMemsetAsync(m->f[k], 0, bytes, m->st));
@@ -532,16 +563,19 @@ static int alloc_all(msom *m) {
     m->sg[k] = make_split(m->nx >> k, m->ny >> k);
     size_t bytes = m->sg[k].ls * m->nl * sizeof(double);
     HIPCHK(hipMalloc(&m->da[k], bytes));
-    HIPCHK(hipMalloc(&m->da_alt[k], bytes));
-    HIPCHK(hipMemsetAsync(m->da_alt[k], 0, bytes, m->st));
     HIPCHK(hipMalloc(&m->res[k], bytes));
-    HIPCHK(hipMalloc(&m->S[k], m->sg[k].ls * m->nlm * sizeof(double)));
     HIPCHK(hipMemsetAsync(m->da[k], 0, bytes, m->st));
     HIPCHK(hipMemsetAsync(m->res[k], 0, bytes, m->st));
+    if (m->model) continue;   // the Helmholtz cycle works in place and has no stretching: no second correction, no S
+    HIPCHK(hipMalloc(&m->da_alt[k], bytes));
+    HIPCHK(hipMemsetAsync(m->da_alt[k], 0, bytes, m->st));
+    HIPCHK(hipMalloc(&m->S[k], m->sg[k].ls * m->nlm * sizeof(double)));
     HIPCHK(hipMemsetAsync(m->S[k], 0, m->sg[k].ls * m->nlm * sizeof(double), m->st));
   }
-  HIPCHK(hipMalloc(&m->psi_alt, m->g.ls * m->nl * sizeof(double)));
-  HIPCHK(hipMemsetAsync(m->psi_alt, 0, m->g.ls * m->nl * sizeof(double), m->st));
+  if (!m->model) {
+    HIPCHK(hipMalloc(&m->psi_alt, m->g.ls * m->nl * sizeof(double)));
+    HIPCHK(hipMemsetAsync(m->psi_alt, 0, m->g.ls * m->nl * sizeof(double), m->st));
+  }
   HIPCHK(hipMalloc(&m->staging, (size_t)m->nl * (m->p.nptr > 1 ? m->p.nptr : 1) * m->nx * m->ny * sizeof(double)));
   HIPCHK(hipMalloc(&m->partial, ((size_t)partial_count(m->g) * m->nl + 64) * sizeof(double)));  // + chunk sums of launch_sum_final
   HIPCHK(hipMalloc(&m->partial_rr, ((size_t)rhs_pipe_blocks(m->g) + 64) * sizeof(double)));
@@ -593,7 +627,8 @@ static int set_vars(msom *m) {
   return r;
 }
 
-static msom *create_common(const Params &p0, int px, int py, int rank, const void *id128) {
+static int nq_alloc(msom *m);
+static msom *create_common(const Params &p0, int px, int py, int rank, const void *id128, const NewqgParams *nq = nullptr) {
   Params p = p0;
   if (p.Ny <= 0) p.Ny = p.N;
   msom_params_derive(&p);
@@ -616,6 +651,7 @@ static msom *create_common(const Params &p0, int px, int py, int rank, const voi
   }
   msom *m = new msom();
   m->p = p;
+  if (nq) { m->model = 1; m->nq = *nq; }
   m->px = px; m->py = py; m->rank = rank; m->nranks = px * py;
   m->ix = rank % px; m->iy = rank / px;
   m->gnx = p.N; m->gny = p.Ny;
@@ -648,7 +684,7 @@ static msom *create_common(const Params &p0, int px, int py, int rank, const voi
                                     // largest message: a MARCH_HALO-deep strip of the widest exchanged field
                                     // (tracer fields carry nl * nptr layers, fill_bc exchanges them whole)
                                     (size_t)MARCH_HALO * ((m->nx > m->ny ? m->nx : m->ny) + 16) * m->nl * (p.nptr > 1 ? p.nptr : 1)) != MSOM_OK) ||
-      set_vars(m) != MSOM_OK) {
+      (nq ? nq_alloc(m) : set_vars(m)) != MSOM_OK) {
     msom_destroy(m);
     return nullptr;
   }
@@ -749,6 +785,7 @@ static int *kernel_opt(KernelOpts &o, const char *key) {
 }
 extern "C" int msom_set_option(msom_t *m, const char *key, double v) {
   if (!m || !key) return MSOM_ERR_ARG;
+  if (m->model) return nq_set_option(m, key, v);
   clear_graphs(m);   // captured cycles hold kernel arguments by value: any option may change them
   if (!strcmp(key, "graph")) { m->use_graph = (int)v; return MSOM_OK; }
   if (!strcmp(key, "TOLERANCE")) m->p.tolerance = v;
@@ -846,6 +883,8 @@ static int level_path(const msom *m, int k);
 static bool restrict2_ok(const msom *m);
 extern "C" double msom_get_param(msom_t *m, const char *key) {
   if (!m || !key) return NAN;
+  if (!strcmp(key, "model")) return m->model;
+  if (m->model) return nq_get_param(m, key);
   const Params &p = m->p;
   if (!strcmp(key, "N") || !strcmp(key, "nx")) return m->gnx;
   if (!strcmp(key, "ny")) return m->gny;
@@ -952,16 +991,18 @@ static int download(msom *m, int field, double *a) {
 }
 
 extern "C" int msom_field_layers(msom_t *m, int field) {
+  if (m && m->model && !(field >= 0 && field < MSOM_NFIELDS && m->f[field])) return 0;
   if (check_field(m, field)) return MSOM_ERR_ARG;
   return m->flayers[field];
 }
 
 static int ensure_field(msom *m, int field);
 extern "C" int msom_set_field(msom_t *m, int field, const double *a) {
-  if (m && (field == MSOM_QOF || (field >= MSOM_DE_BF && field < MSOM_NFIELDS)) && ensure_field(m, field)) return MSOM_ERR_HIP;
+  if (m && !m->model && (field == MSOM_QOF || (field >= MSOM_DE_BF && field < MSOM_NFIELDS)) && ensure_field(m, field)) return MSOM_ERR_HIP;
   if (check_field(m, field) || !a) return MSOM_ERR_ARG;
   int r = upload(m, field, a);
   if (r) return r;
+  if (m->model && (r = nq_after_upload(m, field))) return r;
   if (field == MSOM_RD) m->wv_ready = 0;
   if (field == MSOM_FR || field == MSOM_RO || field == MSOM_S) { m->fr_uniform = 0; m->const_set = 0; }
   // the background flow feeds values cached by msom_set_const (max |u_pg| of the dt limiter, zeta_pg when flsrv = 1;
@@ -975,13 +1016,14 @@ extern "C" int msom_set_field(msom_t *m, int field, const double *a) {
   return sync_stream(m);
 }
 extern "C" int msom_get_field(msom_t *m, int field, double *a) {
-  if (m && (field == MSOM_QOF || (field >= MSOM_DE_BF && field < MSOM_NFIELDS)) && ensure_field(m, field)) return MSOM_ERR_HIP;
+  if (m && !m->model && (field == MSOM_QOF || (field >= MSOM_DE_BF && field < MSOM_NFIELDS)) && ensure_field(m, field)) return MSOM_ERR_HIP;
   if (check_field(m, field) || !a) return MSOM_ERR_ARG;
   return download(m, field, a);
 }
 
 // msqg/qg.c:65-70: po[] -= s.sum/s.volume per layer
 extern "C" int msom_remove_mean(msom_t *m, int field) {
+  MSQG_ONLY(m);
   if (check_field(m, field)) return MSOM_ERR_ARG;
   const int nl = m->flayers[field];
   launch_sum_layers(m->st, m->f[field], m->partial, m->d_scal + SC_LSUM, m->g, nl);
@@ -1185,6 +1227,7 @@ static int build_coefs(msom *m) {
 
 extern "C" int msom_set_const(msom_t *m) {
   if (!m) return MSOM_ERR_ARG;
+  if (m->model) return nq_set_const(m);
   m->s_zero = 0;
   int rr = build_coefs(m);
   if (rr) return rr;
@@ -1835,6 +1878,11 @@ static int helm_ensure(msom *m) {
 }
 // coefficient source of level k: iBu_m by value (compact form; *hc filled) or the level's array of the pyramid
 static const HelmCoef *helm_level_coef(const msom *m, int k, HelmCoef *hc, const double **ibu_sp) {
+  if (m->model) {   // newqg dialect: one problem, lambda = iRd2_low (uniform, newqg/qg.h:348-354)
+    *hc = helm_coef(&m->nq.iRd2_low, 1, m->rc[k].sqD);
+    *ibu_sp = nullptr;
+    return hc;
+  }
   if (m->modes_compact) {
     *hc = helm_coef(m->modes_mc.ibu, m->nl, m->rc[k].sqD);
     *ibu_sp = nullptr;
@@ -1905,22 +1953,19 @@ static void helm_fill(msom *m, double *f) {
   else launch_fill_ghost(m->st, f, m->g, m->nl, BC_DIRICHLET0, m->walls);
 }
 
-// nl times mg_solve(pm, qm, lambda = iBu_m), run side by side: a cycle of the batch is a cycle of every mode that still wants one
-// (helm_inl.h has the bookkeeping).  The host reads the nl maxima once per cycle.
-static int helm_solve(msom *m, const double *q) {
+// nl times mg_solve(a_m, b_m, lambda = iBu_m), run side by side: a cycle of the batch is a cycle of every mode that still wants one
+// (helm_inl.h has the bookkeeping).  The host reads the nl maxima once per cycle.  a: natural field with valid ghosts, warm start and
+// result (its ghosts are the correction's on return); b: natural field.  The sources: the modal inversion's mode-space fields
+// (helm_solve), or psi and q themselves with one problem (nq_solve).
+static int helm_run(msom *m, double *a, const double *b) {
   const Params &p = m->p;
   const int nl = m->nl;
-  int r = helm_ensure(m);
-  if (r) return r;
-  m->res_ready = -1;
-  m->umax_ready = 0;
-  m->spec_valid = 0;
-  if ((r = helm_project(m, q, m->helm_qm, 1))) return r;
+  int r;
   HIPCHK(hipMemsetAsync(m->helm_scal, 0, HS_COUNT * sizeof(double), m->st));
   HelmSolve &h = m->helm;
   helm_begin(h, nl, p.nitermin, p.nitermax, p.tolerance);
   double hs[HS_COUNT];
-  if ((r = helm_residual(m, m->helm_pm, m->helm_qm, HS_RES0, 1))) return r;
+  if ((r = helm_residual(m, a, b, HS_RES0, 1))) return r;
   for (int k = 0; k < nl; k++)
     launch_sum_final(m->st, m->helm_partial + (size_t)k * helm_partial_stride(m), m->helm_scal + HS_BSUM + k, helm_residual_blocks(m->g));
   if (p.nitermin < 1) {   // the first cycle depends on the warm start's residual
@@ -1931,9 +1976,9 @@ static int helm_solve(msom *m, const double *q) {
   int nrelax;
   while ((nrelax = helm_counts(h, cnt.n)) > 0) {
     if ((r = helm_cycle(m, cnt, nrelax))) return r;
-    launch_correct(m->st, m->helm_pm, m->g, m->da[0], m->sg[0], nl, m->walls);   // a frozen mode adds its zero correction
+    launch_correct(m->st, a, m->g, m->da[0], m->sg[0], nl, m->walls);   // a frozen mode adds its zero correction
     HIPCHK(hipMemsetAsync(m->helm_scal + HS_RES1, 0, MSOM_MAXNL * sizeof(double), m->st));
-    if ((r = helm_residual(m, m->helm_pm, m->helm_qm, HS_RES1, 0))) return r;
+    if ((r = helm_residual(m, a, b, HS_RES1, 0))) return r;
     if ((r = helm_read(m, hs))) return r;
     helm_first(h, hs + HS_RES0, hs + HS_BSUM);
     helm_cycle_done(h, cnt.n, hs + HS_RES1);
@@ -1947,6 +1992,16 @@ static int helm_solve(msom *m, const double *q) {
       fprintf(stderr, "WARNING: convergence not reached after %d iterations\n  mode: %d res: %g sum: %g nrelax: %d\n", h.s[k].i, k, h.s[k].resa,
               h.s[k].sum, h.s[k].nrelax);
   m->mg = h.s[nl - 1];   // the reference's mgpsi is overwritten by every poisson() call: the last mode's stay
+  return m->sticky;
+}
+static int helm_solve(msom *m, const double *q) {
+  int r = helm_ensure(m);
+  if (r) return r;
+  m->res_ready = -1;
+  m->umax_ready = 0;
+  m->spec_valid = 0;
+  if ((r = helm_project(m, q, m->helm_qm, 1))) return r;
+  if ((r = helm_run(m, m->helm_pm, m->helm_qm))) return r;
   m->helm_solved = 1;
   if ((r = helm_project(m, m->helm_pm, m->f[MSOM_PSI], 0))) return r;
   fill_bc(m, MSOM_PSI);
@@ -2234,6 +2289,7 @@ static int advance_qg(msom *m, int out, int in, int dq, double dt) {
 
 extern "C" double msom_update(msom_t *m, const double *q, double *dqdt, double dtmax) {
   if (!m) return -1;
+  if (m->model) return nq_update(m, q, dqdt, dtmax);
   if (!m->const_set && msom_set_const(m)) return -1;
   int qf = MSOM_Q;
   if (q) {
@@ -2247,6 +2303,7 @@ extern "C" double msom_update(msom_t *m, const double *q, double *dqdt, double d
 }
 
 extern "C" int msom_advance(msom_t *m, double *qout, const double *qin, const double *dqdt, double dt) {
+  if (m && m->model) return nq_advance(m, qout, qin, dqdt, dt);
   NEED_CONST(m);
   int in = MSOM_Q, out = MSOM_Q, r;
   if (qin) {
@@ -2260,6 +2317,7 @@ extern "C" int msom_advance(msom_t *m, double *qout, const double *qin, const do
 }
 
 extern "C" int msom_invertq(msom_t *m, const double *q, double *psi, msom_mgstats *st) {
+  if (m && m->model) return nq_invertq(m, q, psi, st);
   NEED_CONST(m);
   int qf = MSOM_Q, r;
   if (q) {
@@ -2274,6 +2332,7 @@ extern "C" int msom_invertq(msom_t *m, const double *q, double *psi, msom_mgstat
 }
 
 extern "C" int msom_comp_q(msom_t *m, const double *psi, double *q) {
+  if (m && m->model) return nq_comp_q_api(m, psi, q);
   NEED_CONST(m);
   int r;
   if (psi && (r = upload(m, MSOM_PSI, psi))) return r;
@@ -2290,6 +2349,7 @@ extern "C" int msom_last_mgstats(msom_t *m, msom_mgstats *st) {
 }
 
 extern "C" int msom_modes_mgstats(msom_t *m, int mode, msom_mgstats *st) {
+  MSQG_ONLY(m);
   if (!m || !st) return MSOM_ERR_ARG;
   if (!m->const_set || !m->helm_solved) { msom_set_error("msom_modes_mgstats: no modal solve since msom_set_const"); return MSOM_ERR_STATE; }
   if (mode < 0 || mode >= m->nl) { msom_set_error("msom_modes_mgstats: mode %d outside 0 .. %d", mode, m->nl - 1); return MSOM_ERR_ARG; }
@@ -2310,6 +2370,7 @@ static int check_shape(msom *m, int a, int b, int c) {
 // msqg/qg_bfn.h:21-80
 extern "C" int pystep_bfn(msom_t *m, double *varin_py, int len1, int len2, int len3, double *tend_py, int len4, int len5, int len6,
                           double direction, int vartype) {
+  MSQG_ONLY(m);
   NEED_CONST(m);
   if (check_shape(m, len1, len2, len3) || check_shape(m, len4, len5, len6)) return MSOM_ERR_ARG;
   Params &p = m->p;
@@ -2334,6 +2395,7 @@ extern "C" int pystep_bfn(msom_t *m, double *varin_py, int len1, int len2, int l
 }
 // msqg/qg_bfn.h:85-93
 extern "C" int pyq2p(msom_t *m, double *po_py, int len7, int len8, int len9, double *qo_py, int len10, int len11, int len12) {
+  MSQG_ONLY(m);
   NEED_CONST(m);
   if (check_shape(m, len7, len8, len9) || check_shape(m, len10, len11, len12)) return MSOM_ERR_ARG;
   int r;
@@ -2344,6 +2406,7 @@ extern "C" int pyq2p(msom_t *m, double *po_py, int len7, int len8, int len9, dou
 }
 // msqg/qg_bfn.h:95-103
 extern "C" int pyp2q(msom_t *m, double *po_py, int len13, int len14, int len15, double *qo_py, int len16, int len17, int len18) {
+  MSQG_ONLY(m);
   NEED_CONST(m);
   if (check_shape(m, len13, len14, len15) || check_shape(m, len16, len17, len18)) return MSOM_ERR_ARG;
   return msom_comp_q(m, po_py, qo_py);
@@ -2354,6 +2417,7 @@ extern "C" int pyp2q(msom_t *m, double *po_py, int len13, int len14, int len15, 
 static int ensure_field(msom *m, int field);
 // msqg/qg_bfn.py:49-51: zero history; the AB3 weights apply from the first step on
 extern "C" int msom_bfn_begin(msom_t *m) {
+  MSQG_ONLY(m);
   NEED_CONST(m);
   int r;
   for (int k = MSOM_BFN_F1; k <= MSOM_BFN_F3; k++) {
@@ -2366,6 +2430,7 @@ extern "C" int msom_bfn_begin(msom_t *m) {
 
 // msqg/qg_bfn.py:62-73 with the nudging term of :67-68
 extern "C" int msom_bfn_steps(msom_t *m, int nsteps, double dt, double direction, double k) {
+  MSQG_ONLY(m);
   if (!m) return MSOM_ERR_ARG;
   if (nsteps < 0) { msom_set_error("msom_bfn_steps: nsteps = %d", nsteps); return MSOM_ERR_ARG; }
   if (!m->const_set || !m->bfn_begun) { msom_set_error("msom_bfn_steps before msom_bfn_begin"); return MSOM_ERR_STATE; }
@@ -2401,6 +2466,7 @@ extern "C" int msom_bfn_steps(msom_t *m, int nsteps, double dt, double direction
 }
 
 extern "C" int msom_bfn_misfit(msom_t *m, double *misfit) {
+  MSQG_ONLY(m);
   if (!m || !misfit) return MSOM_ERR_ARG;
   if (!m->bfn_obs_set) { msom_set_error("msom_bfn_misfit: MSOM_BFN_OBS was never set"); return MSOM_ERR_STATE; }
   if (!m->bfn_partial) HIPCHK(hipMalloc(&m->bfn_partial, 2 * ((size_t)bfn_misfit_blocks(m->g) + 64) * sizeof(double)));
@@ -2438,6 +2504,7 @@ static void stats_sample(msom *m, const double *w_dev, double w) {
   } while (0)
 
 extern "C" int msom_stats_begin(msom_t *m, unsigned mask) {
+  MSQG_ONLY(m);
   if (!m) return MSOM_ERR_ARG;
   if (mask == 0 || mask >> MSOM_ST_NACC) { msom_set_error("msom_stats_begin: mask 0x%x", mask); return MSOM_ERR_ARG; }
   if (!m->const_set) { msom_set_error("msom_stats_begin before msom_set_const"); return MSOM_ERR_STATE; }
@@ -2457,6 +2524,7 @@ extern "C" int msom_stats_begin(msom_t *m, unsigned mask) {
 }
 
 extern "C" int msom_stats_accumulate(msom_t *m, double w) {
+  MSQG_ONLY(m);
   if (!m) return MSOM_ERR_ARG;
   if (!std::isfinite(w)) { msom_set_error("msom_stats_accumulate: w = %g", w); return MSOM_ERR_ARG; }
   NEED_STATS(m, "msom_stats_accumulate");
@@ -2465,6 +2533,7 @@ extern "C" int msom_stats_accumulate(msom_t *m, double w) {
 }
 
 extern "C" int msom_stats_weight(msom_t *m, double *W) {
+  MSQG_ONLY(m);
   if (!m || !W) return MSOM_ERR_ARG;
   NEED_STATS(m, "msom_stats_weight");
   HIPCHK(hipMemcpyAsync(W, m->stats_W, sizeof(double), hipMemcpyDeviceToHost, m->st));
@@ -2472,6 +2541,7 @@ extern "C" int msom_stats_weight(msom_t *m, double *W) {
 }
 
 extern "C" int msom_stats_get(msom_t *m, int which, double *out) {
+  MSQG_ONLY(m);
   if (!m || !out) return MSOM_ERR_ARG;
   const size_t n = (size_t)m->nl * m->nx * m->ny;
   if (which == MSOM_ST_QME) {
@@ -2505,6 +2575,7 @@ extern "C" int msom_stats_get(msom_t *m, int which, double *out) {
 
 // time_filter, msqg/qg.h:491-507 (alpha_f = dt / tau_f; qo_me starts from the zeros of a freshly created field)
 extern "C" int msom_time_filter(msom_t *m, double dt) {
+  MSQG_ONLY(m);
   if (!m) return MSOM_ERR_ARG;
   if (!std::isfinite(dt)) { msom_set_error("msom_time_filter: dt = %g", dt); return MSOM_ERR_ARG; }
   if (!m->const_set) { msom_set_error("msom_time_filter before msom_set_const"); return MSOM_ERR_STATE; }
@@ -2546,6 +2617,7 @@ static bool is_device_ptr(const void *p) {
   } while (0)
 
 extern "C" int msom_modes_compute(msom_t *m) {
+  MSQG_ONLY(m);
   NEED_CONST(m);
   const int nl = m->nl, na = nl * nl + nl;
   const int compact = m->modes_compact_opt != 0 && m->fr_uniform;
@@ -2585,12 +2657,14 @@ extern "C" int msom_modes_compute(msom_t *m) {
 }
 
 extern "C" int msom_modes_layers(msom_t *m, int which) {
+  MSQG_ONLY(m);
   if (!m || which < 0 || which >= MSOM_MD_N) return MSOM_ERR_ARG;
   NEED_MODES(m, "msom_modes_layers");
   return which == MSOM_MD_IBU || which == MSOM_MD_RD ? m->nl : m->nl * m->nl;
 }
 
 extern "C" int msom_modes_get(msom_t *m, int which, double *out) {
+  MSQG_ONLY(m);
   if (!m || which < 0 || which >= MSOM_MD_N || !out) return MSOM_ERR_ARG;
   NEED_MODES(m, "msom_modes_get");
   const int nl = m->nl, n = which == MSOM_MD_IBU || which == MSOM_MD_RD ? nl : nl * nl;
@@ -2604,6 +2678,7 @@ extern "C" int msom_modes_get(msom_t *m, int which, double *out) {
 }
 
 extern "C" int msom_modes_project(msom_t *m, int to_modes, const double *in, double *out) {
+  MSQG_ONLY(m);
   if (!m || !in || !out) return MSOM_ERR_ARG;
   NEED_MODES(m, "msom_modes_project");
   const size_t bytes = (size_t)m->nl * m->nx * m->ny * sizeof(double);
@@ -2626,6 +2701,7 @@ static int modes_energy_launch(msom *m) {
   return MSOM_OK;
 }
 extern "C" int msom_modes_energy(msom_t *m, double *ke, double *pe) {
+  MSQG_ONLY(m);
   if (!m || (!ke && !pe)) return MSOM_ERR_ARG;
   NEED_MODES(m, "msom_modes_energy");
   const int nl = m->nl;
@@ -2641,6 +2717,7 @@ extern "C" int msom_modes_energy(msom_t *m, double *ke, double *pe) {
 }
 
 extern "C" int msom_modes_set_rd(msom_t *m, int mode) {
+  MSQG_ONLY(m);
   if (!m || mode < 1 || mode > m->nl - 1) return MSOM_ERR_ARG;
   NEED_MODES(m, "msom_modes_set_rd");
   if (launch_modes_rd(m->st, m->f[MSOM_RD], m->modes_md, modes_mc(m), m->g, m->nl, mode)) return MSOM_ERR_CONFIG;
@@ -2696,6 +2773,7 @@ static bool spec_ok(msom *m) {
 }
 
 extern "C" int msom_step(msom_t *m, double *dt_used) {
+  if (m && m->model) return nq_step(m, dt_used);
   NEED_CONST(m);
   if (m->stats_on && !m->stats_mask) { msom_set_error("msom_step: option stats = 1 and no msom_stats_begin since msom_set_const"); return MSOM_ERR_STATE; }
   const Params &p = m->p;
@@ -2795,6 +2873,302 @@ extern "C" double msom_ke(msom_t *m) {
   launch_ke(m->st, m->f[MSOM_PSI], m->partial, m->d_scal + SC_KE, m->g, m->p.L0 / m->gnx);
   if (reduce_scal(m, SC_KE, 1, RED_SUM)) return NAN;
   return -m->h_scal[SC_KE];
+}
+
+// ------------------------------------------------------------------ newqg dialect (msom_create_newqg)
+//
+// The cell-centred one-layer model of newqg/qg.h with the optional Helmholtz ("1.5-layer", gp_low) inversion on a msom_t: set_vars
+// :291-336, set_const :345-358, invertq :148-157 (Basilisk's poisson(psi, q, lambda = iRd2_low): the multigrid of helm_run with one
+// problem, a = psi in place, b = q), comp_q :184-189, update_qg :264-284, advection_pv's limiter :202-219, advance_qg :249-261, one
+// iteration of run().  One tile; fields MSOM_PSI, Q, ZETA, DQ, QPRED, QFORC, one layer each.
+
+static int nq_alloc(msom *m) {
+  for (int k = 0; k < m->nlev; k++) {   // Delta of every level for the Helmholtz cycle (make_relax_coef's part of it)
+    memset(&m->rc[k], 0, sizeof m->rc[k]);
+    m->rc[k].D = m->p.L0 / (double)(m->gnx >> k);
+    m->rc[k].sqD = m->rc[k].D * m->rc[k].D;
+  }
+  HIPCHK(hipMalloc(&m->helm_scal, HS_COUNT * sizeof(double)));
+  HIPCHK(hipMalloc(&m->helm_partial, (size_t)MSOM_MAXNL * helm_partial_stride(m) * sizeof(double)));
+  return MSOM_OK;
+}
+
+static msom *nq_create(NewqgParams &q, const char *text) {
+  if (msom_newqg_params_derive(&q)) return nullptr;
+  Params p;   // what the shared parts of the handle read: grid, solver controls, limiter
+  msom_params_defaults(&p);
+  p.N = q.N; p.Ny = q.Ny; p.nl = 1; p.L0 = q.L0; p.DT = q.DT; p.CFL = q.CFL; p.tolerance = q.TOLERANCE;
+  p.nitermax = q.nitermax; p.nitermin = q.nitermin; p.sbc = q.sbc; p.beta = q.beta; p.tau0 = q.tau0; p.tend = q.tend; p.dtout = q.dtout;
+  p.dhu[0] = q.dh[0];
+  msom *m = create_common(p, 1, 1, 0, nullptr, &q);
+  if (m) m->params_text = text;
+  return m;
+}
+extern "C" msom_t *msom_create_newqg_str(const char *text) {
+  if (!text) { msom_set_error("null params text"); return nullptr; }
+  NewqgParams q;
+  msom_newqg_params_defaults(&q);
+  msom_newqg_params_parse_text(&q, text);
+  return nq_create(q, text);
+}
+extern "C" msom_t *msom_create_newqg(const char *path) {
+  const char *pp = path ? path : "params.in";
+  FILE *fp = fopen(pp, "rt");
+  if (!fp) {
+    msom_set_error("file %s not found", pp);   // reference: message + exit(0), newqg/extra.h:63-66
+    return nullptr;
+  }
+  std::string text;   // kept as the handle's copy of the file; the parameters come from the file parser, as the reference reads them
+  char buf[4096];
+  size_t n;
+  while ((n = fread(buf, 1, sizeof buf, fp)) > 0) text.append(buf, n);
+  fclose(fp);
+  NewqgParams q;
+  msom_newqg_params_defaults(&q);
+  if (msom_newqg_params_parse_file(&q, pp)) return nullptr;
+  return nq_create(q, text.c_str());
+}
+
+static int nq_set_option(msom *m, const char *key, double v) {
+  if (!strcmp(key, "TOLERANCE")) m->p.tolerance = v;
+  else if (!strcmp(key, "NITERMAX")) m->p.nitermax = (int)v;
+  else if (!strcmp(key, "NITERMIN")) m->p.nitermin = (int)v;
+  else if (!strcmp(key, "DT")) m->p.DT = v;
+  else if (!strcmp(key, "quiet")) m->quiet = (int)v;
+  else if (!strcmp(key, "profile")) m->profile = (int)v;
+  else if (!strcmp(key, "nq_fused")) m->nq_fused = (int)v != 0;
+  else if (!strcmp(key, "nq_adv_fused")) m->nq_adv_fused = (int)v != 0;
+  else if (!strcmp(key, "nq_rows")) {
+    if (!(v >= 0) || v > 4096) { msom_set_error("option nq_rows = %g", v); return MSOM_ERR_ARG; }
+    m->nq_rows = (int)v;
+  } else {
+    msom_set_error("unknown option %s (newqg handle)", key);
+    return MSOM_ERR_ARG;
+  }
+  return MSOM_OK;
+}
+static double nq_get_param(msom *m, const char *key) {
+  const NewqgParams &q = m->nq;
+  if (!strcmp(key, "N") || !strcmp(key, "nx")) return m->gnx;
+  if (!strcmp(key, "ny")) return m->gny;
+  if (!strcmp(key, "nl")) return 1;
+  if (!strcmp(key, "L0")) return q.L0;
+  if (!strcmp(key, "DT")) return m->p.DT;
+  if (!strcmp(key, "CFL")) return q.CFL;
+  if (!strcmp(key, "TOLERANCE")) return m->p.tolerance;
+  if (!strcmp(key, "tend")) return q.tend;
+  if (!strcmp(key, "dtout")) return q.dtout;
+  if (!strcmp(key, "f0")) return q.f0;
+  if (!strcmp(key, "beta")) return q.beta;
+  if (!strcmp(key, "nu")) return q.nu;
+  if (!strcmp(key, "hEkb")) return q.hEkb;
+  if (!strcmp(key, "tau0")) return q.tau0;
+  if (!strcmp(key, "gp_low")) return q.gp_low;
+  if (!strcmp(key, "sbc")) return q.sbc;
+  if (!strcmp(key, "bc_fac")) return q.bc_fac;
+  if (!strcmp(key, "iRd2_low")) return q.iRd2_low;
+  if (!strcmp(key, "dh_0")) return q.dh[0];
+  if (!strcmp(key, "nlevels")) return m->nlev;
+  if (!strcmp(key, "nq_fused")) return m->nq_fused;
+  if (!strcmp(key, "nq_adv_fused")) return m->nq_adv_fused;
+  if (!strcmp(key, "nq_rows")) return nq_rhs_rows(m->g, m->nq_rows);   // the chunk height a launch of k_nq_rhs takes
+  return NAN;
+}
+
+// boundary() of the three kinds of field.  psi: dirichlet(0), corners by the y rule over the x-ghost column (newqg/qg.h:304-307);
+// periodic: wrapped copies, two cells deep because k_nq_rhs forms zeta at the ghost positions from them
+static void nq_fill_psi(msom *m) {
+  if (m->walls & WALL_PER) launch_fill_periodic(m->st, m->f[MSOM_PSI], m->g, 1, 2);
+  else launch_fill_ghost(m->st, m->f[MSOM_PSI], m->g, 1, BC_DIRICHLET0, m->walls);
+}
+// zeta and q: bc_fac * (psi[interior] - psi[ghost]) (:310-318), or wrapped
+static void nq_fill_zq(msom *m, int field) {
+  if (m->walls & WALL_PER) launch_fill_periodic(m->st, m->f[field], m->g, 1, 1);
+  else launch_nq_ghost(m->st, m->f[MSOM_PSI], m->f[field], m->g, m->nq.bc_fac);
+}
+// msom_set_field: upload() applied the generic ghost fill; the fields with a rule of their own take it here
+static int nq_after_upload(msom *m, int field) {
+  if (field == MSOM_PSI) nq_fill_psi(m);
+  else if (field == MSOM_Q || field == MSOM_ZETA) nq_fill_zq(m, field);
+  return MSOM_OK;
+}
+
+// comp_q, newqg/qg.h:184-189: q = lap(psi); gp_low != 0: q = q + iRd2_low * psi; boundary(q)
+static void nq_comp_q(msom *m) {
+  launch_del2(m->st, m->f[MSOM_PSI], m->f[MSOM_Q], m->g, 1, 0., 1., m->p.L0 / m->gnx);
+  if (m->nq.gp_low != 0.) launch_axpy(m->st, m->f[MSOM_Q], m->f[MSOM_PSI], m->g, 1, m->nq.iRd2_low);
+  nq_fill_zq(m, MSOM_Q);
+}
+// set_const, newqg/qg.h:345-358 (event init): the start of a run -- time, iteration count and the limiter's static `previous` (:203)
+// are what they are when the reference's process starts
+static int nq_set_const(msom *m) {
+  nq_fill_psi(m);
+  nq_comp_q(m);
+  m->const_set = 1;
+  m->previous = 0.;
+  m->t = 0.;
+  m->iter = 0;
+  return sync_stream(m);
+}
+#define NQ_NEED_CONST(m, fn)                                          \
+  do {                                                                \
+    if (!(m)->const_set) {                                            \
+      msom_set_error("%s: msom_set_const has not been called", fn);   \
+      return MSOM_ERR_STATE;                                          \
+    }                                                                 \
+  } while (0)
+
+// invertq, newqg/qg.h:148-157: psi is warm start and result; boundary(psi) after the last correction
+static int nq_solve(msom *m, const double *q) {
+  int r = helm_run(m, m->f[MSOM_PSI], q);
+  if (r) return r;
+  nq_fill_psi(m);
+  return m->sticky;
+}
+// the solve and the dt limiter of advection_pv (:202-219): one pass over the faces with one static `previous`.  D / max|u| is the
+// minimum over the faces of D / |u| exactly (division is monotone), so the maximum comes from launch_umax as on the modal path
+static double nq_solve_dt(msom *m, int qfield, double dtmax) {
+  if (nq_solve(m, m->f[qfield])) return -1;
+  launch_umax(m->st, m->f[MSOM_PSI], m->partial_umax, m->d_scal + SC_UMAX, m->g, 1, m->p.L0 / m->gnx);
+  if (reduce_scal(m, SC_UMAX, 1, RED_MAX)) return -1;
+  if (m->sticky) return -1;
+  return limiter(m, m->h_scal[SC_UMAX], dtmax);
+}
+// the tendency after the inversion (:276-281) into MSOM_ZETA and MSOM_DQ; adv_out >= 0 asks for q[adv_out] = q[adv_in] + dt * dq as
+// well (advance_qg), folded into the pass where the options allow (dq is then not stored)
+static int nq_rhs(msom *m, int adv_out, int adv_in, double dt) {
+  const NewqgParams &q = m->nq;
+  const double D = m->p.L0 / m->gnx, cek = q.hEkb * q.f0 / (2 * q.dh[0]);
+  const double *qforc = m->have_qforc ? m->f[MSOM_QFORC] : nullptr;
+  if (m->profile) prof_begin(m, m->prof_rhs);
+  if (m->nq_fused) {
+    const bool adv = adv_out >= 0 && m->nq_adv_fused;
+    launch_nq_rhs(m->st, m->f[MSOM_PSI], qforc, m->f[MSOM_ZETA], m->f[MSOM_DQ], m->g, m->walls, D, q.beta, q.nu, cek, q.bc_fac,
+                  adv ? m->f[adv_in] : nullptr, adv ? m->f[adv_out] : nullptr, dt, m->nq_rows);
+    if (adv) adv_out = -1;
+  } else {   // one launch per loop of the reference
+    launch_del2(m->st, m->f[MSOM_PSI], m->f[MSOM_ZETA], m->g, 1, 0., 1., D);                 // comp_del2(psi, zeta, 0., 1.)
+    nq_fill_zq(m, MSOM_ZETA);
+    launch_nq_adv(m->st, m->f[MSOM_PSI], m->f[MSOM_ZETA], m->f[MSOM_DQ], m->g, D, q.beta);   // advection_pv on the zeroed updates
+    launch_del2(m->st, m->f[MSOM_ZETA], m->f[MSOM_DQ], m->g, 1, 1., q.nu, D);                // dissip: comp_del2(zeta, dqdt, 1., nu)
+    launch_axpy(m->st, m->f[MSOM_DQ], m->f[MSOM_ZETA], m->g, 1, -cek);                       // ekman_friction
+    if (qforc) launch_axpy(m->st, m->f[MSOM_DQ], qforc, m->g, 1, 1.);                        // surface_forcing: the handle's MSOM_QFORC
+  }
+  if (adv_out >= 0) launch_advance(m->st, m->f[adv_out], m->f[adv_in], m->f[MSOM_DQ], nullptr, m->g, 1, dt, 0.);
+  if (m->profile) prof_end(m, m->prof_rhs);
+  return MSOM_OK;
+}
+
+static double nq_update(msom *m, const double *q, double *dqdt, double dtmax) {
+  NQ_NEED_CONST(m, "msom_update");
+  int qf = MSOM_Q;
+  if (q) {
+    if (upload(m, MSOM_QPRED, q)) return -1;
+    qf = MSOM_QPRED;
+  }
+  const double d = nq_solve_dt(m, qf, dtmax);
+  if (d < 0) return d;
+  if (nq_rhs(m, -1, -1, 0.)) return -1;
+  if (dqdt && download(m, MSOM_DQ, dqdt)) return -1;
+  if (sync_stream(m)) return -1;
+  return d;
+}
+static int nq_advance(msom *m, double *qout, const double *qin, const double *dqdt, double dt) {
+  NQ_NEED_CONST(m, "msom_advance");
+  int f = MSOM_Q, r;
+  if (qin) {
+    if ((r = upload(m, MSOM_QPRED, qin))) return r;
+    f = MSOM_QPRED;
+  }
+  if (dqdt && (r = upload(m, MSOM_DQ, dqdt))) return r;
+  launch_advance(m->st, m->f[f], m->f[f], m->f[MSOM_DQ], nullptr, m->g, 1, dt, 0.);
+  if (qout) return download(m, f, qout);
+  return sync_stream(m);
+}
+static int nq_invertq(msom *m, const double *q, double *psi, msom_mgstats *st) {
+  NQ_NEED_CONST(m, "msom_invertq");
+  int qf = MSOM_Q, r;
+  if (q) {
+    if ((r = upload(m, MSOM_QPRED, q))) return r;
+    qf = MSOM_QPRED;
+  }
+  if (psi) {
+    if ((r = upload(m, MSOM_PSI, psi))) return r;
+    nq_fill_psi(m);
+  }
+  if ((r = nq_solve(m, m->f[qf]))) return r;
+  if (st) *st = m->mg;
+  if (psi) return download(m, MSOM_PSI, psi);
+  return sync_stream(m);
+}
+static int nq_comp_q_api(msom *m, const double *psi, double *q) {
+  NQ_NEED_CONST(m, "msom_comp_q");
+  int r;
+  if (psi) {
+    if ((r = upload(m, MSOM_PSI, psi))) return r;
+    nq_fill_psi(m);
+  }
+  nq_comp_q(m);
+  if (q) return download(m, MSOM_Q, q);
+  return sync_stream(m);
+}
+// one iteration of run() [Basilisk predictor-corrector.h] by the rules of msom_step; the limiter is applied once per update and its
+// `previous` moves in the second update as well (advection_pv has one static, :203,216-218).  Synchronous.
+static int nq_step(msom *m, double *dt_used) {
+  NQ_NEED_CONST(m, "msom_step");
+  double tnext;
+  int r;
+  const double d = nq_solve_dt(m, MSOM_Q, m->p.DT);
+  if (d < 0) return m->sticky ? m->sticky : MSOM_ERR_HIP;
+  m->dt = dtnext(m, d, &tnext);
+  if ((r = nq_rhs(m, MSOM_QPRED, MSOM_Q, m->dt / 2.))) return r;
+  const double d2 = nq_solve_dt(m, MSOM_QPRED, m->dt);
+  if (d2 < 0) return m->sticky ? m->sticky : MSOM_ERR_HIP;
+  if ((r = nq_rhs(m, MSOM_Q, MSOM_Q, m->dt))) return r;
+  if ((r = sync_stream(m))) return r;
+  m->t = tnext;
+  m->iter++;
+  if (dt_used) *dt_used = m->dt;
+  return MSOM_OK;
+}
+// back-to-back launches, HIP-event timed: "nq_rhs" (k_nq_rhs with the advance folded in, as a step's first stage runs it),
+// "nq_rhs_dq" (tendency only), "helm_sweep" / "helm_residual" (finest level of the solve)
+static int nq_bench_kernel(msom *m, const char *kernel, int reps, double *avg_ms) {
+  NQ_NEED_CONST(m, "msom_bench_kernel");
+  if (!kernel || reps < 1 || !avg_ms) return MSOM_ERR_ARG;
+  const int which = !strcmp(kernel, "nq_rhs") ? 0 : !strcmp(kernel, "nq_rhs_dq") ? 1 : !strcmp(kernel, "helm_sweep") ? 2 : !strcmp(kernel, "helm_residual") ? 3 : -1;
+  if (which < 0) { msom_set_error("unknown kernel %s (newqg handle)", kernel); return MSOM_ERR_ARG; }
+  const NewqgParams &q = m->nq;
+  const double D = m->p.L0 / m->gnx, cek = q.hEkb * q.f0 / (2 * q.dh[0]);
+  const double *qforc = m->have_qforc ? m->f[MSOM_QFORC] : nullptr;
+  HelmCount all = {};
+  all.n[0] = 1;
+  hipEvent_t a = nullptr, b = nullptr;
+  struct Events {   // destroyed on every way out
+    hipEvent_t &a, &b;
+    ~Events() { if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); }
+  } events{a, b};
+  HIPCHK(hipEventCreate(&a));
+  HIPCHK(hipEventCreate(&b));
+  auto one = [&](void) {
+    if (which == 0)
+      launch_nq_rhs(m->st, m->f[MSOM_PSI], qforc, m->f[MSOM_ZETA], m->f[MSOM_DQ], m->g, m->walls, D, q.beta, q.nu, cek, q.bc_fac, m->f[MSOM_Q],
+                    m->f[MSOM_QPRED], 1e-9, m->nq_rows);
+    else if (which == 1)
+      launch_nq_rhs(m->st, m->f[MSOM_PSI], qforc, m->f[MSOM_ZETA], m->f[MSOM_DQ], m->g, m->walls, D, q.beta, q.nu, cek, q.bc_fac, nullptr, nullptr,
+                    0., m->nq_rows);
+    else if (which == 2) helm_relax_level(m, 0, 2, all, nullptr);
+    else helm_residual(m, m->f[MSOM_PSI], m->f[MSOM_Q], HS_RES1, 0);
+  };
+  for (int k = 0; k < 3; k++) one();
+  HIPCHK(hipEventRecord(a, m->st));
+  for (int k = 0; k < reps; k++) one();
+  HIPCHK(hipEventRecord(b, m->st));
+  HIPCHK(hipEventSynchronize(b));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, a, b));
+  *avg_ms = ms / reps;
+  return MSOM_OK;
 }
 
 // ------------------------------------------------------------------ wavelet scale filter (msqg/qg.h:509-560)
@@ -3066,7 +3440,10 @@ static int wavelet_filter(msom *m, int qof_field, double dtflt) {
   fill_bc(m, qof_field);
   return sync_stream(m);
 }
-extern "C" int msom_wavelet_filter(msom_t *m, double dtflt) { return wavelet_filter(m, MSOM_QOF, dtflt); }
+extern "C" int msom_wavelet_filter(msom_t *m, double dtflt) {
+  MSQG_ONLY(m);
+  return wavelet_filter(m, MSOM_QOF, dtflt);
+}
 
 // ------------------------------------------------------------------ energy / PV budgets (msqg/qg_energy.h)
 
@@ -3095,6 +3472,7 @@ static int de_terms(msom *m, double dt, double ediag) {
   return m->sticky;
 }
 extern "C" int msom_energy_tend(msom_t *m, double dt) {
+  MSQG_ONLY(m);
   NEED_CONST(m);
   int r;
   if ((r = ensure_de_fields(m))) return r;
@@ -3113,12 +3491,14 @@ static int filter_de(msom *m, int pm_field, double dtflt, double ediag) {
   return sync_stream(m);
 }
 extern "C" int msom_filter_de(msom_t *m, int pm_field, double dtflt) {
+  MSQG_ONLY(m);
   NEED_CONST(m);
   if (pm_field < 0 || pm_field >= MSOM_NFIELDS || m->flayers[pm_field] != m->nl) { msom_set_error("bad field id %d", pm_field); return MSOM_ERR_ARG; }
   int r = ensure_field(m, pm_field);
   return r ? r : filter_de(m, pm_field, dtflt, (double)m->p.ediag);
 }
 extern "C" int msom_reset_de(msom_t *m) {
+  MSQG_ONLY(m);
   if (!m) return MSOM_ERR_ARG;
   int r;
   if ((r = ensure_de_fields(m))) return r;
@@ -3132,6 +3512,7 @@ extern "C" int pystep_de(msom_t *m, const double *po_py, int len1, int len2, int
                          double *de_vd_py, int len7, int len8, int len9, double *de_j1_py, int len10, int len11, int len12,
                          double *de_j2_py, int len13, int len14, int len15, double *de_j3_py, int len16, int len17, int len18,
                          double *de_ft_py, int len19, int len20, int len21, int onlyKE) {
+  MSQG_ONLY(m);
   NEED_CONST(m);
   if (check_shape(m, len1, len2, len3) || check_shape(m, len4, len5, len6) || check_shape(m, len7, len8, len9) || check_shape(m, len10, len11, len12) ||
       check_shape(m, len13, len14, len15) || check_shape(m, len16, len17, len18) || check_shape(m, len19, len20, len21))
@@ -3156,11 +3537,13 @@ extern "C" int pystep_de(msom_t *m, const double *po_py, int len1, int len2, int
 }
 
 extern "C" int msom_dbg_wavelet_levels(msom_t *m) {
+  MSQG_ONLY(m);
   if (!m) return MSOM_ERR_ARG;
   int r = wavelet_setup(m);
   return r ? r : m->wv_nlev;
 }
 extern "C" int msom_dbg_siglev(msom_t *m, int level, double *out) {
+  MSQG_ONLY(m);
   if (!m || !out) return MSOM_ERR_ARG;
   int r = wavelet_setup(m);
   if (r) return r;
@@ -3171,6 +3554,7 @@ extern "C" int msom_dbg_siglev(msom_t *m, int level, double *out) {
   return sync_stream(m);
 }
 extern "C" int msom_dbg_wavelet_apply(msom_t *m, int field) {
+  MSQG_ONLY(m);
   NEED_CONST(m);
   if (field < 0 || field >= MSOM_NFIELDS || !m->f[field] || m->flayers[field] != m->nl) { msom_set_error("bad field id %d", field); return MSOM_ERR_ARG; }
   int r = wavelet_apply(m, m->f[field]);
@@ -3221,6 +3605,7 @@ static int scatter_global(msom *m, int field, const std::vector<double> &g) {
 // .bas / NetCDF IO.  Tiled runs: the calls are collective; rank 0 writes the global field, every rank reads the (shared)
 // file and keeps its tile -- what output_matrix_mpi / input_matrixl do in the reference's MPI build (msqg/auxiliar_input.h)
 extern "C" int msom_write_bas(msom_t *m, int field, const char *path) {
+  MSQG_ONLY(m);
   if (check_field(m, field) || !path) return MSOM_ERR_ARG;
   if (m->gnx != m->gny) { msom_set_error(".bas output needs a square grid"); return MSOM_ERR_STATE; }
   std::vector<double> h;
@@ -3230,6 +3615,7 @@ extern "C" int msom_write_bas(msom_t *m, int field, const char *path) {
   return msom_bas_write(path, h.data(), m->flayers[field], m->gnx, m->p.L0) ? MSOM_ERR_IO : MSOM_OK;
 }
 extern "C" int msom_read_bas(msom_t *m, int field, const char *path) {
+  MSQG_ONLY(m);
   if (check_field(m, field) || !path) return MSOM_ERR_ARG;
   if (m->gnx != m->gny) { msom_set_error(".bas input needs a square grid"); return MSOM_ERR_STATE; }
   std::vector<double> h((size_t)m->flayers[field] * m->gnx * m->gny);
@@ -3264,6 +3650,7 @@ static bool file_exists(const char *path) {
 
 // optional input files, msqg/qg.h:940-984 and msqg/qg.c:55-59 (p0.bas)
 extern "C" int msom_read_inputs(msom_t *m, const char *dir) {
+  MSQG_ONLY(m);
   if (!m) return MSOM_ERR_ARG;
   char name[512];
   const char *d = dir ? dir : ".";
@@ -3367,6 +3754,7 @@ static int backup_config(msom *m, const char *dpath) {
 // main loop of msqg/qg.c:34-173: events at the top of every iteration (writestdout i++,
 // output t += dtout), then one predictor-corrector step.
 extern "C" int msom_run(msom_t *m, const char *workdir, long nsteps_max) {
+  MSQG_ONLY(m);
   NEED_CONST(m);
   const Params &p = m->p;
   // tiled runs (one process / thread per tile): every call below that moves field data is collective; rank 0 alone
@@ -3483,6 +3871,7 @@ extern "C" msom_t *msom_create_tiled(const char *params_text, int px, int py, in
   return m;
 }
 extern "C" int msom_tile_info(msom_t *m, int *px, int *py, int *ix, int *iy, int *nx_local, int *ny_local) {
+  MSQG_ONLY(m);
   if (!m) return MSOM_ERR_ARG;
   if (px) *px = m->px;
   if (py) *py = m->py;
@@ -3514,6 +3903,7 @@ static int split_download(msom *m, const double *sp, const SplitGeom &sg, double
 }
 // nsweeps red-black relaxations on level `lev`: da in/out, res in (both [layer][y][x] of that level)
 extern "C" int msom_dbg_relax(msom_t *m, int lev, double *da, const double *res, int nsweeps) {
+  MSQG_ONLY(m);
   if (m) m->res_ready = -1;
   NEED_CONST(m);
   if (lev < 0 || lev >= m->nlev || !da || !res) return MSOM_ERR_ARG;
@@ -3531,6 +3921,7 @@ extern "C" int msom_dbg_relax(msom_t *m, int lev, double *da, const double *res,
   return split_download(m, m->da[lev], m->sg[lev], da, m->nl);
 }
 extern "C" int msom_dbg_residual(msom_t *m, const double *a, const double *b, double *res, double *maxres) {
+  MSQG_ONLY(m);
   if (m) m->res_ready = -1;
   NEED_CONST(m);
   int r;
@@ -3544,6 +3935,7 @@ extern "C" int msom_dbg_residual(msom_t *m, const double *a, const double *b, do
   return MSOM_OK;
 }
 extern "C" int msom_dbg_helm_relax(msom_t *m, int lev, double *da, const double *res, int nhalf, const int *count_per_mode) {
+  MSQG_ONLY(m);
   if (m) m->res_ready = -1;
   NEED_CONST(m);
   if (lev < 0 || lev >= m->nlev || !da || !res || nhalf < 0) return MSOM_ERR_ARG;
@@ -3557,6 +3949,7 @@ extern "C" int msom_dbg_helm_relax(msom_t *m, int lev, double *da, const double 
   return split_download(m, m->da[lev], m->sg[lev], da, m->nl);
 }
 extern "C" int msom_dbg_helm_residual(msom_t *m, const double *a, const double *b, double *res, double *maxres_per_mode) {
+  MSQG_ONLY(m);
   if (m) m->res_ready = -1;
   NEED_CONST(m);
   if (!a || !b || !res) return MSOM_ERR_ARG;
@@ -3577,6 +3970,7 @@ extern "C" int msom_dbg_helm_residual(msom_t *m, const double *a, const double *
   return MSOM_OK;
 }
 extern "C" int msom_dbg_restrict(msom_t *m, int lev_fine, const double *fine, double *coarse) {
+  MSQG_ONLY(m);
   if (m) m->res_ready = -1;
   NEED_CONST(m);
   if (lev_fine < 0 || lev_fine + 1 >= m->nlev) return MSOM_ERR_ARG;
@@ -3586,6 +3980,7 @@ extern "C" int msom_dbg_restrict(msom_t *m, int lev_fine, const double *fine, do
   return split_download(m, m->res[lev_fine + 1], m->sg[lev_fine + 1], coarse, m->nl);
 }
 extern "C" int msom_dbg_prolong(msom_t *m, int lev_coarse, const double *coarse, double *fine) {
+  MSQG_ONLY(m);
   if (m) m->res_ready = -1;
   NEED_CONST(m);
   if (lev_coarse < 1 || lev_coarse >= m->nlev) return MSOM_ERR_ARG;
@@ -3597,6 +3992,7 @@ extern "C" int msom_dbg_prolong(msom_t *m, int lev_coarse, const double *coarse,
 }
 // single operators on the internal fields: "del2", "stretch", "advection", "dissip", "forcing"
 extern "C" int msom_dbg_op(msom_t *m, const char *op, int f_in, int f_out, double add, double fac) {
+  MSQG_ONLY(m);
   if (m) m->res_ready = -1;
   NEED_CONST(m);
   if (check_field(m, f_in) || check_field(m, f_out) || !op) return MSOM_ERR_ARG;
@@ -3636,6 +4032,7 @@ extern "C" int msom_profile_read(msom_t *m, const char *kernel, double *avg_ms, 
 }
 // back-to-back launches of one kernel on the finest level, HIP-event timed
 extern "C" int msom_bench_kernel(msom_t *m, const char *kernel, int reps, double *avg_ms) {
+  if (m && m->model) return nq_bench_kernel(m, kernel, reps, avg_ms);
   if (m) m->res_ready = -1;
   NEED_CONST(m);
   if (!kernel || reps < 1 || !avg_ms) return MSOM_ERR_ARG;

@@ -53,6 +53,22 @@ struct NodeParams {
 void msom_node_params_defaults(struct NodeParams *p);
 int msom_node_params_parse_text(struct NodeParams *p, const char *text);
 int msom_node_params_parse_file(struct NodeParams *p, const char *path);
+
+/* parameters of the cell-centred one-layer model with the optional Helmholtz ("1.5-layer") inversion: key list newqg/extra.h:42-58,
+ * defaults newqg/qg.h:85-94 and the Basilisk globals; Ny, NITERMAX, NITERMIN are extension keys with the meaning they have in
+ * struct Params.  bc_fac and iRd2_low are derived (newqg/qg.h:295,348-354). */
+struct NewqgParams {
+  int N, Ny, nl, nitermax, nitermin;
+  double L0, DT, CFL, TOLERANCE, f0, beta, hEkb, tau0, nu, gp_low, sbc, tend, dtout;
+  double dh[MSOM_MAXARR];
+  double bc_fac, iRd2_low;
+};
+/* params.c: restates read_params of newqg/extra.h:32-75.  msom_create_newqg_str goes through _parse_text, msom_create_newqg through
+ * _parse_file.  _derive returns 0 or MSOM_ERR_CONFIG (message in msom_last_error) */
+void msom_newqg_params_defaults(struct NewqgParams *p);
+int msom_newqg_params_parse_text(struct NewqgParams *p, const char *text);
+int msom_newqg_params_parse_file(struct NewqgParams *p, const char *path);
+int msom_newqg_params_derive(struct NewqgParams *p);
 #ifdef __cplusplus
 }
 #endif

@@ -171,3 +171,68 @@ int msom_node_params_parse_file(struct NodeParams *p, const char *path) {
   fclose(fp);
   return 0;
 }
+
+/* ---- cell-centred one-layer model: parameter list and parser of newqg/extra.h:32-75 (same line rules as above) */
+#define KQ(name, type, member) { name, type, offsetof(struct NewqgParams, member) }
+static const keydef NEWQG_KEYS[] = {
+  KQ("N", T_INT, N), KQ("nl", T_INT, nl), KQ("L0", T_DBL, L0), KQ("DT", T_DBL, DT), KQ("CFL", T_DBL, CFL), KQ("TOLERANCE", T_DBL, TOLERANCE),
+  KQ("f0", T_DBL, f0), KQ("beta", T_DBL, beta), KQ("hEkb", T_DBL, hEkb), KQ("tau0", T_DBL, tau0), KQ("nu", T_DBL, nu), KQ("gp_low", T_DBL, gp_low),
+  KQ("sbc", T_DBL, sbc), KQ("tend", T_DBL, tend), KQ("dtout", T_DBL, dtout), KQ("dh", T_ARR, dh),
+  /* extension keys, unknown to (hence ignored by) the reference parser */
+  KQ("Ny", T_INT, Ny), KQ("NITERMAX", T_INT, nitermax), KQ("NITERMIN", T_INT, nitermin),
+};
+/* defaults: newqg/qg.h:85-94; Basilisk globals N = 64, nl = 1, L0 = 1, DT = 1e10, CFL = 0.5, TOLERANCE = 1e-3 */
+void msom_newqg_params_defaults(struct NewqgParams *p) {
+  memset(p, 0, sizeof *p);
+  p->N = 64; p->nl = 1; p->L0 = 1.; p->DT = 1e10; p->CFL = 0.5; p->TOLERANCE = 1e-3;
+  p->f0 = 1.; p->tend = 1.; p->dtout = 1.; p->dh[0] = 1.;
+  p->nitermax = 100; p->nitermin = 1;
+}
+int msom_newqg_params_parse_text(struct NewqgParams *p, const char *text) {
+  const char *s = text;
+  while (*s) {
+    const char *e = strchr(s, '\n');
+    size_t len = e ? (size_t)(e - s) : strlen(s);
+    char line[300];
+    if (len > sizeof line - 1) len = sizeof line - 1;
+    memcpy(line, s, len);
+    line[len] = '\0';
+    parse_line_tab(p, NEWQG_KEYS, sizeof NEWQG_KEYS / sizeof NEWQG_KEYS[0], line);
+    if (!e) break;
+    s = e + 1;
+  }
+  return 0;
+}
+int msom_newqg_params_parse_file(struct NewqgParams *p, const char *path) {
+  FILE *fp = fopen(path, "rt");
+  if (!fp) { msom_set_error("file %s not found", path); return -2; } /* reference: message + exit(0), extra.h:63-66 */
+  char line[300];
+  while (fgets(line, sizeof line, fp)) parse_line_tab(p, NEWQG_KEYS, sizeof NEWQG_KEYS / sizeof NEWQG_KEYS[0], line);
+  fclose(fp);
+  return 0;
+}
+/* derived values: DT newqg/extra.h:71, bc_fac newqg/qg.h:295, iRd2_low :348-354 (a uniform field there, one number here) */
+int msom_newqg_params_derive(struct NewqgParams *p) {
+  if (p->Ny <= 0) p->Ny = p->N;
+  if (p->nl != 1) {   /* "to be updated for multi layer", newqg/qg.h:347 */
+    msom_set_error("newqg: nl = %d, the model has one layer", p->nl);
+    return MSOM_ERR_CONFIG;
+  }
+  if (p->N < 2 || (p->N & (p->N - 1)) || p->Ny < 2 || (p->Ny & (p->Ny - 1))) {
+    msom_set_error("newqg: grid %d x %d: N and Ny must be powers of two >= 2", p->N, p->Ny);
+    return MSOM_ERR_CONFIG;
+  }
+  if (p->dh[0] == 0.) {
+    msom_set_error("newqg: dh[0] == 0");
+    return MSOM_ERR_CONFIG;
+  }
+  if (p->sbc < 0 && p->sbc != -1) {   /* the reference installs its wall conditions for sbc >= 0 only (newqg/qg.h:303), -1 is periodic */
+    msom_set_error("newqg: sbc = %g: -1 (periodic) or >= 0 (walls)", p->sbc);
+    return MSOM_ERR_CONFIG;
+  }
+  const double D = p->L0 / p->N, D2 = D * D;
+  if (p->nu != 0) p->DT = 0.5 * fmin(p->DT, D2 / p->nu / 4.);
+  p->bc_fac = p->sbc / ((0.5 * p->sbc + 1) * D2);
+  p->iRd2_low = p->gp_low != 0. ? -(p->f0 * p->f0) / (p->gp_low * p->dh[0]) : 0.;
+  return 0;
+}
