@@ -299,6 +299,55 @@ int msom_modes_set_rd(msom_t *m, int mode);                        /* MSOM_RD = 
  *   that only decomposes does not hold it; "modes_bytes" does not count it: 4/3 * 8 nl ny nx more) and dropped with the modes. */
 int msom_modes_mgstats(msom_t *m, int mode, msom_mgstats *st);
 
+/* ---- isotropic wavenumber spectra and spectral fluxes on the device: get_spec_2D, radial_average / get_spec_1D and get_flux of
+ * msqg/scripts/fftlib.py, as msqg/scripts/spectra.py:113-142 (KE / PE spectra) and energy_offline.py:119-124 (fluxes of the budget terms)
+ * use them on .bas files.  The contract is fftlib.py in exact arithmetic, restated with integers so that it does not depend on how fftfreq
+ * rounds.  D = Delta, nmax = max(nx, ny), sx = nmax / nx, sy = nmax / ny; signed wavenumber indices i = -nx/2 .. nx/2 - 1,
+ * j = -ny/2 .. ny/2 - 1; R2(i, j) = (i sx)^2 + (j sy)^2.
+ *   spec_2D(i, j) = Re(A(i, j) conj B(i, j)) D^4 with A = fft2(a), unnormalised (fftlib.py:44-47)
+ *   nbins = nmax / 2 - 2, dk = 1 / (nmax D), kr[r] = (r + 1) dk, r = 0 .. nbins - 1 (:20-33)
+ *   bin r holds the points with r^2 <= R2 <= (r + 1)^2, both ends inclusive as :13 (a point on a circle of integer radius counts in two
+ *     bins); count[r] is their number
+ *   spec[l][r] = 2 pi kr[r] (sum over bin r of spec_2D) / count[r]                                  (:15-16)
+ *   flux[l][r] = (sum over (r + 1)^2 <= R2 of spec_2D) dkx dky, dkx = 1 / (nx D), dky = 1 / (ny D)    (:71-74; dk^2 on the square)
+ *   On the square this is the reference; the rule for nx != ny is this library's extension, like the key Ny.  With L0 = 1 the reference's
+ *   floating-point membership test agrees with the integer rule in every cell for N = 8 .. 256; with other L0 the reference itself moves
+ *   points across bin edges by rounding.
+ * Arrays: a, b [layers][ny][nx] fp64, host or device pointers, a == b allowed; out [layers][ny][nx], host or device; spec, flux, ke, pe, kr
+ *   host pointers; either of spec / flux and either of ke / pe may be NULL.
+ * msom_spec_layout: host code only, no handle and no GPU: nbins and (count != NULL) count[nbins].  A side that is no power of two, below 8
+ *   or above 32768: MSOM_ERR_CONFIG.
+ * msom_spec_bins: nbins of the handle's grid.  msom_spec_kr: kr[nbins].
+ * msom_spec_2d: spec_2D, fftshift-ed: index 0 is the most negative wavenumber on both axes.  The one call that stores the plane.
+ * msom_spec_cross: spec and / or flux, [layers][nbins].
+ * msom_spec_fields: msom_spec_cross on two of the handle's fields, which must have the same layer count; MSOM_PSI with MSOM_DE_* gives the
+ *   budget fluxes of energy_offline.py (the sign of -p is the caller's: the result is linear in each argument).  Nothing leaves the device
+ *   but [layers][nbins] numbers.
+ * msom_spec_energy: from the handle's MSOM_PSI with the ghost values boundary() left there, u, v as the msom_stats_* block defines them,
+ *   dhc_l = 0.5 (dh_l + dh_l+1):  ke[l][r] = 0.5 (spec(u_l, u_l) + spec(v_l, v_l))[r] dh_l, [nl][nbins];
+ *   pe[l][r] = 0.5 spec(g_l, g_l)[r] dhc_l with g_l = sqrt(S_l) (psi_l+1 - psi_l) / dhc_l and S = MSOM_S, [nl - 1][nbins] (spectra.py:113-139;
+ *   b Fr there is g because S = (Fr / Ro)^2).  nl = 1: pe is not touched.
+ * Arithmetic: a pair of real fields goes through one complex transform (Z = fft2(a + i b): Re(A conj B)(k) = Im(Z(k) Z(-k)) / 2 and
+ *   |A|^2 + |B|^2 = (|Z(k)|^2 + |Z(-k)|^2) / 2; a == b and the auto-spectra take a + 0 i).  Twiddle factors come from a table computed on
+ *   the host in long double and rounded once.  The transform's own arithmetic is free in both builds (the results are not bit-comparable
+ *   with another FFT); bin and flux sums are two-stage sums in a fixed order, no atomics: two calls on the same data return the same bits.
+ * Scope: an msqg operator on one tile: a handle of msom_create_tiled with more than one rank answers MSOM_ERR_CONFIG.  Sides: powers of
+ *   two, 8 .. 4096 in any combination (a line of the transform lives in LDS); anything else MSOM_ERR_CONFIG.
+ * Errors: null handle, null a / b / out / kr, layers < 1, both results NULL, an unknown field id or two fields of different layer counts:
+ *   MSOM_ERR_ARG; before msom_set_const: MSOM_ERR_STATE.
+ * Memory: the work arrays (two complex copies of a batch of layers, spec_2D of the half plane, the sums; a batch is as many layers as fit
+ *   1 GiB, at least one) are allocated by the first call, dropped by msom_set_const and freed by msom_destroy; msom_get_param "spec_bytes"
+ *   reports them (0 on a handle that has not called a spectrum function since msom_set_const), "spec_batch" the layers of a batch.
+ *   Every call synchronises the stream and changes nothing in psi, q, dt, mgstats or any field.
+ * msom_bench_kernel names "spec_rows", "spec_transpose", "spec_cols", "spec_shells": the passes on one batch of layers of u + i v. */
+int msom_spec_layout(int nx, int ny, int *nbins, long *count);   /* host only: no handle, no GPU */
+int msom_spec_bins(msom_t *m);                                    /* nbins, or an error code < 0 */
+int msom_spec_kr(msom_t *m, double *kr);                          /* [nbins] host */
+int msom_spec_2d(msom_t *m, const double *a, const double *b, int layers, double *out);
+int msom_spec_cross(msom_t *m, const double *a, const double *b, int layers, double *spec, double *flux);
+int msom_spec_fields(msom_t *m, int field_a, int field_b, double *spec, double *flux);
+int msom_spec_energy(msom_t *m, double *ke, double *pe);
+
 /* ---- time loop of Basilisk predictor-corrector run() as driven by msqg/qg.c
  * msom_step: one RK2 step on the internal state (update, dtnext, advance dt/2, update,
  * advance dt).  msom_set_tnext gives the time of the next t-scheduled event (output). */
@@ -398,7 +447,7 @@ int msom_dbg_wavelet_apply(msom_t *m, int field);
  *   chain; same bits in the strict build), nq_adv_fused [1] (the advance folded into the tendency pass, dq then not stored by
  *   msom_step), nq_rows [0 = automatic] chunk height of the fused kernel.  Any other key: MSOM_ERR_ARG.
  * Every other entry point of this header that takes a msom_t * (msom_run, pystep_*, pyq2p / pyp2q, msom_bfn_*, msom_stats_*,
- *   msom_time_filter, msom_modes_*, msom_wavelet_filter, the energy budgets, .bas IO, msom_read_inputs, msom_remove_mean, msom_tile_info,
+ *   msom_time_filter, msom_modes_*, msom_spec_* with a handle, msom_wavelet_filter, the energy budgets, .bas IO, msom_read_inputs, msom_remove_mean, msom_tile_info,
  *   msom_dbg_relax / _residual / _helm_* / _restrict / _prolong / _op / _wavelet_* / _siglev) is an msqg operator and answers such a handle
  *   with MSOM_ERR_CONFIG, a message naming the call, and no change to its fields.  msom_create_tiled has no newqg form.
  * Expression order of the tendency (the contract of the strict build: true divisions, no contraction; it is how the C of

@@ -29,11 +29,12 @@ from .api import (  # noqa: F401
     set_const,
     set_vars,
     set_vars_bfn,
+    spec_layout,
     trash_vars,
     trash_vars_bfn,
 )
 
 __all__ = [
     "QG", "NodeQG", "NewQG", "NODE_FIELDS", "MGStats", "MsomError", "FIELDS", "STATS", "MODES", "load_library", "read_params", "init_grid", "set_vars",
-    "set_vars_bfn", "set_const", "pystep_bfn", "bfn_begin", "bfn_steps", "bfn_misfit", "pystep_de", "pyq2p", "pyp2q", "trash_vars", "trash_vars_bfn",
+    "set_vars_bfn", "set_const", "pystep_bfn", "bfn_begin", "bfn_steps", "bfn_misfit", "pystep_de", "pyq2p", "pyp2q", "trash_vars", "trash_vars_bfn", "spec_layout",
 ]

@@ -87,6 +87,13 @@ def load_library(strict=False):
         "msom_modes_energy": (ci, [vp, _dp, _dp]),
         "msom_modes_set_rd": (ci, [vp, ci]),
         "msom_modes_mgstats": (ci, [vp, ci, C.POINTER(MGStats)]),
+        "msom_spec_layout": (ci, [ci, ci, C.POINTER(ci), C.POINTER(C.c_long)]),
+        "msom_spec_bins": (ci, [vp]),
+        "msom_spec_kr": (ci, [vp, _dp]),
+        "msom_spec_2d": (ci, [vp, vp, vp, ci, vp]),
+        "msom_spec_cross": (ci, [vp, vp, vp, ci, _dp, _dp]),
+        "msom_spec_fields": (ci, [vp, ci, ci, _dp, _dp]),
+        "msom_spec_energy": (ci, [vp, _dp, _dp]),
         "msom_dbg_helm_relax": (ci, [vp, ci, vp, vp, ci, C.POINTER(ci)]),
         "msom_dbg_helm_residual": (ci, [vp, vp, vp, vp, _dp]),
         "msom_step": (ci, [vp, _dp]),
@@ -171,6 +178,21 @@ def load_library(strict=False):
         f.restype, f.argtypes = res, args
     _libs[name] = L
     return L
+
+
+def spec_layout(nx, ny, strict=False):
+    """(nbins, count[nbins]) of the radial bins of an nx x ny grid (msom_spec_layout): host arithmetic, no handle and no GPU"""
+    L = load_library(strict)
+    nb = C.c_int()
+    r = L.msom_spec_layout(int(nx), int(ny), C.byref(nb), None)
+    if r != 0:
+        raise MsomError(f"error {r}: {L.msom_last_error().decode()}")
+    count = np.zeros(nb.value, dtype=np.int_)
+    assert count.itemsize == C.sizeof(C.c_long)
+    r = L.msom_spec_layout(int(nx), int(ny), C.byref(nb), count.ctypes.data_as(C.POINTER(C.c_long)))
+    if r != 0:
+        raise MsomError(f"error {r}: {L.msom_last_error().decode()}")
+    return nb.value, count
 
 
 def _ptr(a):
@@ -379,6 +401,59 @@ class QG:
         """RD = deformation radius of `mode`, so that the next wavelet_filter builds sig_filt = min(afilt * Rd, Lfmax) from the
         stratification (mode 1: the reference's MODE_PV_INVERT branch, msqg/qg.h:1055-1057)"""
         self._chk(self.L.msom_modes_set_rd(self.h, int(mode)))
+
+    # -- isotropic wavenumber spectra and spectral fluxes on the device (msqg/scripts/fftlib.py, spectra.py, energy_offline.py)
+    def spec_bins(self):
+        """number of radial bins: max(nx, ny) / 2 - 2"""
+        n = self.L.msom_spec_bins(self.h)
+        if n < 0:
+            self._chk(n)
+        return n
+
+    def spec_kr(self):
+        """kr[r] = (r + 1) / (max(nx, ny) Delta)"""
+        kr = np.empty(self.spec_bins())
+        self._chk(self.L.msom_spec_kr(self.h, kr.ctypes.data_as(_dp)))
+        return kr
+
+    @staticmethod
+    def _spec_pair(a, b):
+        a = _f64(a)
+        b = a if b is None else _f64(b)
+        if len(a.shape) != 3 or tuple(a.shape) != tuple(b.shape):
+            raise ValueError(f"arrays of shape {tuple(a.shape)} and {tuple(b.shape)}: want two [layers][ny][nx]")
+        return a, b
+
+    def spec_2d(self, a, b=None, out=None):
+        """Re(fft2(a) conj fft2(b)) Delta^4, fftshift-ed, of [layers][ny][nx] arrays (host or device; b None: a).  out: optional destination"""
+        a, b = self._spec_pair(a, b)
+        if out is None:
+            out = np.empty(tuple(a.shape))
+        self._chk(self.L.msom_spec_2d(self.h, _ptr(a), _ptr(b), int(a.shape[0]), _ptr(out)))
+        return out
+
+    def spec_cross(self, a, b=None, flux=False):
+        """the isotropic cross-spectrum [layers][nbins] of a and b (b None: a), or with flux=True the spectral flux"""
+        a, b = self._spec_pair(a, b)
+        out = np.empty((int(a.shape[0]), self.spec_bins()))
+        p = out.ctypes.data_as(_dp)
+        self._chk(self.L.msom_spec_cross(self.h, _ptr(a), _ptr(b), int(a.shape[0]), None if flux else p, p if flux else None))
+        return out
+
+    def spec_fields(self, fa, fb, flux=False):
+        """spec_cross of two fields the model holds; nothing but [layers][nbins] numbers leaves the device"""
+        n = self.L.msom_field_layers(self.h, int(fa))
+        out = np.empty((max(n, 0), self.spec_bins()))
+        p = out.ctypes.data_as(_dp)
+        self._chk(self.L.msom_spec_fields(self.h, int(fa), int(fb), None if flux else p, p if flux else None))
+        return out
+
+    def spec_energy(self):
+        """(ke [nl][nbins], pe [nl - 1][nbins]): KE and PE wavenumber spectra of the PSI the model holds (spectra.py:113-139)"""
+        nb = self.spec_bins()
+        ke, pe = np.empty((self.nl, nb)), np.empty((max(self.nl - 1, 0), nb))
+        self._chk(self.L.msom_spec_energy(self.h, ke.ctypes.data_as(_dp), pe.ctypes.data_as(_dp) if self.nl > 1 else None))
+        return ke, pe
 
     # -- modal PV inversion: option("mode_pv_invert", 1) sends every inversion through the modes (MODE_PV_INVERT, msqg/qg.h:116-157)
     def modes_mgstats(self, mode):

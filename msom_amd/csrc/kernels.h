@@ -267,6 +267,27 @@ int helm_residual_blocks(const NatGeom &g);
 int launch_helm_residual(hipStream_t st, const double *a, const double *b, const double *ibu_sp, const HelmCoef *hc, const NatGeom &g, double *res,
                          const SplitGeom &sg, int nl, double D, double *maxres, double *sum_partial, int stride, int want_sum);
 
+// ---- kernels_spec.hip: wavenumber spectra and spectral fluxes (msom_spec_*, msqg/scripts/fftlib.py); spec_inl.h has the line transform
+enum { SPEC_IN_AB = 0, SPEC_IN_UV = 1, SPEC_IN_G = 2 };   // what the row pass transforms: a + i b (b null: a + 0 i), u + i v of psi, g + 0 i
+enum { SPEC_CROSS = 0, SPEC_SUM = 1 };                    // what the column pass forms: Re(A conj B) or |A|^2 + |B|^2
+// element (layer l, row y, column x) of an input is at off + (l0 + l) * ls + y * pitch + x: a contiguous array or a natural field
+struct SpecIn {
+  const double *a, *b;      // AB: the two arrays; UV: a = psi; G: a = psi, b = S
+  size_t off, ls;
+  int pitch, l0, mode;
+  double D2, rD2;           // 2 Delta and its reciprocal (UV)
+  double dhc[MSOM_MAXNL];   // (G)
+};
+int spec_prepare_device();   // once per process, before the first launch: the line kernels' dynamic LDS.  -1: refused
+// tw: exp(-2 pi i t / nt), t < nt / 2, nt >= nx, ny.  Z, ZT: [layers][ny][nx] / [layers][nx][ny] complex; V: [layers][nx / 2 + 1][ny];
+// out2d: null or [layers][ny][nx]; TE: [layers][2][smax + 1]; res: [layers][2][nbins] (bin sums, fluxes)
+void launch_spec_rows(hipStream_t st, const SpecIn &in, int nx, int ny, int layers, double2 *Z, const double2 *tw, int nt);
+void launch_spec_transpose(hipStream_t st, const double2 *Z, double2 *ZT, int nx, int ny, int layers);
+void launch_spec_cols(hipStream_t st, const double2 *ZT, int nx, int ny, int layers, int kind, double scale, double *V, double *out2d, const double2 *tw,
+                      int nt);
+void launch_spec_shells(hipStream_t st, const double *V, int nx, int ny, int layers, int smax, double *TE);
+void launch_spec_final(hipStream_t st, const double *TE, int smax, int nbins, int layers, double dk2, double *res);
+
 // ---- kernels_newqg.hip: tendency of the cell-centred one-layer model (newqg/qg.h:264-284), one layer, one tile.
 // One pass psi -> zeta (always stored) and dq, or q_out = q_in + dt * dq when q_out != nullptr (dq then not stored).  psi carries its
 // ghost ring (walls) or wrapped copies two cells deep (walls & WALL_PER).  qforc == nullptr: no forcing term.  cek = (hEkb f0) / (2 dh0).

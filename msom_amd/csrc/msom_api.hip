@@ -26,6 +26,7 @@
 
 #include "comm.h"
 #include "kernels.h"
+#include "spec_inl.h"
 #include "helm_inl.h"
 
 #define HIPCHK(x)                                                                          \
@@ -205,6 +206,17 @@ struct msom {
   HelmSolve helm = {};                    // per-mode mg_solve state (helm_inl.h)
   int helm_solved = 0;                    // a modal solve since the last msom_set_const (msom_modes_mgstats)
   ProfSlot prof_helm_relax, prof_helm_resid, prof_helm_coarse;   // finest-level sweeps, residual passes, levels of <= 64 cells a side
+  // wavenumber spectra (msom_spec_*, msqg/scripts/fftlib.py); nothing is allocated until the first spectrum call after msom_set_const
+  int spc_batch = 0;                      // layers the work arrays hold (0: not allocated)
+  int spc_smax = 0;                       // last shell: floor(sqrt(2) * max(nx, ny) / 2)
+  double2 *spc_z = nullptr, *spc_zt = nullptr;   // row-transformed batch [batch][ny][nx] and its transpose [batch][nx][ny]
+  double2 *spc_tw = nullptr;              // exp(-2 pi i t / nmax), t < nmax / 2 (host long double, rounded once)
+  double *spc_v = nullptr;                // spec_2D of the half plane [batch][nx / 2 + 1][ny]
+  double *spc_te = nullptr, *spc_res = nullptr;  // shell sums [batch][2][smax + 1]; bin sums and fluxes [batch][2][nbins]
+  double *spc_hin = nullptr;              // device copies of a caller's host arrays [2][batch][ny][nx] (first host input)
+  double *spc_o2d = nullptr;              // plane of msom_spec_2d for a host `out` [batch][ny][nx] (first such call)
+  size_t spc_bytes = 0;                   // all of the above
+  std::vector<long> spc_count;            // points per bin (msom_spec_layout of this grid)
   int s_zero = 0;  // pystep_de(onlyKE = 1) zeroed the stretching field S (msqg/qg_energy.h:319-325); undone by msom_set_const
   std::vector<NatGeom> wv_g;
   std::vector<double *> wv_s, wv_r, wv_sig;
@@ -230,6 +242,7 @@ struct msom {
 static void free_agglomeration(msom *m);
 static void stats_drop(msom *m);
 static void modes_drop(msom *m);
+static void spec_drop(msom *m);
 static void helm_drop_pyramid(msom *m) {   // the iBu pyramid of the modal inversion (general form)
   for (double *p : m->helm_ibu)
     if (p) hipFree(p);
@@ -747,6 +760,7 @@ extern "C" int msom_destroy(msom_t *m) {
   if (m->bfn_partial) hipFree(m->bfn_partial);
   stats_drop(m);
   modes_drop(m);
+  spec_drop(m);
   if (m->modes_dev) hipFree(m->modes_dev);
   if (m->modes_flag) hipFree(m->modes_flag);
   if (m->modes_partial) hipFree(m->modes_partial);
@@ -918,6 +932,8 @@ extern "C" double msom_get_param(msom_t *m, const char *key) {
   if (!strcmp(key, "mode_pv_invert")) return m->mode_pv_invert;
   if (!strcmp(key, "modes_ready")) return m->const_set && m->modes_ready;
   if (!strcmp(key, "modes_compact")) return m->const_set && m->modes_ready ? m->modes_compact : (m->modes_compact_opt != 0 && m->fr_uniform);
+  if (!strcmp(key, "spec_bytes")) return (double)m->spc_bytes;   // the work arrays of msom_spec_*: 0 until the first spectrum call
+  if (!strcmp(key, "spec_batch")) return m->spc_batch;
   if (!strcmp(key, "modes_bytes"))   // 8 ny nx per stored array: nl*nl + nl of them in the general form, none in the compact one
     return m->modes_md ? (double)(m->nl * m->nl + m->nl) * m->nx * m->ny * sizeof(double) : 0.;
   // which kernels the dispatch picks for this handle (bench.py names what ran from these, not from a table)
@@ -1257,6 +1273,7 @@ extern "C" int msom_set_const(msom_t *m) {
   m->bfn_begun = 0;
   stats_drop(m);
   modes_drop(m);
+  spec_drop(m);
   m->helm_solved = 0;
   if (m->helm_pm) HIPCHK(hipMemsetAsync(m->helm_pm, 0, m->g.ls * nl * sizeof(double), m->st));   // the reference's freshly created pom
   if (m->mode_pv_invert) {   // eigmod and sig_filt from mode 1, msqg/qg.h:1053-1057
@@ -2726,6 +2743,232 @@ extern "C" int msom_modes_set_rd(msom_t *m, int mode) {
   return sync_stream(m);
 }
 
+// ------------------------------------------------------------------ wavenumber spectra and spectral fluxes (msqg/scripts/fftlib.py)
+
+static bool spec_pow2(int n) { return n > 0 && (n & (n - 1)) == 0; }
+// nbins and the points per bin from the integer rule of include/msom.h, on the quarter plane with weights; no device
+extern "C" int msom_spec_layout(int nx, int ny, int *nbins, long *count) {
+  if (!spec_pow2(nx) || !spec_pow2(ny) || std::min(nx, ny) < SPEC_MINN || std::max(nx, ny) > 32768) {
+    msom_set_error("msom_spec_layout: %d x %d: both sides must be powers of two, 8 .. 32768", nx, ny);
+    return MSOM_ERR_CONFIG;
+  }
+  const int nmax = std::max(nx, ny), sx = nmax / nx, sy = nmax / ny, nb = nmax / 2 - 2, hx = nx / 2, hy = ny / 2;
+  if (nbins) *nbins = nb;
+  if (!count) return MSOM_OK;
+  for (int r = 0; r < nb; r++) count[r] = 0;
+  for (int i = 0; i <= hx; i++) {
+    const long wi = (i == 0 || i == hx) ? 1 : 2;   // +-i; -nx/2 has no partner
+    int s = i * sx;                                 // floor(sqrt(R2)) at j = 0, then followed upwards
+    for (int j = 0; j <= hy; j++) {
+      const long w = wi * ((j == 0 || j == hy) ? 1 : 2);
+      const long R2 = (long)(i * sx) * (i * sx) + (long)(j * sy) * (j * sy);
+      while ((long)(s + 1) * (s + 1) <= R2) s++;
+      if (s < nb) count[s] += w;
+      if ((long)s * s == R2 && s >= 1 && s - 1 < nb) count[s - 1] += w;   // on the circle of radius s: also the bin below
+    }
+  }
+  return MSOM_OK;
+}
+
+static void spec_drop(msom *m) {
+  for (void *p : {(void *)m->spc_z, (void *)m->spc_zt, (void *)m->spc_tw, (void *)m->spc_v, (void *)m->spc_te, (void *)m->spc_res, (void *)m->spc_hin,
+                  (void *)m->spc_o2d})
+    if (p) hipFree(p);
+  m->spc_z = m->spc_zt = m->spc_tw = nullptr;
+  m->spc_v = m->spc_te = m->spc_res = m->spc_hin = m->spc_o2d = nullptr;
+  m->spc_batch = 0;
+  m->spc_bytes = 0;
+}
+// the guards every handle call shares: argument, dialect, tiling, state, size -- in that order
+static int spec_guard(msom *m, const char *fn) {
+  if (m->nranks > 1) { msom_set_error("%s: the spectra run on a single tile, this handle is one of %d", fn, m->nranks); return MSOM_ERR_CONFIG; }
+  if (!m->const_set) { msom_set_error("%s: call msom_set_const first", fn); return MSOM_ERR_STATE; }
+  if (!spec_pow2(m->nx) || !spec_pow2(m->ny) || std::min(m->nx, m->ny) < SPEC_MINN || std::max(m->nx, m->ny) > SPEC_MAXN) {
+    msom_set_error("%s: %d x %d: both sides must be powers of two, %d .. %d", fn, m->nx, m->ny, SPEC_MINN, SPEC_MAXN);
+    return MSOM_ERR_CONFIG;
+  }
+  return MSOM_OK;
+}
+#define SPEC_SCRATCH_CAP ((size_t)1 << 30)   // work arrays of one batch of layers: 4096^2 goes layer by layer (576 MiB), 2048^2 seven at a time
+static int spec_ensure(msom *m) {
+  if (m->spc_batch) return MSOM_OK;
+  if (spec_prepare_device()) { msom_set_error("msom_spec: the device refuses the line kernels' %d KiB of LDS", (int)(2 * spec_line_len(SPEC_MAXN) * 16 / 1024)); return MSOM_ERR_HIP; }
+  const int nx = m->nx, ny = m->ny, nmax = std::max(nx, ny);
+  const size_t cells = (size_t)nx * ny, vcells = (size_t)(nx / 2 + 1) * ny;
+  const size_t per_layer = cells * 2 * sizeof(double2) + vcells * sizeof(double);
+  const int batch = (int)std::min<size_t>(MSOM_MAXNL, std::max<size_t>(1, SPEC_SCRATCH_CAP / per_layer));
+  int nbins = 0;
+  m->spc_count.assign(nmax / 2, 0);
+  msom_spec_layout(nx, ny, &nbins, m->spc_count.data());
+  m->spc_count.resize(nbins);
+  m->spc_smax = (int)floor(sqrt(2. * (nmax / 2) * (double)(nmax / 2)));
+  while ((long)m->spc_smax * m->spc_smax > 2L * (nmax / 2) * (nmax / 2)) m->spc_smax--;
+  while ((long)(m->spc_smax + 1) * (m->spc_smax + 1) <= 2L * (nmax / 2) * (nmax / 2)) m->spc_smax++;
+  const size_t bz = batch * cells * sizeof(double2), bv = batch * vcells * sizeof(double), btw = (size_t)(nmax / 2) * sizeof(double2),
+               bte = (size_t)batch * 2 * (m->spc_smax + 1) * sizeof(double), bres = (size_t)batch * 2 * nbins * sizeof(double);
+  if (hipMalloc(&m->spc_z, bz) != hipSuccess || hipMalloc(&m->spc_zt, bz) != hipSuccess || hipMalloc(&m->spc_v, bv) != hipSuccess ||
+      hipMalloc(&m->spc_tw, btw) != hipSuccess || hipMalloc(&m->spc_te, bte) != hipSuccess || hipMalloc(&m->spc_res, bres) != hipSuccess) {
+    (void)hipGetLastError();
+    spec_drop(m);
+    msom_set_error("msom_spec: no device memory for the work arrays (%zu bytes)", 2 * bz + bv + btw + bte + bres);
+    return MSOM_ERR_HIP;
+  }
+  std::vector<double2> tw(nmax / 2);
+  for (int t = 0; t < nmax / 2; t++) {
+    const long double a = -2.0L * 3.14159265358979323846264338327950288L * (long double)t / (long double)nmax;
+    tw[t] = make_double2((double)cosl(a), (double)sinl(a));
+  }
+  HIPCHK(hipMemcpy(m->spc_tw, tw.data(), btw, hipMemcpyHostToDevice));
+  m->spc_batch = batch;
+  m->spc_bytes = 2 * bz + bv + btw + bte + bres;
+  return MSOM_OK;
+}
+static int spec_nbins(const msom *m) { return std::max(m->nx, m->ny) / 2 - 2; }
+static SpecIn spec_in_nat(const msom *m, int mode, const double *a, const double *b) {
+  SpecIn in = {};
+  in.a = a; in.b = b; in.mode = mode;
+  in.off = nat_idx(m->g, 0, 0, 0); in.ls = m->g.ls; in.pitch = m->g.pitch;
+  const double D = m->p.L0 / m->gnx;
+  in.D2 = 2. * D; in.rD2 = 1. / (2. * D);
+  for (int k = 0; k < m->nl - 1 && k < MSOM_MAXNL; k++) in.dhc[k] = m->dhc[k];
+  return in;
+}
+// the passes of one batch: layers l0 .. l0 + cnt - 1 of `in` into spc_v (and the shifted plane into o2d when it is not null)
+static void spec_batch_2d(msom *m, const SpecIn &in, int cnt, int kind, double *o2d) {
+  const double D = m->p.L0 / m->gnx;
+  const int nt = std::max(m->nx, m->ny);
+  launch_spec_rows(m->st, in, m->nx, m->ny, cnt, m->spc_z, m->spc_tw, nt);
+  launch_spec_transpose(m->st, m->spc_z, m->spc_zt, m->nx, m->ny, cnt);
+  launch_spec_cols(m->st, m->spc_zt, m->nx, m->ny, cnt, kind, (D * D) * (D * D), m->spc_v, o2d, m->spc_tw, nt);
+}
+static void spec_batch_1d(msom *m, int cnt) {
+  const double D = m->p.L0 / m->gnx;
+  launch_spec_shells(m->st, m->spc_v, m->nx, m->ny, cnt, m->spc_smax, m->spc_te);
+  launch_spec_final(m->st, m->spc_te, m->spc_smax, spec_nbins(m), cnt, (1. / (m->nx * D)) * (1. / (m->ny * D)), m->spc_res);
+}
+// `layers` layers of `in` (AB with caller's arrays: ua / ub host or device, contiguous; otherwise the handle's fields).  out2d: the caller's
+// [layers][ny][nx] or null; spec / flux: host [layers][nbins] or null (spec already 2 pi kr sum / count).  Synchronises.
+static int spec_run(msom *m, SpecIn in, const double *ua, const double *ub, int layers, int kind, double *out2d, double *spec, double *flux) {
+  int r = spec_ensure(m);
+  if (r) return r;
+  const int nb = spec_nbins(m), batch = m->spc_batch;
+  const size_t cells = (size_t)m->nx * m->ny;
+  const bool a_host = ua && !is_device_ptr(ua), b_host = ub && !is_device_ptr(ub), o_host = out2d && !is_device_ptr(out2d);
+  if ((a_host || b_host) && !m->spc_hin) {
+    HIPCHK(hipMalloc(&m->spc_hin, 2 * batch * cells * sizeof(double)));
+    m->spc_bytes += 2 * batch * cells * sizeof(double);
+  }
+  if (o_host && !m->spc_o2d) {
+    HIPCHK(hipMalloc(&m->spc_o2d, batch * cells * sizeof(double)));
+    m->spc_bytes += batch * cells * sizeof(double);
+  }
+  std::vector<double> h((size_t)layers * 2 * nb);
+  for (int l0 = 0; l0 < layers; l0 += batch) {
+    const int cnt = std::min(batch, layers - l0);
+    SpecIn bi = in;
+    bi.l0 = l0;
+    if (ua) {   // the caller's arrays: this batch starts at layer 0 of what the kernel is given
+      bi.l0 = 0;
+      bi.a = ua + l0 * cells;
+      if (a_host) {
+        HIPCHK(hipMemcpyAsync(m->spc_hin, ua + l0 * cells, cnt * cells * sizeof(double), hipMemcpyHostToDevice, m->st));
+        bi.a = m->spc_hin;
+      }
+      bi.b = ub ? ub + l0 * cells : nullptr;
+      if (b_host) {
+        HIPCHK(hipMemcpyAsync(m->spc_hin + batch * cells, ub + l0 * cells, cnt * cells * sizeof(double), hipMemcpyHostToDevice, m->st));
+        bi.b = m->spc_hin + batch * cells;
+      }
+    }
+    spec_batch_2d(m, bi, cnt, kind, !out2d ? nullptr : o_host ? m->spc_o2d : out2d + l0 * cells);
+    if (o_host) HIPCHK(hipMemcpyAsync(out2d + l0 * cells, m->spc_o2d, cnt * cells * sizeof(double), hipMemcpyDeviceToHost, m->st));
+    if (spec || flux) {
+      spec_batch_1d(m, cnt);
+      HIPCHK(hipMemcpyAsync(h.data() + (size_t)l0 * 2 * nb, m->spc_res, (size_t)cnt * 2 * nb * sizeof(double), hipMemcpyDeviceToHost, m->st));
+    }
+    if ((a_host || b_host || o_host) && (r = sync_stream(m))) return r;   // the copy buffers are reused by the next batch
+  }
+  if ((r = sync_stream(m))) return r;
+  const double dk = 1. / (std::max(m->nx, m->ny) * (m->p.L0 / m->gnx));
+  for (int l = 0; l < layers; l++)
+    for (int k = 0; k < nb; k++) {
+      if (spec) spec[(size_t)l * nb + k] = 2. * M_PI * ((k + 1) * dk) * h[((size_t)l * 2) * nb + k] / (double)m->spc_count[k];
+      if (flux) flux[(size_t)l * nb + k] = h[((size_t)l * 2 + 1) * nb + k];
+    }
+  return MSOM_OK;
+}
+#define SPEC_ENTRY(m, fn)                  \
+  do {                                     \
+    int g__ = spec_guard(m, fn);           \
+    if (g__) return g__;                   \
+  } while (0)
+
+extern "C" int msom_spec_bins(msom_t *m) {
+  MSQG_ONLY(m);
+  if (!m) return MSOM_ERR_ARG;
+  SPEC_ENTRY(m, "msom_spec_bins");
+  return spec_nbins(m);
+}
+extern "C" int msom_spec_kr(msom_t *m, double *kr) {
+  MSQG_ONLY(m);
+  if (!m || !kr) return MSOM_ERR_ARG;
+  SPEC_ENTRY(m, "msom_spec_kr");
+  const double dk = 1. / (std::max(m->nx, m->ny) * (m->p.L0 / m->gnx));
+  for (int k = 0; k < spec_nbins(m); k++) kr[k] = (k + 1) * dk;
+  return MSOM_OK;
+}
+static SpecIn spec_in_user(const msom *m) {
+  SpecIn in = {};
+  in.mode = SPEC_IN_AB;
+  in.off = 0; in.ls = (size_t)m->nx * m->ny; in.pitch = m->nx;
+  return in;
+}
+extern "C" int msom_spec_2d(msom_t *m, const double *a, const double *b, int layers, double *out) {
+  MSQG_ONLY(m);
+  if (!m || !a || !b || !out || layers < 1) return MSOM_ERR_ARG;
+  SPEC_ENTRY(m, "msom_spec_2d");
+  return spec_run(m, spec_in_user(m), a, a == b ? nullptr : b, layers, a == b ? SPEC_SUM : SPEC_CROSS, out, nullptr, nullptr);
+}
+extern "C" int msom_spec_cross(msom_t *m, const double *a, const double *b, int layers, double *spec, double *flux) {
+  MSQG_ONLY(m);
+  if (!m || !a || !b || layers < 1 || (!spec && !flux)) return MSOM_ERR_ARG;
+  SPEC_ENTRY(m, "msom_spec_cross");
+  return spec_run(m, spec_in_user(m), a, a == b ? nullptr : b, layers, a == b ? SPEC_SUM : SPEC_CROSS, nullptr, spec, flux);
+}
+extern "C" int msom_spec_fields(msom_t *m, int field_a, int field_b, double *spec, double *flux) {
+  MSQG_ONLY(m);
+  if (!m || (!spec && !flux)) return MSOM_ERR_ARG;
+  SPEC_ENTRY(m, "msom_spec_fields");
+  for (int f : {field_a, field_b})
+    if ((f == MSOM_QOF || (f >= MSOM_DE_BF && f < MSOM_NFIELDS)) && ensure_field(m, f)) return MSOM_ERR_HIP;
+  if (check_field(m, field_a) || check_field(m, field_b)) return MSOM_ERR_ARG;
+  if (m->flayers[field_a] != m->flayers[field_b]) {
+    msom_set_error("msom_spec_fields: field %d has %d layers, field %d has %d", field_a, m->flayers[field_a], field_b, m->flayers[field_b]);
+    return MSOM_ERR_ARG;
+  }
+  const bool same = field_a == field_b;
+  return spec_run(m, spec_in_nat(m, SPEC_IN_AB, m->f[field_a], same ? nullptr : m->f[field_b]), nullptr, nullptr, m->flayers[field_a],
+                  same ? SPEC_SUM : SPEC_CROSS, nullptr, spec, flux);
+}
+extern "C" int msom_spec_energy(msom_t *m, double *ke, double *pe) {
+  MSQG_ONLY(m);
+  if (!m || (!ke && !pe)) return MSOM_ERR_ARG;
+  SPEC_ENTRY(m, "msom_spec_energy");
+  const int nl = m->nl, nb = spec_nbins(m);
+  int r;
+  if (ke) {   // Z = u + i v: |U|^2 + |V|^2 through the symmetric pair
+    if ((r = spec_run(m, spec_in_nat(m, SPEC_IN_UV, m->f[MSOM_PSI], nullptr), nullptr, nullptr, nl, SPEC_SUM, nullptr, ke, nullptr))) return r;
+    for (int l = 0; l < nl; l++)
+      for (int k = 0; k < nb; k++) ke[(size_t)l * nb + k] = 0.5 * ke[(size_t)l * nb + k] * m->dhf[l];
+  }
+  if (pe && nl > 1) {
+    if ((r = spec_run(m, spec_in_nat(m, SPEC_IN_G, m->f[MSOM_PSI], m->f[MSOM_S]), nullptr, nullptr, nl - 1, SPEC_SUM, nullptr, pe, nullptr))) return r;
+    for (int l = 0; l < nl - 1; l++)
+      for (int k = 0; k < nb; k++) pe[(size_t)l * nb + k] = 0.5 * pe[(size_t)l * nb + k] * m->dhc[l];
+  }
+  return MSOM_OK;
+}
+
 // ------------------------------------------------------------------ time loop
 
 // dtnext() [Basilisk, SURVEY App. B]
@@ -4046,6 +4289,17 @@ extern "C" int msom_bench_kernel(msom_t *m, const char *kernel, int reps, double
     NEED_MODES(m, "msom_bench_kernel");
     if (!m->modes_partial) HIPCHK(hipMalloc(&m->modes_partial, (size_t)2 * MSOM_MAXNL * modes_energy_stride(m->g) * sizeof(double)));
   }
+  int spec_cnt = 0;
+  if (!strncmp(kernel, "spec_", 5)) {   // the passes of msom_spec_energy's KE half on one batch of layers (the work arrays are overwritten)
+    if (strcmp(kernel, "spec_rows") && strcmp(kernel, "spec_transpose") && strcmp(kernel, "spec_cols") && strcmp(kernel, "spec_shells")) {
+      msom_set_error("unknown kernel %s", kernel);
+      return MSOM_ERR_ARG;
+    }
+    int r = spec_guard(m, "msom_bench_kernel");
+    if (r || (r = spec_ensure(m))) return r;
+    spec_cnt = std::min(m->nl, m->spc_batch);
+    spec_batch_2d(m, spec_in_nat(m, SPEC_IN_UV, m->f[MSOM_PSI], nullptr), spec_cnt, SPEC_SUM, nullptr);   // every pass finds its input
+  }
   HelmCount helm_all = {};
   if (!strncmp(kernel, "helm_", 5)) {   // "helm_sweep": both half-sweeps of the finest level, every mode; "helm_residual"
     if (strcmp(kernel, "helm_sweep") && strcmp(kernel, "helm_residual")) { msom_set_error("unknown kernel %s", kernel); return MSOM_ERR_ARG; }
@@ -4097,6 +4351,14 @@ extern "C" int msom_bench_kernel(msom_t *m, const char *kernel, int reps, double
       launch_modes_project(m->st, m->staging, m->staging, m->modes_md, modes_mc(m), m->g, m->nl, modes_layers(m), 1);
     } else if (!strcmp(kernel, "modes_energy")) {
       modes_energy_launch(m);
+    } else if (!strcmp(kernel, "spec_rows")) {
+      launch_spec_rows(m->st, spec_in_nat(m, SPEC_IN_UV, m->f[MSOM_PSI], nullptr), m->nx, m->ny, spec_cnt, m->spc_z, m->spc_tw, std::max(m->nx, m->ny));
+    } else if (!strcmp(kernel, "spec_transpose")) {
+      launch_spec_transpose(m->st, m->spc_z, m->spc_zt, m->nx, m->ny, spec_cnt);
+    } else if (!strcmp(kernel, "spec_cols")) {
+      launch_spec_cols(m->st, m->spc_zt, m->nx, m->ny, spec_cnt, SPEC_SUM, pow(D, 4), m->spc_v, nullptr, m->spc_tw, std::max(m->nx, m->ny));
+    } else if (!strcmp(kernel, "spec_shells")) {
+      spec_batch_1d(m, spec_cnt);
     }
   };
   for (int k = 0; k < 3; k++) one();
