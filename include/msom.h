@@ -104,7 +104,8 @@ int msom_destroy(msom_t *m);
  * "fused" [1] one-pass tendency kernel, "adv_fused" [1] advance folded into it, "stoch_fused" [1] (product build only) the
  * stochastic variant rides in that kernel too: -q/tau and the noise are read in its finalisation next to q_in, "rhs_variant" [6: one layer per
  * wavefront with register windows; 1: LDS tiles],
- * "rhs_resid" [0] first residual of the next inversion as its by-product, "mg_fused" [1] fused
+ * "rhs_resid" [-1: from the size at which it wins] first residual of the next inversion as its by-product (msom_get_param("rhs_resid"):
+ * whether this handle's passes emit it -- the option resolved and one tile with walls, "mg_fused", more than one level), "mg_fused" [1] fused
  * residual/restriction and correction/residual passes, "prolong_fused" [1], "mg_coarse" [4] coarse levels
  * in one launch (1: their arrays in global memory, 2: resident in LDS, 3: as 2 with the LDS pool pre-filled with NaN -- test aid; round 3,
  * default 4: the lean LDS form k_mg_coarse_lean where it applies -- uniform S or one layer, walls or doubly periodic -- else as 2),
@@ -482,6 +483,11 @@ int msom_dbg_nlevels(msom_t *m);
 int msom_dbg_level_dims(msom_t *m, int lev, int *nx, int *ny);
 int msom_dbg_relax(msom_t *m, int lev, double *da, const double *res, int nsweeps);
 int msom_dbg_residual(msom_t *m, const double *a, const double *b, double *res, double *maxres);
+/* QPRED = Q + dt dq in one tendency pass, then the first residual of its inversion on levels 0 and 1 (raw split arrays of
+   msom_get_param("split_ls_0") / ("split_ls_1") doubles per layer, "split_rp_<k>" per row of two half rows, each with "split_pad" pad
+   doubles on either side; NaN where nothing was written), max|res| and the sum of QPRED:
+   fused != 0: out of the pass itself (option rhs_resid), 0: from the solver's residual pass */
+int msom_dbg_rhs_resid(msom_t *m, int fused, double dt, double *res0, double *res1, double *maxres, double *bsum);
 /* the modal solver's kernels (need the modes: computed if not ready).  da, res: [mode][y][x] of level `lev`; nhalf half-sweeps starting
  * with colour 0 (half-sweep h is sweep h / 2); count_per_mode[m] = sweeps mode m takes (NULL: every mode takes all), a mode whose
  * count is used up keeps its da.  a, b, res: [mode][ny][nx]; maxres_per_mode: nl maxima of |res_m| */

@@ -115,6 +115,7 @@ def load_library(strict=False):
         "msom_dbg_level_dims": (ci, [vp, ci, C.POINTER(ci), C.POINTER(ci)]),
         "msom_dbg_relax": (ci, [vp, ci, vp, vp, ci]),
         "msom_dbg_residual": (ci, [vp, vp, vp, vp, _dp]),
+        "msom_dbg_rhs_resid": (ci, [vp, ci, cd, vp, vp, _dp, _dp]),
         "msom_dbg_restrict": (ci, [vp, ci, vp, vp]),
         "msom_dbg_prolong": (ci, [vp, ci, vp, vp]),
         "msom_dbg_op": (ci, [vp, cs, ci, ci, cd, cd]),
@@ -576,6 +577,16 @@ class QG:
         m = C.c_double()
         self._chk(self.L.msom_dbg_residual(self.h, _ptr(a), _ptr(b), _ptr(res), C.byref(m)))
         return res, m.value
+
+    def dbg_rhs_resid(self, fused, dt):
+        """QPRED = Q + dt dq in one tendency pass, then the first residual of its inversion on levels 0 and 1 (raw split arrays, NaN where
+        nothing was written), max|res| and the sum of QPRED: fused = out of the pass itself, else from the solver's residual pass"""
+        nl = int(self.param("nl"))
+        r0 = np.empty((nl, int(self.param("split_ls_0"))))
+        r1 = np.empty((nl, int(self.param("split_ls_1"))))
+        mx, bs = C.c_double(), C.c_double()
+        self._chk(self.L.msom_dbg_rhs_resid(self.h, int(bool(fused)), float(dt), _ptr(r0), _ptr(r1), C.byref(mx), C.byref(bs)))
+        return r0, r1, mx.value, bs.value
 
     def restrict(self, lev_fine, fine):
         fine = _f64(fine)

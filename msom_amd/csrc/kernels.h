@@ -137,7 +137,7 @@ void launch_filter_de(hipStream_t st, double *ft, const double *tmp2, double *pm
 struct RhsResid {
   double *res, *res_c;       // level-0 residual (split layout) and its restriction to level 1 (or null)
   double *res_max;           // device scalar: max|res| (zeroed by the launcher)
-  double *bsum_partial;      // one partial sum of q_out per workgroup (rhs_pipe_blocks entries)
+  double *bsum_partial;      // one partial sum of q_out per workgroup (rhs_pipe_blocks / rhs_lpw_blocks entries)
   SplitGeom sg, cg;
 };
 int rhs_fused_blocks(const NatGeom &g);
@@ -152,7 +152,8 @@ void launch_rhs_lpw(hipStream_t st, const KernelOpts &o, const double *psi, cons
                     const NatGeom &g, int nl, int walls, int uniformS, const double *Su, int have_qforc, double D, double beta, double iRe, double iRe4,
                     double cs, double cb, double slip_c, const LayerCoef &lc, const double *q_in, double *q_out, double dt, int stoch = 0,
                     const double *q_stage = nullptr, const double *noise = nullptr, double crelax = 0., double dts = 0., int region = 0,
-                    const double *dt_ptr = nullptr);
+                    const double *dt_ptr = nullptr, const RhsResid *rr = nullptr);
+int rhs_lpw_blocks(const KernelOpts &o, const NatGeom &g, int nl);   // workgroups of that launch with the residual by-product
 
 // ---- kernels_mg.hip
 // coarse part of the multigrid cycle in one launch (k_mg_coarse): lev[0] = finest of the group

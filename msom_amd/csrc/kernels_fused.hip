@@ -644,7 +644,7 @@ void launch_rhs_fused(hipStream_t st, const KernelOpts &o, const double *psi, co
                       const LayerCoef &lc, int variant, const double *q_in, double *q_out, double dt, const RhsResid *rr, int region, const double *dt_ptr) {
   if (variant == 6) {
     launch_rhs_lpw(st, o, psi, S, qforc, wind, dq, g, nl, walls, uniformS, Su, have_qforc, D, beta, iRe, iRe4, cs, cb, slip_c, lc, q_in, q_out, dt,
-                   0, nullptr, nullptr, 0., 0., region, dt_ptr);
+                   0, nullptr, nullptr, 0., 0., region, dt_ptr, q_out ? rr : nullptr);
     return;
   }
   RhsArgs a;

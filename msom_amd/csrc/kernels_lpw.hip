@@ -25,6 +25,10 @@
 
 #define LPW_W 58  // output columns of a strip (64 lanes - 2 x 3 halo)
 #define LPW_R 4   // rows per barrier interval
+// The same with the residual by-product (RES).  Its two carried values per row do not fit beside four rows of prefetch and carried terms
+// (4 rows: 60 - 76 VGPRs spilled, 2.0 ms per launch at 4096^2 x 6); with 2 rows the kernel holds 12 values in flight instead of 16 and
+// stays at 3 wavefronts per SIMD (155 - 161 VGPRs, no scratch) for twice the barriers: 0.82 ms
+#define LPW_R_RES 2
 // A workgroup is floor(LPW_MAXW / nl) strips x nl layers.  12 wavefronts = 3 per SIMD is what the register budget of the
 // product build allows (<= 168 VGPRs); a 6-wave workgroup (one strip of 6 layers) left every CU with ONE resident
 // workgroup (2 + 2 + 1 + 1 waves on the SIMDs: the second one did not fit) -- measured 6 waves per CU
@@ -48,6 +52,7 @@ struct LpwArgs {
   int noedge_off;  // every wavefront takes the EDGE instantiation (cross-check)
   int region;  // tiles, overlap with the psi halo exchange: 0 all, 1 only the wavefronts that read no halo cell, 2 only the others
   int dbg;  // timing experiments only (results wrong): 1 = no stores, 2 = every load hits the chunk's first row (no HBM reads)
+  RhsResid rr;  // RES: where the first residual of the next inversion goes
   double D, beta, iRe, iRe4, cs, cb, slip_c;
   LayerCoef lc;
   double Su[MSOM_MAXNL];
@@ -61,8 +66,13 @@ struct LpwArgs {
 // tests were two branches per Laplacian and four per row in EVERY row of EVERY wavefront: 0.60 -> 0.55 ms per launch at
 // 4096^2 x 6 with the tests compiled out everywhere (tools/ab_prof.py lpw_dbg), of a kernel that is issue-bound (0.545 ms
 // with no memory traffic at all)
-template <int R, bool UNI, bool QF, bool ADV, bool STOCH, bool EDGE>
-__device__ __forceinline__ void lpw_body(const LpwArgs &a, double (&ring)[2][LPW_MAXW][R][LPW_NV][64]) {
+// RES (only with ADV, never with STOCH): the pass also emits what k_residual2<write + restrict> would compute next from the same psi
+// and the q_out just formed: res = q_out - (lap + Gamma) psi in the split layout, its level-1 restriction, max|res| and the sum of q_out.
+// Same expression sequence as k_residual2 (kernels_mg.hip), so the same bits.  Per cell and row: wave l publishes d = psi_{l+1} - psi_l as
+// one more ring value (wave l + 1 reads it as psi_l - psi_{l-1}, the number k_residual2 forms in layer l + 1) and carries its two
+// horizontal flux differences to the finalisation, where q_out exists
+template <int R, bool UNI, bool QF, bool ADV, bool STOCH, bool EDGE, bool RES, int NV>
+__device__ __forceinline__ void lpw_body(const LpwArgs &a, double (&ring)[2][LPW_MAXW][R][NV][64], double &res_m, double &res_bs) {
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // ring slot; wv +- 1 = neighbouring layers of the strip
   const int nl = a.nl, nx = a.g.nx, ny = a.g.ny;
@@ -76,6 +86,10 @@ __device__ __forceinline__ void lpw_body(const LpwArgs &a, double (&ring)[2][LPW
   const int gi = x0 - 3 + lane, gic = min(gi, nx + 2);  // lanes past the padded row re-read its last column (never stored)
   const double dtv = a.dt_ptr ? *a.dt_ptr : a.dt;
   const double D = a.D, D2 = D * D, rD2 = 1. / D2, D12 = 12. * D * D, rD12 = 1. / D12, D2x = 2 * D, rD2x = 1. / D2x;
+  const double rD = 1. / D;
+  // column parity of the lane's cell.  NOT the lane's own parity: lane k holds column x0 - 3 + k and x0 is even, so the ODD lanes
+  // (3, 5, ...) hold the even columns and the EVEN lanes the odd ones.  Selects k_residual2's even / odd fused multiply-add forms
+  const bool oddx = !(lane & 1);
   const bool lower = l + 1 < nl, upper = l > 0;
   // lanes / rows that hold the first ghost line of a wall
   const int lW = ((a.walls & WALL_W) && x0 == 0) ? 2 : -1;
@@ -117,6 +131,9 @@ __device__ __forceinline__ void lpw_body(const LpwArgs &a, double (&ring)[2][LPW
   double tlA[R];
 #endif
   double pnext[R], qnext[R], qreg[R], fqreg[R], qsreg[STOCH ? R : 1], nzreg[STOCH ? R : 1];
+  double xdA[R], ydA[R];  // RES: x and y flux differences of a row
+#pragma unroll
+  for (int r = 0; r < R; r++) xdA[r] = ydA[r] = 0.;
 #pragma unroll
   for (int r = 0; r < R; r++) {
 #ifdef MSOM_STRICT
@@ -197,6 +214,21 @@ __device__ __forceinline__ void lpw_body(const LpwArgs &a, double (&ring)[2][LPW
     const double jd = (lower && !STOCH) ? mjac9(p, p1, D12, rD12) : 0.;
     const double zc = Z[1], tc = T[1];
     const double lapT = lap5(tc, TL[0], TR[0], T[2], T[0]);
+    if (RES) {
+      const double dW = P[1] - PL[1], dE = PR[1] - P[1], dS = P[1] - P[0], dN = P[2] - P[1];
+#ifdef MSOM_STRICT
+      xdA[r] = (dW / D - dE / D) / D;
+      ydA[r] = (dS / D - dN / D) / D;
+#else
+      // k_residual2 owns a column pair: the flux across the face inside the pair is rounded once and shared, the other one sits
+      // inside the fused multiply-add.  even x: fma(rD, c - W, -(rD (E - c))); odd x: fma(-rD, E - c, rD (c - W))
+      const double fa = oddx ? dW : dE, fb = oddx ? dE : dW;
+      const double x = fma(rD, fb, -(rD * fa));
+      xdA[r] = oddx ? -x : x;
+      ydA[r] = fma(rD, dS, -(rD * dN));
+#endif
+      ring[b][wv][r][NV - 1][lane] = Q[1] - P[1];
+    }
 #ifdef MSOM_STRICT
     abA[r] = adv + be; jdA[r] = jd; lapTA[r] = lapT; zcA[r] = zc; tcA[r] = tc;
     ring[b][wv][r][0][lane] = zc;
@@ -262,6 +294,23 @@ __device__ __forceinline__ void lpw_body(const LpwArgs &a, double (&ring)[2][LPW
 #endif
   };
 
+  // RES: the residual of row j against q = the q_out value of the cell (k_residual2's order: q, upper and lower coupling, x, y)
+  auto resid = [&](int b, int r, double s0, double s1, double q) -> double {
+    double re = q;
+#ifdef MSOM_STRICT
+    if (upper) re = re + s0 * ring[b][wv - 1][r][NV - 1][lane] * idh0;
+    if (lower) re = re - s1 * ring[b][wv][r][NV - 1][lane] * idh1;
+    re += xdA[r];
+    re += ydA[r];
+#else
+    if (upper) re = fma(idh0, s0 * ring[b][wv - 1][r][NV - 1][lane], re);
+    if (lower) re = fma(-(ring[b][wv][r][NV - 1][lane] * s1), idh1, re);
+    re = fma(rD, xdA[r], re);
+    re = fma(rD, ydA[r], re);
+#endif
+    return re;
+  };
+
   // rows of the first interval start travelling before the warm-up
 #pragma unroll
   for (int r = 0; r < R; r++) {
@@ -308,6 +357,32 @@ __device__ __forceinline__ void lpw_body(const LpwArgs &a, double (&ring)[2][LPW
 #pragma unroll
       for (int r = 0; r < R; r++)
         if (out_ok && jb + r < y1 && !(a.dbg & 1)) outp[nat_idx(a.g, l, jb + r, gic)] = val[r];
+      if (RES) {
+        double re[R];
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+          re[r] = resid(b ^ 1, r, s0[r], s1[r], val[r]);
+          if (out_ok && jb + r < y1) {
+            res_m = fmax(res_m, fabs(re[r]));
+            res_bs += val[r];
+            if (!(a.dbg & 1)) a.rr.res[split_idx(a.rr.sg, l, jb + r, gi)] = re[r];
+          }
+        }
+        // level 1: the 2 x 2 block is this lane (even column), the next one, and two rows of one interval (chunks start at an even
+        // row); restrict_pt's order
+#pragma unroll
+        for (int r = 0; r + 1 < R; r += 2) {
+          const double o0 = lane_above(re[r]), o1 = lane_above(re[r + 1]);
+          if (out_ok && !oddx && jb + r + 1 < y1 && !(a.dbg & 1)) {
+            double sum = 0.;
+            sum += re[r];
+            sum += re[r + 1];
+            sum += o0;
+            sum += o1;
+            a.rr.res_c[split_idx(a.rr.cg, l, (jb + r) >> 1, gi >> 1)] = sum / 4;
+          }
+        }
+      }
     }
     if (k < nblk) {
       const int j0 = y0 + k * R;
@@ -338,9 +413,12 @@ __device__ __forceinline__ void lpw_body(const LpwArgs &a, double (&ring)[2][LPW
   }
 }
 
-template <int R, bool UNI, bool QF, bool ADV, bool STOCH = false>
+template <int R, bool UNI, bool QF, bool ADV, bool STOCH = false, bool RES = false>
 __global__ void __launch_bounds__(64 * LPW_MAXW) k_rhs_lpw(LpwArgs a) {
-  __shared__ double ring[2][LPW_MAXW][R][LPW_NV][64];
+  static_assert(!RES || (ADV && !STOCH && R % 2 == 0), "the residual by-product rides in the plain tendency + advance pass");
+  constexpr int NV = LPW_NV + (RES ? 1 : 0);
+  __shared__ double ring[2][LPW_MAXW][R][NV][64];
+  double res_m = 0., res_bs = 0.;
   // the same geometry as lpw_body (all wavefronts of a workgroup share the chunk, hence the number of barriers)
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int nx = a.g.nx, ny = a.g.ny;
@@ -355,15 +433,75 @@ __global__ void __launch_bounds__(64 * LPW_MAXW) k_rhs_lpw(LpwArgs a) {
     const bool inner = strip < nstrips && x0 - 3 >= 0 && x0 + 60 < nx && y0 - 3 >= 0 && y0 + nblk * R + R + 2 < ny;   // (+ R: the last interval's prefetch)
     if ((a.region == 1) != inner) return;
   }
-  if (xwall || ywall || a.noedge_off) lpw_body<R, UNI, QF, ADV, STOCH, true>(a, ring);
-  else lpw_body<R, UNI, QF, ADV, STOCH, false>(a, ring);
+  if (xwall || ywall || a.noedge_off) lpw_body<R, UNI, QF, ADV, STOCH, true, RES, NV>(a, ring, res_m, res_bs);
+  else lpw_body<R, UNI, QF, ADV, STOCH, false, RES, NV>(a, ring, res_m, res_bs);
+  if (RES) {  // max|res| (order-free) and one partial sum of q_out per workgroup; the ring is free after the body's last barrier
+    const int lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+    for (int o = 32; o > 0; o >>= 1) {
+      res_m = fmax(res_m, __shfl_xor(res_m, o, 64));
+      res_bs += __shfl_xor(res_bs, o, 64);
+    }
+    double *red = &ring[0][0][0][0][0];
+    if (lane == 0) { red[wv] = res_m; red[LPW_MAXW + wv] = res_bs; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double mm = red[0], ss = red[LPW_MAXW];
+      for (int k = 1; k < nw; k++) { mm = fmax(mm, red[k]); ss += red[LPW_MAXW + k]; }
+      atomicMax((unsigned long long *)a.rr.res_max, (unsigned long long)__double_as_longlong(mm));
+      a.rr.bsum_partial[blockIdx.y * gridDim.x + blockIdx.x] = ss;
+    }
+  }
+}
+
+// strips per workgroup and chunk height of a launch (res: the residual by-product pairs rows, so the height is even)
+static void lpw_shape(const KernelOpts &o, const NatGeom &g, int nl, bool res, int &NS, int &H) {
+  const int strips = (g.nx + LPW_W - 1) / LPW_W;
+  H = o.rhs_dbg >> 8;   // tuning: rhs_dbg = rows << 8 overrides the chunk height
+  NS = LPW_MAXW / nl < 1 ? 1 : LPW_MAXW / nl;
+  if (NS > strips) NS = strips;
+  if (H <= 0) {
+    // One workgroup (all of a CU's wavefront slots at the product build's register count) per CU at a time: the launch takes
+    // ceil(workgroups / CUs) rounds of H + 6 row steps (6 warm-up rows per chunk).  Round 3: the chunk height that minimises that product
+    // -- the former rule (about 1024 / strips chunks, at most 64 rows) gave 2048^2 x 3 288 workgroups of 64 rows = 1.125 rounds, i.e. two
+    // rounds of 70 steps where 40 rows give two of 46 (0.117 -> 0.09 ms per launch); 4096^2 x 6 keeps its 64 rows (9 rounds)
+    const int ncu = device_cu_count();
+    const int wgx = (strips + NS - 1) / NS;
+    // (workgroups do not end together: past three rounds the idle tail is taken as half a round rather than a whole one -- with whole
+    // rounds 4096^2 x 3 would take 32 rows, measured 3 % slower than 64)
+    double best = -1.;
+    for (int h = 64; h >= 8; h -= 8) {
+      const double r = (double)wgx * ((g.ny + h - 1) / h) / ncu, cost = (r <= 3. ? ceil(r) : r + 0.5) * (h + 6);
+      if (best < 0. || cost < best) { best = cost; H = h; }
+    }
+  }
+  if (H < 8) H = 8;
+  if (res) H = (H + 1) & ~1;
+}
+// workgroups of the launch = partial sums the residual by-product writes
+int rhs_lpw_blocks(const KernelOpts &o, const NatGeom &g, int nl) {
+  int NS, H;
+  lpw_shape(o, g, nl, true, NS, H);
+  const int strips = (g.nx + LPW_W - 1) / LPW_W;
+  return ((strips + NS - 1) / NS) * ((g.ny + H - 1) / H);
 }
 
 void launch_rhs_lpw(hipStream_t st, const KernelOpts &o, const double *psi, const double *S, const double *qforc, const double *wind, double *dq,
                     const NatGeom &g, int nl, int walls, int uniformS, const double *Su, int have_qforc, double D, double beta, double iRe, double iRe4,
                     double cs, double cb, double slip_c, const LayerCoef &lc, const double *q_in, double *q_out, double dt, int stoch,
-                    const double *q_stage, const double *noise, double crelax, double dts, int region, const double *dt_ptr) {
+                    const double *q_stage, const double *noise, double crelax, double dts, int region, const double *dt_ptr, const RhsResid *rr) {
   LpwArgs a;
+  const bool res = rr != nullptr;
+  if (res && (stoch || !q_out || region || (g.nx & 1) || (g.ny & 1) || !rr->res_c)) {
+    fprintf(stderr, "msom: launch_rhs_lpw: the residual by-product needs the plain tendency + advance pass on one tile with even sides\n");
+    abort();
+  }
+  if (res) {
+    a.rr = *rr;
+    (void)hipMemsetAsync(rr->res_max, 0, sizeof(double), st);
+  } else {
+    a.rr.res = a.rr.res_c = a.rr.res_max = a.rr.bsum_partial = nullptr;
+    a.rr.sg = SplitGeom(); a.rr.cg = SplitGeom();
+  }
   a.region = region;
   a.dt_ptr = dt_ptr;
   a.q_stage = q_stage; a.noise = noise; a.crelax = crelax; a.dts = dts;
@@ -374,25 +512,8 @@ void launch_rhs_lpw(hipStream_t st, const KernelOpts &o, const double *psi, cons
   a.D = D; a.beta = beta; a.iRe = iRe; a.iRe4 = iRe4; a.cs = cs; a.cb = cb; a.slip_c = slip_c; a.lc = lc;
   for (int l = 0; l < MSOM_MAXNL; l++) a.Su[l] = Su ? Su[l] : 0.;
   const int strips = (g.nx + LPW_W - 1) / LPW_W;
-  int H = o.rhs_dbg >> 8;   // tuning: rhs_dbg = rows << 8 overrides the chunk height
-  a.NS = LPW_MAXW / nl < 1 ? 1 : LPW_MAXW / nl;
-  if (a.NS > strips) a.NS = strips;
-  if (H <= 0) {
-    // One workgroup (all of a CU's wavefront slots at the product build's register count) per CU at a time: the launch takes
-    // ceil(workgroups / CUs) rounds of H + 6 row steps (6 warm-up rows per chunk).  Round 3: the chunk height that minimises that product
-    // -- the former rule (about 1024 / strips chunks, at most 64 rows) gave 2048^2 x 3 288 workgroups of 64 rows = 1.125 rounds, i.e. two
-    // rounds of 70 steps where 40 rows give two of 46 (0.117 -> 0.09 ms per launch); 4096^2 x 6 keeps its 64 rows (9 rounds)
-    const int ncu = device_cu_count();
-    const int wgx = (strips + a.NS - 1) / a.NS;
-    // (workgroups do not end together: past three rounds the idle tail is taken as half a round rather than a whole one -- with whole
-    // rounds 4096^2 x 3 would take 32 rows, measured 3 % slower than 64)
-    double best = -1.;
-    for (int h = 64; h >= 8; h -= 8) {
-      const double r = (double)wgx * ((g.ny + h - 1) / h) / ncu, cost = (r <= 3. ? ceil(r) : r + 0.5) * (h + 6);
-      if (best < 0. || cost < best) { best = cost; H = h; }
-    }
-  }
-  if (H < 8) H = 8;
+  int H;
+  lpw_shape(o, g, nl, res, a.NS, H);
   a.H = H;
   const dim3 gr((strips + a.NS - 1) / a.NS, (g.ny + H - 1) / H), bl(64 * nl * a.NS);
   if (stoch && !q_out) {  // only with the advance fused (the caller folds -q/tau and the noise into q_in)
@@ -403,6 +524,7 @@ void launch_rhs_lpw(hipStream_t st, const KernelOpts &o, const double *psi, cons
     with_bool(have_qforc, [&](auto Q) {
       constexpr bool UNI = decltype(U)::value, QF = decltype(Q)::value;
       if (stoch) hipLaunchKernelGGL((k_rhs_lpw<LPW_R, UNI, QF, true, true>), gr, bl, 0, st, a);
+      else if (res) hipLaunchKernelGGL((k_rhs_lpw<LPW_R_RES, UNI, QF, true, false, true>), gr, bl, 0, st, a);
       else if (q_out) hipLaunchKernelGGL((k_rhs_lpw<LPW_R, UNI, QF, true>), gr, bl, 0, st, a);
       else hipLaunchKernelGGL((k_rhs_lpw<LPW_R, UNI, QF, false>), gr, bl, 0, st, a);
     });

@@ -40,6 +40,9 @@
 
 // device scalar slots
 // RES0, RES1 and UMAX[nl] are contiguous: one max all-reduce / one copy brings them to the host
+// option rhs_resid = -1 (default): on from 2^RHS_RESID_MIN cell-layers.  RK2 step on one MI355X, off -> on: 4096^2 x 6 5.65 -> 5.28 ms,
+// 2048^2 x 3 (2^23.6) 1.23 -> 1.10 ms, 512^2 x 3 (2^19.6) 0.350 -> 0.348 ms (inside the noise), 128^2 x 1 0.197 -> 0.21 ms
+#define RHS_RESID_MIN 23
 enum { SC_BSUM = 2, SC_KE = 3, SC_SCRATCH = 4, SC_RES0 = 6, SC_RES1 = 7, SC_UMAX = 8 /* MAXNL */, SC_RESF = 8 + MSOM_MAXNL /* max|res| from the fused tendency pass */, SC_LSUM = 32 /* MAXNL */, SC_SPEC = 48 /* k_step_dt: dt limit, dt, tnext, dt / 2 */, SC_COUNT = 64 };
 static_assert(SC_RESF < SC_LSUM && SC_LSUM + MSOM_MAXNL <= SC_SPEC && SC_SPEC + 4 <= SC_COUNT, "scalar slots overlap");
 
@@ -174,7 +177,9 @@ struct msom {
   int mgc_lean = 0;
   int res_ready = -1;  // field id whose first multigrid residual (levels 0, 1; SC_RESF; partial sums) the last tendency pass already produced
   int adv_fused = 1;   // fold q_out = q_in + dt dq into the tendency pass
-  int rhs_resid = 0;   // let the fused tendency + advance pass produce it: measured slower (23 spilled VGPRs in the 256-VGPR kernel: 2.21 ms vs 1.63 + 0.50 ms), kept as an option
+  int rhs_resid = -1;  // let the fused tendency + advance pass produce it: 1 / 0, -1 = where it measurably wins (rhs_resid_on).  k_rhs_lpw's RES
+                       // instantiation (rhs_variant 6); in the LDS-tile kernel (rhs_variant 1) it lost: 23 spilled VGPRs, 2.21 ms vs 1.63 + 0.50 ms
+  int rr_nparts = 0;   // partial sums of q_out the last such pass wrote
   // back-and-forth nudging loop on the device (msom_bfn_*)
   int bfn_begun = 0;                      // msom_bfn_begin since the last msom_set_const
   int bfn_obs_set = 0, bfn_gain_set = 0;  // MSOM_BFN_OBS / MSOM_BFN_GAIN came in through msom_set_field (gain never set: 1 everywhere)
@@ -591,7 +596,10 @@ static int alloc_all(msom *m) {
   }
   HIPCHK(hipMalloc(&m->staging, (size_t)m->nl * (m->p.nptr > 1 ? m->p.nptr : 1) * m->nx * m->ny * sizeof(double)));
   HIPCHK(hipMalloc(&m->partial, ((size_t)partial_count(m->g) * m->nl + 64) * sizeof(double)));  // + chunk sums of launch_sum_final
-  HIPCHK(hipMalloc(&m->partial_rr, ((size_t)rhs_pipe_blocks(m->g) + 64) * sizeof(double)));
+  {  // one partial sum per workgroup of the pass: the LDS-tile kernel's grid or k_rhs_lpw's with the lowest chunks (8 rows) and one strip each
+    const size_t lpw = (size_t)((m->g.nx + 57) / 58) * ((m->g.ny + 7) / 8), pipe = (size_t)rhs_pipe_blocks(m->g);
+    HIPCHK(hipMalloc(&m->partial_rr, ((lpw > pipe ? lpw : pipe) + 64) * sizeof(double)));
+  }
   {
     size_t nb = (size_t)rhs_fused_blocks(m->g);
     if (nb < 2048) nb = 2048;
@@ -798,6 +806,7 @@ static int *kernel_opt(KernelOpts &o, const char *key) {
   return nullptr;
 }
 extern "C" int msom_set_option(msom_t *m, const char *key, double v) {
+  if (m) m->res_ready = -1;   // nothing cached from psi and q outlives a call that may change them or the solver path
   if (!m || !key) return MSOM_ERR_ARG;
   if (m->model) return nq_set_option(m, key, v);
   clear_graphs(m);   // captured cycles hold kernel arguments by value: any option may change them
@@ -895,6 +904,7 @@ static bool march_lean_fine(const msom *m);
 static bool fine_visit_fused(const msom *m);
 static int level_path(const msom *m, int k);
 static bool restrict2_ok(const msom *m);
+static bool rhs_resid_emits(const msom *m);
 extern "C" double msom_get_param(msom_t *m, const char *key) {
   if (!m || !key) return NAN;
   if (!strcmp(key, "model")) return m->model;
@@ -941,6 +951,10 @@ extern "C" double msom_get_param(msom_t *m, const char *key) {
   // how the wall-ring chunks around the fused visit run (-1: no fused visit on this handle), as launch_relax_visit reads the option
   if (!strcmp(key, "march_visit_ring")) return !fine_visit_fused(m) ? -1 : (m->opt.march_visit_ring >= 2 ? 2 : (m->opt.march_visit_ring == 1 ? 1 : 0));
   if (const int *o = kernel_opt(m->opt, key)) return *o;   // the handle's kernel options (march_rows, march_lean, ... rhs_dbg)
+  if (!strcmp(key, "rhs_resid")) return rhs_resid_emits(m);   // the tendency + advance pass emits the next solve's first residual
+  if (!strncmp(key, "split_ls_", 9)) { const int k = atoi(key + 9); return k >= 0 && k < m->nlev ? (double)m->sg[k].ls : NAN; }
+  if (!strncmp(key, "split_rp_", 9)) { const int k = atoi(key + 9); return k >= 0 && k < m->nlev ? (double)m->sg[k].rp : NAN; }   // doubles per row
+  if (!strcmp(key, "split_pad")) return MSOM_SP;   // pad doubles on each side of a half row of a split field
   if (!strcmp(key, "restrict2")) return restrict2_ok(m);   // the pre-cycle residual pass restricts two levels down
   if (!strcmp(key, "mg_coarse_lean")) return m->mgc_first >= 0 && m->mgc_lean;   // the coarse group runs in k_mg_coarse_lean
   if (!strcmp(key, "march_levels")) return march_levels(m);   // tile levels whose half-sweeps are chained (kernels_march.hip)
@@ -1242,6 +1256,7 @@ static int build_coefs(msom *m) {
 }
 
 extern "C" int msom_set_const(msom_t *m) {
+  if (m) m->res_ready = -1;   // nothing cached from psi and q outlives a call that may change them or the solver path
   if (!m) return MSOM_ERR_ARG;
   if (m->model) return nq_set_const(m);
   m->s_zero = 0;
@@ -1316,6 +1331,18 @@ enum { RP_COLOUR = 0, RP_BLOCK2 = 1, RP_BLOCK8 = 2, RP_MARCH = 3, RP_COARSE = 4,
 // relax_path_<k> report, msom_dbg_relax); residual2 with its max|u| by-product and the marched / fused visits are never reached,
 // because helm_solve does not enter mg_solve.
 static bool layered_fusions(const msom *m) { return !m->mode_pv_invert; }
+// option rhs_resid resolved: asked for, or (-1) the default tendency kernel on a grid big enough for the by-product to pay
+static bool rhs_resid_on(const msom *m) {
+  return m->rhs_resid > 0 || (m->rhs_resid < 0 && m->rhs_variant == 6 && (size_t)m->g.nx * m->g.ny * m->nl >= ((size_t)1 << RHS_RESID_MIN));
+}
+// ... and emitted by this handle's tendency + advance passes: the one statement of use_rr's terms, which rhs_terms and
+// msom_get_param("rhs_resid") both read.  The fused pass with the advance riding along (never the stochastic one), k_rhs_lpw or the
+// LDS-tile kernel, the layered solver's fused residual consumer on more than one level, one tile with walls and even sides
+static bool rhs_resid_emits(const msom *m) {
+  return rhs_resid_on(m) && m->fused && m->adv_fused && m->nl <= MSOM_FASTNL && !m->have_pg && !m->have_zpg && !m->flag_topo && !m->stochastic &&
+         layered_fusions(m) && (m->rhs_variant == 1 || m->rhs_variant == 6) && m->mg_fused && m->nlev > 1 && m->bc != BC_PERIODIC && m->nranks == 1 &&
+         !(m->g.nx & 1) && !(m->g.ny & 1);
+}
 static int sweep_path(const msom *m, const Lev &L) {
   const SplitGeom &g = *L.sg;
   if (!layered_fusions(m)) return RP_COLOUR;
@@ -1769,7 +1796,7 @@ static int mg_solve(msom *m, const double *b, msom_mgstats *s) {
   m->res_ready = -1;
   if (have_res) {  // res[0], res[1], max|res| and the partial sums of b came out of the tendency pass
     HIPCHK(hipMemcpyAsync(m->d_scal + SC_RES0, m->d_scal + SC_RESF, sizeof(double), hipMemcpyDeviceToDevice, m->st));
-    launch_sum_final(m->st, m->partial_rr, m->d_scal + SC_BSUM, rhs_pipe_blocks(m->g));
+    launch_sum_final(m->st, m->partial_rr, m->d_scal + SC_BSUM, m->rr_nparts);
   } else if (fused) {
     residual2(m, 2 | 4, b, SC_RES0, 1);
     launch_sum_final(m->st, m->partial, m->d_scal + SC_BSUM, residual2_blocks(m->g));
@@ -2075,7 +2102,7 @@ static int rhs_terms(msom *m, int qfield, int dqfield, int with_qforcing, double
 #ifdef MSOM_STRICT
   const bool stoch_fused = false;
 #else
-  const bool stoch_fused = m->stochastic && m->stoch_fused && m->adv_fused && adv_out >= 0 && m->rhs_variant == 6 && !m->rhs_resid;
+  const bool stoch_fused = m->stochastic && m->stoch_fused && m->adv_fused && adv_out >= 0 && m->rhs_variant == 6;
 #endif
   if (m->fused && m->nl <= MSOM_FASTNL && !m->have_pg && !m->have_zpg && !m->flag_topo && (!m->stochastic || stoch_fused) &&
       (m->nranks == 1 || (m->nx >= 4 && m->ny >= 4))) {
@@ -2085,9 +2112,9 @@ static int rhs_terms(msom *m, int qfield, int dqfield, int with_qforcing, double
     if (m->bc == BC_PERIODIC && m->nranks == 1) launch_fill_periodic(m->st, m->f[MSOM_PSI], m->g, nl, 3);
     if (!m->adv_fused) adv_out = -1;
     // the advance rides along: the pass can also emit the first residual of the inversion of q[adv_out]
-    // the residual by-product exists only in the LDS-tile kernel: asking for it selects that kernel
-    const int variant = (m->rhs_resid && m->rhs_variant == 6) ? 1 : m->rhs_variant;
-    const bool use_rr = adv_out >= 0 && layered_fusions(m) && m->rhs_resid && variant == 1 && m->mg_fused && m->nlev > 1 && m->bc != BC_PERIODIC;
+    // (k_rhs_lpw's RES instantiation, or the LDS-tile kernel's): one tile with walls and even sides, one residual consumer per solve
+    const int variant = m->rhs_variant;
+    const bool use_rr = adv_out >= 0 && rhs_resid_emits(m);
     RhsResid rr;
     if (use_rr) {
       rr.res = m->res[0]; rr.res_c = m->res[1]; rr.res_max = m->d_scal + SC_RESF; rr.bsum_partial = m->partial_rr;
@@ -2134,7 +2161,10 @@ static int rhs_terms(msom *m, int qfield, int dqfield, int with_qforcing, double
                        variant == 6 ? m->dt_dev : nullptr);
     });
     prof_end(m, m->prof_rhs);
-    if (use_rr) m->res_ready = adv_out;
+    if (use_rr) {
+      m->res_ready = adv_out;
+      m->rr_nparts = variant == 6 ? rhs_lpw_blocks(m->opt, m->g, nl) : rhs_pipe_blocks(m->g);
+    }
     if (advanced && adv_out >= 0) *advanced = 1;
     return MSOM_OK;
   }
@@ -2305,6 +2335,7 @@ static int advance_qg(msom *m, int out, int in, int dq, double dt) {
   } while (0)
 
 extern "C" double msom_update(msom_t *m, const double *q, double *dqdt, double dtmax) {
+  if (m) m->res_ready = -1;   // nothing cached from psi and q outlives a call that may change them or the solver path
   if (!m) return -1;
   if (m->model) return nq_update(m, q, dqdt, dtmax);
   if (!m->const_set && msom_set_const(m)) return -1;
@@ -2320,6 +2351,7 @@ extern "C" double msom_update(msom_t *m, const double *q, double *dqdt, double d
 }
 
 extern "C" int msom_advance(msom_t *m, double *qout, const double *qin, const double *dqdt, double dt) {
+  if (m) m->res_ready = -1;   // nothing cached from psi and q outlives a call that may change them or the solver path
   if (m && m->model) return nq_advance(m, qout, qin, dqdt, dt);
   NEED_CONST(m);
   int in = MSOM_Q, out = MSOM_Q, r;
@@ -2334,6 +2366,7 @@ extern "C" int msom_advance(msom_t *m, double *qout, const double *qin, const do
 }
 
 extern "C" int msom_invertq(msom_t *m, const double *q, double *psi, msom_mgstats *st) {
+  if (m) m->res_ready = -1;   // nothing cached from psi and q outlives a call that may change them or the solver path
   if (m && m->model) return nq_invertq(m, q, psi, st);
   NEED_CONST(m);
   int qf = MSOM_Q, r;
@@ -2349,6 +2382,7 @@ extern "C" int msom_invertq(msom_t *m, const double *q, double *psi, msom_mgstat
 }
 
 extern "C" int msom_comp_q(msom_t *m, const double *psi, double *q) {
+  if (m) m->res_ready = -1;   // nothing cached from psi and q outlives a call that may change them or the solver path
   if (m && m->model) return nq_comp_q_api(m, psi, q);
   NEED_CONST(m);
   int r;
@@ -2387,6 +2421,7 @@ static int check_shape(msom *m, int a, int b, int c) {
 // msqg/qg_bfn.h:21-80
 extern "C" int pystep_bfn(msom_t *m, double *varin_py, int len1, int len2, int len3, double *tend_py, int len4, int len5, int len6,
                           double direction, int vartype) {
+  if (m) m->res_ready = -1;   // nothing cached from psi and q outlives a call that may change them or the solver path
   MSQG_ONLY(m);
   NEED_CONST(m);
   if (check_shape(m, len1, len2, len3) || check_shape(m, len4, len5, len6)) return MSOM_ERR_ARG;
@@ -2416,6 +2451,7 @@ extern "C" int pyq2p(msom_t *m, double *po_py, int len7, int len8, int len9, dou
   NEED_CONST(m);
   if (check_shape(m, len7, len8, len9) || check_shape(m, len10, len11, len12)) return MSOM_ERR_ARG;
   int r;
+  m->res_ready = -1;
   HIPCHK(hipMemsetAsync(m->f[MSOM_PSI], 0, m->g.ls * m->nl * sizeof(double), m->st));
   if ((r = upload(m, MSOM_Q, qo_py))) return r;
   if ((r = invertq(m, m->f[MSOM_Q]))) return r;
@@ -2423,6 +2459,7 @@ extern "C" int pyq2p(msom_t *m, double *po_py, int len7, int len8, int len9, dou
 }
 // msqg/qg_bfn.h:95-103
 extern "C" int pyp2q(msom_t *m, double *po_py, int len13, int len14, int len15, double *qo_py, int len16, int len17, int len18) {
+  if (m) m->res_ready = -1;   // nothing cached from psi and q outlives a call that may change them or the solver path
   MSQG_ONLY(m);
   NEED_CONST(m);
   if (check_shape(m, len13, len14, len15) || check_shape(m, len16, len17, len18)) return MSOM_ERR_ARG;
@@ -2434,6 +2471,7 @@ extern "C" int pyp2q(msom_t *m, double *po_py, int len13, int len14, int len15, 
 static int ensure_field(msom *m, int field);
 // msqg/qg_bfn.py:49-51: zero history; the AB3 weights apply from the first step on
 extern "C" int msom_bfn_begin(msom_t *m) {
+  if (m) m->res_ready = -1;   // nothing cached from psi and q outlives a call that may change them or the solver path
   MSQG_ONLY(m);
   NEED_CONST(m);
   int r;
@@ -2541,6 +2579,7 @@ extern "C" int msom_stats_begin(msom_t *m, unsigned mask) {
 }
 
 extern "C" int msom_stats_accumulate(msom_t *m, double w) {
+  if (m) m->res_ready = -1;   // nothing cached from psi and q outlives a call that may change them or the solver path
   MSQG_ONLY(m);
   if (!m) return MSOM_ERR_ARG;
   if (!std::isfinite(w)) { msom_set_error("msom_stats_accumulate: w = %g", w); return MSOM_ERR_ARG; }
@@ -2592,6 +2631,7 @@ extern "C" int msom_stats_get(msom_t *m, int which, double *out) {
 
 // time_filter, msqg/qg.h:491-507 (alpha_f = dt / tau_f; qo_me starts from the zeros of a freshly created field)
 extern "C" int msom_time_filter(msom_t *m, double dt) {
+  if (m) m->res_ready = -1;   // nothing cached from psi and q outlives a call that may change them or the solver path
   MSQG_ONLY(m);
   if (!m) return MSOM_ERR_ARG;
   if (!std::isfinite(dt)) { msom_set_error("msom_time_filter: dt = %g", dt); return MSOM_ERR_ARG; }
@@ -2634,6 +2674,7 @@ static bool is_device_ptr(const void *p) {
   } while (0)
 
 extern "C" int msom_modes_compute(msom_t *m) {
+  if (m) m->res_ready = -1;   // nothing cached from psi and q outlives a call that may change them or the solver path
   MSQG_ONLY(m);
   NEED_CONST(m);
   const int nl = m->nl, na = nl * nl + nl;
@@ -2695,6 +2736,7 @@ extern "C" int msom_modes_get(msom_t *m, int which, double *out) {
 }
 
 extern "C" int msom_modes_project(msom_t *m, int to_modes, const double *in, double *out) {
+  if (m) m->res_ready = -1;   // nothing cached from psi and q outlives a call that may change them or the solver path
   MSQG_ONLY(m);
   if (!m || !in || !out) return MSOM_ERR_ARG;
   NEED_MODES(m, "msom_modes_project");
@@ -2734,6 +2776,7 @@ extern "C" int msom_modes_energy(msom_t *m, double *ke, double *pe) {
 }
 
 extern "C" int msom_modes_set_rd(msom_t *m, int mode) {
+  if (m) m->res_ready = -1;   // nothing cached from psi and q outlives a call that may change them or the solver path
   MSQG_ONLY(m);
   if (!m || mode < 1 || mode > m->nl - 1) return MSOM_ERR_ARG;
   NEED_MODES(m, "msom_modes_set_rd");
@@ -3011,7 +3054,7 @@ static int tracer_advance(msom *m, int out, int in, double dt) {
 // can a stage's tendency pass be queued speculatively?  One tile, the fused one-layer-per-wavefront kernel with the advance
 // folded in, max|u| out of the solver's last pass, nothing with side effects in the pass (noise draws, tracers)
 static bool spec_ok(msom *m) {
-  return layered_fusions(m) && m->async_solve && m->nranks == 1 && m->fused && m->adv_fused && m->rhs_variant == 6 && !m->rhs_resid && m->mg_fused && m->nlev > 1 &&
+  return layered_fusions(m) && m->async_solve && m->nranks == 1 && m->fused && m->adv_fused && m->rhs_variant == 6 && m->mg_fused && m->nlev > 1 &&
          m->nl <= MSOM_FASTNL && !m->have_pg && !m->have_zpg && !m->flag_topo && !m->stochastic && m->p.nptr == 0 && m->p.nitermin >= 1 && !m->dbg_nosync;
 }
 
@@ -3042,6 +3085,9 @@ extern "C" int msom_step(msom_t *m, double *dt_used) {
   m->spec_hook = nullptr;
   const bool hit1 = spec && m->spec_valid && !spec_rc;
   m->dt_dev = nullptr;
+  // a speculative pass may have emitted the next solve's first residual (rhs_resid): it counts only with the pass itself.  Discarded:
+  // the solve went on and regenerated res[0], res[1] behind it; the re-run below emits them again
+  if (!hit1) m->res_ready = -1;
   if (d < 0) return m->sticky ? m->sticky : MSOM_ERR_HIP;
   if (hit1) {
     m->dt = m->h_scal[SC_SPEC + 1];
@@ -3081,8 +3127,12 @@ extern "C" int msom_step(msom_t *m, double *dt_used) {
   const double d2 = solve_and_dt(m, MSOM_QPRED, m->dt);
   m->spec_hook = nullptr;
   if (d2 < 0) return m->sticky ? m->sticky : MSOM_ERR_HIP;
-  if (spec && m->spec_valid && !spec_rc) std::swap(m->f[MSOM_Q], m->q_alt);
-  else {
+  const bool rr2 = m->res_ready == MSOM_Q;   // the speculative pass emitted the residual of what it wrote, and that is q_alt
+  m->res_ready = -1;
+  if (spec && m->spec_valid && !spec_rc) {
+    std::swap(m->f[MSOM_Q], m->q_alt);
+    if (rr2) m->res_ready = MSOM_Q;   // q_alt is q now: what the next step's first solve is handed
+  } else {
     if ((r = rhs_terms(m, MSOM_QPRED, MSOM_DQ, 1, p.iRe, p.iRe4, p.Eks, p.Ekb, MSOM_Q, MSOM_Q, m->dt, &advanced))) return r;
     if (!advanced && (r = advance_qg(m, MSOM_Q, MSOM_Q, MSOM_DQ, m->dt))) return r;
   }
@@ -3715,6 +3765,7 @@ static int de_terms(msom *m, double dt, double ediag) {
   return m->sticky;
 }
 extern "C" int msom_energy_tend(msom_t *m, double dt) {
+  if (m) m->res_ready = -1;   // nothing cached from psi and q outlives a call that may change them or the solver path
   MSQG_ONLY(m);
   NEED_CONST(m);
   int r;
@@ -3734,6 +3785,7 @@ static int filter_de(msom *m, int pm_field, double dtflt, double ediag) {
   return sync_stream(m);
 }
 extern "C" int msom_filter_de(msom_t *m, int pm_field, double dtflt) {
+  if (m) m->res_ready = -1;   // nothing cached from psi and q outlives a call that may change them or the solver path
   MSQG_ONLY(m);
   NEED_CONST(m);
   if (pm_field < 0 || pm_field >= MSOM_NFIELDS || m->flayers[pm_field] != m->nl) { msom_set_error("bad field id %d", pm_field); return MSOM_ERR_ARG; }
@@ -3755,6 +3807,7 @@ extern "C" int pystep_de(msom_t *m, const double *po_py, int len1, int len2, int
                          double *de_vd_py, int len7, int len8, int len9, double *de_j1_py, int len10, int len11, int len12,
                          double *de_j2_py, int len13, int len14, int len15, double *de_j3_py, int len16, int len17, int len18,
                          double *de_ft_py, int len19, int len20, int len21, int onlyKE) {
+  if (m) m->res_ready = -1;   // nothing cached from psi and q outlives a call that may change them or the solver path
   MSQG_ONLY(m);
   NEED_CONST(m);
   if (check_shape(m, len1, len2, len3) || check_shape(m, len4, len5, len6) || check_shape(m, len7, len8, len9) || check_shape(m, len10, len11, len12) ||
@@ -3858,6 +3911,7 @@ extern "C" int msom_write_bas(msom_t *m, int field, const char *path) {
   return msom_bas_write(path, h.data(), m->flayers[field], m->gnx, m->p.L0) ? MSOM_ERR_IO : MSOM_OK;
 }
 extern "C" int msom_read_bas(msom_t *m, int field, const char *path) {
+  if (m) m->res_ready = -1;   // nothing cached from psi and q outlives a call that may change them or the solver path
   MSQG_ONLY(m);
   if (check_field(m, field) || !path) return MSOM_ERR_ARG;
   if (m->gnx != m->gny) { msom_set_error(".bas input needs a square grid"); return MSOM_ERR_STATE; }
@@ -3879,6 +3933,7 @@ extern "C" int msom_write_nc(msom_t *m, const char *path) {
   return msom_nc_append(path, m->nl, m->gny, m->gnx, 2, names, m->t, f) < 0 ? MSOM_ERR_IO : MSOM_OK;
 }
 extern "C" int msom_read_nc(msom_t *m, int field, const char *path, const char *varname, int record) {
+  if (m) m->res_ready = -1;   // nothing cached from psi and q outlives a call that may change them or the solver path
   if (check_field(m, field) || !path || !varname) return MSOM_ERR_ARG;
   std::vector<double> h((size_t)m->flayers[field] * m->gnx * m->gny);
   int r = msom_nc_read(path, varname, record, m->flayers[field], m->gny, m->gnx, h.data(), nullptr);
@@ -3893,6 +3948,7 @@ static bool file_exists(const char *path) {
 
 // optional input files, msqg/qg.h:940-984 and msqg/qg.c:55-59 (p0.bas)
 extern "C" int msom_read_inputs(msom_t *m, const char *dir) {
+  if (m) m->res_ready = -1;   // nothing cached from psi and q outlives a call that may change them or the solver path
   MSQG_ONLY(m);
   if (!m) return MSOM_ERR_ARG;
   char name[512];
@@ -4162,6 +4218,43 @@ extern "C" int msom_dbg_relax(msom_t *m, int lev, double *da, const double *res,
   }
   m->profile = prof;
   return split_download(m, m->da[lev], m->sg[lev], da, m->nl);
+}
+// One tendency + advance pass q_pred = q + dt dq on the handle's psi and q, then the first residual of the inversion of q_pred on levels 0 and
+// 1 as mg_solve would take it: fused = 1 out of the pass itself (option rhs_resid), 0 from k_residual2<write + restrict>.  res0 / res1: the
+// raw split arrays (split_ls_0 / split_ls_1 doubles per layer), filled with NaN beforehand so that what a kernel leaves alone shows
+extern "C" int msom_dbg_rhs_resid(msom_t *m, int fused, double dt, double *res0, double *res1, double *maxres, double *bsum) {
+  MSQG_ONLY(m);
+  if (m) m->res_ready = -1;
+  NEED_CONST(m);
+  if (!res0 || !res1 || m->nlev < 2) return MSOM_ERR_ARG;
+  const Params &p = m->p;
+  for (int k = 0; k < 2; k++) HIPCHK(hipMemsetAsync(m->res[k], 0xFF, m->sg[k].ls * m->nl * sizeof(double), m->st));
+  HIPCHK(hipMemsetAsync(m->d_scal, 0, (SC_UMAX + MSOM_MAXNL) * sizeof(double), m->st));
+  const int keep = m->rhs_resid;
+  m->rhs_resid = fused ? 1 : 0;
+  int adv = 0;
+  int r = rhs_terms(m, MSOM_Q, MSOM_DQ, 1, p.iRe, p.iRe4, p.Eks, p.Ekb, MSOM_QPRED, MSOM_Q, dt, &adv);
+  m->rhs_resid = keep;
+  if (r) return r;
+  const bool emitted = m->res_ready == MSOM_QPRED;
+  m->res_ready = -1;
+  if (!adv || (fused && !emitted)) { msom_set_error("msom_dbg_rhs_resid: this handle's tendency pass does not %s", adv ? "emit the residual" : "advance"); return MSOM_ERR_CONFIG; }
+  int slot = SC_RESF;
+  if (fused) launch_sum_final(m->st, m->partial_rr, m->d_scal + SC_BSUM, m->rr_nparts);
+  else {
+    residual2(m, 2 | 4, m->f[MSOM_QPRED], SC_RES0, 1);
+    launch_sum_final(m->st, m->partial, m->d_scal + SC_BSUM, residual2_blocks(m->g));
+    slot = SC_RES0;
+  }
+  double h[2] = {0., 0.};
+  HIPCHK(hipMemcpyAsync(&h[0], m->d_scal + slot, sizeof(double), hipMemcpyDeviceToHost, m->st));
+  HIPCHK(hipMemcpyAsync(&h[1], m->d_scal + SC_BSUM, sizeof(double), hipMemcpyDeviceToHost, m->st));
+  HIPCHK(hipMemcpyAsync(res0, m->res[0], m->sg[0].ls * m->nl * sizeof(double), hipMemcpyDeviceToHost, m->st));
+  HIPCHK(hipMemcpyAsync(res1, m->res[1], m->sg[1].ls * m->nl * sizeof(double), hipMemcpyDeviceToHost, m->st));
+  if ((r = sync_stream(m))) return r;
+  if (maxres) *maxres = h[0];
+  if (bsum) *bsum = h[1];
+  return MSOM_OK;
 }
 extern "C" int msom_dbg_residual(msom_t *m, const double *a, const double *b, double *res, double *maxres) {
   MSQG_ONLY(m);
