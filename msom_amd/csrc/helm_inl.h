@@ -1,5 +1,5 @@
 // helm_inl.h -- host state of the modal PV inversion: nl independent mg_solve loops (mspg/elliptic.h:145-229) that share their
-// launches.  Plain C++, no HIP: msom_api.hip drives it with the maxima the device returns, tools/helm_host_check.cpp with a script.
+// launches.  Plain C++, no HIP: msom_helm.hip drives it with the maxima the device returns, tools/helm_host_check.cpp with a script.
 //
 // A cycle of the batch is a cycle of every mode that still wants one.  helm_counts gives the sweeps each mode takes in it -- its own
 // nrelax, or 0 for a frozen mode (TOLERANCE met after NITERMIN cycles, or NITERMAX done) -- and helm_cycle_done books the cycle on
