@@ -105,7 +105,8 @@ int msom_destroy(msom_t *m);
  * stochastic variant rides in that kernel too: -q/tau and the noise are read in its finalisation next to q_in, "rhs_variant" [6: one layer per
  * wavefront with register windows; 1: LDS tiles],
  * "rhs_resid" [-1: from the size at which it wins] first residual of the next inversion as its by-product (msom_get_param("rhs_resid"):
- * whether this handle's passes emit it -- the option resolved and one tile with walls, "mg_fused", more than one level), "mg_fused" [1] fused
+ * whether this handle's passes emit it -- the option resolved and one tile with walls, "mg_fused", more than one level, "rhs_variant" 6, or 1 in
+ * the strict build, whose by-products have the residual pass's bits), "mg_fused" [1] fused
  * residual/restriction and correction/residual passes, "prolong_fused" [1], "mg_coarse" [4] coarse levels
  * in one launch (1: their arrays in global memory, 2: resident in LDS, 3: as 2 with the LDS pool pre-filled with NaN -- test aid; round 3,
  * default 4: the lean LDS form k_mg_coarse_lean where it applies -- uniform S or one layer, walls or doubly periodic -- else as 2),

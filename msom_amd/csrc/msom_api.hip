@@ -794,12 +794,34 @@ extern "C" int msom_remove_mean(msom_t *m, int field) {
   MSQG_ONLY(m);
   if (check_field(m, field)) return MSOM_ERR_ARG;
   const int nl = m->flayers[field];
+  m->res_ready = -1;
+#ifdef MSOM_STRICT
+  // validation build, one tile: the mean as the oracle forms it -- the cells column by column (x outer, y inner), each times Delta^2,
+  // over the volume summed the same way (the statsf of msqg/qg.c:65-70 run serially) -- so that the field keeps the oracle's bits
+  // through the steps that follow; the parallel sum below differs from it in the last place.  An initialisation call: one download
+  std::vector<double> mean(nl);
+  if (m->nranks == 1) {
+    std::vector<double> h((size_t)nl * m->nx * m->ny);
+    int r = download(m, field, h.data());
+    if (r) return r;
+    const double D2 = (m->p.L0 / m->gnx) * (m->p.L0 / m->gnx);
+    for (int l = 0; l < nl; l++) {
+      double sum = 0, vol = 0;
+      for (int i = 0; i < m->nx; i++)
+        for (int j = 0; j < m->ny; j++) { sum += h[((size_t)l * m->ny + j) * m->nx + i] * D2; vol += D2; }
+      mean[l] = sum / vol;
+    }
+    HIPCHK(hipMemcpyAsync(m->d_scal + SC_LSUM, mean.data(), nl * sizeof(double), hipMemcpyHostToDevice, m->st));
+    launch_sub_layer_const(m->st, m->f[field], m->d_scal + SC_LSUM, m->g, nl, 1.);
+    fill_bc(m, field);
+    return sync_stream(m);
+  }
+#endif
   launch_sum_layers(m->st, m->f[field], m->partial, m->d_scal + SC_LSUM, m->g, nl);
   if (m->nranks > 1) {
     int r = reduce_scal(m, SC_LSUM, nl, RED_SUM);
     if (r) return r;
   }
-  m->res_ready = -1;
   launch_sub_layer_const(m->st, m->f[field], m->d_scal + SC_LSUM, m->g, nl, 1. / ((double)m->gnx * m->gny));
   fill_bc(m, field);
   return sync_stream(m);
@@ -1059,12 +1081,22 @@ static bool layered_fusions(const msom *m) { return !m->mode_pv_invert; }
 static bool rhs_resid_on(const msom *m) {
   return m->rhs_resid > 0 || (m->rhs_resid < 0 && m->rhs_variant == 6 && (size_t)m->g.nx * m->g.ny * m->nl >= ((size_t)1 << RHS_RESID_MIN));
 }
+// the tendency kernels whose by-product has k_residual2's bits, so that the option never changes a result: k_rhs_lpw in both builds; the
+// LDS-tile kernel in the validation build only (its product form carries -(lap + Gamma) psi as one reassociated number per cell, and a run
+// with it does not keep the bits of the run with the option off -- tests/test_gpu_call_sequences.py, row opt_rhs_variant)
+static bool rhs_resid_variant(const msom *m) {
+#ifdef MSOM_STRICT
+  return m->rhs_variant == 1 || m->rhs_variant == 6;
+#else
+  return m->rhs_variant == 6;
+#endif
+}
 // ... and emitted by this handle's tendency + advance passes: the one statement of use_rr's terms, which rhs_terms and
 // msom_get_param("rhs_resid") both read.  The fused pass with the advance riding along (never the stochastic one), k_rhs_lpw or the
 // LDS-tile kernel, the layered solver's fused residual consumer on more than one level, one tile with walls and even sides
 static bool rhs_resid_emits(const msom *m) {
   return rhs_resid_on(m) && m->fused && m->adv_fused && m->nl <= MSOM_FASTNL && !m->have_pg && !m->have_zpg && !m->flag_topo && !m->stochastic &&
-         layered_fusions(m) && (m->rhs_variant == 1 || m->rhs_variant == 6) && m->mg_fused && m->nlev > 1 && m->bc != BC_PERIODIC && m->nranks == 1 &&
+         layered_fusions(m) && rhs_resid_variant(m) && m->mg_fused && m->nlev > 1 && m->bc != BC_PERIODIC && m->nranks == 1 &&
          !(m->g.nx & 1) && !(m->g.ny & 1);
 }
 static int sweep_path(const msom *m, const Lev &L) {
@@ -1527,6 +1559,14 @@ static int mg_solve(msom *m, const double *b, msom_mgstats *s) {
   } else {
     residual(m, m->f[MSOM_PSI], b, SC_RES0, 1);
     launch_sum_final(m->st, m->partial, m->d_scal + SC_BSUM, partial_count(m->g));
+  }
+  // The correction passes form the ghost values of a + da from those of a and of da, which is boundary(a + da) only while the ghosts
+  // of a belong to its cells.  After pystep_de they do not (filter_de zeroes the cells of psi alone): the first residual reads them as
+  // they are, as the reference's does, and the reference's boundary(a) after the correction is made here, ahead of the cycle
+  // (tests/test_gpu_call_sequences.py, row pystep_de at TOLERANCE 1e-7: max|res| after the first cycle was 4.7e-5 for the oracle's 1.4e-4)
+  if (m->psi_ghosts_stale) {
+    m->psi_ghosts_stale = 0;
+    fill_bc(m, MSOM_PSI);
   }
   bool have_first = false;
   double resb = 0;

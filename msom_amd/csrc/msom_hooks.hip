@@ -290,6 +290,7 @@ extern "C" int msom_bench_kernel(msom_t *m, const char *kernel, int reps, double
   float ms = 0;
   HIPCHK(hipEventElapsedTime(&ms, a, b));
   *avg_ms = ms / reps;
+  m->res_ready = -1;   // "rhs_adv" goes through rhs_terms, which arms it for MSOM_QPRED again: the handle leaves a measurement disarmed
   hipEventDestroy(a);
   hipEventDestroy(b);
   return MSOM_OK;

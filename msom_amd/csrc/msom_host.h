@@ -172,6 +172,7 @@ struct msom {
   int mgc_first = -1, mgc_opt = 4;  // first (finest) level of the group, -1: none; option "mg_coarse" (1: through global memory, 2: levels resident in LDS,
                                     // 3: as 2 with a NaN-filled pool, 4: the lean LDS form k_mg_coarse_lean where it applies, else 2)
   int mgc_lean = 0;
+  int psi_ghosts_stale = 0;  // filter_de zeroed the cells of MSOM_PSI and left its ghost values, as the reference does: the next mg_solve refills them after its first residual
   int res_ready = -1;  // field id whose first multigrid residual (levels 0, 1; SC_RESF; partial sums) the last tendency pass already produced
   int adv_fused = 1;   // fold q_out = q_in + dt dq into the tendency pass
   int rhs_resid = -1;  // let the fused tendency + advance pass produce it: 1 / 0, -1 = where it measurably wins (rhs_resid_on).  k_rhs_lpw's RES

@@ -312,6 +312,7 @@ int filter_de(msom *m, int pm_field, double dtflt, double ediag) {
   if ((r = ensure_de_fields(m))) return r;
   if ((r = wavelet_filter(m, MSOM_TMP2, -dtflt))) return r;  // tmp2: tmp is used inside wavelet_filter (:210-213)
   launch_filter_de(m->st, m->f[MSOM_DE_FT], m->f[MSOM_TMP2], m->f[pm_field], m->g, m->nl, dtflt, ediag);
+  if (pm_field == MSOM_PSI) m->psi_ghosts_stale = 1;   // pm[] = 0 in the cells only (msqg/qg_energy.h:223): pystep_de leaves psi like this
   m->nme_ft = 0;
   return sync_stream(m);
 }
