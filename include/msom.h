@@ -363,6 +363,7 @@ int msom_last_mgstats(msom_t *m, msom_mgstats *st);
 /* msom_run: whole main() loop of msqg/qg.c:34-173 (stdout line, po/qo .bas every dtout,
  * outdir_%04d creation, params.in backup).  nsteps_max < 0: run to tend. */
 int msom_run(msom_t *m, const char *workdir, long nsteps_max);
+/* lossless fp64 checkpoint and bit-exact restart of a msom_t, and the options "ckpt_steps" / "resume" of this loop: msom_state.h */
 
 /* ---- .bas IO, msqg/auxiliar_input.h:24-59 (input_matrixl), :101-167 (output_matrixl, write_field) */
 /* tiled models: msom_write_* / msom_read_* / msom_read_inputs / msom_run are collective (every rank calls them): the

@@ -19,6 +19,7 @@ from .api import (  # noqa: F401
     bfn_begin,
     bfn_misfit,
     bfn_steps,
+    from_state,
     init_grid,
     load_library,
     pyp2q,
@@ -26,15 +27,20 @@ from .api import (  # noqa: F401
     pystep_bfn,
     pystep_de,
     read_params,
+    read_state,
     set_const,
     set_vars,
     set_vars_bfn,
     spec_layout,
+    state_check,
+    state_info,
     trash_vars,
     trash_vars_bfn,
+    write_state,
 )
 
 __all__ = [
     "QG", "NodeQG", "NewQG", "NODE_FIELDS", "MGStats", "MsomError", "FIELDS", "STATS", "MODES", "load_library", "read_params", "init_grid", "set_vars",
     "set_vars_bfn", "set_const", "pystep_bfn", "bfn_begin", "bfn_steps", "bfn_misfit", "pystep_de", "pyq2p", "pyp2q", "trash_vars", "trash_vars_bfn", "spec_layout",
+    "from_state", "read_state", "write_state", "state_check", "state_info",
 ]

@@ -5,6 +5,8 @@ import os
 
 import numpy as np
 
+from .state import read_state, write_state  # noqa: F401  (the state file in pure Python)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIBDIR = os.path.join(_HERE, "lib")
 
@@ -31,6 +33,12 @@ class MGStats(C.Structure):
 
     def __repr__(self):
         return f"MGStats(i={self.i}, resb={self.resb:g}, resa={self.resa:g}, sum={self.sum:g}, nrelax={self.nrelax})"
+
+
+class StateInfo(C.Structure):
+    """msom_state_info_t of include/msom_state.h"""
+    _fields_ = [(k, C.c_int) for k in ("version", "dialect", "nx", "ny", "nl", "nptr", "stochastic", "noise_mode", "mode_pv_invert",
+                                        "flag_topo", "nrecords")] + [("iter", C.c_long), ("t", C.c_double), ("dt", C.c_double)]
 
 
 _libs = {}
@@ -132,6 +140,13 @@ def load_library(strict=False):
         "msom_dbg_wavelet_levels": (ci, [vp]),
         "msom_dbg_siglev": (ci, [vp, ci, vp]),
         "msom_dbg_wavelet_apply": (ci, [vp, ci]),
+        # lossless checkpoint / restart (include/msom_state.h)
+        "msom_state_save": (ci, [vp, cs, C.c_uint]),
+        "msom_state_load": (ci, [vp, cs]),
+        "msom_create_from_state": (vp, [cs]),
+        "msom_state_check": (ci, [cs, C.POINTER(ci)]),
+        "msom_state_info": (ci, [cs, C.POINTER(StateInfo), C.c_char_p, C.c_size_t]),
+        "msom_state_dbg_flip": (ci, [vp, C.c_long]),
         # vertex-grid variant (qg-node/)
         "msomn_create": (vp, [cs]),
         "msomn_create_str": (vp, [cs]),
@@ -194,6 +209,49 @@ def spec_layout(nx, ny, strict=False):
     if r != 0:
         raise MsomError(f"error {r}: {L.msom_last_error().decode()}")
     return nb.value, count
+
+
+def state_check(path, strict=False):
+    """msom_state_check: walks the records of a state file and verifies every digest on the host (no handle, no GPU); the number of
+    records, or MsomError with the library's code in .code"""
+    L = load_library(strict)
+    n = C.c_int()
+    r = L.msom_state_check(os.fsencode(path), C.byref(n))
+    if r != 0:
+        e = MsomError(f"error {r}: {L.msom_last_error().decode()}")
+        e.code = r
+        raise e
+    return n.value
+
+
+def state_info(path, strict=False):
+    """msom_state_info: dict of the header, t, dt, iter and the record names of a state file (host only)"""
+    L = load_library(strict)
+    info, names = StateInfo(), C.create_string_buffer(4096)
+    r = L.msom_state_info(os.fsencode(path), C.byref(info), names, len(names))
+    if r != 0:
+        e = MsomError(f"error {r}: {L.msom_last_error().decode()}")
+        e.code = r
+        raise e
+    out = {k: getattr(info, k) for k, _ in StateInfo._fields_}
+    out["names"] = names.value.decode().split(",") if names.value else []
+    return out
+
+
+def from_state(path, strict=False):
+    """msom_create_from_state: a single-tile model (QG or NewQG, as the file says) made from the params text in the file, loaded"""
+    L = load_library(strict)
+    h = L.msom_create_from_state(os.fsencode(path))
+    if not h:
+        raise MsomError(L.msom_last_error().decode())
+    newqg = L.msom_get_param(h, b"model") == 1
+    g = (NewQG if newqg else QG).__new__(NewQG if newqg else QG)
+    g.L, g.h = L, h
+    g.nl = int(g.param("nl"))
+    g.nx, g.ny = int(g.param("nx")), int(g.param("ny"))
+    if not newqg:
+        g.tile = (1, 1, 0, 0)
+    return g
 
 
 def _ptr(a):
@@ -623,6 +681,16 @@ class QG:
         self._chk(self.L.msom_bench_kernel(self.h, kernel.encode(), reps, C.byref(ms)))
         return ms.value
 
+    # -- lossless checkpoint / restart (include/msom_state.h)
+    def save_state(self, path, constants=False):
+        self._chk(self.L.msom_state_save(self.h, os.fsencode(path), 1 if constants else 0))
+
+    def load_state(self, path):
+        self._chk(self.L.msom_state_load(self.h, os.fsencode(path)))
+
+    def state_dbg_flip(self, element):
+        self._chk(self.L.msom_state_dbg_flip(self.h, int(element)))
+
 
 class NewQG:
     """The cell-centred one-layer model with the optional Helmholtz ("1.5-layer", gp_low) inversion: one `qg.e` process of newqg/qg.c
@@ -646,6 +714,7 @@ class NewQG:
     step, set_tnext, t, iter, ke, mgstats = QG.step, QG.set_tnext, QG.t, QG.iter, QG.ke, QG.mgstats
     write_nc, read_nc = QG.write_nc, QG.read_nc
     profile_read, profile_reset, sync, bench_kernel = QG.profile_read, QG.profile_reset, QG.sync, QG.bench_kernel
+    save_state, load_state, state_dbg_flip = QG.save_state, QG.load_state, QG.state_dbg_flip
 
     def shape(self, field):
         return (self.L.msom_field_layers(self.h, field), self.ny, self.nx)

@@ -375,4 +375,19 @@ void launch_n_add_noise(hipStream_t st, double *q, const double *n, const NatGeo
 void launch_n_diag1d(hipStream_t st, const double *psi, const double *q, const double *qf, double *partial, double *out3, const NatGeom &g, double nu, double D);
 void launch_n_ke(hipStream_t st, const double *psi, double *partial, double *out, const NatGeom &g, double D);
 
+// ---- kernels_state.hip: rows of one layer of a natural field <-> a contiguous staging chunk, with the record digest of the state file
+struct StateChunk {
+  NatGeom g;        // the tile's natural layout
+  int ring;         // 1: the record carries the ghost ring (one tile only): rows and columns count from the ghost cell
+  int layer;        // layer of the record
+  int y0, rows;     // record rows y0 .. y0 + rows - 1 of that layer, all inside this tile
+  int ox, oy;       // the tile's offset in the global grid (cells)
+  int gW, gH;       // row width and rows per layer of the record on the GLOBAL grid (ring included): the digest's index space
+  int sx0, sw;      // staging: record column of its first column, and its row width
+};
+void launch_state_pack(hipStream_t st, const double *nat, double *stage, const StateChunk &c, unsigned long long *digest);
+void launch_state_unpack(hipStream_t st, const double *stage, double *nat, const StateChunk &c);
+void launch_state_digest(hipStream_t st, const double *nat, const StateChunk &c, unsigned long long *digest);
+void launch_state_flip(hipStream_t st, double *nat, size_t idx);
+
 #endif

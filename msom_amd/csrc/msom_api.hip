@@ -597,6 +597,11 @@ extern "C" int msom_set_option(msom_t *m, const char *key, double v) {
     if (!(v >= 1)) { msom_set_error("option stats_every = %g", v); return MSOM_ERR_ARG; }
     m->stats_every = (int)v;
   }
+  else if (!strcmp(key, "ckpt_steps")) {   // msom_run: <workdir>/state.msom every that many steps (msom_state.h); 0: off
+    if (!(v >= 0)) { msom_set_error("option ckpt_steps = %g", v); return MSOM_ERR_ARG; }
+    m->ckpt_steps = (int)v;
+  }
+  else if (!strcmp(key, "resume")) m->resume = (int)v != 0;   // msom_run: continue from <workdir>/state.msom if it is there
   else if (!strcmp(key, "tau_f")) {
     if (!(v > 0) || !std::isfinite(v)) { msom_set_error("option tau_f = %g", v); return MSOM_ERR_ARG; }
     m->tau_f = v;

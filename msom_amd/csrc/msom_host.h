@@ -1,6 +1,6 @@
 // msom_host.h -- private to the host side of the layered model: struct msom, the error macros, the device scalar slots and the host
 // functions that one msom_*.hip unit calls in another.  Included by msom_api.hip, msom_helm.hip, msom_diag.hip, msom_newqg.hip,
-// msom_wavelet.hip, msom_io.hip and msom_hooks.hip, and by nothing else (no kernel file, not comm.hip, not msom_node.hip).
+// msom_wavelet.hip, msom_io.hip, msom_state.hip and msom_hooks.hip, and by nothing else (no kernel file, not comm.hip, not msom_node.hip).
 #ifndef MSOM_HOST_H
 #define MSOM_HOST_H
 
@@ -229,6 +229,12 @@ struct msom {
   int nq_fused = 1;      // option: the tendency in one pass (k_nq_rhs); 0: one launch per reference loop (validation chain)
   int nq_adv_fused = 1;  // option: q_out = q_in + dt dq folded into that pass
   int nq_rows = 0;       // option: chunk height of k_nq_rhs (0: automatic)
+  // state file (msom_state.hip): options "ckpt_steps" / "resume" of msom_run, the test aid of msom_state_dbg_flip, and msom_run's
+  // own locals (next output and filter events, number of the output directory) as the last load found them in the file
+  int ckpt_steps = 0, resume = 0;
+  long state_flip = -1;
+  int run_loaded = 0, run_outdir = 0;
+  double run_tout = 0, run_tflt = 0;
   // time loop
   double t = 0, dt = 1., tnext = HUGE_VAL, previous = 0;
   int iter = 0;
@@ -354,6 +360,8 @@ int nq_step(msom *m, double *dt_used);
 int nq_bench_kernel(msom *m, const char *kernel, int reps, double *avg_ms);
 // msom_wavelet.hip
 int filter_de(msom *m, int pm_field, double dtflt, double ediag);
+// msom_state.hip: msom_state_save with msom_run's locals (tout, tflt, number of the output directory; null: none) in a record
+int state_save_run(msom *m, const char *path, unsigned flags, const double *run3);
 // msom_hooks.hip: the profile slots of a handle under the names msom_profile_read takes
 std::vector<std::pair<const char *, ProfSlot *>> prof_slots(msom *m);
 #pragma GCC visibility pop

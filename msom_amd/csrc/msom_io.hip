@@ -1,6 +1,7 @@
 // msom_io.hip -- .bas / NetCDF IO, msom_read_inputs (msqg/qg.h:940-984), backup_config (:782-835) and msom_run: the main loop of
 // msqg/qg.c:34-173 with its writestdout / output events (:101-173).
 #include "msom_host.h"
+#include "../../include/msom_state.h"
 
 // ------------------------------------------------------------------ .bas IO and the qg.c driver loop
 
@@ -199,6 +200,17 @@ static int backup_config(msom *m, const char *dpath) {
 // output t += dtout), then one predictor-corrector step.
 extern "C" int msom_run(msom_t *m, const char *workdir, long nsteps_max) {
   MSQG_ONLY(m);
+  // option "resume": <workdir>/state.msom, if it is there, is loaded before anything else -- a handle without constants takes them from
+  // the file -- and the loop below is entered where the checkpoint was taken: after the events of that iteration, before its step
+  char ckpt[700];
+  snprintf(ckpt, sizeof ckpt, "%s/state.msom", workdir ? workdir : ".");
+  bool resumed = false;
+  if (m && m->resume && file_exists(ckpt)) {
+    int rl = msom_state_load(m, ckpt);
+    if (rl) return rl;
+    if (!m->run_loaded) { msom_set_error("msom_run: %s was not written by msom_run (no record `run`)", ckpt); return MSOM_ERR_CONFIG; }
+    resumed = true;
+  }
   NEED_CONST(m);
   const Params &p = m->p;
   // tiled runs (one process / thread per tile): every call below that moves field data is collective; rank 0 alone
@@ -207,10 +219,12 @@ extern "C" int msom_run(msom_t *m, const char *workdir, long nsteps_max) {
   char dpath[600] = "", name[700];
   const char *wd = workdir ? workdir : ".";
   // create_outdir, msqg/qg.h:766-776
-  for (int i = 1; root && i < 10000; i++) {
+  int outdir = 0;
+  for (int i = 1; root && !resumed && i < 10000; i++) {
     snprintf(dpath, sizeof dpath, "%s/outdir_%04d/", wd, i);
     if (mkdir(dpath, 0777) == 0) {
       fprintf(stdout, "Writing output in %s\n", dpath);
+      outdir = i;
       break;
     }
   }
@@ -219,24 +233,31 @@ extern "C" int msom_run(msom_t *m, const char *workdir, long nsteps_max) {
   const bool filtering = p.dtflt > 0;
   long steps = 0;
   int r;
-  if (m->iter == 0 && (r = backup_config(m, dpath))) return r;  // event write_const (t = 0)
+  if (resumed) {   // the recorded output directory and event schedule
+    outdir = m->run_outdir; tout = m->run_tout; tflt = m->run_tflt;
+    snprintf(dpath, sizeof dpath, "%s/outdir_%04d/", wd, outdir);
+    if (root) { mkdir(dpath, 0777); fprintf(stdout, "Resuming from %s at i = %d, output in %s\n", ckpt, m->iter, dpath); }
+  }
+  if (!resumed && m->iter == 0 && (r = backup_config(m, dpath))) return r;  // event write_const (t = 0)
   for (;;) {
-    if (filtering && tflt <= p.tend + 1e-10 && m->t >= tflt - 1e-12 * fmax(1., fabs(tflt))) {
+    const bool skip = resumed;   // resumed: the events of this iteration ran before the checkpoint was written
+    resumed = false;
+    if (!skip && filtering && tflt <= p.tend + 1e-10 && m->t >= tflt - 1e-12 * fmax(1., fabs(tflt))) {
       // two events named `filter`: the later-defined one (qg_energy.h:269-272) runs first [BASILISK RULE 8]
       if (p.ediag > -1 && (r = filter_de(m, MSOM_PO_MFT, p.dtflt, (double)p.ediag))) return r;
       fprintf(stdout, "Filter solution\n");
       if ((r = msom_wavelet_filter(m, p.dtflt))) return r;
       tflt += p.dtflt;
     }
-    if (p.ediag > -1 && (r = msom_energy_tend(m, m->dt))) return r;  // event comp_diag (i++), qg_energy.h:289-291
+    if (!skip && p.ediag > -1 && (r = msom_energy_tend(m, m->dt))) return r;  // event comp_diag (i++), qg_energy.h:289-291
     // writestdout, msqg/qg.c:101-109
-    {
+    if (!skip) {
       const double ke = msom_ke(m);
       if (root) fprintf(stdout, "i = %i, dt = %g, t = %g, ke_1 = %g\n", m->iter, m->dt, m->t, ke);
     }
     // output, msqg/qg.c:112-122
     bool out_pending = tout <= p.tend + 1e-10;
-    if (out_pending && m->t >= tout - 1e-12 * fmax(1., fabs(tout))) {
+    if (!skip && out_pending && m->t >= tout - 1e-12 * fmax(1., fabs(tout))) {
       if (root) fprintf(stdout, "write file\n");
       if ((r = invertq(m, m->f[MSOM_Q]))) return r;
       snprintf(name, sizeof name, "%spo%09d.bas", dpath, m->iter);
@@ -279,6 +300,11 @@ extern "C" int msom_run(msom_t *m, const char *workdir, long nsteps_max) {
       out_pending = tout <= p.tend + 1e-10;
     }
     if (!out_pending) break;  // no scheduled event left: run() ends
+    // option "ckpt_steps": the checkpoint never moves tnext, so the run takes the dt sequence of a run without it
+    if (!skip && m->ckpt_steps > 0 && steps > 0 && m->iter % m->ckpt_steps == 0) {
+      const double run3[3] = {tout, tflt, (double)outdir};
+      if ((r = state_save_run(m, ckpt, MSOM_STATE_CONSTANTS, run3))) return r;
+    }
     if (nsteps_max >= 0 && steps >= nsteps_max) break;
     m->tnext = filtering && tflt <= p.tend + 1e-10 ? fmin(tout, tflt) : tout;
     if ((r = msom_step(m, nullptr))) return r;
