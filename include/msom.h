@@ -612,6 +612,7 @@ int msomn_read_nc(msomn_t *m, int field, const char *path, const char *varname, 
  * restart.nc and input_vars_<nl>l_N<N>.nc when present in the working directory, vars.nc in
  * <workdir>/outdir_%04d/, one stdout line per iteration; nsteps_max < 0: run to tend.
  * Returns the iteration count or < 0. */
+/* lossless fp64 checkpoint and bit-exact restart of a msomn_t, and the options "ckpt_steps" / "resume" of this loop: msomn_state.h */
 int msomn_run(msomn_t *m, const char *workdir, long nsteps_max);
 /* wavelet_filter of the vertex model, qg_baroclinic_ms.h:346-400 (event filter :405-408, driven by msomn_run when dtflt > 0):
  * invert q, masked wavelet transform (qg-node/wavelet_vertex.h:10-46) of the cell average of psi scaled by sig_lev

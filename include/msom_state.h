@@ -3,7 +3,7 @@
  * The reference restarts from p0.bas / restart.nc: psi as float32, q recomputed, time loop and statistics from zero.  These calls
  * save the model state of a handle in fp64 with everything the next step reads, so that a run that is stopped, saved, destroyed,
  * re-created, loaded and continued gives the bits of the run that was never stopped.  File format: DESIGN.md, "State file".
- * The vertex model (msomn_t) has no such file.
+ * The vertex model (msomn_t) has its own calls on the same container, dialect 2: msomn_state.h.
  *
  * What is saved: psi (the solver's first guess; with its ghost ring while they are stale after pystep_de), q, tracers, qof, the six
  *   MSOM_DE_* budgets, po_mft, the noise field, the AB3 history of the nudging loop by logical slot, the selected statistics
@@ -48,7 +48,7 @@ extern "C" {
 #define MSOM_STATE_CONSTANTS 1u
 
 typedef struct {
-  int version, dialect;          /* dialect: 0 msqg, 1 newqg */
+  int version, dialect;          /* dialect: 0 msqg, 1 newqg, 2 vertex model (msomn_state.h) */
   int nx, ny, nl, nptr;          /* global grid */
   int stochastic, noise_mode, mode_pv_invert, flag_topo;
   int nrecords;

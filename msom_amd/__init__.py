@@ -22,6 +22,7 @@ from .api import (  # noqa: F401
     from_state,
     init_grid,
     load_library,
+    node_from_state,
     pyp2q,
     pyq2p,
     pystep_bfn,
@@ -42,5 +43,5 @@ from .api import (  # noqa: F401
 __all__ = [
     "QG", "NodeQG", "NewQG", "NODE_FIELDS", "MGStats", "MsomError", "FIELDS", "STATS", "MODES", "load_library", "read_params", "init_grid", "set_vars",
     "set_vars_bfn", "set_const", "pystep_bfn", "bfn_begin", "bfn_steps", "bfn_misfit", "pystep_de", "pyq2p", "pyp2q", "trash_vars", "trash_vars_bfn", "spec_layout",
-    "from_state", "read_state", "write_state", "state_check", "state_info",
+    "from_state", "node_from_state", "read_state", "write_state", "state_check", "state_info",
 ]

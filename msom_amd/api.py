@@ -188,6 +188,11 @@ def load_library(strict=False):
         "msomn_wavelet_filter": (ci, [vp, cd]),
         "msomn_dbg_wv_get": (ci, [vp, ci, ci, vp]),
         "msomn_dbg_wv_apply": (ci, [vp, vp, vp]),
+        # lossless checkpoint / restart of the vertex model (include/msomn_state.h)
+        "msomn_state_save": (ci, [vp, cs, C.c_uint]),
+        "msomn_state_load": (ci, [vp, cs]),
+        "msomn_create_from_state": (vp, [cs]),
+        "msomn_state_dbg_flip": (ci, [vp, C.c_long]),
     }
     for fn, (res, args) in sig.items():
         f = getattr(L, fn)  # AttributeError if the library does not export a declared symbol
@@ -251,6 +256,19 @@ def from_state(path, strict=False):
     g.nx, g.ny = int(g.param("nx")), int(g.param("ny"))
     if not newqg:
         g.tile = (1, 1, 0, 0)
+    return g
+
+
+def node_from_state(path, strict=False):
+    """msomn_create_from_state: a vertex-grid model made from the params text in a state file saved with constants, loaded"""
+    L = load_library(strict)
+    h = L.msomn_create_from_state(os.fsencode(path))
+    if not h:
+        raise MsomError(L.msom_last_error().decode())
+    g = NodeQG.__new__(NodeQG)
+    g.L, g.h = L, h
+    g.N, g.nl = int(g.param("N")), int(g.param("nl"))
+    g.nlevels = int(g.param("nlevels"))
     return g
 
 
@@ -834,7 +852,9 @@ class NodeQG:
 
     def _chk(self, r):
         if r != 0:
-            raise MsomError(f"error {r}: {self.L.msom_last_error().decode()}")
+            e = MsomError(f"error {r}: {self.L.msom_last_error().decode()}")
+            e.code = r
+            raise e
 
     def _fid(self, f):
         return NODE_FIELDS[f] if isinstance(f, str) else int(f)
@@ -1009,3 +1029,13 @@ class NodeQG:
         out = np.empty_like(cells)
         self._chk(self.L.msomn_dbg_wv_apply(self.h, _ptr(cells), _ptr(out)))
         return out
+
+    # -- lossless checkpoint / restart (include/msomn_state.h)
+    def save_state(self, path, constants=False):
+        self._chk(self.L.msomn_state_save(self.h, os.fsencode(path), 1 if constants else 0))
+
+    def load_state(self, path):
+        self._chk(self.L.msomn_state_load(self.h, os.fsencode(path)))
+
+    def state_dbg_flip(self, element):
+        self._chk(self.L.msomn_state_dbg_flip(self.h, int(element)))

@@ -23,8 +23,9 @@ int main(int argc, char **argv) {
       bad = 1;
       continue;
     }
-    printf("%s: ok, version %d, dialect %d, %d x %d x %d, t = %.17g, iter = %ld, %d records: %s\n", argv[k], info.version, info.dialect, info.nx,
-           info.ny, info.nl, info.t, info.iter, nrec, names);
+    static const char *const dialects[] = {"msqg", "newqg", "vertex"};
+    printf("%s: ok, version %d, dialect %d (%s), %d x %d x %d, t = %.17g, iter = %ld, %d records: %s\n", argv[k], info.version, info.dialect,
+           info.dialect >= 0 && info.dialect < 3 ? dialects[info.dialect] : "unknown", info.nx, info.ny, info.nl, info.t, info.iter, nrec, names);
   }
   return bad;
 }

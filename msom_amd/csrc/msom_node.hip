@@ -4,114 +4,7 @@
 // :258-284, set_vars :404-450, set_const :465-524), qg_baroclinic_ms.h (rhs_pv_baroclinic :104-196,
 // comp_q :199-211, invert_q :217-225, init :449-510), qg_barotropic.h and the nodal multigrid
 // vpoisson (nodal-poisson.h:19-143) on top of the kernels of kernels_node.hip.  No CPU fallback.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <sys/stat.h>
-
-#include <algorithm>
-#include <string>
-#include <vector>
-
-#include "kernels.h"
-
-#define HIPCHK(x)                                                                          \
-  do {                                                                                     \
-    hipError_t e__ = (x);                                                                  \
-    if (e__ != hipSuccess) {                                                               \
-      msom_set_error("HIP error %s at %s:%d (%s)", hipGetErrorString(e__), __FILE__, __LINE__, #x); \
-      return MSOM_ERR_HIP;                                                                 \
-    }                                                                                      \
-  } while (0)
-
-struct NLevel {
-  int n;        // cells per side: (n + 1)^2 vertices
-  double D;     // L0 / n
-  NatGeom g;
-  double *da, *res, *mask, *S2;  // level 0: mask and S2 alias the model fields
-  double *da2;                   // second correction buffer (the tiled smoother works out of place)
-  // wide levels (option node_split): da and res in the x-parity split layout of geometry ga, with split copies of mask and S2
-  int sp = 0;
-  NatGeom ga;                    // geometry of da / res: g, or the split geometry
-  double *mask_s = nullptr, *S2_s = nullptr;
-  double *S2row_buf = nullptr;   // allocation behind S2row
-  double *S2row = nullptr;       // [nlm][n + 1] when S2 does not depend on x (and the option s2_rows is on), else null
-};
-enum { NSC_RES = 0, NSC_UMAX = 1, NSC_KE = 2, NSC_DIAG = 3 /* 3 slots */, NSC_COUNT = 8 };
-
-// option profile: HIP-event pairs around the finest-level launches of the vertex model (bench.py's per-kernel entries)
-struct NProf {
-  std::vector<hipEvent_t> ev;
-  size_t used = 0;
-  double total_ms = 0;
-  long launches = 0;
-};
-enum { NP_RELAX, NP_RELAX_PROLONG, NP_RESIDUAL, NP_CORRECT, NP_RHS, NP_COARSE, NP_MARCH, NP_CORR_RES, NP_COUNT };
-static const char *const NP_NAMES[NP_COUNT] = {"relax_fine", "relax_prolong_fine", "residual", "correct", "rhs", "coarse", "march_fine", "correct_residual"};
-
-struct msomn {
-  NodeParams p;
-  int profile = 0;
-  NProf prof[NP_COUNT];
-  std::string params_text;
-  int N = 0, nl = 1, nlm = 1;
-  double D = 0, psi_bc = 0., iRd2_low = 0.;
-  double tolerance = 1e-3;
-  int nitermax = 100, nitermin = 1, nrelax = 5, quiet = 0;  // nodal-poisson.h:19-23
-  // stochastic forcing (-D_STOCHASTIC of the reference): cell-scalar noise n_stoch, wavelet-filtered (qg-node/qg_stochastic.h)
-  int stochastic = 0, corrector_step = 0, cnlev = 0;
-  // option noise_mode: 0 the reference's serial rand() stream on the host (one per process), 1 the counter-based device generator
-  // k_n_noise, keyed by the handle's seed and numbered by the handle's draw counter (set_const: 0)
-  int noise_mode = 0;
-  unsigned seed = 1, noise_draw = 0;
-  int pg_set = 0, topo_set = 0;   // psi_pg / topo have been set (zero until then: their terms of the tendency are skipped by k_n_rhs_all)
-  int forcing_3d = 0;  // -DFORCING_3D: switched on by setting MSOMN_QFORC3D
-  int sqg = 0;         // surface-QG variant (params key sqg): sqg_baroclinic_ms.h:77-98,502,545-547
-  double *qeff = nullptr, *d2bs = nullptr;  // sqg scratch: rhs of the inversion, laplacian(bs)
-  // wavelet filter of the vertex model (qg_baroclinic_ms.h:346-400): cell pyramids of s, r (nl layers), sig_lev, mask_c
-  std::vector<NatGeom> wg;
-  std::vector<double *> ws, wr, wsig, wmc;
-  int wv_ready = 0, nbar = 0;
-  std::vector<NatGeom> cg;
-  std::vector<double *> cs, cr, csig;  // cs[0] = n_stoch
-  int mg_coarse = 32;   // the levels of <= (mg_coarse + 1)^2 vertices of a cycle in one launch (k_n_mg_coarse); 0: off
-  int node_march_rows = 0;  // option: chunk height of the marching passes (0: automatic; k_n_relax_march_s: 12)
-  int node_march = 0;   // levels of >= node_march vertices per side: K = 4 chained colour half-sweeps per pass (k_n_relax_march, rows
-                        // software-prefetched one step ahead).  Measured at 2049^2 x 3: 27.1 vs 26.6 ms per step, 513^2 x 3: 4.2 vs 3.1 --
-                        // half the bytes, but in the natural layout half of the lanes idle in every half-sweep and the vertex column
-                        // solve (vertex-dependent coefficients, one reciprocal per layer) is arithmetic-bound: off
-  int node_pfused = 1;   // option: prolongation folded into the first colour pass of the split levels
-  int node_tile_max = 513;  // option: ... and of <= node_tile_max vertices per side (wider levels: the colour passes are no longer launch-bound)
-  int node_march_tail1 = 1; // option: 9 half-sweeps as passes of 4 + 4 + a colour pass (measured 13.96 -> 13.43 ms per step) instead of 4 + 3 + 2 (0)
-  int node_tile_k = 8;      // option: half-sweeps per LDS-tiled pass (2..8)
-  int node_tile_s = 65;     // option: split levels of >= node_tile_s (and < node_march_s) vertices per side: LDS-tiled passes of up to 4 colour half-sweeps (0: off)
-  int node_rhs_fused = 1;   // option: the baroclinic tendency in three passes (k_n_rhs_pre, k_n_del2_bnd, k_n_rhs_all) instead of twelve
-  int node_corr_fused = 2;  // option: the correction a += da rides in the next cycle's residual pass (k_n_correct_residual)
-  double *psi_alt = nullptr;
-  hipEvent_t ev_res = nullptr;   // marks the copy of max |res| to the host inside vpoisson
-  int node_march_s = 2049;  // option: split levels of >= node_march_s vertices per side chain up to 4 colour half-sweeps per pass (k_n_relax_march_s,
-                            // round 3).  2049^2 x 3, 9 cycles per solve (tools/ab_node_prof.py): 3 passes of 83 us replace 9 colour launches of 33 us:
-                            // 17.3 -> 16.6 ms per step; on the 1025^2 and 513^2 levels the pass loses (17.4 / 18.4): too few chunks for a
-                            // marching wavefront; three steps of software prefetch instead of one and chunk heights 8 .. 24 change nothing
-  int s2_xuniform = 0;   // set_const: S2 does not depend on x
-  int s2_rows = 1;       // option: use row tables of S2 in the smoother and the residual when S2 does not depend on x
-  int node_split = 65;   // option: levels of >= node_split vertices per side keep da / res / mask / S2 copies in the x-parity split layout (0: off)
-  int tiled_relax = 0;  // option: LDS-tiled smoother passes (1-2 sweeps per pass) on the wide levels; measured 3 % faster at 4097^2 x 3, 7 % slower at 2049^2 x 3
-  NatGeom g;
-  double *f[MSOMN_NFIELDS] = {nullptr};
-  int fl[MSOMN_NFIELDS] = {0};
-  LayerCoef lc;
-  int nlev = 0;
-  std::vector<NLevel> lev;
-  double *d_scal = nullptr, *h_scal = nullptr, *partial = nullptr, *d_row = nullptr, *h_row = nullptr;
-  hipStream_t st = nullptr;
-  int const_set = 0;
-  double t = 0, dt = 1., tnext = HUGE_VAL, previous = 0;
-  int iter = 0;
-  msom_mgstats mg = {0, 0, 0, 0, 0};
-};
+#include "msomn_host.h"
 
 static void nprof_begin(msomn *m, int slot) {
   if (!m->profile) return;
@@ -167,7 +60,7 @@ static int field_layers(const msomn *m, int f) {
 }
 
 // [layers][n+1][n+1] contiguous (host or device) <-> padded natural layout
-static int upload_g(msomn *m, double *dst, const NatGeom &g, int nl, const double *a) {
+int upload_g(msomn *m, double *dst, const NatGeom &g, int nl, const double *a) {
   const size_t n1 = g.nx;
   for (int l = 0; l < nl; l++)
     HIPCHK(hipMemcpy2DAsync(dst + nat_idx(g, l, 0, 0), g.pitch * sizeof(double), a + (size_t)l * n1 * n1, n1 * sizeof(double), n1 * sizeof(double), n1,
@@ -175,7 +68,7 @@ static int upload_g(msomn *m, double *dst, const NatGeom &g, int nl, const doubl
   HIPCHK(hipStreamSynchronize(m->st));
   return MSOM_OK;
 }
-static int download_g(msomn *m, const double *src, const NatGeom &g, int nl, double *a) {
+int download_g(msomn *m, const double *src, const NatGeom &g, int nl, double *a) {
   const size_t n1 = g.nx;
   for (int l = 0; l < nl; l++)
     HIPCHK(hipMemcpy2DAsync(a + (size_t)l * n1 * n1, n1 * sizeof(double), src + nat_idx(g, l, 0, 0), g.pitch * sizeof(double), n1 * sizeof(double), n1,
@@ -335,6 +228,8 @@ extern "C" int msomn_set_option(msomn_t *m, const char *key, double v) {
   else if (!strcmp(key, "node_march_rows")) m->node_march_rows = (int)v;
   else if (!strcmp(key, "mg_coarse")) { m->mg_coarse = (int)v; if (m->const_set) return choose_layouts(m); }
   else if (!strcmp(key, "stochastic")) m->stochastic = (int)v;
+  else if (!strcmp(key, "ckpt_steps")) m->ckpt_steps = (int)v;   // msomn_run, include/msomn_state.h
+  else if (!strcmp(key, "resume")) m->resume = (int)v;
   else if (!strcmp(key, "seed")) { m->seed = (unsigned)v; srand(m->seed); }
   else if (!strcmp(key, "noise_mode")) {
     if (v != 0. && v != 1.) { msom_set_error("noise_mode = %g: 0 (serial rand() stream on the host) or 1 (device generator)", v); return MSOM_ERR_ARG; }
@@ -784,7 +679,7 @@ static int adjust_dt(msomn *m, double dtmax, double *out) {
 }
 
 // ---- stochastic forcing: qg-node/qg_stochastic.h (init_stoch :15-47, generate_noise :49-65), advance qg-node/qg.h:306-320
-static NatGeom cell_geom(int n) {
+NatGeom cell_geom(int n) {
   NatGeom g;
   g.nx = g.ny = n;
   g.pitch = ((n + 15) / 16) * 16 + 2 * MSOM_XP;
@@ -836,6 +731,7 @@ static int stoch_setup(msomn *m) {  // pyramids of the cell scalar + wavelet coe
   return MSOM_OK;
 }
 static void cell_bc(msomn *m, double *f, const NatGeom &g) { launch_fill_ghost(m->st, f, g, 1, BC_NEUMANN, WALL_ALL); }
+void node_noise_ghosts(msomn *m) { cell_bc(m, m->cs[0], m->cg[0]); }
 // wavelet -> scale by sig_lev -> inverse wavelet of the cell field cs[0] (kernels_wavelet.hip, one layer, default BC)
 // ghosts_set: the ghost ring of cs[0] is already what cell_bc would write (k_n_noise)
 static int cell_wavelet_filter(msomn *m, int ghosts_set = 0) {
@@ -1041,53 +937,82 @@ extern "C" int msomn_dbg_wv_apply(msomn_t *m, const double *in, double *out) {
   return MSOM_OK;
 }
 
-extern "C" int msomn_set_const(msomn_t *m) {
-  if (!m) return MSOM_ERR_ARG;
-  NodeParams &p = m->p;
-  const int nl = m->nl, N = m->N;
-  const size_t n1 = N + 1;
+// msomn_set_const in two parts (msomn_host.h): the state file holds the inputs after node_const_inputs, and a load into a handle
+// without constants installs them as they are and runs node_const_derived alone
+static int check_dh(const msomn *m) {
+  for (int l = 0; m->nl > 1 && l < m->nl; l++)
+    if (m->p.dh[l] == 0.) { msom_set_error("thickness = 0: check the definition of dh in params.in"); return MSOM_ERR_CONFIG; }
+  return MSOM_OK;
+}
+int node_const_inputs(msomn *m) {
+  const NodeParams &p = m->p;
+  const int nl = m->nl;
+  const size_t n1 = m->N + 1;
   int r;
+  if ((r = check_dh(m))) return r;
+  if (nl == 1) return MSOM_OK;
+  // S2: N^2 -> f^2 / N^2 with f = f0 + flag_ms beta (y - L0/2)  (qg_baroclinic_ms.h:501-505); init-time host pass
+  std::vector<double> h(n1 * n1 * m->nlm);
+  if ((r = download_g(m, m->f[MSOMN_S2], m->g, m->nlm, h.data()))) return r;
+  for (int l = 0; l < nl - 1; l++) for (size_t j = 0; j < n1; j++) {
+    const double f = p.f0 + p.flag_ms * p.beta * (j * m->D - 0.5 * p.L0);
+    for (size_t i = 0; i < n1; i++) { double &s = h[(l * n1 + j) * n1 + i]; s = f * f / s; }
+  }
+  if ((r = upload_g(m, m->f[MSOMN_S2], m->g, m->nlm, h.data()))) return r;
+  if (m->sqg) {  // :545 surface layer: f / N^2 (f, not f^2)
+    std::vector<double> hs(n1 * n1);
+    if ((r = download_g(m, m->f[MSOMN_S2S], m->g, 1, hs.data()))) return r;
+    for (size_t j = 0; j < n1; j++) {
+      const double f = p.f0 + p.flag_ms * p.beta * (j * m->D - 0.5 * p.L0);
+      for (size_t i = 0; i < n1; i++) hs[j * n1 + i] = f / hs[j * n1 + i];
+    }
+    if ((r = upload_g(m, m->f[MSOMN_S2S], m->g, 1, hs.data()))) return r;
+  }
+  if (p.scale_topo != 1.) {
+    std::vector<double> tp(n1 * n1);
+    if ((r = download_g(m, m->f[MSOMN_TOPO], m->g, 1, tp.data()))) return r;
+    for (double &v : tp) v *= p.scale_topo;
+    if ((r = upload_g(m, m->f[MSOMN_TOPO], m->g, 1, tp.data()))) return r;
+  }
+  return MSOM_OK;
+}
+double node_clamped_dt(const msomn *m) {
+  const NodeParams &p = m->p;
+  double DT = p.DT;
+  if (p.nu != 0) DT = 0.5 * fmin(DT, m->D * m->D / p.nu / 4.);  // qg-node/qg.h:511-512
+  if (p.beta != 0) DT = fmin(DT, 1 / (2. * p.beta * p.L0));
+  return DT;
+}
+int node_const_derived(msomn *m) {
+  NodeParams &p = m->p;
+  const int nl = m->nl;
+  const size_t n1 = m->N + 1;
+  int r;
+  if ((r = check_dh(m))) return r;
   if (nl > 1) {
-    for (int l = 0; l < nl; l++) if (p.dh[l] == 0.) { msom_set_error("thickness = 0: check the definition of dh in params.in"); return MSOM_ERR_CONFIG; }
     double dhc[MSOM_MAXNL];
     for (int l = 0; l < nl - 1; l++) dhc[l] = 0.5 * (p.dh[l] + p.dh[l + 1]);
     m->lc.idh0[0] = m->sqg ? 1. / p.dh[0] : 0.;  // sqg_baroclinic_ms.h:502 "surface layer: 1/h"
     m->lc.idh1[0] = 1. / (dhc[0] * p.dh[0]);
     for (int l = 1; l < nl - 1; l++) { m->lc.idh0[l] = 1. / (dhc[l - 1] * p.dh[l]); m->lc.idh1[l] = 1. / (dhc[l] * p.dh[l]); }
     m->lc.idh0[nl - 1] = 1. / (dhc[nl - 2] * p.dh[nl - 1]); m->lc.idh1[nl - 1] = 0.;
-    // S2: N^2 -> f^2 / N^2 with f = f0 + flag_ms beta (y - L0/2)  (qg_baroclinic_ms.h:501-505); init-time host pass
-    std::vector<double> h(n1 * n1 * m->nlm);
+    std::vector<double> h(n1 * n1 * m->nlm);   // the transformed S2
     if ((r = download_g(m, m->f[MSOMN_S2], m->g, m->nlm, h.data()))) return r;
-    for (int l = 0; l < nl - 1; l++) for (size_t j = 0; j < n1; j++) {
-      const double f = p.f0 + p.flag_ms * p.beta * (j * m->D - 0.5 * p.L0);
-      for (size_t i = 0; i < n1; i++) { double &s = h[(l * n1 + j) * n1 + i]; s = f * f / s; }
-    }
-    if ((r = upload_g(m, m->f[MSOMN_S2], m->g, m->nlm, h.data()))) return r;
     m->s2_xuniform = 1;
     for (size_t r0 = 0; r0 < (size_t)(nl - 1) * n1 && m->s2_xuniform; r0++)
       for (size_t i = 1; i < n1; i++) if (h[r0 * n1 + i] != h[r0 * n1]) { m->s2_xuniform = 0; break; }
-    if (m->sqg) {  // :545 surface layer: f / N^2 (f, not f^2)
-      std::vector<double> hs(n1 * n1);
-      if ((r = download_g(m, m->f[MSOMN_S2S], m->g, 1, hs.data()))) return r;
-      for (size_t j = 0; j < n1; j++) {
-        const double f = p.f0 + p.flag_ms * p.beta * (j * m->D - 0.5 * p.L0);
-        for (size_t i = 0; i < n1; i++) hs[j * n1 + i] = f / hs[j * n1 + i];
-      }
-      if ((r = upload_g(m, m->f[MSOMN_S2S], m->g, 1, hs.data()))) return r;
-    }
-    if (p.scale_topo != 1.) {
-      std::vector<double> tp(n1 * n1);
-      if ((r = download_g(m, m->f[MSOMN_TOPO], m->g, 1, tp.data()))) return r;
-      for (double &v : tp) v *= p.scale_topo;
-      if ((r = upload_g(m, m->f[MSOMN_TOPO], m->g, 1, tp.data()))) return r;
-    }
   } else if (p.gp_low != 0.) m->iRd2_low = p.f0 * p.f0 / (p.gp_low * p.dh[nl - 1]);
   if ((r = build_levels(m))) return r;
   if (m->stochastic && (r = stoch_setup(m))) return r;  // event init_stoch
-  m->noise_draw = 0;
   bnd_psi(m);
-  if (p.nu != 0) p.DT = 0.5 * fmin(p.DT, m->D * m->D / p.nu / 4.);  // qg-node/qg.h:511-512
-  if (p.beta != 0) p.DT = fmin(p.DT, 1 / (2. * p.beta * p.L0));
+  p.DT = node_clamped_dt(m);
+  return MSOM_OK;
+}
+extern "C" int msomn_set_const(msomn_t *m) {
+  if (!m) return MSOM_ERR_ARG;
+  int r;
+  if ((r = node_const_inputs(m)) || (r = node_const_derived(m))) return r;
+  m->noise_draw = 0;
   if ((r = comp_q(m, m->f[MSOMN_PSI], m->f[MSOMN_Q]))) return r;
   HIPCHK(hipStreamSynchronize(m->st));
   m->const_set = 1;
@@ -1255,120 +1180,4 @@ extern "C" int msomn_dbg_prolong(msomn_t *m, int k, const double *coarse, double
 extern "C" int msomn_dbg_level_mask(msomn_t *m, int k, double *out) {
   NEED_NCONST(m); NEED_LEVEL(m, k);
   return download_g(m, m->lev[k].mask, m->lev[k].g, 1, out);
-}
-
-// ---- NetCDF-3 IO of vertex fields (qg-node/netcdf_vertex_bas.h:95-424)
-extern "C" int msomn_write_nc(msomn_t *m, const char *path) {
-  if (!m || !path) return MSOM_ERR_ARG;
-  const size_t n1 = m->N + 1, sz = n1 * n1 * m->nl;
-  std::vector<double> psi(sz), q(sz);
-  int r;
-  if ((r = download_g(m, m->f[MSOMN_PSI], m->g, m->nl, psi.data())) || (r = download_g(m, m->f[MSOMN_Q], m->g, m->nl, q.data()))) return r;
-  const char *names[2] = {"psi", "q"};
-  struct stat sb;
-  if (stat(path, &sb) != 0 && msom_nc_create2(path, m->nl, (int)n1, (int)n1, m->p.L0, 2, names, 1)) return MSOM_ERR_IO;
-  const double *fields[2] = {psi.data(), q.data()};
-  return msom_nc_append(path, m->nl, (int)n1, (int)n1, 2, names, m->t, fields) < 0 ? MSOM_ERR_IO : MSOM_OK;
-}
-extern "C" int msomn_read_nc(msomn_t *m, int field, const char *path, const char *varname, int record) {
-  NEED_FIELD(m, field);
-  if (!path || !varname) return MSOM_ERR_ARG;
-  const size_t n1 = m->N + 1;
-  std::vector<double> h(n1 * n1 * m->fl[field]);
-  if (msom_nc_read(path, varname, record, m->fl[field], (int)n1, (int)n1, h.data(), nullptr)) return MSOM_ERR_IO;
-  if (field == MSOMN_PSIPG) m->pg_set = 1;
-  if (field == MSOMN_TOPO) m->topo_set = 1;
-  return upload_g(m, m->f[field], m->g, m->fl[field], h.data());
-}
-
-// main() + events of qg-node/qg.c:58-181
-extern "C" int msomn_run(msomn_t *m, const char *workdir, long nsteps_max) {
-  if (!m) return MSOM_ERR_ARG;
-  const NodeParams &p = m->p;
-  const char *wd = workdir ? workdir : ".";
-  char dpath[600] = "", name[800];
-  int r;
-  const size_t n1 = m->N + 1;
-  for (int i = 1; i < 10000; i++) {  // create_outdir, extra.h:122-135
-    snprintf(dpath, sizeof dpath, "%s/outdir_%04d/", wd, i);
-    if (mkdir(dpath, 0777) == 0) { fprintf(stdout, "Writing output in %s\n", dpath); break; }
-  }
-  snprintf(name, sizeof name, "%sparams.in", dpath);  // backup_config
-  if (FILE *fp = fopen(name, "w")) { fwrite(m->params_text.data(), 1, m->params_text.size(), fp); fclose(fp); }
-  if (!m->const_set) {
-    // init (qg_baroclinic_ms.h:478-492): optional input file, variables N2, psi_pg, mask, topo, q_forcing
-    if (m->nl > 1) {
-      snprintf(name, sizeof name, "%s/input_vars_%dl_N%d.nc", wd, m->nl, m->N);
-      struct stat sb;
-      if (stat(name, &sb) == 0) {
-        fprintf(stdout, "Read input files:\n");
-        const struct { int f; const char *v; } in[] = {{MSOMN_S2, "N2"}, {MSOMN_PSIPG, "psi_pg"}, {MSOMN_MASK, "mask"}, {MSOMN_TOPO, "topo"}, {MSOMN_QFORC, "q_forcing"}};
-        for (auto &e : in) (void)msomn_read_nc(m, e.f, name, e.v, 0);  // absent variables keep their defaults
-        {  // q_forcing_3d: only when the file has it (msomn_read_nc would switch FORCING_3D on)
-          std::vector<double> h3((size_t)(m->N + 1) * (m->N + 1) * m->nl);
-          if (!msom_nc_read(name, "q_forcing_3d", 0, m->nl, m->N + 1, m->N + 1, h3.data(), nullptr)) (void)msomn_set_field(m, MSOMN_QFORC3D, h3.data());
-        }
-        fprintf(stdout, "%s .. ok\n", name);
-      }
-    }
-    // set_const qg-node/qg.h:475-479: psi = noise_init (noise() + sin(2 pi y / L0)); noise() in [-1, 1]
-    std::vector<double> h(n1 * n1 * m->nl);
-    for (size_t j = 0; j < n1; j++) for (size_t i = 0; i < n1; i++) for (int l = 0; l < m->nl; l++)
-      h[(l * n1 + j) * n1 + i] = p.noise_init * ((1. - 2. * rand() / (double)RAND_MAX) + sin(2 * M_PI * (j * m->D) / p.L0));
-    if ((r = upload_g(m, m->f[MSOMN_PSI], m->g, m->nl, h.data()))) return r;
-    snprintf(name, sizeof name, "%s/restart.nc", wd);
-    struct stat sb;
-    if (stat(name, &sb) == 0) {
-      fprintf(stdout, "Read restart file:\n");
-      if ((r = msomn_read_nc(m, MSOMN_PSI, name, "psi", -1))) return r;
-      fprintf(stdout, "%s .. ok\n", name);
-    }
-    if ((r = msomn_set_const(m))) return r;
-  }
-  snprintf(name, sizeof name, "%svars.nc", dpath);
-  double tout = 0., tdiag = 0., tflt = p.dtflt;   // event filter (t = dtflt; t <= tend + 1e-10; t += dtflt), qg_baroclinic_ms.h:405-408
-  const bool diag = p.dtdiag > 0, filt = p.dtflt > 0;
-  char dname[800];
-  snprintf(dname, sizeof dname, "%sdiag_1d.dat", dpath);
-  long steps = 0;
-  for (;;) {
-    if (diag && tdiag <= p.tend + 1e-10 && m->t >= tdiag - 1e-12 * fmax(1., fabs(tdiag))) {  // write_1d_diag (qg.h:361-399)
-      if (FILE *fp = fopen(dname, "a")) {
-        if (m->iter == 0) fprintf(fp, "# time, ke, dissipation, forcing\n");
-        else {
-          double d3[3];
-          if ((r = msomn_diag1d(m, d3))) { fclose(fp); return r; }
-          fprintf(fp, "%e, %e, %e, %e\n", m->t, d3[0], d3[1], d3[2]);
-        }
-        fclose(fp);
-      }
-      tdiag += p.dtdiag;
-    }
-    if ((r = msomn_forcing(m))) return r;  // forcing (i++)
-    if (filt && tflt <= p.tend + 1e-10 && m->t >= tflt - 1e-12 * fmax(1., fabs(tflt))) {
-      fprintf(stdout, "Filter solution\n");
-      if ((r = msomn_wavelet_filter(m, p.dtflt))) return r;
-      tflt += p.dtflt;
-    }
-    bool pending = tout <= p.tend + 1e-10;
-    if (pending && m->t >= tout - 1e-12 * fmax(1., fabs(tout))) {  // output (t = 0; t <= tend + 1e-10; t += dtout)
-      fprintf(stdout, "write file\n");
-      if (m->iter == 0 && (r = invert_q(m, m->f[MSOMN_Q]))) return r;
-      if ((r = msomn_write_nc(m, name))) return r;
-      fprintf(stdout, "file written \n");
-      tout += p.dtout;
-      pending = tout <= p.tend + 1e-10;
-    }
-    double ke;
-    if ((r = msomn_ke(m, &ke))) return r;
-    fprintf(stdout, "i = %i, dt = %g, t = %g, ke_1 = %g\n", m->iter, m->dt, m->t, ke);  // writestdout
-    if (!pending) break;
-    if (nsteps_max >= 0 && steps >= nsteps_max) break;
-    m->tnext = diag && tdiag <= p.tend + 1e-10 ? fmin(tout, tdiag) : tout;
-    if (filt && tflt <= p.tend + 1e-10) m->tnext = fmin(m->tnext, tflt);
-    if ((r = msomn_step(m, 0))) return r;
-    steps++;
-  }
-  fflush(stdout);
-  return m->iter;
 }

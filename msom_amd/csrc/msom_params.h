@@ -37,6 +37,8 @@ int msom_nc_create(const char *path, int nl, int ny, int nx, double L0, int nvar
 int msom_nc_create2(const char *path, int nl, int ny, int nx, double L0, int nvars, const char *const *names, int vertex);
 int msom_nc_append(const char *path, int nl, int ny, int nx, int nvars, const char *const *names, double time, const double *const *fields);
 int msom_nc_read(const char *path, const char *name, int rec, int nl, int ny, int nx, double *out, double *time_out);
+/* sets a file back to its first nrec records (numrecs rewritten, the rest cut off); a file that holds fewer is refused */
+int msom_nc_truncate(const char *path, long nrec);
 void msom_set_error(const char *fmt, ...);
 
 /* parameters of the vertex-grid variant: qg-node/qg.c:72-107 (add_param list), defaults

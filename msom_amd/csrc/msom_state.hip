@@ -5,6 +5,7 @@
 
 #include "msom_host.h"
 #include "state_io.h"
+#include "state_pipe.h"
 #include "../../include/msom_state.h"
 
 namespace {
@@ -43,47 +44,12 @@ int target_layers(const msom *m, const RecName &n) {
 struct Item { const char *name; const double *dev; int layers, ring; };
 struct Scal { const char *name; std::vector<double> v; };
 
-const size_t CHUNK_DOUBLES = (size_t)4 << 20;   // 32 MB per staging chunk
-
 StateChunk chunk_of(const msom *m, int ring, int layer, int y0, int rows, int sx0, int sw) {
   StateChunk c;
   c.g = m->g; c.ring = ring; c.layer = layer; c.y0 = y0; c.rows = rows; c.ox = m->ix * m->nx; c.oy = m->iy * m->ny;
   c.gW = m->gnx + 2 * ring; c.gH = m->gny + 2 * ring; c.sx0 = sx0; c.sw = sw;
   return c;
 }
-
-// staging of one call: two device chunks and two pinned host chunks, a second stream for the copies, events between the two streams
-struct Pipe {
-  double *d[2] = {nullptr, nullptr}, *h[2] = {nullptr, nullptr};
-  hipStream_t s2 = nullptr;
-  hipEvent_t packed[2] = {nullptr, nullptr}, copied[2] = {nullptr, nullptr};
-  unsigned long long *dig = nullptr, *h_dig = nullptr;   // device digest words (this rank's, then one per rank), pinned copy
-  size_t cap = 0;
-  int init(size_t doubles, int nranks) {
-    cap = doubles;
-    for (int b = 0; b < 2; b++) {
-      HIPCHK(hipMalloc(&d[b], cap * sizeof(double)));
-      HIPCHK(hipHostMalloc(&h[b], cap * sizeof(double)));
-      HIPCHK(hipEventCreateWithFlags(&packed[b], hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&copied[b], hipEventDisableTiming));
-    }
-    HIPCHK(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
-    HIPCHK(hipMalloc(&dig, (size_t)(nranks + 1) * sizeof(unsigned long long)));
-    HIPCHK(hipHostMalloc(&h_dig, (size_t)(nranks + 1) * sizeof(unsigned long long)));
-    return MSOM_OK;
-  }
-  ~Pipe() {
-    if (s2) { (void)hipStreamSynchronize(s2); (void)hipStreamDestroy(s2); }
-    for (int b = 0; b < 2; b++) {
-      if (d[b]) (void)hipFree(d[b]);
-      if (h[b]) (void)hipHostFree(h[b]);
-      if (packed[b]) (void)hipEventDestroy(packed[b]);
-      if (copied[b]) (void)hipEventDestroy(copied[b]);
-    }
-    if (dig) (void)hipFree(dig);
-    if (h_dig) (void)hipHostFree(h_dig);
-  }
-};
 
 // this rank's digest word, summed over the ranks (tiles: one all-gather of the words; integer sums, so the order is free)
 int digest_total(msom *m, Pipe &pp, uint64_t *out) {
@@ -565,6 +531,11 @@ extern "C" msom_t *msom_create_from_state(const char *path) {
   if (!path) { msom_set_error("msom_create_from_state: null path"); return nullptr; }
   msom_sfile sf;
   if (msom_sfile_open(path, &sf, 0)) return nullptr;
+  if (sf.dialect > 1) {   // a newer dialect must not become a newqg handle
+    msom_set_error("msom_create_from_state: %s holds dialect %u%s", path, sf.dialect, sf.dialect == 2 ? ", the vertex model: use msomn_create_from_state" : "");
+    msom_sfile_free(&sf);
+    return nullptr;
+  }
   msom_t *m = sf.dialect ? msom_create_newqg_str(sf.params) : msom_create_str(sf.params);
   int r = m ? MSOM_OK : MSOM_ERR_CONFIG;
   if (m && !sf.dialect) {

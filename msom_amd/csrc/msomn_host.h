@@ -1,0 +1,137 @@
+// msomn_host.h -- the vertex-grid handle (struct msomn) and the host helpers its units share: msom_node.hip (model and multigrid),
+// msomn_io.hip (NetCDF IO and the driver msomn_run), msomn_state.hip (state file, include/msomn_state.h).  Not installed.
+#ifndef MSOMN_HOST_H
+#define MSOMN_HOST_H
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <sys/stat.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "kernels.h"
+
+#define HIPCHK(x)                                                                          \
+  do {                                                                                     \
+    hipError_t e__ = (x);                                                                  \
+    if (e__ != hipSuccess) {                                                               \
+      msom_set_error("HIP error %s at %s:%d (%s)", hipGetErrorString(e__), __FILE__, __LINE__, #x); \
+      return MSOM_ERR_HIP;                                                                 \
+    }                                                                                      \
+  } while (0)
+
+struct NLevel {
+  int n;        // cells per side: (n + 1)^2 vertices
+  double D;     // L0 / n
+  NatGeom g;
+  double *da, *res, *mask, *S2;  // level 0: mask and S2 alias the model fields
+  double *da2;                   // second correction buffer (the tiled smoother works out of place)
+  // wide levels (option node_split): da and res in the x-parity split layout of geometry ga, with split copies of mask and S2
+  int sp = 0;
+  NatGeom ga;                    // geometry of da / res: g, or the split geometry
+  double *mask_s = nullptr, *S2_s = nullptr;
+  double *S2row_buf = nullptr;   // allocation behind S2row
+  double *S2row = nullptr;       // [nlm][n + 1] when S2 does not depend on x (and the option s2_rows is on), else null
+};
+enum { NSC_RES = 0, NSC_UMAX = 1, NSC_KE = 2, NSC_DIAG = 3 /* 3 slots */, NSC_COUNT = 8 };
+
+// option profile: HIP-event pairs around the finest-level launches of the vertex model (bench.py's per-kernel entries)
+struct NProf {
+  std::vector<hipEvent_t> ev;
+  size_t used = 0;
+  double total_ms = 0;
+  long launches = 0;
+};
+enum { NP_RELAX, NP_RELAX_PROLONG, NP_RESIDUAL, NP_CORRECT, NP_RHS, NP_COARSE, NP_MARCH, NP_CORR_RES, NP_COUNT };
+static const char *const NP_NAMES[NP_COUNT] = {"relax_fine", "relax_prolong_fine", "residual", "correct", "rhs", "coarse", "march_fine", "correct_residual"};
+
+struct msomn {
+  NodeParams p;
+  int profile = 0;
+  NProf prof[NP_COUNT];
+  std::string params_text;
+  int N = 0, nl = 1, nlm = 1;
+  double D = 0, psi_bc = 0., iRd2_low = 0.;
+  double tolerance = 1e-3;
+  int nitermax = 100, nitermin = 1, nrelax = 5, quiet = 0;  // nodal-poisson.h:19-23
+  // stochastic forcing (-D_STOCHASTIC of the reference): cell-scalar noise n_stoch, wavelet-filtered (qg-node/qg_stochastic.h)
+  int stochastic = 0, corrector_step = 0, cnlev = 0;
+  // option noise_mode: 0 the reference's serial rand() stream on the host (one per process), 1 the counter-based device generator
+  // k_n_noise, keyed by the handle's seed and numbered by the handle's draw counter (set_const: 0)
+  int noise_mode = 0;
+  unsigned seed = 1, noise_draw = 0;
+  int pg_set = 0, topo_set = 0;   // psi_pg / topo have been set (zero until then: their terms of the tendency are skipped by k_n_rhs_all)
+  int forcing_3d = 0;  // -DFORCING_3D: switched on by setting MSOMN_QFORC3D
+  int sqg = 0;         // surface-QG variant (params key sqg): sqg_baroclinic_ms.h:77-98,502,545-547
+  double *qeff = nullptr, *d2bs = nullptr;  // sqg scratch: rhs of the inversion, laplacian(bs)
+  // wavelet filter of the vertex model (qg_baroclinic_ms.h:346-400): cell pyramids of s, r (nl layers), sig_lev, mask_c
+  std::vector<NatGeom> wg;
+  std::vector<double *> ws, wr, wsig, wmc;
+  int wv_ready = 0, nbar = 0;
+  std::vector<NatGeom> cg;
+  std::vector<double *> cs, cr, csig;  // cs[0] = n_stoch
+  int mg_coarse = 32;   // the levels of <= (mg_coarse + 1)^2 vertices of a cycle in one launch (k_n_mg_coarse); 0: off
+  int node_march_rows = 0;  // option: chunk height of the marching passes (0: automatic; k_n_relax_march_s: 12)
+  int node_march = 0;   // levels of >= node_march vertices per side: K = 4 chained colour half-sweeps per pass (k_n_relax_march, rows
+                        // software-prefetched one step ahead).  Measured at 2049^2 x 3: 27.1 vs 26.6 ms per step, 513^2 x 3: 4.2 vs 3.1 --
+                        // half the bytes, but in the natural layout half of the lanes idle in every half-sweep and the vertex column
+                        // solve (vertex-dependent coefficients, one reciprocal per layer) is arithmetic-bound: off
+  int node_pfused = 1;   // option: prolongation folded into the first colour pass of the split levels
+  int node_tile_max = 513;  // option: ... and of <= node_tile_max vertices per side (wider levels: the colour passes are no longer launch-bound)
+  int node_march_tail1 = 1; // option: 9 half-sweeps as passes of 4 + 4 + a colour pass (measured 13.96 -> 13.43 ms per step) instead of 4 + 3 + 2 (0)
+  int node_tile_k = 8;      // option: half-sweeps per LDS-tiled pass (2..8)
+  int node_tile_s = 65;     // option: split levels of >= node_tile_s (and < node_march_s) vertices per side: LDS-tiled passes of up to 4 colour half-sweeps (0: off)
+  int node_rhs_fused = 1;   // option: the baroclinic tendency in three passes (k_n_rhs_pre, k_n_del2_bnd, k_n_rhs_all) instead of twelve
+  int node_corr_fused = 2;  // option: the correction a += da rides in the next cycle's residual pass (k_n_correct_residual)
+  double *psi_alt = nullptr;
+  hipEvent_t ev_res = nullptr;   // marks the copy of max |res| to the host inside vpoisson
+  int node_march_s = 2049;  // option: split levels of >= node_march_s vertices per side chain up to 4 colour half-sweeps per pass (k_n_relax_march_s,
+                            // round 3).  2049^2 x 3, 9 cycles per solve (tools/ab_node_prof.py): 3 passes of 83 us replace 9 colour launches of 33 us:
+                            // 17.3 -> 16.6 ms per step; on the 1025^2 and 513^2 levels the pass loses (17.4 / 18.4): too few chunks for a
+                            // marching wavefront; three steps of software prefetch instead of one and chunk heights 8 .. 24 change nothing
+  int s2_xuniform = 0;   // set_const: S2 does not depend on x
+  int s2_rows = 1;       // option: use row tables of S2 in the smoother and the residual when S2 does not depend on x
+  int node_split = 65;   // option: levels of >= node_split vertices per side keep da / res / mask / S2 copies in the x-parity split layout (0: off)
+  int tiled_relax = 0;  // option: LDS-tiled smoother passes (1-2 sweeps per pass) on the wide levels; measured 3 % faster at 4097^2 x 3, 7 % slower at 2049^2 x 3
+  NatGeom g;
+  double *f[MSOMN_NFIELDS] = {nullptr};
+  int fl[MSOMN_NFIELDS] = {0};
+  LayerCoef lc;
+  int nlev = 0;
+  std::vector<NLevel> lev;
+  double *d_scal = nullptr, *h_scal = nullptr, *partial = nullptr, *d_row = nullptr, *h_row = nullptr;
+  hipStream_t st = nullptr;
+  int const_set = 0;
+  double t = 0, dt = 1., tnext = HUGE_VAL, previous = 0;
+  int iter = 0;
+  msom_mgstats mg = {0, 0, 0, 0, 0};
+  // state file and the driver's checkpoints (include/msomn_state.h)
+  long state_flip = -1;             // msomn_state_dbg_flip: element the next load flips on the device (< 0: off)
+  int ckpt_steps = 0, resume = 0;   // options of msomn_run
+  int run_loaded = 0;               // the last load found the driver record `run`: run_ev holds it
+  double run_ev[6] = {0, 0, 0, 0, 0, 0};   // tout, tdiag, tflt, output directory number, records of vars.nc, bytes of diag_1d.dat
+};
+
+// ---- msom_node.hip
+// [layers][n+1][n+1] contiguous (host or device) <-> padded natural layout
+int upload_g(msomn *m, double *dst, const NatGeom &g, int nl, const double *a);
+int download_g(msomn *m, const double *src, const NatGeom &g, int nl, double *a);
+// msomn_set_const in two parts.  node_const_inputs transforms the inputs in place (S2: N^2 -> f^2 / N^2, S2S: N^2 -> f / N^2, topo *=
+// scale_topo) and is not idempotent; node_const_derived builds everything that follows from the transformed values (layer metrics,
+// iRd2_low, s2_xuniform, the levels and their layouts, the noise pyramid, the DT clamps, boundary(psi)) and leaves q and noise_draw alone.
+int node_const_inputs(msomn *m);
+int node_const_derived(msomn *m);
+double node_clamped_dt(const msomn *m);   // p.DT after the clamps of node_const_derived
+NatGeom cell_geom(int n);                 // natural layout of an n x n cell field (the noise and wavelet pyramids)
+void node_noise_ghosts(msomn *m);         // the ghost ring of the noise field cs[0], as the filter leaves it
+
+// ---- msomn_state.hip
+// msomn_state_save with the driver record `run` (run6: tout, tdiag, tflt, directory number, records of vars.nc, bytes of diag_1d.dat)
+int nstate_save_run(msomn *m, const char *path, unsigned flags, const double *run6);
+
+#endif

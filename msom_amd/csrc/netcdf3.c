@@ -16,6 +16,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <unistd.h>
 
 #include "msom_params.h"
 
@@ -233,6 +234,78 @@ int msom_nc_read(const char *path, const char *name, int rec, int nl, int ny, in
     }
   }
   free(h); fclose(fp);
+  return 0;
+bad:
+  free(h); fclose(fp);
+  msom_set_error("truncated NetCDF file %s", path);
+  return -2;
+}
+
+/* Sets a classic file back to its first nrec records: numrecs rewritten, everything behind record nrec - 1 cut off (msomn_run resuming
+ * from a checkpoint drops what a run that died wrote after it).  The header is walked as in msom_nc_read: the record section begins at
+ * the smallest `begin` of a record variable, a record is the sum of the record variables' padded sizes. */
+int msom_nc_truncate(const char *path, long nrec) {
+  FILE *fp = fopen(path, "r+b");
+  if (!fp) { msom_set_error("file %s not found", path); return -2; }
+  fseeko(fp, 0, SEEK_END);
+  const off_t fsize = ftello(fp);
+  const size_t hmax = fsize < (1 << 20) ? (size_t)fsize : (1u << 20);
+  unsigned char *h = (unsigned char *)malloc(hmax ? hmax : 1);
+  fseeko(fp, 0, SEEK_SET);
+  if (!h || hmax < 8 || fread(h, 1, hmax, fp) != hmax || memcmp(h, "CDF", 3) || (h[3] != 1 && h[3] != 2)) {
+    free(h); fclose(fp); msom_set_error("%s is not a NetCDF classic file", path); return -2;
+  }
+  const int v2 = h[3] == 2;
+  const uint32_t numrecs = get32(h + 4);
+  size_t p = 8;
+  uint32_t dimlen[64]; int ndims = 0, recdim = -1;
+  NEED(8);
+  uint32_t tag = get32(h + p), cnt = get32(h + p + 4); p += 8;
+  for (uint32_t d = 0; tag == NC_DIMENSION && d < cnt; d++) {
+    NEED(4); uint32_t n = get32(h + p); p += 4 + ((n + 3) & ~3u);
+    NEED(4); const uint32_t len = get32(h + p); p += 4;
+    if (d >= 64) continue;
+    dimlen[ndims] = len;
+    if (len == 0) recdim = ndims;
+    ndims++;
+  }
+  SKIP_ATTS();
+  NEED(8);
+  tag = get32(h + p); cnt = get32(h + p + 4); p += 8;
+  uint64_t recsize = 0, rec_begin = UINT64_MAX;
+  for (uint32_t v = 0; tag == NC_VARIABLE && v < cnt; v++) {
+    NEED(4); uint32_t n = get32(h + p); p += 4 + ((n + 3) & ~3u);
+    NEED(4); uint32_t nd = get32(h + p); p += 4;
+    int isrec = 0; uint64_t inner = 1;
+    for (uint32_t d = 0; d < nd; d++) {
+      NEED(4); uint32_t id = get32(h + p); p += 4;
+      if ((int)id == recdim && d == 0) isrec = 1;
+      else if (id < 64 && (int)id < ndims) inner *= dimlen[id];
+    }
+    SKIP_ATTS();
+    NEED(8 + (v2 ? 8 : 4));
+    uint32_t ty = get32(h + p), vsize = get32(h + p + 4); p += 8;
+    uint64_t begin = v2 ? get64(h + p) : get32(h + p); p += v2 ? 8 : 4;
+    if (!isrec) continue;
+    recsize += vsize == 0xffffffffu ? inner * (ty == NC_DOUBLE ? 8 : 4) : ((vsize + 3) & ~3u);
+    if (begin < rec_begin) rec_begin = begin;
+  }
+  free(h);
+  if (nrec < 0 || (uint64_t)nrec > numrecs || recsize == 0 || rec_begin == UINT64_MAX ||
+      rec_begin + (uint64_t)nrec * recsize > (uint64_t)fsize) {
+    fclose(fp);
+    msom_set_error("%s holds %u records: it cannot be set back to %ld", path, numrecs, nrec);
+    return -2;
+  }
+  unsigned char t[4];
+  put32(t, (uint32_t)nrec);
+  fseeko(fp, 4, SEEK_SET);
+  const int bad_write = fwrite(t, 1, 4, fp) != 4;
+  const int bad_close = fclose(fp);
+  if (bad_write || bad_close || truncate(path, (off_t)(rec_begin + (uint64_t)nrec * recsize))) {
+    msom_set_error("cannot truncate %s", path);
+    return -2;
+  }
   return 0;
 bad:
   free(h); fclose(fp);

@@ -1,6 +1,9 @@
-"""The state file of include/msom_state.h in pure Python, written from the format text of DESIGN.md ("State file"), not by calling
+"""The state file of include/msom_state.h and include/msomn_state.h in pure Python, written from the format text of DESIGN.md ("State file"), not by calling
 the library: `read_state` and `write_state` are the independent statement of the format (the tests hold the library to them), and
-`write_state` is how a user builds an fp64 initial state for `QG.load_state`.
+`write_state` is how a user builds an fp64 initial state for `QG.load_state` or `NodeQG.load_state`.
+
+Dialects: 0 msqg and 1 newqg (cell-centred, nx x ny cells), 2 the vertex model (nx = ny = N + 1 vertices; its noise is a cell scalar,
+a field record with its own shape (1, N, N): a record's ny and nx are its own and need not be the header's).
 
 Layout (little-endian):
   header   64 bytes: magic "MSOMSTAT", then 12 uint32: version, dialect, nx, ny, nl, nptr, stochastic, noise_mode, mode_pv_invert,
@@ -44,10 +47,11 @@ def digest(a):
 
 
 def write_state(path, records, nx, ny, nl, params="", dialect=0, nptr=0, stochastic=0, noise_mode=0, mode_pv_invert=0, flag_topo=0,
-                t=0.0, dt=1.0, previous=0.0, tnext=float("inf"), iter=0, ring=()):
+                t=0.0, dt=1.0, previous=0.0, tnext=float("inf"), iter=0, ring=(), cells=()):
     """Write a state file.  records: name -> array; a 3-d array of shape (layers, ny, nx) is a field record (names in `ring`:
-    (layers, ny + 2, nx + 2) with the ghost cells), a 1-d array a record of scalars.  The record "time" is made from t, dt,
-    previous, tnext, iter unless `records` brings its own."""
+    (layers, ny + 2, nx + 2) with the ghost cells; names in `cells`: (layers, ny - 1, nx - 1), a field on the cells between the
+    vertices of a dialect-2 file, stored with its own ny - 1 and nx - 1), a 1-d array a record of scalars.  The record "time" is
+    made from t, dt, previous, tnext, iter unless `records` brings its own."""
     recs = OrderedDict()
     if "time" not in records:
         recs["time"] = np.array([t, dt, previous, tnext, iter], dtype=np.float64)
@@ -62,12 +66,13 @@ def write_state(path, records, nx, ny, nl, params="", dialect=0, nptr=0, stochas
         if not 0 < len(nm) <= 16:
             raise StateFormatError(f"record name {name!r}: 1 to 16 bytes")
         g = 2 if name in ring else 0
+        ry, rx = (ny - 1, nx - 1) if name in cells else (ny, nx)
         if a.ndim == 1:
             kind, shape = KIND_SCALARS, (a.size, 1, 1)
-        elif a.ndim == 3 and a.shape[1:] == (ny + g, nx + g):
-            kind, shape = KIND_FIELD, (a.shape[0], ny, nx)
+        elif a.ndim == 3 and a.shape[1:] == (ry + g, rx + g):
+            kind, shape = KIND_FIELD, (a.shape[0], ry, rx)
         else:
-            raise StateFormatError(f"record {name!r}: shape {a.shape} is neither 1-d nor (layers, {ny + g}, {nx + g})")
+            raise StateFormatError(f"record {name!r}: shape {a.shape} is neither 1-d nor (layers, {ry + g}, {rx + g})")
         d = digest(a)
         dsum = (dsum + d) % 2**64
         out += [nm.ljust(16, b"\0"), struct.pack("<6I3Q", kind, *shape, 1 if g else 0, 0, a.nbytes, d, 0), a.astype("<f8").tobytes()]
