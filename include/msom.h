@@ -555,6 +555,26 @@ typedef struct msomn msomn_t;
  * vertices, S2 = N2[l], everything else 0.  Extension: none.  NULL on error. */
 msomn_t *msomn_create(const char *params_path);
 msomn_t *msomn_create_str(const char *params_text);
+/* Vertex model on tiles.  The global grid of N x N cells is covered by px x py tiles (powers of two, px != py allowed), rank r = tile
+ * (r % px, r / px) as msom_create_tiled; id128 from msom_comm_unique_id (in-process transport if it starts with "MSOMLOCL", RCCL
+ * otherwise).  A tile of Tx = N / px by Ty = N / py cells HOLDS (Tx + 1) x (Ty + 1) vertices, the ones on its interior edges too: a
+ * vertex on a shared edge exists on both tiles (on all four at a cross point) and every holder computes it.  The result equals the
+ * single tile's of the same global grid bit for bit (dt, t, iter, mgstats identical on all ranks; msomn_ke and msomn_diag1d differ in
+ * their summation order only).  msomn_set_field / msomn_get_field take and return the tile's [layers][Ty + 1][Tx + 1]; the caller
+ * gives shared vertices the same values on every holder (not checked).  msomn_set_field, msomn_set_const and every call that
+ * computes are COLLECTIVE: all ranks call them, in the same order.  Everything that depends on x or y uses the global vertex index.
+ * px = py = 1 gives the plain handle.  NULL with msom_last_error set for px / py not a power of two, N not divisible, a tile side
+ * below 2 cells, a bad rank, bc_fac = -1, sqg = 1 on more than one tile.
+ * On more than one tile the multigrid levels down to the gather level (msomn_get_param "agg_level": the first level of at most
+ * max(mg_coarse, px, py) cells a side, at least level 1) live on the tiles, the coarser ones are gathered and solved on every rank;
+ * set option mg_coarse before msomn_set_const.  The fused passes resolve to off (options node_pfused, node_tile_s, node_march_s,
+ * node_march, tiled_relax, node_corr_fused, node_rhs_fused read 0 and stay 0); msomn_get_param "exchanges" counts halo exchanges.
+ * msomn_dbg_relax / _residual / _restrict / _prolong / _level_mask work on the tiled levels with tile-sized arrays (a gathered
+ * level: MSOM_ERR_ARG).  Refused with MSOM_ERR_CONFIG and a message naming the call, the handle unchanged: option stochastic,
+ * msomn_noise_draw, msomn_dbg_noise, msomn_dbg_csig, msomn_wavelet_filter, msomn_dbg_wv_get / _apply, msomn_run, msomn_write_nc,
+ * msomn_read_nc, msomn_state_save / _load, msomn_dbg_del2_zeta. */
+msomn_t *msomn_create_tiled(const char *params_text, int px, int py, int rank, const void *id128);
+int msomn_tile_info(msomn_t *m, int *px, int *py, int *ix, int *iy, int *nx_local, int *ny_local);  /* vertices: Tx + 1, Ty + 1 */
 void msomn_destroy(msomn_t *m);                                 /* trash_vars qg.h:537-544 */
 /* keys: TOLERANCE NITERMAX NITERMIN (nodal-poisson.h:19-23) DT quiet stochastic seed (kept in the handle, and srand) noise_mode [0] (0: the
  * noise is drawn from the serial rand() stream on the host, 1: on the device by k_n_noise; other values: MSOM_ERR_ARG); implementation switches (result-preserving in

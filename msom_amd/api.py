@@ -150,6 +150,8 @@ def load_library(strict=False):
         # vertex-grid variant (qg-node/)
         "msomn_create": (vp, [cs]),
         "msomn_create_str": (vp, [cs]),
+        "msomn_create_tiled": (vp, [cs, ci, ci, ci, vp]),
+        "msomn_tile_info": (ci, [vp] + [C.POINTER(ci)] * 6),
         "msomn_destroy": (None, [vp]),
         "msomn_set_option": (ci, [vp, cs, cd]),
         "msomn_get_param": (cd, [vp, cs]),
@@ -267,8 +269,7 @@ def node_from_state(path, strict=False):
         raise MsomError(L.msom_last_error().decode())
     g = NodeQG.__new__(NodeQG)
     g.L, g.h = L, h
-    g.N, g.nl = int(g.param("N")), int(g.param("nl"))
-    g.nlevels = int(g.param("nlevels"))
+    g._read_shape()
     return g
 
 
@@ -829,15 +830,29 @@ NODE_FIELDS = dict(PSI=0, Q=1, ZETA=2, TMP=3, PSIPG=4, S2=5, TOPO=6, QFORC=7, MA
 
 class NodeQG:
     """Vertex-grid (masked-domain) model: one `qg.e` process of qg-node/qg.c.  Field arrays are
-    [layers][N+1][N+1] (qg-node/netcdf_vertex_bas.h:253)."""
+    [layers][N+1][N+1] (qg-node/netcdf_vertex_bas.h:253).
+    tiled = (px, py, rank, uid): this rank's tile of a px x py decomposition (msomn_create_tiled); field arrays are then the tile's
+    [layers][ny][nx] with nx = N / px + 1, ny = N / py + 1 vertices, the ones on the interior edges included
+    (msom_amd.tiling.node_tile_window), and set(), set_const() and every call that computes are collective."""
 
-    def __init__(self, params=None, path=None, strict=False):
+    def __init__(self, params=None, path=None, strict=False, tiled=None):
         self.L = load_library(strict)
-        self.h = self.L.msomn_create(path.encode()) if path is not None else self.L.msomn_create_str(params.encode())
+        if tiled is not None:
+            px, py, rank, uid = tiled
+            self.h = self.L.msomn_create_tiled(params.encode(), px, py, rank, uid)
+        else:
+            self.h = self.L.msomn_create(path.encode()) if path is not None else self.L.msomn_create_str(params.encode())
         if not self.h:
             raise MsomError(self.L.msom_last_error().decode())
+        self._read_shape()
+
+    def _read_shape(self):
         self.N, self.nl = int(self.param("N")), int(self.param("nl"))
         self.nlevels = int(self.param("nlevels"))
+        px_, py_, ix, iy, nx, ny = (C.c_int() for _ in range(6))
+        self.L.msomn_tile_info(self.h, *(C.byref(v) for v in (px_, py_, ix, iy, nx, ny)))
+        self.nx, self.ny = nx.value, ny.value
+        self.tile = (px_.value, py_.value, ix.value, iy.value)
 
     def close(self):
         if self.h:
@@ -877,7 +892,7 @@ class NodeQG:
         return self.L.msomn_field_layers(self.h, self._fid(f))
 
     def shape(self, f):
-        return (self.layers(f), self.N + 1, self.N + 1)
+        return (self.layers(f), self.ny, self.nx)
 
     def set(self, f, a):
         a = _f64(a, self.shape(f))
@@ -958,10 +973,9 @@ class NodeQG:
             self._chk(r)
         return r
 
-    # multigrid pieces (parity tests); level k has (N >> k) + 1 vertices per side
+    # multigrid pieces (parity tests); level k has (N >> k) + 1 vertices per side (a tile: its share of them, plus one)
     def _lshape(self, k, nl=None):
-        n1 = (self.N >> k) + 1
-        return (self.nl if nl is None else nl, n1, n1)
+        return (self.nl if nl is None else nl, ((self.ny - 1) >> k) + 1, ((self.nx - 1) >> k) + 1)
 
     def dbg_relax(self, k, da, res, nsweeps):
         da = np.array(_f64(da, self._lshape(k)))

@@ -14,6 +14,7 @@
 #include "kernels.h"
 #include "rhs_inl.h"
 #include "noise_inl.h"
+#include "node_tile_inl.h"
 
 #ifdef MSOM_STRICT
 #define DIVC(x, c, rc) ((x) / (c))
@@ -24,6 +25,11 @@
 #define BY 4
 static inline dim3 grid2d(int nx, int ny) { return dim3((nx + BX - 1) / BX, (ny + BY - 1) / BY); }
 static inline dim3 block2d() { return dim3(BX, BY); }
+// the ranges of node_tile_inl.h for a level geometry and its wall bits (the tile's place in the grid does not enter)
+static inline NodeTile n_tile_of(const NatGeom &g, int walls) {
+  NodeTile t = {0, 0, walls, g.nx - 1, g.ny - 1, 0, 0};
+  return t;
+}
 static inline dim3 grid_capped(int nx, int ny) {
   dim3 g = grid2d(nx, ny);
   const unsigned cap = 2048 / g.x > 0 ? 2048 / g.x : 1;
@@ -61,41 +67,48 @@ __device__ __forceinline__ double jacn(const double *__restrict__ p, const doubl
 // ---------------------------------------------------------------- boundary vertices
 // f_bnd = c * (g_first_interior - (use_g_bnd ? g_bnd : gbc)); x sides first, then y sides (corners
 // end up with the y rule).  One thread per boundary vertex and layer.
-__global__ void k_n_bnd_from(double *f, const double *g, NatGeom ge, int nl, double c, int use_g_bnd, double gbc) {
-  const int n = ge.nx - 1, per = 4 * n;
+// walls (vertex model on tiles): only the sides of the tile that are sides of the domain; a wall side spans the whole tile edge,
+// and "corners take the y rule" holds where a y side is a wall.  Slot r of a layer: 2 nx slots of the y sides, then 2 ny of the x sides
+__device__ __forceinline__ bool n_bnd_slot(const NatGeom &ge, int walls, int r, int &i, int &j, int &ii, int &jj) {
+  if (r < 2 * ge.nx) {  // y sides, all i (corners included -> y rule)
+    i = ii = r >> 1;
+    if (r & 1) { j = ge.ny - 1; jj = j - 1; } else { j = 0; jj = 1; }
+    return walls & ((r & 1) ? WALL_N : WALL_S);
+  }
+  const int q = r - 2 * ge.nx;  // x sides without the vertices a y wall has taken
+  j = jj = q >> 1;
+  if (q & 1) { i = ge.nx - 1; ii = i - 1; } else { i = 0; ii = 1; }
+  if ((j == 0 && (walls & WALL_S)) || (j == ge.ny - 1 && (walls & WALL_N))) return false;
+  return walls & ((q & 1) ? WALL_E : WALL_W);
+}
+__global__ void k_n_bnd_from(double *f, const double *g, NatGeom ge, int nl, double c, int use_g_bnd, double gbc, int walls) {
+  const int per = 2 * (ge.nx + ge.ny);
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= per * nl) return;
   const int l = t / per, r = t % per;
   int i, j, ii, jj;  // boundary vertex and its first interior neighbour
-  if (r < 2 * (n + 1)) {  // y sides, all i (corners included -> y rule)
-    i = ii = r >> 1;
-    if (r & 1) { j = n; jj = n - 1; } else { j = 0; jj = 1; }
-  } else {  // x sides without the corners
-    const int q = r - 2 * (n + 1);
-    j = jj = 1 + (q >> 1);
-    if (q & 1) { i = n; ii = n - 1; } else { i = 0; ii = 1; }
-  }
+  if (!n_bnd_slot(ge, walls, r, i, j, ii, jj)) return;
   const size_t b = nat_idx(ge, l, j, i);
   // corner: the y rule reads g at (i, jj), which is an x-side boundary vertex; for use_g_bnd its
   // value must be the one the x pass gave it -- g is a different field here (zeta for tmp), so ok
   f[b] = c * (g[nat_idx(ge, l, jj, ii)] - (use_g_bnd ? g[b] : gbc));
 }
-void launch_n_bnd_from(hipStream_t st, double *f, const double *g, const NatGeom &ge, int nl, double c, int use_g_bnd, double gbc) {
-  const int n = 4 * (ge.nx - 1) * nl;
-  hipLaunchKernelGGL(k_n_bnd_from, dim3((n + 255) / 256), dim3(256), 0, st, f, g, ge, nl, c, use_g_bnd, gbc);
+void launch_n_bnd_from(hipStream_t st, double *f, const double *g, const NatGeom &ge, int nl, double c, int use_g_bnd, double gbc, int walls) {
+  const int n = 2 * (ge.nx + ge.ny) * nl;
+  hipLaunchKernelGGL(k_n_bnd_from, dim3((n + 255) / 256), dim3(256), 0, st, f, g, ge, nl, c, use_g_bnd, gbc, walls);
 }
-__global__ void k_n_bnd_const(double *f, NatGeom ge, int nl, double v, int sp) {
-  const int n = ge.nx - 1, per = 4 * n;
+__global__ void k_n_bnd_const(double *f, NatGeom ge, int nl, double v, int sp, int walls) {
+  const int per = 2 * (ge.nx + ge.ny);
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= per * nl) return;
   const int l = t / per, r = t % per;
-  int i, j;
-  if (r < 2 * (n + 1)) { i = r >> 1; j = (r & 1) ? n : 0; } else { const int q = r - 2 * (n + 1); j = 1 + (q >> 1); i = (q & 1) ? n : 0; }
+  int i, j, ii, jj;
+  if (!n_bnd_slot(ge, walls, r, i, j, ii, jj)) return;
   f[gidx(ge, sp, l, j, i)] = v;
 }
-void launch_n_bnd_const(hipStream_t st, double *f, const NatGeom &ge, int nl, double v, int sp) {
-  const int n = 4 * (ge.nx - 1) * nl;
-  hipLaunchKernelGGL(k_n_bnd_const, dim3((n + 255) / 256), dim3(256), 0, st, f, ge, nl, v, sp);
+void launch_n_bnd_const(hipStream_t st, double *f, const NatGeom &ge, int nl, double v, int sp, int walls) {
+  const int n = 2 * (ge.nx + ge.ny) * nl;
+  hipLaunchKernelGGL(k_n_bnd_const, dim3((n + 255) / 256), dim3(256), 0, st, f, ge, nl, v, sp, walls);
 }
 
 // ---------------------------------------------------------------- pointwise / stencil operators
@@ -505,9 +518,15 @@ __device__ __forceinline__ void n_col_solve(const NRelaxArgs &p, size_t c, const
   n_col_solve_vals<NL>(p, bv, p.mk[c], sv, ew, ns, x);
 }
 template <int NL>
+__device__ __forceinline__ void n_relax_at(const NRelaxArgs &p, int i, int j);
+template <int NL>
 __device__ __forceinline__ void n_relax_pt(const NRelaxArgs &p, int i, int j) {
   const int n = p.g.nx - 1;
   if (i >= n || j >= n) return;
+  n_relax_at<NL>(p, i, j);
+}
+template <int NL>
+__device__ __forceinline__ void n_relax_at(const NRelaxArgs &p, int i, int j) {
   const int pitch = p.g.pitch;
   const size_t ls = p.g.ls, c = nat_idx(p.g, 0, j, i);
   double ew[NL], ns[NL], x[NL];
@@ -534,6 +553,27 @@ __global__ void __launch_bounds__(BX *BY) k_n_relax_s(NRelaxArgs p) {
   const int i = 1 + 2 * (blockIdx.x * BX + threadIdx.x) + ((j + p.color + 1) & 1);
   const int n = p.g.nx - 1;
   if (i >= n || j >= n) return;
+  const int pitch = p.g.pitch;
+  const size_t ls = p.g.ls, c = gidx(p.g, 1, 0, j, i), e = gidx(p.g, 1, 0, j, i + 1), w = gidx(p.g, 1, 0, j, i - 1);
+  double ew[NL], ns[NL], x[NL];
+#pragma unroll
+  for (int l = 0; l < NL; l++) {
+    ew[l] = p.a[e + l * ls] + p.a[w + l * ls];
+    ns[l] = p.a[c + l * ls + pitch] + p.a[c + l * ls - pitch];
+  }
+  n_col_solve<NL>(p, c, ew, ns, x, j);
+#pragma unroll
+  for (int l = 0; l < NL; l++) p.a[c + l * ls] = x[l];
+}
+// The colour pass of a tile of the vertex model on tiles (either layout): the vertices i0 .. i1 x j0 .. j1 of the tile that are not on a
+// wall (node_tile_inl.h, ntile_update_range), rectangular.  Tile origins are even, so the local colour is the global one.  Same
+// n_relax_at / n_col_solve as the single tile's passes, which keep their own kernels (and their registers).
+template <int NL, bool SP>
+__global__ void __launch_bounds__(BX *BY) k_n_relax_w(NRelaxArgs p, int i0, int i1, int j0, int j1) {
+  const int j = j0 + blockIdx.y * BY + threadIdx.y;
+  const int i = i0 + 2 * (blockIdx.x * BX + threadIdx.x) + ((j + p.color + i0) & 1);  // (i + j) & 1 == color
+  if (i > i1 || j > j1) return;
+  if (!SP) { n_relax_at<NL>(p, i, j); return; }
   const int pitch = p.g.pitch;
   const size_t ls = p.g.ls, c = gidx(p.g, 1, 0, j, i), e = gidx(p.g, 1, 0, j, i + 1), w = gidx(p.g, 1, 0, j, i - 1);
   double ew[NL], ns[NL], x[NL];
@@ -1003,9 +1043,18 @@ int launch_n_relax_tile(hipStream_t st, const double *a_in, double *a_out, const
   return ns;
 }
 void launch_n_relax(hipStream_t st, double *a, const double *b, const double *mk, const double *S2, const NatGeom &g, int nl, int color, double D,
-                    double iRd2, const LayerCoef &lc, int sp, const double *S2row) {
+                    double iRd2, const LayerCoef &lc, int sp, const double *S2row, int walls) {
   NRelaxArgs p;
   p.a = a; p.b = b; p.mk = mk; p.S2 = S2; p.g = g; p.color = color; p.sqD = D * D; p.iRd2 = iRd2; p.lc = lc; p.S2row = S2row;
+  if (walls != WALL_ALL || g.nx != g.ny) {   // a tile of the vertex model on tiles
+    const NodeRange u = ntile_update_range(n_tile_of(g, walls));
+    dim3 gw = grid2d((u.i1 - u.i0) / 2 + 1, u.j1 - u.j0 + 1);
+    const bool okw = with_int<1, MSOM_FASTNL>(nl, [&](auto N) {
+      with_bool(sp != 0, [&](auto S) { hipLaunchKernelGGL((k_n_relax_w<N(), S()>), gw, block2d(), 0, st, p, u.i0, u.i1, u.j0, u.j1); });
+    });
+    if (!okw) no_kernel("launch_n_relax", nl);
+    return;
+  }
   const int n = g.nx - 1;
   dim3 gr = grid2d((n + 1) / 2, n - 1);
   const bool ok = with_int<1, MSOM_FASTNL>(nl, [&](auto N) {
@@ -1022,9 +1071,14 @@ struct NResArgs {
   const double *S2row;  // S2 independent of x: [l * g.ny + j], else null
   int nl, sp;
   int zb;   // 1: the boundary vertices of res get 0 after the maximum took their value (boundary_level; formerly a launch of k_n_bnd_const)
+  int walls = WALL_ALL;   // the sides of the tile that are sides of the domain (k_n_residual)
   double sqD, iRd2;
   LayerCoef lc;
 };
+// vertex (i, j) of a tile lies on a side of the domain
+__device__ __forceinline__ bool n_on_wall(const NatGeom &g, int walls, int i, int j) {
+  return (i == 0 && (walls & WALL_W)) || (i == g.nx - 1 && (walls & WALL_E)) || (j == 0 && (walls & WALL_S)) || (j == g.ny - 1 && (walls & WALL_N));
+}
 // at most ~2048 workgroups (rows strided over gridDim.y): one atomicMax per workgroup on a single word
 // saturates at ~88 per microsecond, which would dominate a pass launched with one workgroup per 64 x 4 cells
 __global__ void k_n_residual(NResArgs p) {
@@ -1034,7 +1088,7 @@ __global__ void k_n_residual(NResArgs p) {
     const int nl = p.nl, pitch = p.g.pitch;
     const size_t ls = p.g.ls, c0 = nat_idx(p.g, 0, j, i);
     const double m = p.mk[c0], sq = p.sqD, rsq = 1. / sq;
-    const bool zb = p.zb && (i == 0 || j == 0 || i == p.g.nx - 1 || j == p.g.ny - 1);
+    const bool zb = p.zb && n_on_wall(p.g, p.walls, i, j);
     for (int l = 0; l < nl; l++) {
       const size_t c = c0 + l * ls;
       const double a1 = p.a[c];
@@ -1062,9 +1116,9 @@ __global__ void k_n_residual(NResArgs p) {
   }
 }
 void launch_n_residual(hipStream_t st, const double *a, const double *b, const double *mk, const double *S2, double *res, double *maxres,
-                       const NatGeom &g, int nl, double D, double iRd2, const LayerCoef &lc, const NatGeom *gres, const double *S2row, int zb) {
+                       const NatGeom &g, int nl, double D, double iRd2, const LayerCoef &lc, const NatGeom *gres, const double *S2row, int zb, int walls) {
   NResArgs p;
-  p.zb = zb;
+  p.zb = zb; p.walls = walls;
   p.S2row = S2row;
   p.a = a; p.b = b; p.mk = mk; p.S2 = S2; p.res = res; p.maxres = maxres; p.g = g; p.nl = nl; p.sqD = D * D; p.iRd2 = iRd2; p.lc = lc;
   p.sp = gres != nullptr; p.gr = gres ? *gres : g;
@@ -1223,9 +1277,9 @@ __device__ __forceinline__ void n_restrict_pt(const double *__restrict__ f, cons
   }
 }
 // zb: the boundary vertices of the coarse level get 0 (boundary_level of the residual, formerly a launch of k_n_bnd_const)
-__global__ void k_n_restrict(const double *__restrict__ f, NatGeom fg, double *c, NatGeom cg, int nl, int kind, int zb) {
+__global__ void k_n_restrict(const double *__restrict__ f, NatGeom fg, double *c, NatGeom cg, int nl, int kind, int zb, int walls) {
   VTX(cg, I, J);
-  if (zb && (I == 0 || J == 0 || I == cg.nx - 1 || J == cg.ny - 1)) {
+  if (zb && n_on_wall(cg, walls, I, J)) {
     for (int l = 0; l < nl; l++) c[nat_idx(cg, l, J, I)] = 0.;
     return;
   }
@@ -1233,9 +1287,9 @@ __global__ void k_n_restrict(const double *__restrict__ f, NatGeom fg, double *c
 }
 // residual restriction (kind 0) with either side in the split layout: the five fine vertices of a coarse one are unit-stride
 // runs of the even half (2I) and of the odd half (2I +- 1)
-__global__ void k_n_restrict_s(const double *__restrict__ f, NatGeom fg, int fsp, double *c, NatGeom cg, int csp, int nl, int zb) {
+__global__ void k_n_restrict_s(const double *__restrict__ f, NatGeom fg, int fsp, double *c, NatGeom cg, int csp, int nl, int zb, int walls) {
   VTX(cg, I, J);
-  if (zb && (I == 0 || J == 0 || I == cg.nx - 1 || J == cg.ny - 1)) {
+  if (zb && n_on_wall(cg, walls, I, J)) {
     for (int l = 0; l < nl; l++) c[gidx(cg, csp, l, J, I)] = 0.;
     return;
   }
@@ -1245,18 +1299,19 @@ __global__ void k_n_restrict_s(const double *__restrict__ f, NatGeom fg, int fsp
     c[gidx(cg, csp, l, J, I)] = v;
   }
 }
-void launch_n_restrict(hipStream_t st, const double *f, const NatGeom &fg, double *c, const NatGeom &cg, int nl, int kind, int fsp, int csp, int zb) {
+void launch_n_restrict(hipStream_t st, const double *f, const NatGeom &fg, double *c, const NatGeom &cg, int nl, int kind, int fsp, int csp, int zb, int walls) {
   if (fsp || csp) {
     if (kind != 0) { fprintf(stderr, "msom: launch_n_restrict: split layout only for the residual\n"); abort(); }
-    hipLaunchKernelGGL(k_n_restrict_s, grid2d(cg.nx, cg.ny), block2d(), 0, st, f, fg, fsp, c, cg, csp, nl, zb);
+    hipLaunchKernelGGL(k_n_restrict_s, grid2d(cg.nx, cg.ny), block2d(), 0, st, f, fg, fsp, c, cg, csp, nl, zb, walls);
     return;
   }
-  hipLaunchKernelGGL(k_n_restrict, grid2d(cg.nx, cg.ny), block2d(), 0, st, f, fg, c, cg, nl, kind, zb);
+  hipLaunchKernelGGL(k_n_restrict, grid2d(cg.nx, cg.ny), block2d(), 0, st, f, fg, c, cg, nl, kind, zb, walls);
 }
 // refine_vert my_vertex.h:82-105 followed by boundary_level(da) = 0 on the boundary vertices; one thread per FINE vertex
-__device__ __forceinline__ void n_prolong_pt(const double *__restrict__ c, const NatGeom &cg, double *f, const NatGeom &fg, int nl, int i, int j) {
-  const int n = fg.nx - 1, I = i >> 1, J = j >> 1;
-  const bool bnd = i == 0 || j == 0 || i == n || j == n;
+__device__ __forceinline__ void n_prolong_pt(const double *__restrict__ c, const NatGeom &cg, double *f, const NatGeom &fg, int nl, int i, int j,
+                                             int walls = WALL_ALL) {
+  const int I = i >> 1, J = j >> 1;
+  const bool bnd = n_on_wall(fg, walls, i, j);
   for (int l = 0; l < nl; l++) {
     const size_t k = nat_idx(cg, l, J, I);
     double v;
@@ -1268,14 +1323,14 @@ __device__ __forceinline__ void n_prolong_pt(const double *__restrict__ c, const
     f[nat_idx(fg, l, j, i)] = v;
   }
 }
-__global__ void k_n_prolong(const double *__restrict__ c, NatGeom cg, double *f, NatGeom fg, int nl) {
+__global__ void k_n_prolong(const double *__restrict__ c, NatGeom cg, double *f, NatGeom fg, int nl, int walls) {
   VTX(fg, i, j);
-  n_prolong_pt(c, cg, f, fg, nl, i, j);
+  n_prolong_pt(c, cg, f, fg, nl, i, j, walls);
 }
-__global__ void k_n_prolong_s(const double *__restrict__ c, NatGeom cg, int csp, double *f, NatGeom fg, int fsp, int nl) {
+__global__ void k_n_prolong_s(const double *__restrict__ c, NatGeom cg, int csp, double *f, NatGeom fg, int fsp, int nl, int walls) {
   VTX(fg, i, j);
-  const int n = fg.nx - 1, I = i >> 1, J = j >> 1;
-  const bool bnd = i == 0 || j == 0 || i == n || j == n;
+  const int I = i >> 1, J = j >> 1;
+  const bool bnd = n_on_wall(fg, walls, i, j);
   for (int l = 0; l < nl; l++) {
     double v;
     if (bnd) v = 0.;
@@ -1355,20 +1410,19 @@ void launch_n_mg_coarse(hipStream_t st, const NCoarseArgs &a, int nrelax, int nl
   if (!with_int<1, MSOM_FASTNL>(nl, [&](auto N) { hipLaunchKernelGGL(k_n_mg_coarse<N()>, dim3(1), dim3(NMGC_NT), 0, st, a, nrelax); }))
     no_kernel("launch_n_mg_coarse", nl);
 }
-void launch_n_prolong(hipStream_t st, const double *c, const NatGeom &cg, double *f, const NatGeom &fg, int nl, int csp, int fsp) {
-  if (csp || fsp) hipLaunchKernelGGL(k_n_prolong_s, grid2d(fg.nx, fg.ny), block2d(), 0, st, c, cg, csp, f, fg, fsp, nl);
-  else hipLaunchKernelGGL(k_n_prolong, grid2d(fg.nx, fg.ny), block2d(), 0, st, c, cg, f, fg, nl);
+void launch_n_prolong(hipStream_t st, const double *c, const NatGeom &cg, double *f, const NatGeom &fg, int nl, int csp, int fsp, int walls) {
+  if (csp || fsp) hipLaunchKernelGGL(k_n_prolong_s, grid2d(fg.nx, fg.ny), block2d(), 0, st, c, cg, csp, f, fg, fsp, nl, walls);
+  else hipLaunchKernelGGL(k_n_prolong, grid2d(fg.nx, fg.ny), block2d(), 0, st, c, cg, f, fg, nl, walls);
 }
 // a += da, then boundary(a): psi_bc on the boundary vertices (nodal-poisson.h:119-128)
-__global__ void k_n_correct(double *a, const double *__restrict__ da, NatGeom g, NatGeom gd, int sp, int nl, double bcv) {
+__global__ void k_n_correct(double *a, const double *__restrict__ da, NatGeom g, NatGeom gd, int sp, int nl, double bcv, int walls) {
   VTX(g, i, j);
-  const int n = g.nx - 1;
-  const bool bnd = i == 0 || j == 0 || i == n || j == n;
+  const bool bnd = n_on_wall(g, walls, i, j);
   size_t k = nat_idx(g, 0, j, i), kd = gidx(gd, sp, 0, j, i);
   for (int l = 0; l < nl; l++, k += g.ls, kd += gd.ls) a[k] = bnd ? bcv : a[k] + da[kd];
 }
-void launch_n_correct(hipStream_t st, double *a, const double *da, const NatGeom &g, int nl, double bcv, const NatGeom *gda) {
-  hipLaunchKernelGGL(k_n_correct, grid2d(g.nx, g.ny), block2d(), 0, st, a, da, g, gda ? *gda : g, gda != nullptr, nl, bcv);
+void launch_n_correct(hipStream_t st, double *a, const double *da, const NatGeom &g, int nl, double bcv, const NatGeom *gda, int walls) {
+  hipLaunchKernelGGL(k_n_correct, grid2d(g.nx, g.ny), block2d(), 0, st, a, da, g, gda ? *gda : g, gda != nullptr, nl, bcv, walls);
 }
 // adjust_dt qg-node/qg.h:258-284: max |psi[0,1] - psi[]| / D and |psi[1,0] - psi[]| / D over faces and layers
 __global__ void k_n_umax(const double *__restrict__ psi, double *out, NatGeom g, int nl, double D) {
@@ -1396,10 +1450,11 @@ void launch_n_umax(hipStream_t st, const double *psi, double *out, const NatGeom
   hipLaunchKernelGGL(k_n_umax, grid_capped(g.nx, g.ny), block2d(), 0, st, psi, out, g, nl, D);
 }
 // KE diagnostic qg-node/qg.c:172-178 (per-block partials, summed by launch_sum_final)
-__global__ void k_n_ke(const double *__restrict__ psi, double *partial, NatGeom g, double D2, double rD2) {
+// nxs, nys: the vertices the tile adds to the sum (all of them on one tile; ntile_sum_range of node_tile_inl.h)
+__global__ void k_n_ke(const double *__restrict__ psi, double *partial, NatGeom g, double D2, double rD2, int nxs, int nys) {
   const int i = blockIdx.x * BX + threadIdx.x, j = blockIdx.y * BY + threadIdx.y;
   double v = 0.;
-  if (i < g.nx && j < g.ny) {
+  if (i < nxs && j < nys) {
     const size_t c = nat_idx(g, 0, j, i);
     v = 0.5 * psi[c] * DIVC(LAPN(psi, c, g.pitch), D2, rD2) * D2;
   }
@@ -1413,9 +1468,10 @@ __global__ void k_n_ke(const double *__restrict__ psi, double *partial, NatGeom 
     partial[blockIdx.y * gridDim.x + blockIdx.x] = s;
   }
 }
-void launch_n_ke(hipStream_t st, const double *psi, double *partial, double *out, const NatGeom &g, double D) {
+void launch_n_ke(hipStream_t st, const double *psi, double *partial, double *out, const NatGeom &g, double D, int walls) {
   dim3 gr = grid2d(g.nx, g.ny);
-  hipLaunchKernelGGL(k_n_ke, gr, block2d(), 0, st, psi, partial, g, D * D, 1. / (D * D));
+  const NodeRange sr = ntile_sum_range(n_tile_of(g, walls));
+  hipLaunchKernelGGL(k_n_ke, gr, block2d(), 0, st, psi, partial, g, D * D, 1. / (D * D), sr.i1 + 1, sr.j1 + 1);
   launch_sum_final(st, partial, out, (int)(gr.x * gr.y));
 }
 
@@ -1474,4 +1530,44 @@ void launch_n_diag1d(hipStream_t st, const double *psi, const double *q, const d
   hipLaunchKernelGGL(k_n_diag1d, gr, block2d(), 0, st, psi, q, qf, partial, g, nu, D * D, 1. / (D * D));
   const int nb = (int)(gr.x * gr.y);
   for (int k = 0; k < 3; k++) launch_sum_final(st, partial + (size_t)k * (nb + 64), out3 + k, nb);
+}
+
+// ---------------------------------------------------------------- vertex model on tiles: halo strips and the gather
+// region columns [i0, i0 + w), rows [j0, j0 + h), all layers <-> contiguous [l][h][w], the field in either layout (sp: x-parity split
+// of gidx; tile origins are even, so the halves of two neighbours line up)
+__global__ void k_n_pack_strip(const double *__restrict__ f, NatGeom g, int sp, int nl, int i0, int j0, int w, int h, double *buf) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= w * h * nl) return;
+  const int i = t % w, j = (t / w) % h, l = t / (w * h);
+  buf[t] = f[gidx(g, sp, l, j0 + j, i0 + i)];
+}
+__global__ void k_n_unpack_strip(double *f, NatGeom g, int sp, int nl, int i0, int j0, int w, int h, const double *__restrict__ buf) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= w * h * nl) return;
+  const int i = t % w, j = (t / w) % h, l = t / (w * h);
+  f[gidx(g, sp, l, j0 + j, i0 + i)] = buf[t];
+}
+void launch_n_pack_strip(hipStream_t st, const double *f, const NatGeom &g, int sp, int nl, int i0, int j0, int w, int h, double *buf) {
+  hipLaunchKernelGGL(k_n_pack_strip, dim3((w * h * nl + 255) / 256), dim3(256), 0, st, f, g, sp, nl, i0, j0, w, h, buf);
+}
+void launch_n_unpack_strip(hipStream_t st, double *f, const NatGeom &g, int sp, int nl, int i0, int j0, int w, int h, const double *buf) {
+  hipLaunchKernelGGL(k_n_unpack_strip, dim3((w * h * nl + 255) / 256), dim3(256), 0, st, f, g, sp, nl, i0, j0, w, h, buf);
+}
+// the gathered pieces of level k ([rank][l][ty + 1][tx + 1], comm_allgather) -> the global level in the natural layout; a shared
+// vertex has identical copies, ntile_gather_src picks one
+__global__ void k_n_assemble(const double *__restrict__ recv, double *f, NatGeom g, int nl, int N, int px, int py, int k) {
+  VTX(g, I, J);
+  for (int l = 0; l < nl; l++) f[nat_idx(g, l, J, I)] = recv[ntile_gather_src(N, px, py, k, nl, l, I, J)];
+}
+void launch_n_assemble(hipStream_t st, const double *recv, double *f, const NatGeom &g, int nl, int N, int px, int py, int k) {
+  hipLaunchKernelGGL(k_n_assemble, grid2d(g.nx, g.ny), block2d(), 0, st, recv, f, g, nl, N, px, py, k);
+}
+// the tile's window of a global level with one halo column / row all round (beyond a wall: the global pad, 0)
+__global__ void k_n_extract(const double *__restrict__ f, NatGeom g, double *t, NatGeom tg, int nl, int ox, int oy) {
+  const int i = (int)(blockIdx.x * BX + threadIdx.x) - 1, j = (int)(blockIdx.y * BY + threadIdx.y) - 1;
+  if (i > tg.nx || j > tg.ny) return;
+  for (int l = 0; l < nl; l++) t[nat_idx(tg, l, j, i)] = f[nat_idx(g, l, oy + j, ox + i)];
+}
+void launch_n_extract(hipStream_t st, const double *f, const NatGeom &g, double *t, const NatGeom &tg, int nl, int ox, int oy) {
+  hipLaunchKernelGGL(k_n_extract, grid2d(tg.nx + 2, tg.ny + 2), block2d(), 0, st, f, g, t, tg, nl, ox, oy);
 }

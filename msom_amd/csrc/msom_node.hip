@@ -31,24 +31,10 @@ static void nprof_collect(msomn *m, NProf &ps) {
   ps.used = 0;
 }
 
-static NatGeom node_geom(int n) {
-  NatGeom g;
-  g.nx = g.ny = n + 1;
-  g.pitch = ((n + 1 + 15) / 16) * 16 + 2 * MSOM_XP;
-  g.rows = n + 1 + 2 * MSOM_YP;
-  g.ls = (size_t)g.pitch * g.rows;
-  return g;
-}
-// x-parity split rows [even-i half | odd-i half]: n / 2 + 1 and n / 2 vertices, one pad slot at least after each half
-static NatGeom node_geom_split(int n) {
-  NatGeom g;
-  g.nx = g.ny = n + 1;
-  const int hp = ((n / 2 + 2 + 15) / 16) * 16;
-  g.pitch = 2 * hp + 2 * MSOM_XP;
-  g.rows = n + 1 + 2 * MSOM_YP;
-  g.ls = (size_t)g.pitch * g.rows;
-  return g;
-}
+// the square grid of n x n cells (msomn_tiles.hip has the rectangular forms a tile uses)
+static NatGeom node_geom(int n) { return node_geom_rect(n, n); }
+static NatGeom node_geom_split(int n) { return node_geom_split_rect(n, n); }
+static void free_level(NLevel &L, int k);
 static int dalloc(double **p, size_t n) {
   HIPCHK(hipMalloc((void **)p, n * sizeof(double)));
   HIPCHK(hipMemset(*p, 0, n * sizeof(double)));
@@ -59,37 +45,48 @@ static int field_layers(const msomn *m, int f) {
   return f == MSOMN_S2 ? m->nlm : (f == MSOMN_TOPO || f == MSOMN_QFORC || f == MSOMN_MASK || f == MSOMN_BS || f == MSOMN_S2S) ? 1 : m->nl;
 }
 
-// [layers][n+1][n+1] contiguous (host or device) <-> padded natural layout
+// [layers][ny][nx] contiguous (host or device) <-> padded natural layout
 int upload_g(msomn *m, double *dst, const NatGeom &g, int nl, const double *a) {
-  const size_t n1 = g.nx;
+  const size_t n1 = g.nx, n2 = g.ny;
   for (int l = 0; l < nl; l++)
-    HIPCHK(hipMemcpy2DAsync(dst + nat_idx(g, l, 0, 0), g.pitch * sizeof(double), a + (size_t)l * n1 * n1, n1 * sizeof(double), n1 * sizeof(double), n1,
+    HIPCHK(hipMemcpy2DAsync(dst + nat_idx(g, l, 0, 0), g.pitch * sizeof(double), a + (size_t)l * n1 * n2, n1 * sizeof(double), n1 * sizeof(double), n2,
                             hipMemcpyDefault, m->st));
   HIPCHK(hipStreamSynchronize(m->st));
   return MSOM_OK;
 }
 int download_g(msomn *m, const double *src, const NatGeom &g, int nl, double *a) {
-  const size_t n1 = g.nx;
+  const size_t n1 = g.nx, n2 = g.ny;
   for (int l = 0; l < nl; l++)
-    HIPCHK(hipMemcpy2DAsync(a + (size_t)l * n1 * n1, n1 * sizeof(double), src + nat_idx(g, l, 0, 0), g.pitch * sizeof(double), n1 * sizeof(double), n1,
+    HIPCHK(hipMemcpy2DAsync(a + (size_t)l * n1 * n2, n1 * sizeof(double), src + nat_idx(g, l, 0, 0), g.pitch * sizeof(double), n1 * sizeof(double), n2,
                             hipMemcpyDefault, m->st));
   HIPCHK(hipStreamSynchronize(m->st));
   return MSOM_OK;
 }
 
+static void free_level(NLevel &L, int k) {
+  for (double **q : {&L.da, &L.da2, &L.res, &L.mask_s, &L.S2_s, &L.S2row_buf}) { if (*q) (void)hipFree(*q); *q = nullptr; }
+  if (k > 0) for (double **q : {&L.mask, &L.S2}) { if (*q) (void)hipFree(*q); *q = nullptr; }
+  L.S2row = nullptr;
+}
+// buffers of level k with the natural geometry g: da and res are sized for either layout (the layout is chosen in choose_layouts from
+// the option node_split); level 0's mask and S2 are the model fields
+static int alloc_level(msomn *m, NLevel &L, int k, const NatGeom &g) {
+  L.n = m->N >> k;
+  L.D = m->p.L0 / L.n;
+  L.g = L.ga = g;
+  L.sp = 0;
+  int r;
+  const size_t lsa = std::max(g.ls, node_geom_split_rect(g.nx - 1, g.ny - 1).ls);
+  if ((r = dalloc(&L.da, lsa * m->nl)) || (r = dalloc(&L.da2, lsa * m->nl)) || (r = dalloc(&L.res, lsa * m->nl))) return r;
+  if (k == 0) { L.mask = m->f[MSOMN_MASK]; L.S2 = m->f[MSOMN_S2]; }
+  else if ((r = dalloc(&L.mask, g.ls)) || (r = dalloc(&L.S2, g.ls * m->nlm))) return r;
+  return MSOM_OK;
+}
 extern "C" void msomn_destroy(msomn_t *m) {
   if (!m) return;
   for (int k = 0; k < MSOMN_NFIELDS; k++) if (m->f[k]) (void)hipFree(m->f[k]);
-  for (size_t k = 0; k < m->lev.size(); k++) {
-    if (m->lev[k].da) (void)hipFree(m->lev[k].da);
-    if (m->lev[k].da2) (void)hipFree(m->lev[k].da2);
-    if (m->lev[k].res) (void)hipFree(m->lev[k].res);
-    if (m->lev[k].mask_s) (void)hipFree(m->lev[k].mask_s);
-    if (m->lev[k].S2_s) (void)hipFree(m->lev[k].S2_s);
-    if (m->lev[k].S2row_buf) (void)hipFree(m->lev[k].S2row_buf);
-    if (k > 0 && m->lev[k].mask) (void)hipFree(m->lev[k].mask);
-    if (k > 0 && m->lev[k].S2) (void)hipFree(m->lev[k].S2);
-  }
+  for (size_t k = 0; k < m->lev.size(); k++) free_level(m->lev[k], (int)k);
+  nt_free(m);
   for (size_t k = 0; k < m->cs.size(); k++) {
     if (m->cs[k]) (void)hipFree(m->cs[k]);
     if (m->cr[k]) (void)hipFree(m->cr[k]);
@@ -111,26 +108,16 @@ extern "C" void msomn_destroy(msomn_t *m) {
 }
 
 static int node_alloc(msomn *m) {
-  HIPCHK(hipStreamCreate(&m->st));
   for (int k = 0; k < MSOMN_NFIELDS; k++) {
     m->fl[k] = field_layers(m, k);
     int r = dalloc(&m->f[k], m->g.ls * m->fl[k]);
     if (r) return r;
   }
   m->lev.resize(m->nlev);
-  for (int k = 0; k < m->nlev; k++) {
-    NLevel &L = m->lev[k];
-    L.n = m->N >> k;
-    L.D = m->p.L0 / L.n;
-    L.g = node_geom(L.n);
-    L.da = L.da2 = L.res = L.mask = L.S2 = nullptr;
-    L.ga = L.g;
-    int r;
-    // da and res are sized for either layout (the layout is chosen in build_levels from the option node_split)
-    const size_t lsa = std::max(L.g.ls, node_geom_split(L.n).ls);
-    if ((r = dalloc(&L.da, lsa * m->nl)) || (r = dalloc(&L.da2, lsa * m->nl)) || (r = dalloc(&L.res, lsa * m->nl))) return r;
-    if (k == 0) { L.mask = m->f[MSOMN_MASK]; L.S2 = m->f[MSOMN_S2]; }
-    else if ((r = dalloc(&L.mask, L.g.ls)) || (r = dalloc(&L.S2, L.g.ls * m->nlm))) return r;
+  // on tiles the levels are allocated by msomn_set_const: which of them live on the tile depends on the option mg_coarse
+  for (int k = 0; k < m->nlev && m->ntiles == 1; k++) {
+    int r = alloc_level(m, m->lev[k], k, node_geom(m->N >> k));
+    if (r) return r;
   }
   int r;
   if ((r = dalloc(&m->d_scal, NSC_COUNT))) return r;
@@ -141,27 +128,36 @@ static int node_alloc(msomn *m) {
   HIPCHK(hipHostMalloc((void **)&m->h_row, (m->N + 1) * sizeof(double)));
   // set_vars qg-node/qg.h:426-430: mask = 1 on every vertex, its BC 0 on the four walls; S2 = N2[l]
   // (qg_baroclinic_ms.h:471-476)
-  const size_t n1 = m->N + 1;
-  std::vector<double> h(n1 * n1 * (m->nlm > 1 ? m->nlm : 1));
-  for (size_t j = 0; j < n1; j++) for (size_t i = 0; i < n1; i++) h[j * n1 + i] = (i == 0 || j == 0 || i == n1 - 1 || j == n1 - 1) ? 0. : 1.;
+  // (a tile: the walls are the sides of the tile that are sides of the domain)
+  const size_t n1 = m->g.nx, n2 = m->g.ny;
+  std::vector<double> h(n1 * n2 * (m->nlm > 1 ? m->nlm : 1));
+  for (size_t j = 0; j < n2; j++)
+    for (size_t i = 0; i < n1; i++)
+      h[j * n1 + i] = ((i == 0 && (m->walls & WALL_W)) || (j == 0 && (m->walls & WALL_S)) || (i == n1 - 1 && (m->walls & WALL_E)) || (j == n2 - 1 && (m->walls & WALL_N))) ? 0. : 1.;
   if ((r = upload_g(m, m->f[MSOMN_MASK], m->g, 1, h.data()))) return r;
   if (m->nl > 1) {
     // sqg: N2 = [surface, interfaces ...]; S2 layers 1..nl-1 of sqg_baroclinic_ms.h are the interfaces below layers 0..nl-2
-    for (int l = 0; l < m->nlm; l++) for (size_t k = 0; k < n1 * n1; k++) h[l * n1 * n1 + k] = m->p.N2[l + (m->sqg ? 1 : 0)];
+    for (int l = 0; l < m->nlm; l++) for (size_t k = 0; k < n1 * n2; k++) h[l * n1 * n2 + k] = m->p.N2[l + (m->sqg ? 1 : 0)];
     if ((r = upload_g(m, m->f[MSOMN_S2], m->g, m->nlm, h.data()))) return r;
     if (m->sqg) {
-      for (size_t k = 0; k < n1 * n1; k++) h[k] = m->p.N2[0];
+      for (size_t k = 0; k < n1 * n2; k++) h[k] = m->p.N2[0];
       if ((r = upload_g(m, m->f[MSOMN_S2S], m->g, 1, h.data())) || (r = dalloc(&m->qeff, m->g.ls * m->nl)) || (r = dalloc(&m->d2bs, m->g.ls))) return r;
     }
   }
   return MSOM_OK;
 }
 
-static msomn *node_create(const NodeParams &p, const char *text) {
+static msomn *node_create(const NodeParams &p, const char *text, int px = 1, int py = 1, int rank = 0, const void *id128 = nullptr) {
   if (p.nl < 1 || p.nl > MSOM_FASTNL) { msom_set_error("nl = %d outside the supported range 1..%d", p.nl, MSOM_FASTNL); return nullptr; }
   if (p.N < 2 || (p.N & (p.N - 1))) { msom_set_error("N = %d must be a power of two >= 2", p.N); return nullptr; }
   if (p.bc_fac == -1) { msom_set_error("bc_fac = -1 (periodic vertex grid) is not supported"); return nullptr; }
   if (p.sqg && p.nl < 2) { msom_set_error("sqg = 1 needs nl >= 2 (qg-node/sqg_baroclinic_ms.h is the multi-layer model)"); return nullptr; }
+  if (const char *why = ntile_check(p.N, px, py, rank)) {
+    msom_set_error("msomn_create_tiled: %s (N = %d, %d x %d tiles, rank %d)", why, p.N, px, py, rank);
+    return nullptr;
+  }
+  if (px * py > 1 && p.sqg) { msom_set_error("msomn_create_tiled: sqg = 1 is not available on more than one tile"); return nullptr; }
+  if (px * py > 1 && !id128) { msom_set_error("msomn_create_tiled: null communicator id"); return nullptr; }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
     msom_set_error("no HIP device available: libmsomhip has no CPU fallback");
@@ -174,13 +170,19 @@ static msomn *node_create(const NodeParams &p, const char *text) {
   m->sqg = p.sqg != 0;
   m->D = p.L0 / p.N;
   m->tolerance = p.TOLERANCE;
-  m->g = node_geom(p.N);
-  int n = 0;
-  while ((p.N >> n) >= 2) n++;
-  m->nlev = n;  // coarsest level: 2 x 2 cells, one interior vertex
+  m->nlev = ntile_nlev(p.N);  // coarsest level: 2 x 2 cells, one interior vertex
+  m->kg = m->nlev;
   memset(&m->lc, 0, sizeof m->lc);
-  if (node_alloc(m) != MSOM_OK) { msomn_destroy(m); return nullptr; }
+  if (hipStreamCreate(&m->st) != hipSuccess) { msom_set_error("hipStreamCreate failed"); delete m; return nullptr; }
+  if (nt_setup(m, px, py, rank, id128) != MSOM_OK || node_alloc(m) != MSOM_OK) { msomn_destroy(m); return nullptr; }
   return m;
+}
+extern "C" msomn_t *msomn_create_tiled(const char *text, int px, int py, int rank, const void *id128) {
+  if (!text) { msom_set_error("null params text"); return nullptr; }
+  NodeParams p;
+  msom_node_params_defaults(&p);
+  msom_node_params_parse_text(&p, text);
+  return node_create(p, text, px, py, rank, id128);
 }
 extern "C" msomn_t *msomn_create_str(const char *text) {
   if (!text) { msom_set_error("null params text"); return nullptr; }
@@ -207,6 +209,16 @@ extern "C" msomn_t *msomn_create(const char *path) {
 static int choose_layouts(msomn *m);
 extern "C" int msomn_set_option(msomn_t *m, const char *key, double v) {
   if (!m || !key) return MSOM_ERR_ARG;
+  if (m->ntiles > 1) {
+    // the fused passes have no tiled form: they stay off, whatever is asked for (msomn_get_param shows the resolved value)
+    for (const char *off : {"tiled_relax", "node_pfused", "node_corr_fused", "node_rhs_fused", "node_tile_s", "node_march", "node_march_s"})
+      if (!strcmp(key, off)) return MSOM_OK;
+    if (!strcmp(key, "stochastic") && v != 0.) return nt_refuse(m, "option stochastic");
+    if (!strcmp(key, "mg_coarse") && m->const_set) {
+      msom_set_error("option mg_coarse decides which levels live on the tiles: set it before msomn_set_const");
+      return MSOM_ERR_STATE;
+    }
+  }
   if (!strcmp(key, "TOLERANCE")) m->tolerance = v;
   else if (!strcmp(key, "NITERMAX")) m->nitermax = (int)v;
   else if (!strcmp(key, "NITERMIN")) m->nitermin = (int)v;
@@ -255,6 +267,7 @@ extern "C" int msomn_profile_reset(msomn_t *m) {
   if (!m) return MSOM_ERR_ARG;
   hipStreamSynchronize(m->st);
   for (auto &ps : m->prof) { ps.used = 0; ps.total_ms = 0; ps.launches = 0; }
+  m->nexch = 0;
   return MSOM_OK;
 }
 // K cap of the chained split pass (k_n_relax_march_s) on level L: windows of K stages x nl layers in registers.  0 where the pass
@@ -269,6 +282,7 @@ static int node_march_kmax(const msomn *m, const NLevel &L) {
 enum { NRP_COLOR = 0, NRP_SPLIT = 1, NRP_TILE_S = 2, NRP_MARCH_S = 3, NRP_COARSE = 4, NRP_MARCH = 5, NRP_TILE = 6 };
 static int sweep_path(const msomn *m, int k) {
   const NLevel &L = m->lev[k];
+  if (L.tiled) return L.sp ? NRP_SPLIT : NRP_COLOR;   // a tiled level: one launch and one halo exchange per colour
   if (L.sp && m->node_march_s && L.n + 1 >= m->node_march_s && node_march_kmax(m, L)) return NRP_MARCH_S;
   if (L.sp && m->node_tile_s && L.n + 1 >= m->node_tile_s && L.n + 1 <= m->node_tile_max && m->nl <= 4 && (m->nl == 1 || L.S2row)) return NRP_TILE_S;
   if (L.sp) return NRP_SPLIT;
@@ -301,6 +315,19 @@ extern "C" double msomn_get_param(msomn_t *m, const char *k) {
   if (!strcmp(k, "noise_mode")) return m->noise_mode;
   if (!strcmp(k, "seed")) return m->seed;
   if (!strcmp(k, "noise_draw")) return m->noise_draw;   // number of the next draw of the device generator
+  // tiles: the decomposition, the gather level (levels below live on the tiles), halo exchanges since the last msomn_profile_reset
+  if (!strcmp(k, "px")) return m->px;
+  if (!strcmp(k, "py")) return m->py;
+  if (!strcmp(k, "agg_level")) return m->ntiles > 1 ? (m->const_set ? m->kg : ntile_kg(m->N, m->px, m->py, m->mg_coarse)) : m->nlev;
+  if (!strcmp(k, "exchanges")) return (double)m->nexch;
+  if (!strcmp(k, "mg_coarse")) return m->mg_coarse;
+  if (!strcmp(k, "node_split")) return m->node_split;
+  if (!strcmp(k, "node_pfused")) return m->node_pfused;
+  if (!strcmp(k, "node_tile_s")) return m->node_tile_s;
+  if (!strcmp(k, "node_march")) return m->node_march;
+  if (!strcmp(k, "tiled_relax")) return m->tiled_relax;
+  if (!strcmp(k, "node_corr_fused")) return m->node_corr_fused;
+  if (!strcmp(k, "node_rhs_fused")) return m->node_rhs_fused;
   if (!strcmp(k, "node_march_s")) return m->node_march_s;   // split levels of >= this many vertices a side take k_n_relax_march_s
   if (!strcmp(k, "node_march_rows")) return m->node_march_rows;
   if (!strncmp(k, "split_", 6)) { int l = atoi(k + 6); return l >= 0 && l < m->nlev ? m->lev[l].sp : NAN; }
@@ -323,7 +350,9 @@ extern "C" int msomn_set_field(msomn_t *m, int f, const double *a) {
   if (f == MSOMN_QFORC3D) m->forcing_3d = 1;
   if (f == MSOMN_PSIPG) m->pg_set = 1;
   if (f == MSOMN_TOPO) m->topo_set = 1;
-  return upload_g(m, m->f[f], m->g, m->fl[f], a);
+  int r = upload_g(m, m->f[f], m->g, m->fl[f], a);
+  // tiles: every stencil that reads the field across a tile edge finds its halo (collective)
+  return r ? r : nt_exchange(m, m->f[f], m->g, 0, m->fl[f]);
 }
 extern "C" int msomn_get_field(msomn_t *m, int f, double *a) {
   NEED_FIELD(m, f);
@@ -333,20 +362,16 @@ extern "C" int msomn_get_field(msomn_t *m, int f, double *a) {
 
 // ---- boundary conditions with set_bc_ms() in force (qg-node/qg.h:197-214, qg_baroclinic_ms.h:55-70)
 static double bcc(const msomn *m) { return 2 * m->p.bc_fac / (m->D * m->D); }
-static void bnd_psi(msomn *m) { launch_n_bnd_const(m->st, m->f[MSOMN_PSI], m->g, m->nl, m->psi_bc); }
-static void bnd_q(msomn *m, double *q) { launch_n_bnd_from(m->st, q, m->f[MSOMN_PSI], m->g, m->nl, bcc(m), 0, m->psi_bc); }
+static void bnd_psi(msomn *m) { launch_n_bnd_const(m->st, m->f[MSOMN_PSI], m->g, m->nl, m->psi_bc, 0, m->walls); }
+static void bnd_q(msomn *m, double *q) { launch_n_bnd_from(m->st, q, m->f[MSOMN_PSI], m->g, m->nl, bcc(m), 0, m->psi_bc, m->walls); }
 // sqg_baroclinic_ms.h:64-67: the tmp rule subtracts psi_bc instead of the boundary value of zeta
-static void bnd_tmp(msomn *m) { launch_n_bnd_from(m->st, m->f[MSOMN_TMP], m->f[MSOMN_ZETA], m->g, m->nl, bcc(m), m->sqg ? 0 : 1, m->sqg ? m->psi_bc : 0.); }
+static void bnd_tmp(msomn *m) { launch_n_bnd_from(m->st, m->f[MSOMN_TMP], m->f[MSOMN_ZETA], m->g, m->nl, bcc(m), m->sqg ? 0 : 1, m->sqg ? m->psi_bc : 0., m->walls); }
 
-static int read_scalar(msomn *m, int slot, double *out) {
-  HIPCHK(hipMemcpyAsync(m->h_scal + slot, m->d_scal + slot, sizeof(double), hipMemcpyDeviceToHost, m->st));
-  HIPCHK(hipStreamSynchronize(m->st));
-  *out = m->h_scal[slot];
-  return MSOM_OK;
-}
 
 // comp_q_baroclinic / comp_q_barotropic
 static int comp_q(msomn *m, const double *psi, double *q) {
+  int rx = nt_exchange(m, const_cast<double *>(psi), m->g, 0, m->nl);   // the laplacian reads psi across the tile edges
+  if (rx) return rx;
   if (m->nl == 1) launch_n_helm(m->st, psi, q, m->g, m->D, m->iRd2_low);
   else {
     launch_n_del2(m->st, psi, q, m->g, m->nl, 0., 1., m->D);
@@ -379,7 +404,9 @@ static int rhs_pv_body(msomn *m, double *q, double *dq) {
   const NodeParams &p = m->p;
   const int nl = m->nl;
   const double drag = p.hEkb * p.f0 / (2 * p.dh[nl - 1]);
+  int rx;
   if (nl == 1) {
+    if ((rx = nt_exchange(m, m->f[MSOMN_PSI], m->g, 0, 1)) || (rx = nt_exchange(m, q, m->g, 0, 1))) return rx;   // the Jacobian reads both
     launch_n_rhs_barotropic(m->st, m->f[MSOMN_PSI], q, m->f[MSOMN_QFORC], dq, m->g, m->D, p.beta, drag, p.nu);
     HIPCHK(hipGetLastError());
     return MSOM_OK;
@@ -398,9 +425,12 @@ static int rhs_pv_body(msomn *m, double *q, double *dq) {
     HIPCHK(hipGetLastError());
     return MSOM_OK;
   }
+  // tiles run this chain (node_rhs_fused resolves to off): psi, zeta and tmp get their halos before the stencils that read them
   launch_n_mul_mask(m->st, q, psi, m->f[MSOMN_MASK], m->g, nl);                 // :110-116
+  if ((rx = nt_exchange(m, psi, m->g, 0, nl))) return rx;
   launch_n_del2(m->st, psi, zeta, m->g, nl, 0., 1., m->D);                      // comp_del2(psi, zeta, 0, 1)
   bnd_q(m, zeta);
+  if ((rx = nt_exchange(m, zeta, m->g, 0, nl))) return rx;
   launch_n_rhs_main(m->st, psi, zeta, m->f[MSOMN_PSIPG], S2, m->f[MSOMN_TOPO], dq, m->g, nl, 1, 1, m->D, p.beta, drag, p.f0, p.dh[nl - 1], m->lc);
   if (m->sqg) {                                                                 // sqg_baroclinic_ms.h:160-174: del2_bs = laplacian(bs)
     launch_n_lap_bs(m->st, m->f[MSOMN_BS], m->d2bs, m->g, m->D);
@@ -408,6 +438,7 @@ static int rhs_pv_body(msomn *m, double *q, double *dq) {
   } else launch_n_stretch(m->st, zeta, dq, S2, m->g, nl, 1., p.nu, m->lc);      // :160
   launch_n_del2(m->st, zeta, tmp, m->g, nl, 0., 1.0, m->D);                     // :162 + boundary(tmp)
   bnd_tmp(m);
+  if ((rx = nt_exchange(m, tmp, m->g, 0, nl))) return rx;
   launch_n_axpy(m->st, dq, tmp, m->g, nl, p.nu);                               // :164-167
   const double minus_nu4 = -p.nu4;
   if (m->sqg) launch_n_stretch_sqg(m->st, tmp, m->d2bs, m->f[MSOMN_S2S], dq, S2, m->g, nl, 1., minus_nu4, m->lc);   // del4_bs is laplacian(bs) again, :187-201
@@ -425,9 +456,12 @@ static void relax_level(msomn *m, int k, double *da, const double *res) {
   NLevel &L = m->lev[k];
   for (int c = 0; c < 2; c++) {
     if (k == 0) nprof_begin(m, NP_RELAX);
-    if (L.sp) launch_n_relax(m->st, da, res, L.mask_s, L.S2_s, L.ga, m->nl, c, L.D, m->iRd2_low, m->lc, 1, L.S2row);
-    else launch_n_relax(m->st, da, res, L.mask, L.S2, L.g, m->nl, c, L.D, m->iRd2_low, m->lc, 0, L.S2row);
+    if (L.sp) launch_n_relax(m->st, da, res, L.mask_s, L.S2_s, L.ga, m->nl, c, L.D, m->iRd2_low, m->lc, 1, L.S2row, L.walls);
+    else launch_n_relax(m->st, da, res, L.mask, L.S2, L.g, m->nl, c, L.D, m->iRd2_low, m->lc, 0, L.S2row, L.walls);
     if (k == 0) nprof_end(m, NP_RELAX);
+    // a tiled level: the other colour of the neighbours reads this one across the edge (an error stays in msom_last_error and
+    // stops the solve at its next reduction)
+    if (L.tiled && nt_exchange(m, da, L.ga, L.sp, m->nl)) m->tile_err = 1;
   }
 }
 // nsweeps red-black sweeps of level k on L.da.  Wide levels: LDS-tiled passes of 2 (or 1) sweeps, out of place
@@ -529,7 +563,7 @@ static int choose_layouts(msomn *m) {
     L.S2row = nullptr;
     if (m->nl > 1 && m->s2_xuniform && m->s2_rows) {
       int r;
-      if (!L.S2row_buf && (r = dalloc(&L.S2row_buf, (size_t)m->nlm * (L.n + 1)))) return r;
+      if (!L.S2row_buf && (r = dalloc(&L.S2row_buf, (size_t)m->nlm * L.g.ny))) return r;
       launch_n_row_table(m->st, L.S2, L.g, m->nlm, L.S2row_buf);
       L.S2row = L.S2row_buf;
     }
@@ -537,7 +571,13 @@ static int choose_layouts(msomn *m) {
   for (int k = 0; k < m->nlev; k++) {
     NLevel &L = m->lev[k];
     L.sp = m->node_split > 0 && L.n + 1 >= m->node_split && L.n >= 64 && L.n > m->mg_coarse;
-    L.ga = L.sp ? node_geom_split(L.n) : L.g;
+    // (a tiled level compares the GLOBAL side with node_split, so a tiled handle takes the layouts of the single tile)
+    const int was = L.ga.pitch;
+    L.ga = L.sp ? node_geom_split_rect(L.g.nx - 1, L.g.ny - 1) : L.g;
+    if (L.tiled && was != L.ga.pitch) {   // the halo slots of the new layout hold whatever the old one kept there
+      const size_t bytes = std::max(L.g.ls, node_geom_split_rect(L.g.nx - 1, L.g.ny - 1).ls) * m->nl * sizeof(double);
+      for (double *q : {L.da, L.da2, L.res}) HIPCHK(hipMemsetAsync(q, 0, bytes, m->st));
+    }
     if (!L.sp) continue;
     int r;
     if (!L.mask_s && ((r = dalloc(&L.mask_s, L.ga.ls)) || (m->nl > 1 && (r = dalloc(&L.S2_s, L.ga.ls * m->nlm))))) return r;
@@ -547,7 +587,50 @@ static int choose_layouts(msomn *m) {
   HIPCHK(hipGetLastError());
   return MSOM_OK;
 }
+// tiles: levels below the gather level kg hold the tile's window, kg and up the global grid (the same values on every rank, the ones
+// the single tile holds): the level-kg mask and S2 are restricted on the tiles, gathered once, and the coarser ones built from them
+static int build_levels_tiled(msomn *m) {
+  int r;
+  m->kg = ntile_kg(m->N, m->px, m->py, m->mg_coarse);
+  for (int k = 0; k < m->nlev; k++) free_level(m->lev[k], k);
+  nt_free_gather(m);
+  for (int k = 0; k <= m->nlev; k++) {   // k == nlev: the piece, the tile's window of level kg
+    const bool piece = k == m->nlev;
+    if (!piece && k >= m->kg) { if ((r = alloc_level(m, m->lev[k], k, node_geom(m->N >> k)))) return r; m->lev[k].tiled = 0; m->lev[k].walls = WALL_ALL; continue; }
+    const NodeTile t = ntile_level(m->N, m->px, m->py, m->rank, piece ? m->kg : k);
+    NLevel &L = piece ? m->piece : m->lev[k];
+    if ((r = alloc_level(m, L, piece ? m->kg : k, node_geom_rect(t.tx, t.ty)))) return r;
+    L.tiled = 1; L.walls = m->walls;
+  }
+  m->gcount = (size_t)(m->nl > m->nlm ? m->nl : m->nlm) * m->piece.g.nx * m->piece.g.ny;
+  HIPCHK(hipMalloc((void **)&m->gsend, m->gcount * sizeof(double)));
+  HIPCHK(hipMalloc((void **)&m->grecv, m->gcount * m->ntiles * sizeof(double)));
+  launch_n_bnd_const(m->st, m->f[MSOMN_MASK], m->g, 1, 0., 0, m->walls);
+  // the static fields the tendency reads across the tile edges (the inputs were transformed in place since msomn_set_field)
+  for (int f : {MSOMN_MASK, MSOMN_S2, MSOMN_TOPO, MSOMN_PSIPG})
+    if ((r = nt_exchange(m, m->f[f], m->g, 0, m->fl[f]))) return r;
+  for (int k = 1; k <= m->kg; k++) {
+    NLevel &F = m->lev[k - 1], &C = k < m->kg ? m->lev[k] : m->piece;
+    launch_n_restrict(m->st, F.mask, F.g, C.mask, C.g, 1, 1);   // the 9-point full weighting reads the halo with its corners
+    launch_n_bnd_const(m->st, C.mask, C.g, 1, 0., 0, m->walls);
+    if ((r = nt_exchange(m, C.mask, C.g, 0, 1))) return r;
+    if (m->nl > 1) {
+      launch_n_restrict(m->st, F.S2, F.g, C.S2, C.g, m->nlm, 2);
+      if ((r = nt_exchange(m, C.S2, C.g, 0, m->nlm))) return r;
+    }
+  }
+  NLevel &G = m->lev[m->kg];
+  if ((r = nt_gather(m, m->piece.mask, m->piece.g, 1, G.mask, G.g))) return r;
+  if (m->nl > 1 && (r = nt_gather(m, m->piece.S2, m->piece.g, m->nlm, G.S2, G.g))) return r;
+  for (int k = m->kg + 1; k < m->nlev; k++) {
+    launch_n_restrict(m->st, m->lev[k - 1].mask, m->lev[k - 1].g, m->lev[k].mask, m->lev[k].g, 1, 1);
+    launch_n_bnd_const(m->st, m->lev[k].mask, m->lev[k].g, 1, 0.);
+    if (m->nl > 1) launch_n_restrict(m->st, m->lev[k - 1].S2, m->lev[k - 1].g, m->lev[k].S2, m->lev[k].g, m->nlm, 2);
+  }
+  return choose_layouts(m);
+}
 static int build_levels(msomn *m) {
+  if (m->ntiles > 1) return build_levels_tiled(m);
   launch_n_bnd_const(m->st, m->f[MSOMN_MASK], m->g, 1, 0.);
   for (int k = 1; k < m->nlev; k++) {
     launch_n_restrict(m->st, m->lev[k - 1].mask, m->lev[k - 1].g, m->lev[k].mask, m->lev[k].g, 1, 1);
@@ -569,8 +652,88 @@ static int download_lev(msomn *m, NLevel &L, const double *src, double *a) {
   launch_n_relayout(m->st, src, L.ga, 1, L.da2, L.g, 0, m->nl);
   return download_g(m, L.da2, L.g, m->nl, a);
 }
+// The levels kg .. nlev - 1 of a tiled handle's cycle, on the global grid and the same on every rank: lev[kg].res -> lev[kg].da by the
+// launches the single tile makes for these levels -- the one-launch group where coarse_first qualifies (it starts at kg at the
+// earliest), level by level otherwise
+static int gathered_solve(msomn *m, int nrelax) {
+  const int nl = m->nl, nlev = m->nlev, kg = m->kg;
+  const int kc = std::max(coarse_first(m), kg);
+  for (int k = kg + 1; k < nlev && k <= kc; k++) launch_n_restrict(m->st, m->lev[k - 1].res, m->lev[k - 1].ga, m->lev[k].res, m->lev[k].ga, nl, 0, 0, 0, 1);
+  if (kc < nlev) {
+    NCoarseArgs ca;
+    ca.n = nlev - kc; ca.iRd2 = m->iRd2_low; ca.lc = m->lc;
+    for (int k = kc; k < nlev; k++) {
+      NLevel &L = m->lev[k];
+      ca.lev[k - kc] = NCoarseLev{L.da, L.res, L.mask, L.S2, L.g, L.D * L.D};
+    }
+    nprof_begin(m, NP_COARSE);
+    launch_n_mg_coarse(m->st, ca, nrelax, nl);
+    nprof_end(m, NP_COARSE);
+    if (kc > kg) launch_n_prolong(m->st, m->lev[kc].da, m->lev[kc].ga, m->lev[kc - 1].da, m->lev[kc - 1].ga, nl);
+  } else HIPCHK(hipMemsetAsync(m->lev[nlev - 1].da, 0, m->lev[nlev - 1].g.ls * nl * sizeof(double), m->st));
+  for (int k = (kc < nlev ? kc : nlev) - 1; k >= kg; k--) {
+    relax_sweeps(m, k, nrelax);
+    if (k > kg) launch_n_prolong(m->st, m->lev[k].da, m->lev[k].ga, m->lev[k - 1].da, m->lev[k - 1].ga, nl);
+  }
+  HIPCHK(hipGetLastError());
+  return MSOM_OK;
+}
+// vpoisson on tiles.  Per cycle: halo of a, residual, all-reduce of max |res| (every rank takes the same decision); the residual goes
+// down the tiled levels (halo, restriction), the level-kg pieces are gathered, every rank solves the gathered levels, takes its
+// window of the level-kg correction and goes up the tiled levels (prolongation, halo, colour passes with a halo each); a += da.
+static int vpoisson_tiled(msomn *m, double *&a, const double *b) {
+  msom_mgstats mg;
+  mg.sum = HUGE_VAL; mg.resa = HUGE_VAL; mg.resb = 0; mg.nrelax = m->nrelax;
+  const int nl = m->nl, kg = m->kg;
+  NLevel &L0 = m->lev[0], &P = m->piece, &G = m->lev[kg];
+  const NodeTile tg = ntile_level(m->N, m->px, m->py, m->rank, kg);
+  bool pending_correct = false;
+  int r;
+  m->tile_err = 0;
+  auto correct = [&]() {
+    nprof_begin(m, NP_CORRECT);
+    launch_n_correct(m->st, a, L0.da, m->g, nl, m->psi_bc, L0.sp ? &L0.ga : nullptr, m->walls);
+    nprof_end(m, NP_CORRECT);
+  };
+  for (mg.i = 0; mg.i < m->nitermax; mg.i++) {
+    HIPCHK(hipMemsetAsync(m->d_scal + NSC_RES, 0, sizeof(double), m->st));
+    if (pending_correct) correct();
+    pending_correct = false;
+    if ((r = nt_exchange(m, a, m->g, 0, nl))) return r;
+    nprof_begin(m, NP_RESIDUAL);
+    launch_n_residual(m->st, a, b, L0.mask, L0.S2, L0.res, m->d_scal + NSC_RES, m->g, nl, m->D, m->iRd2_low, m->lc, L0.sp ? &L0.ga : nullptr, L0.S2row, 1, m->walls);
+    nprof_end(m, NP_RESIDUAL);
+    if ((r = nt_reduce(m, NSC_RES, 1, RED_MAX))) return r;
+    const double max = m->h_scal[NSC_RES];
+    mg.resa = max;
+    if (mg.i == 0) mg.resb = max;
+    if (max < m->tolerance && mg.i >= m->nitermin) break;
+    for (int k = 1; k <= kg; k++) {
+      NLevel &F = m->lev[k - 1], &C = k < kg ? m->lev[k] : P;
+      if ((r = nt_exchange(m, F.res, F.ga, F.sp, nl))) return r;
+      launch_n_restrict(m->st, F.res, F.ga, C.res, C.ga, nl, 0, F.sp, C.sp, 1, m->walls);
+    }
+    if ((r = nt_gather(m, P.res, P.g, nl, G.res, G.g)) || (r = gathered_solve(m, mg.nrelax))) return r;
+    launch_n_extract(m->st, G.da, G.g, P.da, P.g, nl, tg.ox, tg.oy);
+    for (int k = kg - 1; k >= 0; k--) {
+      NLevel &C = k + 1 < kg ? m->lev[k + 1] : P, &L = m->lev[k];
+      launch_n_prolong(m->st, C.da, C.ga, L.da, L.ga, nl, C.sp, L.sp, m->walls);
+      if ((r = nt_exchange(m, L.da, L.ga, L.sp, nl))) return r;
+      relax_sweeps(m, k, mg.nrelax);
+      if (m->tile_err) return MSOM_ERR_COMM;
+    }
+    pending_correct = true;
+  }
+  if (pending_correct) correct();
+  HIPCHK(hipGetLastError());
+  if (mg.resa > m->tolerance && !m->quiet)
+    fprintf(stderr, "Convergence for psi not reached.\nmg.i = %d, mg.resb: %g mg.resa: %g\n", mg.i, mg.resb, mg.resa);
+  m->mg = mg;
+  return MSOM_OK;
+}
 // vpoisson, nodal-poisson.h:19-143: residual first, then (unless converged) one cycle
 static int vpoisson(msomn *m, double *&a, const double *b) {
+  if (m->ntiles > 1) return vpoisson_tiled(m, a, b);
   msom_mgstats mg;
   mg.sum = HUGE_VAL; mg.resa = HUGE_VAL; mg.resb = 0; mg.nrelax = m->nrelax;
   const int nl = m->nl, nlev = m->nlev;
@@ -666,9 +829,10 @@ static int invert_q(msomn *m, double *q) {
 static int adjust_dt(msomn *m, double dtmax, double *out) {
   HIPCHK(hipMemsetAsync(m->d_scal + NSC_UMAX, 0, sizeof(double), m->st));
   launch_n_umax(m->st, m->f[MSOMN_PSI], m->d_scal + NSC_UMAX, m->g, m->nl, m->D);
-  double um;
-  int r = read_scalar(m, NSC_UMAX, &um);
+  // (tiles: a face on a shared edge is seen by both tiles, the maximum does not mind)
+  int r = nt_reduce(m, NSC_UMAX, 1, RED_MAX);
   if (r) return r;
+  const double um = m->h_scal[NSC_UMAX];
   dtmax /= m->p.CFL;
   if (um != 0.) { const double dt = m->D / um; if (dt < dtmax) dtmax = dt; }
   dtmax *= m->p.CFL;
@@ -781,11 +945,13 @@ static int generate_noise(msomn *m, int filter = 1) {
   return r || !filter ? r : cell_wavelet_filter(m);
 }
 extern "C" int msomn_noise_draw(msomn_t *m, int filter) {
+  if (int rt = nt_refuse(m, "msomn_noise_draw")) return rt;
   NEED_NCONST(m);
   if (m->cnlev == 0) { msom_set_error("stochastic forcing is off"); return MSOM_ERR_STATE; }
   return generate_noise(m, filter);
 }
 extern "C" int msomn_dbg_noise(msomn_t *m, const double *set, int filter, double *get) {
+  if (int rt = nt_refuse(m, "msomn_dbg_noise")) return rt;
   NEED_NCONST(m);
   if (m->cnlev == 0) { msom_set_error("stochastic forcing is off"); return MSOM_ERR_STATE; }
   int r;
@@ -799,6 +965,7 @@ extern "C" int msomn_dbg_noise(msomn_t *m, const double *set, int filter, double
   return MSOM_OK;
 }
 extern "C" int msomn_dbg_csig(msomn_t *m, int level, double *out) {
+  if (int rt = nt_refuse(m, "msomn_dbg_csig")) return rt;
   NEED_NCONST(m);
   if (level < 0 || level >= m->cnlev || !out) { msom_set_error("bad level %d", level); return MSOM_ERR_ARG; }
   const NatGeom &g = m->cg[level];
@@ -893,6 +1060,7 @@ static int wv_masked_apply(msomn *m) {
 static int invert_q(msomn *m, double *q);
 static int comp_q(msomn *m, const double *psi, double *q);
 extern "C" int msomn_wavelet_filter(msomn_t *m, double dtflt) {
+  if (int rt = nt_refuse(m, "msomn_wavelet_filter")) return rt;
   NEED_NCONST(m);
   int r;
   if (!m->wv_ready && (r = wv_setup(m))) return r;
@@ -909,6 +1077,7 @@ extern "C" int msomn_wavelet_filter(msomn_t *m, double dtflt) {
 }
 // what = 0: sig_lev as used at the cells, 1: mask_c; level k, out [n][n]
 extern "C" int msomn_dbg_wv_get(msomn_t *m, int what, int level, double *out) {
+  if (int rt = nt_refuse(m, "msomn_dbg_wv_get")) return rt;
   NEED_NCONST(m);
   int r;
   if (!m->wv_ready && (r = wv_setup(m))) return r;
@@ -921,6 +1090,7 @@ extern "C" int msomn_dbg_wv_get(msomn_t *m, int what, int level, double *out) {
 }
 // the masked transform pair alone on a cell field [nl][N][N]
 extern "C" int msomn_dbg_wv_apply(msomn_t *m, const double *in, double *out) {
+  if (int rt = nt_refuse(m, "msomn_dbg_wv_apply")) return rt;
   NEED_NCONST(m);
   int r;
   if (!m->wv_ready && (r = wv_setup(m))) return r;
@@ -947,29 +1117,29 @@ static int check_dh(const msomn *m) {
 int node_const_inputs(msomn *m) {
   const NodeParams &p = m->p;
   const int nl = m->nl;
-  const size_t n1 = m->N + 1;
+  const size_t n1 = m->g.nx, n2 = m->g.ny;   // the tile's vertices; y of row j is that of the GLOBAL row oy + j
   int r;
   if ((r = check_dh(m))) return r;
   if (nl == 1) return MSOM_OK;
   // S2: N^2 -> f^2 / N^2 with f = f0 + flag_ms beta (y - L0/2)  (qg_baroclinic_ms.h:501-505); init-time host pass
-  std::vector<double> h(n1 * n1 * m->nlm);
+  std::vector<double> h(n1 * n2 * m->nlm);
   if ((r = download_g(m, m->f[MSOMN_S2], m->g, m->nlm, h.data()))) return r;
-  for (int l = 0; l < nl - 1; l++) for (size_t j = 0; j < n1; j++) {
-    const double f = p.f0 + p.flag_ms * p.beta * (j * m->D - 0.5 * p.L0);
-    for (size_t i = 0; i < n1; i++) { double &s = h[(l * n1 + j) * n1 + i]; s = f * f / s; }
+  for (int l = 0; l < nl - 1; l++) for (size_t j = 0; j < n2; j++) {
+    const double f = p.f0 + p.flag_ms * p.beta * ((j + m->oy) * m->D - 0.5 * p.L0);
+    for (size_t i = 0; i < n1; i++) { double &s = h[(l * n2 + j) * n1 + i]; s = f * f / s; }
   }
   if ((r = upload_g(m, m->f[MSOMN_S2], m->g, m->nlm, h.data()))) return r;
   if (m->sqg) {  // :545 surface layer: f / N^2 (f, not f^2)
-    std::vector<double> hs(n1 * n1);
+    std::vector<double> hs(n1 * n2);   // (sqg runs on one tile only: n2 = n1, oy = 0)
     if ((r = download_g(m, m->f[MSOMN_S2S], m->g, 1, hs.data()))) return r;
-    for (size_t j = 0; j < n1; j++) {
+    for (size_t j = 0; j < n2; j++) {
       const double f = p.f0 + p.flag_ms * p.beta * (j * m->D - 0.5 * p.L0);
       for (size_t i = 0; i < n1; i++) hs[j * n1 + i] = f / hs[j * n1 + i];
     }
     if ((r = upload_g(m, m->f[MSOMN_S2S], m->g, 1, hs.data()))) return r;
   }
   if (p.scale_topo != 1.) {
-    std::vector<double> tp(n1 * n1);
+    std::vector<double> tp(n1 * n2);
     if ((r = download_g(m, m->f[MSOMN_TOPO], m->g, 1, tp.data()))) return r;
     for (double &v : tp) v *= p.scale_topo;
     if ((r = upload_g(m, m->f[MSOMN_TOPO], m->g, 1, tp.data()))) return r;
@@ -986,7 +1156,7 @@ double node_clamped_dt(const msomn *m) {
 int node_const_derived(msomn *m) {
   NodeParams &p = m->p;
   const int nl = m->nl;
-  const size_t n1 = m->N + 1;
+  const size_t n1 = m->g.nx, n2 = m->g.ny;
   int r;
   if ((r = check_dh(m))) return r;
   if (nl > 1) {
@@ -996,11 +1166,17 @@ int node_const_derived(msomn *m) {
     m->lc.idh1[0] = 1. / (dhc[0] * p.dh[0]);
     for (int l = 1; l < nl - 1; l++) { m->lc.idh0[l] = 1. / (dhc[l - 1] * p.dh[l]); m->lc.idh1[l] = 1. / (dhc[l] * p.dh[l]); }
     m->lc.idh0[nl - 1] = 1. / (dhc[nl - 2] * p.dh[nl - 1]); m->lc.idh1[nl - 1] = 0.;
-    std::vector<double> h(n1 * n1 * m->nlm);   // the transformed S2
+    std::vector<double> h(n1 * n2 * m->nlm);   // the transformed S2
     if ((r = download_g(m, m->f[MSOMN_S2], m->g, m->nlm, h.data()))) return r;
     m->s2_xuniform = 1;
-    for (size_t r0 = 0; r0 < (size_t)(nl - 1) * n1 && m->s2_xuniform; r0++)
+    for (size_t r0 = 0; r0 < (size_t)(nl - 1) * n2 && m->s2_xuniform; r0++)
       for (size_t i = 1; i < n1; i++) if (h[r0 * n1 + i] != h[r0 * n1]) { m->s2_xuniform = 0; break; }
+    if (m->ntiles > 1) {   // every tile takes the same path: row tables only if S2 is x-independent on all of them
+      m->h_scal[NSC_RES] = m->s2_xuniform;
+      HIPCHK(hipMemcpyAsync(m->d_scal + NSC_RES, m->h_scal + NSC_RES, sizeof(double), hipMemcpyHostToDevice, m->st));
+      if ((r = nt_reduce(m, NSC_RES, 1, RED_MIN))) return r;
+      m->s2_xuniform = m->h_scal[NSC_RES] != 0.;
+    }
   } else if (p.gp_low != 0.) m->iRd2_low = p.f0 * p.f0 / (p.gp_low * p.dh[nl - 1]);
   if ((r = build_levels(m))) return r;
   if (m->stochastic && (r = stoch_setup(m))) return r;  // event init_stoch
@@ -1057,6 +1233,7 @@ extern "C" int msomn_invert_q(msomn_t *m, int qf, msom_mgstats *st) {
 extern "C" int msomn_comp_q(msomn_t *m, int pf, int qf) { NEED_NCONST(m); NEED_FIELD(m, pf); NEED_FIELD(m, qf); return comp_q(m, m->f[pf], m->f[qf]); }
 extern "C" int msomn_rhs_pv(msomn_t *m, int qf, int dqf) { NEED_NCONST(m); NEED_FIELD(m, qf); NEED_FIELD(m, dqf); return rhs_pv(m, m->f[qf], m->f[dqf]); }
 extern "C" int msomn_dbg_del2_zeta(msomn_t *m) {
+  if (int rt = nt_refuse(m, "msomn_dbg_del2_zeta")) return rt;
   NEED_NCONST(m);
   launch_n_del2(m->st, m->f[MSOMN_PSI], m->f[MSOMN_ZETA], m->g, m->nl, 0., 1., m->D);
   bnd_q(m, m->f[MSOMN_ZETA]);
@@ -1075,7 +1252,7 @@ extern "C" int msomn_forcing(msomn_t *m) {
                   sin(p.forc_mode * M_PI * (y + y * (y - L0) * 2 / (L0 * L0) * p.dy_ws * sin(2 * M_PI * t / p.tf2)) / L0);
   }
   HIPCHK(hipMemcpyAsync(m->d_row, m->h_row, (m->N + 1) * sizeof(double), hipMemcpyHostToDevice, m->st));
-  launch_n_rowfill(m->st, m->f[MSOMN_QFORC], m->d_row, m->g);
+  launch_n_rowfill(m->st, m->f[MSOMN_QFORC], m->d_row + m->oy, m->g);   // a tile takes its rows of the global profile
   HIPCHK(hipGetLastError());
   return MSOM_OK;
 }
@@ -1116,33 +1293,40 @@ extern "C" int msomn_iter(msomn_t *m) { return m ? m->iter : MSOM_ERR_ARG; }
 extern "C" int msomn_last_mgstats(msomn_t *m, msom_mgstats *s) { if (!m || !s) return MSOM_ERR_ARG; *s = m->mg; return MSOM_OK; }
 extern "C" int msomn_ke(msomn_t *m, double *ke) {
   if (!m || !ke) return MSOM_ERR_ARG;
-  launch_n_ke(m->st, m->f[MSOMN_PSI], m->partial, m->d_scal + NSC_KE, m->g, m->D);
-  double v;
-  int r = read_scalar(m, NSC_KE, &v);
+  // tiles: every vertex is counted once (a tile leaves out its east and north edge unless that edge is a wall)
+  int r = nt_exchange(m, m->f[MSOMN_PSI], m->g, 0, 1);
   if (r) return r;
-  *ke = -v;
+  launch_n_ke(m->st, m->f[MSOMN_PSI], m->partial, m->d_scal + NSC_KE, m->g, m->D, m->walls);
+  if ((r = nt_reduce(m, NSC_KE, 1, RED_SUM))) return r;
+  *ke = -m->h_scal[NSC_KE];
   return MSOM_OK;
 }
 
 // event write_1d_diag (qg-node/qg.h:361-399): out = {ke, dissipation, forcing}
 extern "C" int msomn_diag1d(msomn_t *m, double *out3) {
   if (!m || !out3) return MSOM_ERR_ARG;
+  // (the cell loop leaves out the last column and row of vertices: on tiles that is the east and north edge of every tile)
+  int r;
+  if ((r = nt_exchange(m, m->f[MSOMN_PSI], m->g, 0, 1)) || (r = nt_exchange(m, m->f[MSOMN_Q], m->g, 0, 1))) return r;
   launch_n_diag1d(m->st, m->f[MSOMN_PSI], m->f[MSOMN_Q], m->f[MSOMN_QFORC], m->partial, m->d_scal + NSC_DIAG, m->g, m->p.nu, m->D);
-  HIPCHK(hipMemcpyAsync(m->h_scal + NSC_DIAG, m->d_scal + NSC_DIAG, 3 * sizeof(double), hipMemcpyDeviceToHost, m->st));
-  HIPCHK(hipStreamSynchronize(m->st));
+  if ((r = nt_reduce(m, NSC_DIAG, 3, RED_SUM))) return r;
   for (int k = 0; k < 3; k++) out3[k] = -m->h_scal[NSC_DIAG + k];
   return MSOM_OK;
 }
 
 // ---- raw multigrid pieces (parity tests)
-#define NEED_LEVEL(m, k) if (!(m) || (k) < 0 || (k) >= (m)->nlev) { msom_set_error("bad level %d", (int)(k)); return MSOM_ERR_ARG; }
+// (a tiled handle: the levels that live on the tile; a gathered level has no tile-sized arrays)
+#define NEED_LEVEL(m, k) if (!(m) || (k) < 0 || (k) >= ((m)->ntiles > 1 ? (m)->kg : (m)->nlev)) { msom_set_error("bad level %d", (int)(k)); return MSOM_ERR_ARG; }
 extern "C" int msomn_dbg_relax(msomn_t *m, int k, double *da, const double *res, int nsweeps) {
   NEED_NCONST(m); NEED_LEVEL(m, k);
   NLevel &L = m->lev[k];
   int r;
   if ((r = upload_lev(m, L, L.da, da)) || (r = upload_lev(m, L, L.res, res))) return r;
-  launch_n_bnd_const(m->st, L.da, L.ga, m->nl, 0., L.sp);
+  launch_n_bnd_const(m->st, L.da, L.ga, m->nl, 0., L.sp, L.walls);
+  if (L.tiled && (r = nt_exchange(m, L.da, L.ga, L.sp, m->nl))) return r;
+  m->tile_err = 0;
   relax_sweeps(m, k, nsweeps);
+  if (m->tile_err) return MSOM_ERR_COMM;
   HIPCHK(hipGetLastError());
   return download_lev(m, L, L.da, da);
 }
@@ -1151,11 +1335,11 @@ extern "C" int msomn_dbg_residual(msomn_t *m, const double *a, const double *b, 
   int r;
   if ((r = upload_g(m, m->f[MSOMN_TMP], m->g, m->nl, a)) || (r = upload_g(m, m->f[MSOMN_DQ], m->g, m->nl, b))) return r;
   HIPCHK(hipMemsetAsync(m->d_scal + NSC_RES, 0, sizeof(double), m->st));
+  if ((r = nt_exchange(m, m->f[MSOMN_TMP], m->g, 0, m->nl))) return r;
   launch_n_residual(m->st, m->f[MSOMN_TMP], m->f[MSOMN_DQ], m->lev[0].mask, m->lev[0].S2, m->lev[0].res, m->d_scal + NSC_RES, m->g, m->nl, m->D, m->iRd2_low,
-                    m->lc, m->lev[0].sp ? &m->lev[0].ga : nullptr, m->lev[0].S2row);
-  double mx;
-  if ((r = read_scalar(m, NSC_RES, &mx))) return r;
-  if (maxres) *maxres = mx;
+                    m->lc, m->lev[0].sp ? &m->lev[0].ga : nullptr, m->lev[0].S2row, 0, m->walls);
+  if ((r = nt_reduce(m, NSC_RES, 1, RED_MAX))) return r;
+  if (maxres) *maxres = m->h_scal[NSC_RES];
   return download_lev(m, m->lev[0], m->lev[0].res, res);
 }
 extern "C" int msomn_dbg_restrict(msomn_t *m, int k, const double *fine, double *coarse) {
@@ -1163,9 +1347,10 @@ extern "C" int msomn_dbg_restrict(msomn_t *m, int k, const double *fine, double 
   int r;
   NLevel &Lf = m->lev[k], &Lc = m->lev[k + 1];
   if ((r = upload_lev(m, Lf, Lf.res, fine))) return r;
-  launch_n_bnd_const(m->st, Lf.res, Lf.ga, m->nl, 0., Lf.sp);
+  launch_n_bnd_const(m->st, Lf.res, Lf.ga, m->nl, 0., Lf.sp, Lf.walls);
+  if (Lf.tiled && (r = nt_exchange(m, Lf.res, Lf.ga, Lf.sp, m->nl))) return r;
   launch_n_restrict(m->st, Lf.res, Lf.ga, Lc.res, Lc.ga, m->nl, 0, Lf.sp, Lc.sp);
-  launch_n_bnd_const(m->st, Lc.res, Lc.ga, m->nl, 0., Lc.sp);
+  launch_n_bnd_const(m->st, Lc.res, Lc.ga, m->nl, 0., Lc.sp, Lc.walls);
   return download_lev(m, Lc, Lc.res, coarse);
 }
 extern "C" int msomn_dbg_prolong(msomn_t *m, int k, const double *coarse, double *fine) {
@@ -1173,8 +1358,8 @@ extern "C" int msomn_dbg_prolong(msomn_t *m, int k, const double *coarse, double
   int r;
   NLevel &Lc = m->lev[k], &Lf = m->lev[k - 1];
   if ((r = upload_lev(m, Lc, Lc.da, coarse))) return r;
-  launch_n_bnd_const(m->st, Lc.da, Lc.ga, m->nl, 0., Lc.sp);
-  launch_n_prolong(m->st, Lc.da, Lc.ga, Lf.da, Lf.ga, m->nl, Lc.sp, Lf.sp);
+  launch_n_bnd_const(m->st, Lc.da, Lc.ga, m->nl, 0., Lc.sp, Lc.walls);
+  launch_n_prolong(m->st, Lc.da, Lc.ga, Lf.da, Lf.ga, m->nl, Lc.sp, Lf.sp, Lf.walls);
   return download_lev(m, Lf, Lf.da, fine);
 }
 extern "C" int msomn_dbg_level_mask(msomn_t *m, int k, double *out) {

@@ -1,5 +1,6 @@
 // msomn_host.h -- the vertex-grid handle (struct msomn) and the host helpers its units share: msom_node.hip (model and multigrid),
-// msomn_io.hip (NetCDF IO and the driver msomn_run), msomn_state.hip (state file, include/msomn_state.h).  Not installed.
+// msomn_tiles.hip (the model on tiles: decomposition, halo exchange, gather), msomn_io.hip (NetCDF IO and the driver msomn_run),
+// msomn_state.hip (state file, include/msomn_state.h).  Not installed.
 #ifndef MSOMN_HOST_H
 #define MSOMN_HOST_H
 
@@ -14,7 +15,9 @@
 #include <string>
 #include <vector>
 
+#include "comm.h"
 #include "kernels.h"
+#include "node_tile_inl.h"
 
 #define HIPCHK(x)                                                                          \
   do {                                                                                     \
@@ -29,14 +32,17 @@ struct NLevel {
   int n;        // cells per side: (n + 1)^2 vertices
   double D;     // L0 / n
   NatGeom g;
-  double *da, *res, *mask, *S2;  // level 0: mask and S2 alias the model fields
-  double *da2;                   // second correction buffer (the tiled smoother works out of place)
+  double *da = nullptr, *res = nullptr, *mask = nullptr, *S2 = nullptr;  // level 0: mask and S2 alias the model fields
+  double *da2 = nullptr;         // second correction buffer (the tiled smoother works out of place)
   // wide levels (option node_split): da and res in the x-parity split layout of geometry ga, with split copies of mask and S2
   int sp = 0;
   NatGeom ga;                    // geometry of da / res: g, or the split geometry
   double *mask_s = nullptr, *S2_s = nullptr;
   double *S2row_buf = nullptr;   // allocation behind S2row
   double *S2row = nullptr;       // [nlm][n + 1] when S2 does not depend on x (and the option s2_rows is on), else null
+  // vertex model on tiles: a level above the gather level holds the tile's window (g rectangular, n still the global side); walls are
+  // the sides of g that are sides of the domain
+  int tiled = 0, walls = WALL_ALL;
 };
 enum { NSC_RES = 0, NSC_UMAX = 1, NSC_KE = 2, NSC_DIAG = 3 /* 3 slots */, NSC_COUNT = 8 };
 
@@ -110,6 +116,18 @@ struct msomn {
   double t = 0, dt = 1., tnext = HUGE_VAL, previous = 0;
   int iter = 0;
   msom_mgstats mg = {0, 0, 0, 0, 0};
+  // vertex model on tiles (msomn_create_tiled, msomn_tiles.hip, node_tile_inl.h).  One tile: ntiles = 1, walls = WALL_ALL, g square,
+  // no communicator, and none of the rest is used
+  int px = 1, py = 1, rank = 0, ntiles = 1, walls = WALL_ALL;
+  int ox = 0, oy = 0;          // global index of the tile's vertex (0, 0)
+  int kg = 0;                  // gather level (msomn_set_const): levels below live on the tiles, kg and up on the global grid on every rank
+  Comm *comm = nullptr;
+  int nb[4] = {-1, -1, -1, -1};   // ranks behind the W, E, S, N sides (DIR_* of comm.h), -1: wall
+  NLevel piece;                // the tile's window of level kg in the natural layout: what the rank gives to and takes from the gather
+  double *gsend = nullptr, *grecv = nullptr;   // gather buffers: one piece, ntiles pieces
+  size_t gcount = 0;           // doubles of gsend
+  int tile_err = 0;            // a halo exchange inside a sweep failed: the solve answers with it
+  long nexch = 0;              // halo exchanges since the last msomn_profile_reset (msomn_get_param("exchanges"))
   // state file and the driver's checkpoints (include/msomn_state.h)
   long state_flip = -1;             // msomn_state_dbg_flip: element the next load flips on the device (< 0: off)
   int ckpt_steps = 0, resume = 0;   // options of msomn_run
@@ -129,6 +147,21 @@ int node_const_derived(msomn *m);
 double node_clamped_dt(const msomn *m);   // p.DT after the clamps of node_const_derived
 NatGeom cell_geom(int n);                 // natural layout of an n x n cell field (the noise and wavelet pyramids)
 void node_noise_ghosts(msomn *m);         // the ghost ring of the noise field cs[0], as the filter leaves it
+
+// ---- msomn_tiles.hip
+NatGeom node_geom_rect(int tx, int ty);         // natural layout of a tile of tx x ty cells: (tx + 1) x (ty + 1) vertices
+NatGeom node_geom_split_rect(int tx, int ty);   // its x-parity split layout
+// one-deep halo of a field of the tile in either layout, corners included: x phase, then y phase over the fresh halo columns.
+// Collective; a no-op on one tile
+int nt_exchange(msomn *m, double *f, const NatGeom &g, int sp, int nl);
+int nt_reduce(msomn *m, int slot, int n, int op);   // all-reduce of d_scal[slot .. slot + n) into h_scal (one tile: a plain read)
+// the tiles' pieces of level kg (natural layout, geometry pg) -> the global level (geometry gg) on every rank
+int nt_gather(msomn *m, const double *piece, const NatGeom &pg, int nl, double *global, const NatGeom &gg);
+int nt_setup(msomn *m, int px, int py, int rank, const void *id128);   // decomposition, communicator, the fused options off
+void nt_free_gather(msomn *m);   // the piece and the gather buffers (msomn_set_const allocates them again)
+void nt_free(msomn *m);
+// MSOM_ERR_CONFIG with a message naming the call if the handle has more than one tile
+int nt_refuse(const msomn *m, const char *call);
 
 // ---- msomn_state.hip
 // msomn_state_save with the driver record `run` (run6: tout, tdiag, tflt, directory number, records of vars.nc, bytes of diag_1d.dat)

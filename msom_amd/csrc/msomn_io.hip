@@ -9,6 +9,7 @@
 
 // ---- NetCDF-3 IO of vertex fields (qg-node/netcdf_vertex_bas.h:95-424)
 extern "C" int msomn_write_nc(msomn_t *m, const char *path) {
+  if (int rt = nt_refuse(m, "msomn_write_nc")) return rt;
   if (!m || !path) return MSOM_ERR_ARG;
   const size_t n1 = m->N + 1, sz = n1 * n1 * m->nl;
   std::vector<double> psi(sz), q(sz);
@@ -21,6 +22,7 @@ extern "C" int msomn_write_nc(msomn_t *m, const char *path) {
   return msom_nc_append(path, m->nl, (int)n1, (int)n1, 2, names, m->t, fields) < 0 ? MSOM_ERR_IO : MSOM_OK;
 }
 extern "C" int msomn_read_nc(msomn_t *m, int field, const char *path, const char *varname, int record) {
+  if (int rt = nt_refuse(m, "msomn_read_nc")) return rt;
   NEED_FIELD(m, field);
   if (!path || !varname) return MSOM_ERR_ARG;
   const size_t n1 = m->N + 1;
@@ -33,6 +35,7 @@ extern "C" int msomn_read_nc(msomn_t *m, int field, const char *path, const char
 
 // main() + events of qg-node/qg.c:58-181
 extern "C" int msomn_run(msomn_t *m, const char *workdir, long nsteps_max) {
+  if (int rt = nt_refuse(m, "msomn_run")) return rt;
   if (!m) return MSOM_ERR_ARG;
   const NodeParams &p = m->p;
   const char *wd = workdir ? workdir : ".";

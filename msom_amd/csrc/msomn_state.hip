@@ -117,6 +117,7 @@ void collect(msomn *m, unsigned flags, const double *run6, std::vector<Item> &it
 
 int nstate_save_run(msomn *m, const char *path, unsigned flags, const double *run6) {
   if (!m || !path) { msom_set_error("msomn_state_save: null argument"); return MSOM_ERR_ARG; }
+  if (int rt = nt_refuse(m, "msomn_state_save")) return rt;
   if (!m->const_set) { msom_set_error("msomn_state_save: call msomn_set_const first"); return MSOM_ERR_STATE; }
   if (m->stochastic && m->noise_mode == 0) {
     msom_set_error("msomn_state_save: a stochastic run with noise_mode = 0 draws from libc's process-wide rand(), whose state cannot be "
@@ -250,6 +251,7 @@ double *target_ptr(msomn *m, const RecName &n) { return n.field == F_NOISE ? (m-
 }  // namespace
 
 extern "C" int msomn_state_load(msomn_t *m, const char *path) {
+  if (int rt = nt_refuse(m, "msomn_state_load")) return rt;
   if (!m || !path) { msom_set_error("msomn_state_load: null argument"); return MSOM_ERR_ARG; }
   msom_sfile sf;
   int r = msom_sfile_open(path, &sf, 0);   // the whole structure: header, every record header against the file size, trailer

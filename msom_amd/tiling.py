@@ -61,6 +61,54 @@ def tile_slice(rank, px, py, nx, ny):
     return slice(iy * ny, (iy + 1) * ny), slice(ix * nx, (ix + 1) * nx)
 
 
+def _node_tile_cells(N, px, py):
+    for name, v in (("N", N), ("px", px), ("py", py)):
+        if v < 1 or v & (v - 1):
+            raise ValueError(f"{name} = {v} must be a power of two")
+    if N % px or N % py or (px * py > 1 and (N // px < 2 or N // py < 2)):
+        raise ValueError(f"{px} x {py} tiles of at least 2 cells a side do not divide N = {N}")
+    return N // px, N // py
+
+
+def node_tile_window(N, px, py, rank):
+    """(slice_y, slice_x) of this rank's vertices in a global [.., N + 1, N + 1] array of the vertex model.  A tile of
+    Tx x Ty cells holds (Tx + 1) x (Ty + 1) vertices, the ones on its interior edges included: neighbouring windows
+    overlap by one column or row (msom_amd/csrc/node_tile_inl.h)."""
+    tx, ty = _node_tile_cells(N, px, py)
+    if not 0 <= rank < px * py:
+        raise ValueError(f"rank {rank} outside 0 .. {px * py - 1}")
+    ix, iy = tile_of_rank(rank, px, py)
+    return slice(iy * ty, (iy + 1) * ty + 1), slice(ix * tx, (ix + 1) * tx + 1)
+
+
+def node_assemble(pieces, N, px, py, check_shared=True):
+    """Global [.., N + 1, N + 1] array from the px * py tile arrays [.., Ty + 1, Tx + 1] (in rank order) of the vertex model.
+    check_shared: raise ValueError if two holders of a shared vertex disagree in any bit (-0. against 0. and different NaN
+    payloads count)."""
+    tx, ty = _node_tile_cells(N, px, py)
+    if len(pieces) != px * py:
+        raise ValueError(f"{len(pieces)} pieces for {px} x {py} tiles")
+    pieces = [np.ascontiguousarray(p) for p in pieces]
+    lead, dtype = pieces[0].shape[:-2], pieces[0].dtype
+    bits = np.dtype(f"u{dtype.itemsize}") if dtype.kind in "fc" and dtype.itemsize in (2, 4, 8) else dtype
+    out = np.empty(lead + (N + 1, N + 1), dtype)
+    seen = np.zeros((N + 1, N + 1), bool)
+    for rank, p in enumerate(pieces):
+        if p.shape != lead + (ty + 1, tx + 1) or p.dtype != dtype:
+            raise ValueError(f"piece of rank {rank}: {p.dtype}{p.shape}, expected {dtype}{lead + (ty + 1, tx + 1)}")
+        sy, sx = node_tile_window(N, px, py, rank)
+        if check_shared:
+            shared = seen[sy, sx]
+            differ = (out[..., sy, sx].view(bits) != p.view(bits)) & shared
+            if differ.any():
+                j, i = np.argwhere(differ.reshape((-1,) + differ.shape[-2:]).any(0))[0]
+                raise ValueError(f"shared vertex ({sx.start + i}, {sy.start + j}): rank {rank} disagrees with a lower rank "
+                                 f"({int(differ.sum())} values differ)")
+        out[..., sy, sx] = p
+        seen[sy, sx] = True
+    return out
+
+
 def broadcast_unique_id(dist, make_id, device="cpu"):
     """Rank 0 creates the 128-byte communicator id (ncclUniqueId), everybody receives it."""
     import torch
