@@ -619,6 +619,35 @@ double msomn_dt(msomn_t *m);
 int msomn_iter(msomn_t *m);
 int msomn_ke(msomn_t *m, double *ke);                                      /* event writestdout qg.c:171-178 */
 int msomn_last_mgstats(msomn_t *m, msom_mgstats *stats);
+/* Running time means and eddy statistics of the vertex model on the device: the twin of msom_stats_* above, with its ids (MSOM_ST_*,
+ * no second enum): the accumulators MSOM_ST_PSI .. MSOM_ST_VQ (bit k of the mask = accumulator k) and the derived MSOM_ST_EKE,
+ * MSOM_ST_UQ_EDDY, MSOM_ST_VQ_EDDY.  MSOM_ST_QME is not offered (MSOM_ERR_ARG): the vertex model's running mean is psi_f.
+ * One sample reads MSOMN_PSI, MSOMN_Q and MSOMN_MASK as the handle holds them; for every held vertex and layer, in this expression
+ *   order (the strict build's contract; the product build multiplies by 1 / (2 Delta) and contracts): acc = acc + w * x with x = psi,
+ *   q, psi*psi, q*q, 0.5 * (u*u + v*v), u*q, v*q, where u = ((psi[j-1][i] - psi[j+1][i]) / (2 Delta)) * mask[j][i] and
+ *   v = ((psi[j][i+1] - psi[j][i-1]) / (2 Delta)) * mask[j][i]; on a vertex of the DOMAIN boundary (global i or j equal to 0 or N)
+ *   u = v = 0 and the neighbour beyond the wall is not read; on a tile's interior edge the neighbour is the halo.  W = W + w.
+ *   No atomics, no reductions: the same bits on every run, and every holder of a shared vertex accumulates the same bits.
+ * msomn_stats_begin allocates the selected arrays only, zeroes them and W, restarts the counts, and may be called again;
+ *   msomn_set_const drops everything; a handle that never calls it allocates nothing.
+ * msomn_stats_accumulate: one sample by hand; on tiles it exchanges the halo of psi first (collective).
+ * msomn_stats_get: `which` < MSOM_ST_NACC: S / W (a true division in both builds).  Derived ids: the mean psi goes into the scratch
+ *   field MSOMN_TMP, its sides get the boundary rule of psi, on tiles its halo is exchanged (collective), um and vm are the same masked
+ *   differences, and EKE = S_KE/W - 0.5 * (um*um + vm*vm), UQ_EDDY = S_UQ/W - um * (S_Q/W), VQ_EDDY = S_VQ/W - vm * (S_Q/W); nothing
+ *   derived is stored.  out: the tile's [nl][Ty+1][Tx+1] as msomn_get_field, host or device pointer.
+ * Option "stats" [0] = 1: msomn_step (and so msomn_run) queues one sample right after stage 1's update, before the first advance: q is
+ *   q_n, psi what stage 1 inverted from it (masked, sides set, on tiles already exchanged by the tendency: no further exchange), the
+ *   weight the dt the step then uses.  "stats_every" [1] = n: only every n-th step since msomn_stats_begin.  msomn_update,
+ *   msomn_advance and msomn_invert_q on their own never sample; psi, q, dt, t, mgstats and noise_draw of a run do not depend on the option.
+ * Errors: null handle, mask 0 or a bit >= MSOM_ST_NACC, w not finite, stats_every < 1, `which` unknown or its accumulators not in the
+ *   mask: MSOM_ERR_ARG; any of these calls before msomn_set_const, any but msomn_stats_begin (or option "stats" = 1, or a msomn_step
+ *   with it) with no msomn_stats_begin since msomn_set_const, msomn_stats_get with W == 0: MSOM_ERR_STATE.
+ * msomn_get_param "stats_mask", "stats_bytes" (8 nl (Ty+1) (Tx+1) per accumulator held), "stats_samples" (samples since
+ *   msomn_stats_begin, automatic and by hand).  The state file carries the accumulators (msomn_state.h). */
+int msomn_stats_begin(msomn_t *m, unsigned mask);
+int msomn_stats_accumulate(msomn_t *m, double w);
+int msomn_stats_weight(msomn_t *m, double *W);
+int msomn_stats_get(msomn_t *m, int which, double *out);   /* [nl][Ty+1][Tx+1], host or device pointer */
 /* measurement only (option "profile" = 1): HIP-event timing of the finest-level launches; slots "relax_fine", "relax_prolong_fine",
  * "residual", "correct", "rhs" (the whole rhs_pv chain), "coarse" (the one-launch coarse levels) */
 int msomn_profile_read(msomn_t *m, const char *slot, double *avg_ms, long *launches);

@@ -13,6 +13,9 @@
  *   saved between the two stages of a step (corrector_step = 1: the second msomn_update reads it); scalars `time` (t, dt, the dt
  *   limiter's previous, tnext, iter), `mgstats` (i, resb, resa, nrelax; sum is not saved: 0 after a load) and `node` (seed, noise_draw,
  *   corrector_step, nbar, pg_set, topo_set, forcing_3d, sqg, the clamped DT).
+ *   A handle with running statistics (msomn_stats_begin, stats_mask != 0) also saves its accumulators as st_psi, st_q, st_psi2, st_q2,
+ *   st_ke, st_uq, st_vq (the selected ones) and the scalars `stats` (mask, steps counted, stats_every, option stats, W, samples); a
+ *   load allocates the mask the file holds and restores them.  A handle without statistics writes none of these records.
  * flags & MSOM_STATE_CONSTANTS: the constants too, as msomn_set_const left them -- mask, S2 (f^2 / N^2), S2S and bs when sqg, topo
  *   (times scale_topo) when set, psi_pg when set, q_forcing_3d when on -- so that the file alone restarts a run.
  * msomn_state_save: waits for the stream, writes `path`.tmp and renames it to `path`.  Changes nothing the next step reads.  Before

@@ -172,6 +172,10 @@ def load_library(strict=False):
         "msomn_iter": (ci, [vp]),
         "msomn_ke": (ci, [vp, _dp]),
         "msomn_last_mgstats": (ci, [vp, C.POINTER(MGStats)]),
+        "msomn_stats_begin": (ci, [vp, C.c_uint]),
+        "msomn_stats_accumulate": (ci, [vp, cd]),
+        "msomn_stats_weight": (ci, [vp, _dp]),
+        "msomn_stats_get": (ci, [vp, ci, vp]),
         "msomn_profile_read": (ci, [vp, cs, _dp, C.POINTER(C.c_long)]),
         "msomn_profile_reset": (ci, [vp]),
         "msomn_diag1d": (ci, [vp, _dp]),
@@ -955,6 +959,28 @@ class NodeQG:
         st = MGStats()
         self._chk(self.L.msomn_last_mgstats(self.h, C.byref(st)))
         return st
+
+    # -- running time means and eddy statistics on the device (STATS without QME; msomn_stats_* of include/msom.h)
+    def stats_begin(self, mask):
+        """allocate and zero the accumulators of `mask` (bit STATS[name] each) and the weight sum; set_option("stats", 1) then lets
+        every step() take one sample of (q_n, psi_n) with weight dt_n"""
+        self._chk(self.L.msomn_stats_begin(self.h, int(mask)))
+
+    def stats_accumulate(self, w):
+        """one sample of the PSI, Q and MASK the model holds now, weight w (collective on tiles)"""
+        self._chk(self.L.msomn_stats_accumulate(self.h, float(w)))
+
+    def stats_weight(self):
+        out = C.c_double()
+        self._chk(self.L.msomn_stats_weight(self.h, C.byref(out)))
+        return out.value
+
+    def stats_get(self, which, out=None):
+        """mean of accumulator `which` (sum / weight) or a derived quantity (EKE, UQ_EDDY, VQ_EDDY; collective on tiles);
+        [nl][ny][nx] of this tile.  out: optional destination, a numpy array or a tensor (host or device)"""
+        a = np.empty((self.nl, self.ny, self.nx)) if out is None else out
+        self._chk(self.L.msomn_stats_get(self.h, int(which), _ptr(a)))
+        return a
 
     def diag1d(self):
         out = (C.c_double * 3)()

@@ -380,6 +380,17 @@ void launch_n_unpack_strip(hipStream_t st, double *f, const NatGeom &g, int sp, 
 void launch_n_assemble(hipStream_t st, const double *recv, double *f, const NatGeom &g, int nl, int N, int px, int py, int k);
 void launch_n_extract(hipStream_t st, const double *f, const NatGeom &g, double *t, const NatGeom &tg, int nl, int ox, int oy);
 
+// ---- kernels_node_stats.hip: running statistics of the vertex model (msomn_stats_*); StatsAcc as above, on the held vertices
+struct NStatsTile { int ox, oy, N; };   // global index of the tile's vertex (0, 0) and the global side in cells: i or j in {0, N} is the domain boundary
+// one sample of weight w into the accumulators of `mask` (1 .. 2^MSOM_ST_NACC - 1); mk: the land mask (1 layer); D2 = 2 Delta.
+// -1: no kernel for that mask
+int launch_n_stats_acc(hipStream_t st, unsigned mask, const double *psi, const double *q, const double *mk, const StatsAcc &a, const NatGeom &g,
+                       int nl, const NStatsTile &t, double w, double D2);
+void launch_n_stats_mean(hipStream_t st, double *out, const double *s, double W, const NatGeom &g, int nl);
+// which = MSOM_ST_EKE / UQ_EDDY / VQ_EDDY from the mean psi pm (sides set, halo exchanged), sa = KE / UQ / VQ, sq = Q (eddy fluxes); out: natural
+void launch_n_stats_derive(hipStream_t st, double *out, const double *pm, const double *mk, const double *sa, const double *sq, double W,
+                           const NatGeom &g, int nl, int which, const NStatsTile &t, double D2);
+
 // ---- kernels_state.hip: rows of one layer of a natural field <-> a contiguous staging chunk, with the record digest of the state file
 struct StateChunk {
   NatGeom g;        // the tile's natural layout

@@ -87,6 +87,7 @@ extern "C" void msomn_destroy(msomn_t *m) {
   for (int k = 0; k < MSOMN_NFIELDS; k++) if (m->f[k]) (void)hipFree(m->f[k]);
   for (size_t k = 0; k < m->lev.size(); k++) free_level(m->lev[k], (int)k);
   nt_free(m);
+  nstats_drop(m);
   for (size_t k = 0; k < m->cs.size(); k++) {
     if (m->cs[k]) (void)hipFree(m->cs[k]);
     if (m->cr[k]) (void)hipFree(m->cr[k]);
@@ -242,6 +243,14 @@ extern "C" int msomn_set_option(msomn_t *m, const char *key, double v) {
   else if (!strcmp(key, "stochastic")) m->stochastic = (int)v;
   else if (!strcmp(key, "ckpt_steps")) m->ckpt_steps = (int)v;   // msomn_run, include/msomn_state.h
   else if (!strcmp(key, "resume")) m->resume = (int)v;
+  else if (!strcmp(key, "stats")) {   // msomn_step takes one sample per stats_every steps (msomn_stats.hip)
+    if ((int)v && !m->stats_mask) { msom_set_error("option stats = 1 before msomn_stats_begin"); return MSOM_ERR_STATE; }
+    m->stats_on = (int)v != 0;
+  }
+  else if (!strcmp(key, "stats_every")) {
+    if (!(v >= 1)) { msom_set_error("option stats_every = %g", v); return MSOM_ERR_ARG; }
+    m->stats_every = (int)v;
+  }
   else if (!strcmp(key, "seed")) { m->seed = (unsigned)v; srand(m->seed); }
   else if (!strcmp(key, "noise_mode")) {
     if (v != 0. && v != 1.) { msom_set_error("noise_mode = %g: 0 (serial rand() stream on the host) or 1 (device generator)", v); return MSOM_ERR_ARG; }
@@ -320,6 +329,10 @@ extern "C" double msomn_get_param(msomn_t *m, const char *k) {
   if (!strcmp(k, "py")) return m->py;
   if (!strcmp(k, "agg_level")) return m->ntiles > 1 ? (m->const_set ? m->kg : ntile_kg(m->N, m->px, m->py, m->mg_coarse)) : m->nlev;
   if (!strcmp(k, "exchanges")) return (double)m->nexch;
+  // running statistics: the mask, 8 nl ny nx bytes per accumulator held (the tile's vertices), samples since msomn_stats_begin
+  if (!strcmp(k, "stats_mask")) return m->stats_mask;
+  if (!strcmp(k, "stats_bytes")) return (double)__builtin_popcount(m->stats_mask) * m->nl * m->g.ny * m->g.nx * 8;
+  if (!strcmp(k, "stats_samples")) return (double)m->stats_samples;
   if (!strcmp(k, "mg_coarse")) return m->mg_coarse;
   if (!strcmp(k, "node_split")) return m->node_split;
   if (!strcmp(k, "node_pfused")) return m->node_pfused;
@@ -1187,6 +1200,8 @@ int node_const_derived(msomn *m) {
 extern "C" int msomn_set_const(msomn_t *m) {
   if (!m) return MSOM_ERR_ARG;
   int r;
+  HIPCHK(hipStreamSynchronize(m->st));   // a sample may still be running into the arrays that go
+  nstats_drop(m);
   if ((r = node_const_inputs(m)) || (r = node_const_derived(m))) return r;
   m->noise_draw = 0;
   if ((r = comp_q(m, m->f[MSOMN_PSI], m->f[MSOMN_Q]))) return r;
@@ -1274,11 +1289,14 @@ static double dtnext(msomn *m, double dt, double *tnext_out) {  // dtnext() [Bas
 }
 extern "C" int msomn_step(msomn_t *m, int with_forcing_event) {
   NEED_NCONST(m);
+  if (m->stats_on && !m->stats_mask) { msom_set_error("msomn_step: option stats = 1 and no msomn_stats_begin since msomn_set_const"); return MSOM_ERR_STATE; }
   int r;
   double d, tn;
   if (with_forcing_event && (r = msomn_forcing(m))) return r;
   if ((r = msomn_update(m, MSOMN_Q, MSOMN_DQ, m->p.DT, &d))) return r;
   m->dt = dtnext(m, d, &tn);
+  // the automatic sample: q_n and the psi stage 1 inverted from it (masked, sides set, on tiles exchanged by the tendency), weight dt_n
+  if (m->stats_on && m->stats_count++ % m->stats_every == 0 && (r = nstats_sample(m, m->dt))) return r;
   if ((r = msomn_advance(m, MSOMN_QPRED, MSOMN_Q, MSOMN_DQ, m->dt / 2.))) return r;
   if ((r = msomn_update(m, MSOMN_QPRED, MSOMN_DQ, m->dt, &d))) return r;
   if ((r = msomn_advance(m, MSOMN_Q, MSOMN_Q, MSOMN_DQ, m->dt))) return r;

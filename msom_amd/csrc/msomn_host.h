@@ -133,6 +133,14 @@ struct msomn {
   int ckpt_steps = 0, resume = 0;   // options of msomn_run
   int run_loaded = 0;               // the last load found the driver record `run`: run_ev holds it
   double run_ev[6] = {0, 0, 0, 0, 0, 0};   // tout, tdiag, tflt, output directory number, records of vars.nc, bytes of diag_1d.dat
+  // running statistics on the device (msomn_stats_*, msomn_stats.hip); nothing is allocated until msomn_stats_begin
+  unsigned stats_mask = 0;                // accumulators selected by the last msomn_stats_begin since msomn_set_const (0: none)
+  StatsAcc stats = {};                    // the selected accumulators, natural layout of the tile, nl layers each
+  double *stats_scr = nullptr;            // where a derived quantity is formed (allocated by the first msomn_stats_get that needs it)
+  double stats_W = 0.;                    // sum of the weights: every weight is known on the host, so W = W + w is formed there
+  int stats_on = 0, stats_every = 1;      // options "stats", "stats_every"
+  long stats_count = 0;                   // msomn_step calls seen since msomn_stats_begin (every stats_every-th one samples)
+  long stats_samples = 0;                 // samples taken since msomn_stats_begin, automatic and by hand
 };
 
 // ---- msom_node.hip
@@ -162,6 +170,10 @@ void nt_free_gather(msomn *m);   // the piece and the gather buffers (msomn_set_
 void nt_free(msomn *m);
 // MSOM_ERR_CONFIG with a message naming the call if the handle has more than one tile
 int nt_refuse(const msomn *m, const char *call);
+
+// ---- msomn_stats.hip
+void nstats_drop(msomn *m);               // frees everything msomn_stats_begin allocated (msomn_set_const, msomn_destroy)
+int nstats_sample(msomn *m, double w);    // one sample of MSOMN_PSI / MSOMN_Q as held (halo of psi fresh), W = W + w; queued, not synchronised
 
 // ---- msomn_state.hip
 // msomn_state_save with the driver record `run` (run6: tout, tdiag, tflt, directory number, records of vars.nc, bytes of diag_1d.dat)

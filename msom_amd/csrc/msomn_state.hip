@@ -15,18 +15,30 @@ namespace {
 
 enum { NSTATE_DIALECT = 2 };
 enum { EVOLVING = 0, CONSTANT = 1 };
-enum { F_NOISE = -1 };   // not one of m->f: the cell scalar cs[0]
+enum { F_NOISE = -1, F_ACC0 = -2 };   // not one of m->f: the cell scalar cs[0]; accumulator k of the running statistics is F_ACC0 - k
 struct RecName { const char *name; int field, role; };
 const RecName NAMES[] = {
     {"psi", MSOMN_PSI, EVOLVING}, {"q", MSOMN_Q, EVOLVING}, {"q_forcing", MSOMN_QFORC, EVOLVING}, {"psi_f", MSOMN_PSIF, EVOLVING},
     {"noise", F_NOISE, EVOLVING}, {"qpred", MSOMN_QPRED, EVOLVING},
     {"mask", MSOMN_MASK, CONSTANT}, {"S2", MSOMN_S2, CONSTANT}, {"S2S", MSOMN_S2S, CONSTANT}, {"bs", MSOMN_BS, CONSTANT},
-    {"topo", MSOMN_TOPO, CONSTANT}, {"psi_pg", MSOMN_PSIPG, CONSTANT}, {"q_forcing_3d", MSOMN_QFORC3D, CONSTANT}};
+    {"topo", MSOMN_TOPO, CONSTANT}, {"psi_pg", MSOMN_PSIPG, CONSTANT}, {"q_forcing_3d", MSOMN_QFORC3D, CONSTANT},
+    // the accumulators of msomn_stats_begin, in the order of MSOM_ST_PSI .. MSOM_ST_VQ
+    {"st_psi", F_ACC0 - MSOM_ST_PSI, EVOLVING}, {"st_q", F_ACC0 - MSOM_ST_Q, EVOLVING}, {"st_psi2", F_ACC0 - MSOM_ST_PSI2, EVOLVING},
+    {"st_q2", F_ACC0 - MSOM_ST_Q2, EVOLVING}, {"st_ke", F_ACC0 - MSOM_ST_KE, EVOLVING}, {"st_uq", F_ACC0 - MSOM_ST_UQ, EVOLVING},
+    {"st_vq", F_ACC0 - MSOM_ST_VQ, EVOLVING}};
+const char *acc_name(int k) {
+  for (const RecName &n : NAMES)
+    if (n.field == F_ACC0 - k) return n.name;
+  return nullptr;
+}
+bool is_acc(const RecName &n) { return n.field <= F_ACC0; }
 const RecName *find_name(const char *name) {
   for (const RecName &n : NAMES)
     if (!strcmp(n.name, name)) return &n;
   return nullptr;
 }
+// the scalars of record `stats` (written only by a handle with stats_mask != 0)
+enum { SS_MASK, SS_COUNT, SS_EVERY, SS_ON, SS_W, SS_SAMPLES, SS_N };
 // the scalars of record `node`
 enum { NS_SEED, NS_DRAW, NS_CORRECTOR, NS_NBAR, NS_PG, NS_TOPO, NS_F3D, NS_SQG, NS_DT, NS_COUNT };
 
@@ -34,7 +46,7 @@ struct Item { const char *name; const double *dev; int layers; NatGeom g; };
 struct Scal { const char *name; std::vector<double> v; };
 
 NatGeom rec_geom(const msomn *m, const RecName &n) { return n.field == F_NOISE ? cell_geom(m->N) : m->g; }
-int rec_layers(const msomn *m, const RecName &n) { return n.field == F_NOISE ? 1 : m->fl[n.field]; }
+int rec_layers(const msomn *m, const RecName &n) { return n.field == F_NOISE ? 1 : is_acc(n) ? m->nl : m->fl[n.field]; }
 
 StateChunk chunk_of(const NatGeom &g, int layer, int y0, int rows) {
   StateChunk c;
@@ -103,6 +115,12 @@ void collect(msomn *m, unsigned flags, const double *run6, std::vector<Item> &it
   // between the two stages of a step (only a stochastic handle knows that it is: corrector_step) the second update reads the predictor;
   // at a step boundary QPRED is scratch and is not written
   if (m->stochastic && m->corrector_step) fld("qpred", MSOMN_QPRED);
+  if (m->stats_mask) {   // a handle without statistics writes the records it always wrote
+    scal.push_back({"stats", {(double)m->stats_mask, (double)m->stats_count, (double)m->stats_every, (double)m->stats_on, m->stats_W,
+                              (double)m->stats_samples}});
+    for (int k = 0; k < MSOM_ST_NACC; k++)
+      if (m->stats.s[k]) items.push_back({acc_name(k), m->stats.s[k], m->nl, m->g});
+  }
   if (flags & MSOM_STATE_CONSTANTS) {
     fld("mask", MSOMN_MASK);
     if (m->nl > 1) fld("S2", MSOMN_S2);
@@ -246,7 +264,10 @@ int upload_record(msomn *m, Pipe &pp, FILE *fp, const char *path, const Loaded &
   return digest_read(m, pp, digest);
 }
 
-double *target_ptr(msomn *m, const RecName &n) { return n.field == F_NOISE ? (m->cnlev > 0 ? m->cs[0] : nullptr) : m->f[n.field]; }
+double *target_ptr(msomn *m, const RecName &n) {
+  if (is_acc(n)) return m->stats.s[F_ACC0 - n.field];
+  return n.field == F_NOISE ? (m->cnlev > 0 ? m->cs[0] : nullptr) : m->f[n.field];
+}
 
 }  // namespace
 
@@ -278,7 +299,7 @@ extern "C" int msomn_state_load(msomn_t *m, const char *path) {
   for (uint32_t k = 0; k < sf.nrec; k++) {
     const msom_srec *rec = &sf.rec[k];
     if (rec->kind == MSOM_SK_SCALARS) {
-      static const struct { const char *name; uint32_t n; } known[] = {{"time", 5}, {"mgstats", 4}, {"node", NS_COUNT}, {"run", 6}};
+      static const struct { const char *name; uint32_t n; } known[] = {{"time", 5}, {"mgstats", 4}, {"node", NS_COUNT}, {"run", 6}, {"stats", SS_N}};
       bool ok = false;
       for (const auto &kn : known) ok |= !strcmp(kn.name, rec->name) && rec->layers == kn.n;
       if (!ok) { msom_set_error("msomn_state_load: %s: scalar record %s with %u numbers is not one this library reads", path, rec->name, rec->layers); return MSOM_ERR_CONFIG; }
@@ -295,6 +316,17 @@ extern "C" int msomn_state_load(msomn_t *m, const char *path) {
       return MSOM_ERR_CONFIG;
     }
     tmp.v.push_back(l);
+  }
+  unsigned file_mask = 0;
+  {  // the statistics: a mask msomn_stats_begin would take, and exactly the accumulators it selects
+    unsigned recs = 0;
+    for (const Loaded &l : tmp.v) if (is_acc(*l.n)) recs |= 1u << (F_ACC0 - l.n->field);
+    if (sc.count("stats")) {
+      const double fm = sc["stats"][SS_MASK];
+      if (!(fm >= 1) || fm >= (double)(1u << MSOM_ST_NACC) || fm != floor(fm)) { msom_set_error("msomn_state_load: %s: statistics mask %g", path, fm); return MSOM_ERR_CONFIG; }
+      file_mask = (unsigned)fm;
+    }
+    if (recs != file_mask) { msom_set_error("msomn_state_load: %s: accumulator records 0x%x, the mask of record `stats` is 0x%x", path, recs, file_mask); return MSOM_ERR_CONFIG; }
   }
   if (!sc.count("node") || !sc.count("time")) { msom_set_error("msomn_state_load: %s has no record `%s`", path, sc.count("node") ? "time" : "node"); return MSOM_ERR_CONFIG; }
   const std::vector<double> &ns = sc["node"];
@@ -368,6 +400,12 @@ extern "C" int msomn_state_load(msomn_t *m, const char *path) {
     if ((r = node_const_derived(m))) return r;
     m->const_set = 1;
   } else if (!m->const_set && (r = msomn_set_const(m))) return r;
+  if (file_mask) {   // the arrays the file holds, allocated as msomn_stats_begin allocates them; then its counters
+    if (file_mask != m->stats_mask && (r = msomn_stats_begin(m, file_mask))) return r;
+    const std::vector<double> &s = sc["stats"];
+    m->stats_count = (long)s[SS_COUNT]; m->stats_every = (int)s[SS_EVERY] < 1 ? 1 : (int)s[SS_EVERY]; m->stats_on = s[SS_ON] != 0;
+    m->stats_W = s[SS_W]; m->stats_samples = (long)s[SS_SAMPLES];
+  }
   for (const Loaded &l : tmp.v) {
     if (l.n->role == CONSTANT) continue;
     // psi through the live pointer.  The buffer that is not psi (psi_alt, if the handle has one yet) stays as it is: k_n_rhs_pre and

@@ -24,6 +24,10 @@ VERSION = 1
 KIND_FIELD, KIND_SCALARS = 0, 1
 HEADER_KEYS = ("version", "dialect", "nx", "ny", "nl", "nptr", "stochastic", "noise_mode", "mode_pv_invert", "flag_topo")
 TIME_KEYS = ("t", "dt", "previous", "tnext", "iter")   # the scalars of record "time", in this order
+# dialect 2, a handle with running statistics (msomn_stats_begin): field record k holds accumulator MSOM_ST_k (the selected ones are
+# written, [nl][N + 1][N + 1]), and the scalars of record "stats" in this order
+NODE_STATS_RECORDS = ("st_psi", "st_q", "st_psi2", "st_q2", "st_ke", "st_uq", "st_vq")
+NODE_STATS_KEYS = ("mask", "count", "every", "on", "W", "samples")
 
 
 class StateFormatError(ValueError):
