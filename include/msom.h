@@ -512,7 +512,9 @@ int msom_profile_read(msom_t *m, const char *kernel, double *avg_ms, long *launc
 int msom_profile_reset(msom_t *m);
 /* waits for everything the handle has queued on its stream.  With option "step_sync" = 0 (default -1: on grids below 2^23 cell-layers;
  * 1: never) and "async_solve", msom_step returns while its last tendency pass is still running; every call that returns device data
- * to the host synchronises by itself, so this is for timing and for callers that share the fields' device pointers with their own streams. */
+ * to the host synchronises by itself, so this is for timing and for callers that share the fields' device pointers with their own streams.
+ * Where option "rhs_close" resolves to 2 (msom_get_param) the second stage's tendency pass also produces the residual that decides the
+ * step, msom_step waits for it and "step_sync" = 0 leaves no pass running. */
 int msom_sync(msom_t *m);
 int msom_bench_kernel(msom_t *m, const char *kernel, int reps, double *avg_ms);
 /* one-rank RCCL communicator on the current device: grouped send/recv to self, all-reduce and

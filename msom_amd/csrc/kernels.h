@@ -139,6 +139,12 @@ struct RhsResid {
   double *res_max;           // device scalar: max|res| (zeroed by the launcher)
   double *bsum_partial;      // one partial sum of q_out per workgroup (rhs_pipe_blocks / rhs_lpw_blocks entries)
   SplitGeom sg, cg;
+  // k_rhs_lpw only (option rhs_close): the pass also closes the solve that produced its psi.  cls = 1: b of that solve is q_in; 2: b is a
+  // field of its own, and max|u| of psi per layer comes out as well.  Both accumulators were zeroed with the solve's scalars
+  int cls = 0;
+  const double *cls_b = nullptr;   // cls = 2: the solve's right-hand side
+  double *cls_max = nullptr;       // device scalar: max|b - (lap + Gamma) psi|
+  double *cls_umax = nullptr;      // cls = 2: nl device scalars, max|u| per layer
 };
 int rhs_fused_blocks(const NatGeom &g);
 void launch_rhs_fused(hipStream_t st, const KernelOpts &o, const double *psi, const double *S, const double *qforc, const double *wind, double *dq,

@@ -35,9 +35,11 @@
 #ifdef MSOM_STRICT
 #define LPW_NV 3  // zeta, tmp, jd
 #define LPW_MAXW 8
+#define LPW_CLS_PARK(CLS) 0  // (the closing chain reuses the flux differences of RES)
 #else
 #define LPW_NV 2  // X = iRe zeta + iRe4 tmp, jd
 #define LPW_MAXW 12
+#define LPW_CLS_PARK(CLS) ((CLS) == 2 ? 3 : (CLS) == 1 ? 1 : 0)  // ring slots beyond RES's, private to the wave: values a row carries to its finalisation
 #endif
 
 struct LpwArgs {
@@ -71,8 +73,17 @@ struct LpwArgs {
 // Same expression sequence as k_residual2 (kernels_mg.hip), so the same bits.  Per cell and row: wave l publishes d = psi_{l+1} - psi_l as
 // one more ring value (wave l + 1 reads it as psi_l - psi_{l-1}, the number k_residual2 forms in layer l + 1) and carries its two
 // horizontal flux differences to the finalisation, where q_out exists
-template <int R, bool UNI, bool QF, bool ADV, bool STOCH, bool EDGE, bool RES, int NV>
-__device__ __forceinline__ void lpw_body(const LpwArgs &a, double (&ring)[2][LPW_MAXW][R][NV][64], double &res_m, double &res_bs) {
+// CLS (only with RES and uniform S, option rhs_close): the pass also CLOSES the solve that produced its psi, in place of a launch of
+// k_resmax_march on the same psi: max|b - (lap + Gamma) psi| over the grid.  1: b is q_in (first RK stage), the residual is one more chain from
+// qreg[r] and the operands resid() has; 2: b is a field of its own (second stage), prefetched next to q_in, and max|u| of the wave's layer
+// comes out of row() too.  k_resmax_march's expressions and, in the product build, its fused multiply-add pattern: the same bits
+template <int R, bool UNI, bool QF, bool ADV, bool STOCH, bool EDGE, bool RES, int CLS, int NV>
+__device__ __forceinline__ void lpw_body(const LpwArgs &a, double (&ring)[2][LPW_MAXW][R][NV][64], double &res_m, double &res_bs, double &cls_m,
+                                         double &cls_u) {
+  // ring values of RES (psi_{l+1} - psi_l) and of CLS in the product build: the x term, and with CLS = 2 (PARK3) both flux differences of RES
+  // as well, parked in slots of the wave's own from row() to the finalisation, for want of registers
+  constexpr int DS = RES ? LPW_NV : 0, XS = LPW_CLS_PARK(CLS) ? LPW_NV + 1 : 0;
+  constexpr bool PARK3 = LPW_CLS_PARK(CLS) == 3;
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // ring slot; wv +- 1 = neighbouring layers of the strip
   const int nl = a.nl, nx = a.g.nx, ny = a.g.ny;
@@ -132,8 +143,11 @@ __device__ __forceinline__ void lpw_body(const LpwArgs &a, double (&ring)[2][LPW
 #endif
   double pnext[R], qnext[R], qreg[R], fqreg[R], qsreg[STOCH ? R : 1], nzreg[STOCH ? R : 1];
   double xdA[R], ydA[R];  // RES: x and y flux differences of a row
+  double breg[CLS == 2 ? R : 1];  // CLS = 2: b of the row
 #pragma unroll
   for (int r = 0; r < R; r++) xdA[r] = ydA[r] = 0.;
+#pragma unroll
+  for (int r = 0; r < (CLS == 2 ? R : 1); r++) breg[r] = 0.;
 #pragma unroll
   for (int r = 0; r < R; r++) {
 #ifdef MSOM_STRICT
@@ -224,10 +238,17 @@ __device__ __forceinline__ void lpw_body(const LpwArgs &a, double (&ring)[2][LPW
       // inside the fused multiply-add.  even x: fma(rD, c - W, -(rD (E - c))); odd x: fma(-rD, E - c, rD (c - W))
       const double fa = oddx ? dW : dE, fb = oddx ? dE : dW;
       const double x = fma(rD, fb, -(rD * fa));
-      xdA[r] = oddx ? -x : x;
-      ydA[r] = fma(rD, dS, -(rD * dN));
+      const double xd = oddx ? -x : x, yd = fma(rD, dS, -(rD * dN));
+      if (PARK3) { ring[b][wv][r][XS + 1][lane] = xd; ring[b][wv][r][XS + 2][lane] = yd; }
+      else { xdA[r] = xd; ydA[r] = yd; }
+      // k_resmax_march owns one column per lane: the even-column form everywhere (the y term and the couplings are k_residual2's)
+      if (CLS) ring[b][wv][r][XS][lane] = fma(rD, dW, -(rD * dE));
 #endif
-      ring[b][wv][r][NV - 1][lane] = Q[1] - P[1];
+      if (CLS == 2) {  // face velocities as k_resmax_march forms them: N, S, E, W, NW, SW, SE of the cell
+        const double u = fabs(DIVC(0.25 * (P[2] - P[0] + PL[2] - PL[0]), D, rD)), v = fabs(DIVC(0.25 * (PR[1] - PL[1] + PR[0] - PL[0]), D, rD));
+        if (out_ok && j < y1) cls_u = fmax(cls_u, fmax(u, v));
+      }
+      ring[b][wv][r][DS][lane] = Q[1] - P[1];
     }
 #ifdef MSOM_STRICT
     abA[r] = adv + be; jdA[r] = jd; lapTA[r] = lapT; zcA[r] = zc; tcA[r] = tc;
@@ -298,15 +319,31 @@ __device__ __forceinline__ void lpw_body(const LpwArgs &a, double (&ring)[2][LPW
   auto resid = [&](int b, int r, double s0, double s1, double q) -> double {
     double re = q;
 #ifdef MSOM_STRICT
-    if (upper) re = re + s0 * ring[b][wv - 1][r][NV - 1][lane] * idh0;
-    if (lower) re = re - s1 * ring[b][wv][r][NV - 1][lane] * idh1;
+    if (upper) re = re + s0 * ring[b][wv - 1][r][DS][lane] * idh0;
+    if (lower) re = re - s1 * ring[b][wv][r][DS][lane] * idh1;
     re += xdA[r];
     re += ydA[r];
 #else
-    if (upper) re = fma(idh0, s0 * ring[b][wv - 1][r][NV - 1][lane], re);
-    if (lower) re = fma(-(ring[b][wv][r][NV - 1][lane] * s1), idh1, re);
-    re = fma(rD, xdA[r], re);
-    re = fma(rD, ydA[r], re);
+    if (upper) re = fma(idh0, s0 * ring[b][wv - 1][r][DS][lane], re);
+    if (lower) re = fma(-(ring[b][wv][r][DS][lane] * s1), idh1, re);
+    re = fma(rD, PARK3 ? ring[b][wv][r][XS + 1][lane] : xdA[r], re);
+    re = fma(rD, PARK3 ? ring[b][wv][r][XS + 2][lane] : ydA[r], re);
+#endif
+    return re;
+  };
+  // CLS: the residual of row j against the b of the solve that produced psi (k_resmax_march's order: b, upper and lower coupling, x, y)
+  auto resid_close = [&](int b, int r, double s0, double s1, double q) -> double {
+    double re = q;
+#ifdef MSOM_STRICT
+    if (upper) re = re + s0 * ring[b][wv - 1][r][DS][lane] * idh0;
+    if (lower) re = re - s1 * ring[b][wv][r][DS][lane] * idh1;
+    re += xdA[r];
+    re += ydA[r];
+#else
+    if (upper) re = fma(idh0, s0 * ring[b][wv - 1][r][DS][lane], re);
+    if (lower) re = fma(-(ring[b][wv][r][DS][lane] * s1), idh1, re);
+    re = fma(rD, ring[b][wv][r][XS][lane], re);
+    re = fma(rD, PARK3 ? ring[b][wv][r][XS + 2][lane] : ydA[r], re);
 #endif
     return re;
   };
@@ -357,6 +394,13 @@ __device__ __forceinline__ void lpw_body(const LpwArgs &a, double (&ring)[2][LPW
 #pragma unroll
       for (int r = 0; r < R; r++)
         if (out_ok && jb + r < y1 && !(a.dbg & 1)) outp[nat_idx(a.g, l, jb + r, gic)] = val[r];
+      if (CLS) {
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+          const double cr = resid_close(b ^ 1, r, s0[r], s1[r], CLS == 2 ? breg[r] : qreg[r]);
+          if (out_ok && jb + r < y1) cls_m = fmax(cls_m, fabs(cr));
+        }
+      }
       if (RES) {
         double re[R];
 #pragma unroll
@@ -392,6 +436,7 @@ __device__ __forceinline__ void lpw_body(const LpwArgs &a, double (&ring)[2][LPW
       for (int r = 0; r < R; r++) {
         const size_t c = nat_idx(a.g, l, (a.dbg & 2) ? y0 : (EDGE ? min(j0 + r, ny - 1) : j0 + r), gic);
         if (ADV) qreg[r] = a.q_in[c];
+        if (CLS == 2) breg[r] = a.rr.cls_b[c];
         if (QF) fqreg[r] = a.qforc[c];
         if (STOCH) { qsreg[r] = a.q_stage[c]; nzreg[r] = a.noise[c]; }
       }
@@ -413,12 +458,13 @@ __device__ __forceinline__ void lpw_body(const LpwArgs &a, double (&ring)[2][LPW
   }
 }
 
-template <int R, bool UNI, bool QF, bool ADV, bool STOCH = false, bool RES = false>
+template <int R, bool UNI, bool QF, bool ADV, bool STOCH = false, bool RES = false, int CLS = 0>
 __global__ void __launch_bounds__(64 * LPW_MAXW) k_rhs_lpw(LpwArgs a) {
   static_assert(!RES || (ADV && !STOCH && R % 2 == 0), "the residual by-product rides in the plain tendency + advance pass");
-  constexpr int NV = LPW_NV + (RES ? 1 : 0);
+  static_assert(!CLS || (RES && UNI), "the closing by-product rides beside the residual by-product, uniform S");
+  constexpr int NV = LPW_NV + (RES ? 1 : 0) + LPW_CLS_PARK(CLS);
   __shared__ double ring[2][LPW_MAXW][R][NV][64];
-  double res_m = 0., res_bs = 0.;
+  double res_m = 0., res_bs = 0., cls_m = 0., cls_u = 0.;
   // the same geometry as lpw_body (all wavefronts of a workgroup share the chunk, hence the number of barriers)
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int nx = a.g.nx, ny = a.g.ny;
@@ -433,22 +479,38 @@ __global__ void __launch_bounds__(64 * LPW_MAXW) k_rhs_lpw(LpwArgs a) {
     const bool inner = strip < nstrips && x0 - 3 >= 0 && x0 + 60 < nx && y0 - 3 >= 0 && y0 + nblk * R + R + 2 < ny;   // (+ R: the last interval's prefetch)
     if ((a.region == 1) != inner) return;
   }
-  if (xwall || ywall || a.noedge_off) lpw_body<R, UNI, QF, ADV, STOCH, true, RES, NV>(a, ring, res_m, res_bs);
-  else lpw_body<R, UNI, QF, ADV, STOCH, false, RES, NV>(a, ring, res_m, res_bs);
+  if (xwall || ywall || a.noedge_off) lpw_body<R, UNI, QF, ADV, STOCH, true, RES, CLS, NV>(a, ring, res_m, res_bs, cls_m, cls_u);
+  else lpw_body<R, UNI, QF, ADV, STOCH, false, RES, CLS, NV>(a, ring, res_m, res_bs, cls_m, cls_u);
   if (RES) {  // max|res| (order-free) and one partial sum of q_out per workgroup; the ring is free after the body's last barrier
     const int lane = threadIdx.x & 63, nw = blockDim.x >> 6;
     for (int o = 32; o > 0; o >>= 1) {
       res_m = fmax(res_m, __shfl_xor(res_m, o, 64));
       res_bs += __shfl_xor(res_bs, o, 64);
+      if (CLS) cls_m = fmax(cls_m, __shfl_xor(cls_m, o, 64));
+      if (CLS == 2) cls_u = fmax(cls_u, __shfl_xor(cls_u, o, 64));
     }
     double *red = &ring[0][0][0][0][0];
-    if (lane == 0) { red[wv] = res_m; red[LPW_MAXW + wv] = res_bs; }
+    if (lane == 0) {
+      red[wv] = res_m; red[LPW_MAXW + wv] = res_bs;
+      if (CLS) red[2 * LPW_MAXW + wv] = cls_m;
+      if (CLS == 2) red[3 * LPW_MAXW + wv] = cls_u;
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
       double mm = red[0], ss = red[LPW_MAXW];
       for (int k = 1; k < nw; k++) { mm = fmax(mm, red[k]); ss += red[LPW_MAXW + k]; }
       atomicMax((unsigned long long *)a.rr.res_max, (unsigned long long)__double_as_longlong(mm));
       a.rr.bsum_partial[blockIdx.y * gridDim.x + blockIdx.x] = ss;
+      if (CLS) {   // max of non-negative doubles by bit pattern, as k_resmax_march leaves it
+        double cm = red[2 * LPW_MAXW];
+        for (int k = 1; k < nw; k++) cm = fmax(cm, red[2 * LPW_MAXW + k]);
+        atomicMax((unsigned long long *)a.rr.cls_max, (unsigned long long)__double_as_longlong(cm));
+      }
+    }
+    if (CLS == 2 && (int)threadIdx.x < a.nl) {   // wavefronts l, l + nl, ... hold layer l of the workgroup's strips
+      double um = red[3 * LPW_MAXW + threadIdx.x];
+      for (int k = threadIdx.x + a.nl; k < nw; k += a.nl) um = fmax(um, red[3 * LPW_MAXW + k]);
+      atomicMax((unsigned long long *)(a.rr.cls_umax + threadIdx.x), (unsigned long long)__double_as_longlong(um));
     }
   }
 }
@@ -495,6 +557,10 @@ void launch_rhs_lpw(hipStream_t st, const KernelOpts &o, const double *psi, cons
     fprintf(stderr, "msom: launch_rhs_lpw: the residual by-product needs the plain tendency + advance pass on one tile with even sides\n");
     abort();
   }
+  if (res && rr->cls && (!uniformS || rr->cls < 0 || rr->cls > 2 || !rr->cls_max || (rr->cls == 2 && (!rr->cls_b || !rr->cls_umax)))) {
+    fprintf(stderr, "msom: launch_rhs_lpw: the closing by-product needs uniform S, its accumulators and (second stage) the solve's right-hand side\n");
+    abort();
+  }
   if (res) {
     a.rr = *rr;
     (void)hipMemsetAsync(rr->res_max, 0, sizeof(double), st);
@@ -524,6 +590,8 @@ void launch_rhs_lpw(hipStream_t st, const KernelOpts &o, const double *psi, cons
     with_bool(have_qforc, [&](auto Q) {
       constexpr bool UNI = decltype(U)::value, QF = decltype(Q)::value;
       if (stoch) hipLaunchKernelGGL((k_rhs_lpw<LPW_R, UNI, QF, true, true>), gr, bl, 0, st, a);
+      else if (res && UNI && a.rr.cls == 1) hipLaunchKernelGGL((k_rhs_lpw<LPW_R_RES, UNI, QF, true, false, true, UNI ? 1 : 0>), gr, bl, 0, st, a);
+      else if (res && UNI && a.rr.cls == 2) hipLaunchKernelGGL((k_rhs_lpw<LPW_R_RES, UNI, QF, true, false, true, UNI ? 2 : 0>), gr, bl, 0, st, a);
       else if (res) hipLaunchKernelGGL((k_rhs_lpw<LPW_R_RES, UNI, QF, true, false, true>), gr, bl, 0, st, a);
       else if (q_out) hipLaunchKernelGGL((k_rhs_lpw<LPW_R, UNI, QF, true>), gr, bl, 0, st, a);
       else hipLaunchKernelGGL((k_rhs_lpw<LPW_R, UNI, QF, false>), gr, bl, 0, st, a);

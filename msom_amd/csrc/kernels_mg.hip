@@ -468,8 +468,10 @@ __global__ void __launch_bounds__(BX *BY, UNIFORM ? 4 : 3) k_correct_residual(Re
 // from the shifts of the previous row, rows prefetched two steps ahead.  No LDS tile, no barrier per layer, halo 2 lanes in 64
 // and 2 rows per chunk: the pass reads psi and q once.  Uniform S only; the expressions are those of k_correct_residual, so
 // both maxima are the same numbers.
+// PSI_ONLY (option rhs_close, first RK stage): max |u(a)| alone -- no load of b, no residual chain, p.maxres untouched; the tendency pass
+// behind it forms max |res| from the b it reads anyway.  u, v, `own` and the reductions are the same code, so max |u| keeps its bits
 #define RM_OW 62
-template <int NL>
+template <int NL, bool PSI_ONLY = false>
 __global__ void __launch_bounds__(256) k_resmax_march(Res2Args p, int H) {
   __shared__ double smm[4];
   __shared__ double smu[MSOM_MAXNL][4];
@@ -493,30 +495,32 @@ __global__ void __launch_bounds__(256) k_resmax_march(Res2Args p, int H) {
       Wm[l] = pa[l * ls + (ptrdiff_t)(y0 - 1) * pitch];
       Wc[l] = pa[l * ls + (ptrdiff_t)y0 * pitch];
       Wp[l] = pa[l * ls + (ptrdiff_t)min(y0 + 1, ny) * pitch];
-      qc[l] = pb[l * ls + (ptrdiff_t)y0 * pitch];
+      qc[l] = PSI_ONLY ? 0. : pb[l * ls + (ptrdiff_t)y0 * pitch];
     }
 #pragma unroll
     for (int l = 0; l < NL; l++) { Em[l] = lane_above(Wm[l]); Mm[l] = lane_below(Wm[l]); }
     for (int j = y0; j < y1; j++) {
       const ptrdiff_t rn = (ptrdiff_t)min(j + 2, ny) * pitch, rq = (ptrdiff_t)min(j + 1, ny - 1) * pitch;
 #pragma unroll
-      for (int l = 0; l < NL; l++) { Wn[l] = pa[l * ls + rn]; qn[l] = pb[l * ls + rq]; }
+      for (int l = 0; l < NL; l++) { Wn[l] = pa[l * ls + rn]; qn[l] = PSI_ONLY ? 0. : pb[l * ls + rq]; }
 #pragma unroll
       for (int l = 0; l < NL; l++) {
         const double c = Wc[l], E = lane_above(c), W = lane_below(c), N = Wp[l], S = Wm[l], NW = lane_below(N), SE = Em[l], SW = Mm[l];
         const double be = qc[l];
         double re = be;
-        if (NL > 1) {
+        if (NL > 1 && !PSI_ONLY) {
           const double i0 = p.rc.idh0[l], i1 = p.rc.idh1[l];
           const double z0 = l > 0 ? p.rc.S[l - 1] : 0., z1 = l < NL - 1 ? p.rc.S[l] : 0.;
           if (l == 0) re = be + z1 * (c - Wc[l + 1 < NL ? l + 1 : l]) * i1;
           else if (l < NL - 1) re = be + z0 * (c - Wc[l - 1]) * i0 - z1 * (Wc[l + 1 < NL ? l + 1 : l] - c) * i1;
           else re = be + z0 * (c - Wc[l - 1]) * i0;
         }
-        re += DIVC(DIVC(c - W, D, rD) - DIVC(E - c, D, rD), D, rD);
-        re += DIVC(DIVC(c - S, D, rD) - DIVC(N - c, D, rD), D, rD);
+        if (!PSI_ONLY) {
+          re += DIVC(DIVC(c - W, D, rD) - DIVC(E - c, D, rD), D, rD);
+          re += DIVC(DIVC(c - S, D, rD) - DIVC(N - c, D, rD), D, rD);
+        }
         const double u = fabs(DIVC(0.25 * (N - S + NW - SW), D, rD)), v = fabs(DIVC(0.25 * (E - W + SE - SW), D, rD));
-        if (own) { m = fmax(m, fabs(re)); uu[l] = fmax(uu[l], fmax(u, v)); }
+        if (own) { if (!PSI_ONLY) m = fmax(m, fabs(re)); uu[l] = fmax(uu[l], fmax(u, v)); }
         Em[l] = E; Mm[l] = W;
       }
 #pragma unroll
@@ -531,7 +535,7 @@ __global__ void __launch_bounds__(256) k_resmax_march(Res2Args p, int H) {
     if (lane == 0) smu[l][wv] = w;
   }
   __syncthreads();
-  if (threadIdx.x == 0) {
+  if (threadIdx.x == 0 && !PSI_ONLY) {
     const double mm = fmax(fmax(smm[0], smm[1]), fmax(smm[2], smm[3]));
     atomicMax((unsigned long long *)p.maxres, (unsigned long long)__double_as_longlong(mm));
   }
@@ -540,15 +544,16 @@ __global__ void __launch_bounds__(256) k_resmax_march(Res2Args p, int H) {
         fmax(fmax(smu[threadIdx.x][0], smu[threadIdx.x][1]), fmax(smu[threadIdx.x][2], smu[threadIdx.x][3]));
 }
 template <int NL>
-static dim3 resmax_march_launch(hipStream_t st, const Res2Args &p, int H) {
+static dim3 resmax_march_launch(hipStream_t st, const Res2Args &p, int H, bool psi_only) {
   const int nstrips = (p.g.nx + RM_OW - 1) / RM_OW;
   dim3 gr((nstrips + 3) / 4, (p.g.ny + H - 1) / H);
-  hipLaunchKernelGGL(k_resmax_march<NL>, gr, dim3(256), 0, st, p, H);
+  if (psi_only) hipLaunchKernelGGL((k_resmax_march<NL, true>), gr, dim3(256), 0, st, p, H);
+  else hipLaunchKernelGGL((k_resmax_march<NL, false>), gr, dim3(256), 0, st, p, H);
   return gr;
 }
-static dim3 launch_resmax_march(hipStream_t st, const Res2Args &p, int H) {
+static dim3 launch_resmax_march(hipStream_t st, const Res2Args &p, int H, bool psi_only) {
   dim3 gr;
-  if (!with_int<1, MSOM_FASTNL>(p.nl, [&](auto N) { gr = resmax_march_launch<N()>(st, p, H); })) no_kernel("launch_resmax_march", p.nl);
+  if (!with_int<1, MSOM_FASTNL>(p.nl, [&](auto N) { gr = resmax_march_launch<N()>(st, p, H, psi_only); })) no_kernel("launch_resmax_march", p.nl);
   return gr;
 }
 
@@ -612,9 +617,15 @@ void launch_residual2(hipStream_t st, const KernelOpts &o, int mode, const doubl
     case 2: hipLaunchKernelGGL((k_residual2<false, true, false>), gr, block2d(), 0, st, p); break;
     case 6: hipLaunchKernelGGL((k_residual2<false, true, true>), gr, block2d(), (size_t)nl * (BY * BX * 2 + 2 * BX) * sizeof(double), st, p); break;
     case 0: hipLaunchKernelGGL((k_residual2<false, false, false>), gr, block2d(), 0, st, p); break;
+    case 8 | 16:  // max |u(a)| alone (option rhs_close): the marching kernel's psi-only form; the caller has checked that it applies
+      if (!(uniformS && g.nx >= 64 && g.ny >= 16 && o.resmax_rows >= 0 && nl <= MSOM_FASTNL)) no_kernel("launch_residual2 (psi only)", nl);
+      gr = launch_resmax_march(st, p, o.resmax_rows ? o.resmax_rows : 32, true);
+      if (!umax_clean) (void)hipMemsetAsync(umax_out, 0, nl * sizeof(double), st);
+      hipLaunchKernelGGL(k_max_final_mg, dim3(64), dim3(256), 0, st, umax_partial, umax_out, (int)(gr.x * gr.y), nl);
+      break;
     case 8:  // max |res(a)| and max |u(a)| of an a that is already corrected
       if (uniformS && g.nx >= 64 && g.ny >= 16 && o.resmax_rows >= 0 && nl <= MSOM_FASTNL) {   // option resmax_rows
-        gr = launch_resmax_march(st, p, o.resmax_rows ? o.resmax_rows : 32);
+        gr = launch_resmax_march(st, p, o.resmax_rows ? o.resmax_rows : 32, false);
       } else if (g.nx % 2 == 0 && g.nx >= CR_TW && g.ny >= CR_TR && !(p.dbg & 128)) {
         gr = dim3((g.nx + CR_TW - 1) / CR_TW, (g.ny + CR_TR - 1) / CR_TR);
         if (uniformS) hipLaunchKernelGGL((k_correct_residual<true, false>), gr, block2d(), 0, st, p);

@@ -14,6 +14,12 @@
 // option rhs_resid = -1 (default): on from 2^RHS_RESID_MIN cell-layers.  RK2 step on one MI355X, off -> on: 4096^2 x 6 5.65 -> 5.28 ms,
 // 2048^2 x 3 (2^23.6) 1.23 -> 1.10 ms, 512^2 x 3 (2^19.6) 0.350 -> 0.348 ms (inside the noise), 128^2 x 1 0.197 -> 0.21 ms
 #define RHS_RESID_MIN 23
+// option rhs_close = -1 (default): RHS_CLOSE_DEFAULT (both RK stages; first stage only with a 3-D forcing) from 2^RHS_CLOSE_MIN cell-layers,
+// off below.  RK2 step on one MI355X, 0 -> 1 -> 2: 4096^2 x 6 5.50 -> 5.38 -> 5.26 ms, 2048^2 x 3 1.098 -> 1.097 -> 1.074 ms, 512^2 x 3 0.353
+// all three: the finest level is not marched there and the option resolves to 0 ("The tendency pass closes the solve
+// in front of it")
+#define RHS_CLOSE_MIN 23
+#define RHS_CLOSE_DEFAULT 2
 #define MARCH_HALO 4    // rows (= cells in x) of neighbour data a pass of up to 4 chained half-sweeps reads
 
 static void free_agglomeration(msom *m);
@@ -586,6 +592,10 @@ extern "C" int msom_set_option(msom_t *m, const char *key, double v) {
   else if (!strcmp(key, "adv_fused")) m->adv_fused = (int)v;
   else if (!strcmp(key, "overlap")) m->overlap = (int)v;
   else if (!strcmp(key, "rhs_resid")) { m->rhs_resid = (int)v; m->res_ready = -1; }
+  else if (!strcmp(key, "rhs_close")) {
+    if ((int)v < -1 || (int)v > 2) { msom_set_error("option rhs_close = %g (-1, 0, 1 or 2)", v); return MSOM_ERR_ARG; }
+    m->rhs_close = (int)v; m->res_ready = -1;
+  }
   else if (!strcmp(key, "seed")) { m->seed = (unsigned)v; srand(m->seed); }
   else if (!strcmp(key, "noise_mode")) m->noise_mode = (int)v;
   else if (!strcmp(key, "stoch_fused")) m->stoch_fused = (int)v;
@@ -642,6 +652,7 @@ static bool fine_visit_fused(const msom *m);
 static int level_path(const msom *m, int k);
 static bool restrict2_ok(const msom *m);
 static bool rhs_resid_emits(const msom *m);
+static int rhs_close_mode(const msom *m);
 extern "C" double msom_get_param(msom_t *m, const char *key) {
   if (!m || !key) return NAN;
   if (!strcmp(key, "model")) return m->model;
@@ -689,6 +700,7 @@ extern "C" double msom_get_param(msom_t *m, const char *key) {
   if (!strcmp(key, "march_visit_ring")) return !fine_visit_fused(m) ? -1 : (m->opt.march_visit_ring >= 2 ? 2 : (m->opt.march_visit_ring == 1 ? 1 : 0));
   if (const int *o = kernel_opt(m->opt, key)) return *o;   // the handle's kernel options (march_rows, march_lean, ... rhs_dbg)
   if (!strcmp(key, "rhs_resid")) return rhs_resid_emits(m);   // the tendency + advance pass emits the next solve's first residual
+  if (!strcmp(key, "rhs_close")) return rhs_close_mode(m);    // ... and closes the solve in front of it: 0 no, 1 first RK stage, 2 both
   if (!strncmp(key, "split_ls_", 9)) { const int k = atoi(key + 9); return k >= 0 && k < m->nlev ? (double)m->sg[k].ls : NAN; }
   if (!strncmp(key, "split_rp_", 9)) { const int k = atoi(key + 9); return k >= 0 && k < m->nlev ? (double)m->sg[k].rp : NAN; }   // doubles per row
   if (!strcmp(key, "split_pad")) return MSOM_SP;   // pad doubles on each side of a half row of a split field
@@ -1210,6 +1222,34 @@ static bool fine_visit_fused(const msom *m) {
   return march_next(m, L, fuse_prolong(m, L, 4) ? &C : nullptr, 8, corr_wanted(m)).kind == MA_VISIT;
 }
 
+// does the finest level's visit of a first cycle (nrelax = 4) end in a pass that applies the correction (mg_solve then finds corr_done)?
+// The same walk through march_next as relax_sweeps makes
+static bool fine_corr_in_smoother(const msom *m) {
+  if (m->nlev < 2 || level_path(m, 0) != RP_MARCH || !corr_wanted(m)) return false;
+  const Lev L = tile_lev(m, 0), C = tile_lev(m, 1);
+  const Lev *src = fuse_prolong(m, L, 4) ? &C : nullptr;
+  for (int n = 8;;) {
+    const MarchAct a = march_next(m, L, src, n, true);
+    if (a.kind == MA_HALF || a.kind == MA_DONE) return false;
+    if (a.kind == MA_VISIT || a.corr) return true;
+    src = nullptr; n -= a.K;
+  }
+}
+// option rhs_close resolved: what the speculative tendency passes of this handle do beside their own work (0: nothing, 1: the first
+// stage's pass forms max|res| of the solve in front of it, 2: the second stage's too, with max|u|).  The one statement of the conditions,
+// read by mg_solve and msom_get_param("rhs_close"): a speculative pass that emits the next residual (k_rhs_lpw RES), uniform S with the
+// marching max-only pass (whose numbers the by-product repeats), the correction applied by the smoother's last pass
+static bool spec_ok(const msom *m);
+static int rhs_close_mode(const msom *m) {
+  int v = m->rhs_close;
+  // (default with a 3-D forcing: first stage only -- the CLS = 2 form that also reads qforc keeps 6 spilled VGPRs inside its marching loop)
+  if (v < 0) v = (size_t)m->g.nx * m->g.ny * m->nl >= ((size_t)1 << RHS_CLOSE_MIN) ? (m->have_qforc ? 1 : RHS_CLOSE_DEFAULT) : 0;
+  if (v <= 0) return 0;
+  const bool resmax_marching = m->uniformS && m->nl <= MSOM_FASTNL && m->g.nx >= 64 && m->g.ny >= 16 && m->opt.resmax_rows >= 0;
+  if (!spec_ok(m) || !rhs_resid_emits(m) || !resmax_marching || !fine_corr_in_smoother(m)) return 0;
+  return v;
+}
+
 // level k's four deep-halo arrays of the chained smoother (MARCH_HALO rows each), allocated when a pass first needs them, as the
 // kernels take them: those of the correction and, res, of the residual; wrap: the doubly periodic single tile is its own neighbour
 static bool march_halo(msom *m, int k, bool wrap, bool res, MarchHalo *h) {
@@ -1595,7 +1635,16 @@ static int mg_solve(msom *m, const double *b, msom_mgstats *s) {
       if (m->nranks > 1) STICKY(m, exch_nat(m, m->f[MSOM_PSI], m->nl, m->bc, 1));
       else if (m->bc == BC_PERIODIC) launch_fill_periodic(m->st, m->f[MSOM_PSI], m->g, m->nl, 1);
       else launch_fill_ghost(m->st, m->f[MSOM_PSI], m->g, m->nl, m->bc, m->walls);   // the LDS-DMA pass leaves the wall ghosts to this
-      residual2(m, 8, b, SC_RES1, 0);
+      // option rhs_close: the speculative tendency pass queued below reads this psi anyway and forms max|res| (second stage: max|u|
+      // too) on the side.  First stage: dt comes from max|u|, which therefore stays in front of the pass, from psi alone
+      const int cls = (s->i == 0 && m->spec_hook && m->nranks == 1) ? rhs_close_mode(m) : 0;
+      m->close_cls = !cls ? 0 : (m->dt_dev ? 1 : (cls >= 2 ? 2 : 0));
+      m->close_b = b;
+      if (m->close_cls == 2) {   // the pass accumulates into the block zeroed with the solve's scalars
+        if (!m->umax_clean) HIPCHK(hipMemsetAsync(m->d_scal + SC_UMAX, 0, m->nl * sizeof(double), m->st));
+        m->umax_clean = 0;
+      }
+      else residual2(m, m->close_cls ? 8 | 16 : 8, b, SC_RES1, 0);
       m->umax_ready = 1;
     } else if (fused) {
       residual2(m, 1, b, SC_RES1, 0);            // a_new = a + da -> psi_alt, max |res(a_new)|, max |u(a_new)|
@@ -1611,6 +1660,7 @@ static int mg_solve(msom *m, const double *b, msom_mgstats *s) {
       m->spec_hook([&]() {});
       m->spec_launched = 1;
     }
+    m->close_cls = 0;
     int rr = read_residuals(m);
     if (rr) { m->spec_launched = 0; return rr; }
     if (m->spec_launched) {   // its output counts only if this solve ends here
@@ -1710,6 +1760,9 @@ int rhs_terms(msom *m, int qfield, int dqfield, int with_qforcing, double iRe, d
     if (use_rr) {
       rr.res = m->res[0]; rr.res_c = m->res[1]; rr.res_max = m->d_scal + SC_RESF; rr.bsum_partial = m->partial_rr;
       rr.sg = m->sg[0]; rr.cg = m->sg[1];
+      if (m->close_cls) {   // the speculative pass of mg_solve: max|res| of the solve that made psi, as k_resmax_march would leave it
+        rr.cls = m->close_cls; rr.cls_b = m->close_b; rr.cls_max = m->d_scal + SC_RES1; rr.cls_umax = m->d_scal + SC_UMAX;
+      }
     }
     // the psi halo exchange of a tile around the launch(es) of the pass; splittable: the kernel takes a region argument
     auto with_psi_halo = [&](bool splittable, auto launch) {
@@ -2155,7 +2208,7 @@ static int tracer_advance(msom *m, int out, int in, double dt) {
 // (q_out = q_in + dt * dq) whenever the fused kernel applies; dq is then never stored.
 // can a stage's tendency pass be queued speculatively?  One tile, the fused one-layer-per-wavefront kernel with the advance
 // folded in, max|u| out of the solver's last pass, nothing with side effects in the pass (noise draws, tracers)
-static bool spec_ok(msom *m) {
+static bool spec_ok(const msom *m) {
   return layered_fusions(m) && m->async_solve && m->nranks == 1 && m->fused && m->adv_fused && m->rhs_variant == 6 && m->mg_fused && m->nlev > 1 &&
          m->nl <= MSOM_FASTNL && !m->have_pg && !m->have_zpg && !m->flag_topo && !m->stochastic && m->p.nptr == 0 && m->p.nitermin >= 1 && !m->dbg_nosync;
 }
@@ -2176,11 +2229,16 @@ extern "C" int msom_step(msom_t *m, double *dt_used) {
       for (int l = 0; l < MSOM_MAXNL; l++) a.umax_pg[l] = m->umax_pg[l];
       a.D = p.L0 / m->gnx; a.CFL = p.CFL; a.previous = m->previous; a.dtmax = p.DT; a.t = m->t; a.tnext = m->tnext; a.nl = m->nl;
       a.with_dt = 1; a.seq = ++m->pub_seq;
-      hipLaunchKernelGGL(k_step_dt, dim3(1), dim3(64), 0, m->st, m->d_scal, a, m->d_pub);
+      // (rhs_close: max|res| comes out of the pass, so the scalars are published behind it)
+      hipLaunchKernelGGL(k_step_dt, dim3(1), dim3(64), 0, m->st, m->d_scal, a, m->close_cls ? nullptr : m->d_pub);
       host_read();
       int adv = 0;
       spec_rc = rhs_terms(m, MSOM_Q, MSOM_DQ, 1, p.iRe, p.iRe4, p.Eks, p.Ekb, MSOM_QPRED, MSOM_Q, 0., &adv);
       if (!adv && !spec_rc) spec_rc = MSOM_ERR_STATE;
+      if (m->close_cls) {
+        a.with_dt = 0;
+        hipLaunchKernelGGL(k_step_dt, dim3(1), dim3(64), 0, m->st, m->d_scal, a, m->d_pub);
+      }
     };
   }
   const double d = solve_and_dt(m, MSOM_Q, p.DT);
@@ -2217,13 +2275,15 @@ extern "C" int msom_step(msom_t *m, double *dt_used) {
       StepDtArgs a;
       memset(&a, 0, sizeof a);
       a.with_dt = 0; a.seq = ++m->pub_seq;
-      hipLaunchKernelGGL(k_step_dt, dim3(1), dim3(64), 0, m->st, m->d_scal, a, m->d_pub);   // publish only
+      // publish only: in front of the pass, or (rhs_close: max|res| and max|u| come out of the pass) behind it
+      if (!m->close_cls) hipLaunchKernelGGL(k_step_dt, dim3(1), dim3(64), 0, m->st, m->d_scal, a, m->d_pub);
       host_read();
       int adv = 0;
       m->adv_out_override = m->q_alt;
       spec_rc = rhs_terms(m, MSOM_QPRED, MSOM_DQ, 1, p.iRe, p.iRe4, p.Eks, p.Ekb, MSOM_Q, MSOM_Q, m->dt, &adv);
       m->adv_out_override = nullptr;
       if (!adv && !spec_rc) spec_rc = MSOM_ERR_STATE;
+      if (m->close_cls) hipLaunchKernelGGL(k_step_dt, dim3(1), dim3(64), 0, m->st, m->d_scal, a, m->d_pub);
     };
   }
   const double d2 = solve_and_dt(m, MSOM_QPRED, m->dt);

@@ -70,7 +70,8 @@ struct msom {
   // altogether, tools/ab_nosync.py).  If the solve turns out to need another cycle the pass is simply run again afterwards:
   // its output went to the predictor (stage 1) or to a spare buffer that only replaces q when the solve had converged (stage 2).
   int async_solve = 1;               // option
-  int step_sync = -1;                // option: 0 = msom_step returns without waiting for its last tendency pass (async_solve only), 1 = it waits,
+  int step_sync = -1;                // option: 0 = msom_step returns without waiting for its last tendency pass (async_solve only; with rhs_close = 2
+                                     // that pass carries the solve's closing residual and the host has waited for it anyway), 1 = it waits,
                                      // -1 (default) = it waits on grids of >= 2^23 cell-layers.  Measured (same process): 128^2 x 1 0.203 -> 0.185 ms per
                                      // step, 512^2 x 3 0.374 -> 0.352, 2048^2 x 3 1.238 -> 1.226, 4096^2 x 6 6.15 -> 6.20 (worse)
   std::function<void(const std::function<void()> &)> spec_hook;   // queued by mg_solve after the first cycle's residual pass; calls its
@@ -178,6 +179,10 @@ struct msom {
   int rhs_resid = -1;  // let the fused tendency + advance pass produce it: 1 / 0, -1 = where it measurably wins (rhs_resid_on).  k_rhs_lpw's RES
                        // instantiation (rhs_variant 6); in the LDS-tile kernel (rhs_variant 1) it lost: 23 spilled VGPRs, 2.21 ms vs 1.63 + 0.50 ms
   int rr_nparts = 0;   // partial sums of q_out the last such pass wrote
+  int rhs_close = -1;  // the speculative tendency pass also closes the solve in front of it (k_rhs_lpw CLS, max|res| of the solve's b) in place of
+                       // k_resmax_march: 0 never, 1 first RK stage (a psi-only max|u| pass stays), 2 both stages, -1 = where it measurably wins
+  int close_cls = 0;   // set by mg_solve around its call of spec_hook: the CLS form this speculative pass takes (nothing outlives the solve)
+  const double *close_b = nullptr;   // ... and the solve's right-hand side
   // back-and-forth nudging loop on the device (msom_bfn_*)
   int bfn_begun = 0;                      // msom_bfn_begin since the last msom_set_const
   int bfn_obs_set = 0, bfn_gain_set = 0;  // MSOM_BFN_OBS / MSOM_BFN_GAIN came in through msom_set_field (gain never set: 1 everywhere)
