@@ -10,6 +10,7 @@
 //   update_qg msqg/qg.h:609-650, advance_qg :594-606, run() of Basilisk predictor-corrector.h
 //   (SURVEY App. B), pystep_bfn msqg/qg_bfn.h:21-103, its time loop msqg/qg_bfn.py:47-73 (msom_bfn_steps).
 #include "msom_host.h"
+#include "step_dt_inl.h"
 
 // option rhs_resid = -1 (default): on from 2^RHS_RESID_MIN cell-layers.  RK2 step on one MI355X, off -> on: 4096^2 x 6 5.65 -> 5.28 ms,
 // 2048^2 x 3 (2^23.6) 1.23 -> 1.10 ms, 512^2 x 3 (2^19.6) 0.350 -> 0.348 ms (inside the noise), 128^2 x 1 0.197 -> 0.21 ms
@@ -275,7 +276,6 @@ static int exch_split_deep(msom *m, double *f, const SplitGeom &sg, double *fs, 
 
 static int alloc_all(msom *m) {
   HIPCHK(hipStreamCreate(&m->st));
-  HIPCHK(hipEventCreateWithFlags(&m->ev_spec, hipEventDisableTiming));
   HIPCHK(hipHostMalloc(&m->h_pub, (SC_COUNT + 1) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
   memset(m->h_pub, 0, (SC_COUNT + 1) * sizeof(double));
   HIPCHK(hipHostGetDevicePointer((void **)&m->d_pub, m->h_pub, 0));
@@ -499,7 +499,6 @@ extern "C" int msom_destroy(msom_t *m) {
   }
   if (m->psi_alt) hipFree(m->psi_alt);
   if (m->q_alt) hipFree(m->q_alt);
-  if (m->ev_spec) hipEventDestroy(m->ev_spec);
   if (m->h_pub) hipHostFree(m->h_pub);
   if (m->staging) hipFree(m->staging);
   if (m->partial) hipFree(m->partial);
@@ -651,7 +650,7 @@ static bool march_lean_fine(const msom *m);
 static bool fine_visit_fused(const msom *m);
 static int level_path(const msom *m, int k);
 static bool restrict2_ok(const msom *m);
-static bool rhs_resid_emits(const msom *m);
+static bool rhs_resid_emits(const msom *m, int want = -1);
 static int rhs_close_mode(const msom *m);
 extern "C" double msom_get_param(msom_t *m, const char *key) {
   if (!m || !key) return NAN;
@@ -1111,8 +1110,9 @@ static bool rhs_resid_variant(const msom *m) {
 // ... and emitted by this handle's tendency + advance passes: the one statement of use_rr's terms, which rhs_terms and
 // msom_get_param("rhs_resid") both read.  The fused pass with the advance riding along (never the stochastic one), k_rhs_lpw or the
 // LDS-tile kernel, the layered solver's fused residual consumer on more than one level, one tile with walls and even sides
-static bool rhs_resid_emits(const msom *m) {
-  return rhs_resid_on(m) && m->fused && m->adv_fused && m->nl <= MSOM_FASTNL && !m->have_pg && !m->have_zpg && !m->flag_topo && !m->stochastic &&
+// (want: what one pass asks for, RhsPass::emit_resid -- -1 the option, 1 / 0 in its place)
+static bool rhs_resid_emits(const msom *m, int want) {
+  return (want < 0 ? rhs_resid_on(m) : want > 0) && m->fused && m->adv_fused && m->nl <= MSOM_FASTNL && !m->have_pg && !m->have_zpg && !m->flag_topo && !m->stochastic &&
          layered_fusions(m) && rhs_resid_variant(m) && m->mg_fused && m->nlev > 1 && m->bc != BC_PERIODIC && m->nranks == 1 &&
          !(m->g.nx & 1) && !(m->g.ny & 1);
 }
@@ -1289,7 +1289,9 @@ static void march_pass(msom *m, bool overlap, ProfSlot *ps, Launch launch, Halos
 // nrelax red-black relaxations of L.da against L.res (each followed by boundary_level).
 // coarse != nullptr: L.da has not been prolongated yet -- the first pass interpolates it from
 // the coarser level on the fly.  corners_last: the last exchange also carries corner ghosts.
-void relax_sweeps(msom *m, Lev &L, const Lev *coarse, int nrelax, int corners_last) {
+// corr_req: the solve wants the finest level's last pass to apply the correction (march_next); returns whether one did -- psi + da
+// then sits in psi_alt and L.da is not to be read
+bool relax_sweeps(msom *m, Lev &L, const Lev *coarse, int nrelax, int corners_last, bool corr_req) {
   const bool prof = m->profile && L.fine;
   const int nl = m->nl;
   const int path = sweep_path(m, L);
@@ -1310,29 +1312,28 @@ void relax_sweeps(msom *m, Lev &L, const Lev *coarse, int nrelax, int corners_la
       else { launch_split_wrap(m->st, f, m->sg[k], fs, fn, hgeo, nl, MARCH_HALO, 0); launch_split_wrap(m->st, f, m->sg[k], fs, fn, hgeo, nl, MARCH_HALO, 1); }
     };
     MarchHalo mh{nullptr, nullptr, nullptr, nullptr, 0, MARCH_HALO}, ch = mh;
-    if (deep && !march_halo(m, L.k, wrap, true, &mh)) return;
+    if (deep && !march_halo(m, L.k, wrap, true, &mh)) return false;
     const bool ovl = L.tiled && m->overlap;
     bool res_halo = deep;   // the residual's deep halo is constant during the sweeps: it rides with the first pass
     const MarchCorrect mc{m->f[MSOM_PSI], m->psi_alt, m->g};
     const Lev *src = coarse;
     int n = 2 * nrelax, c = 0;
     for (;;) {
-      const MarchAct a = march_next(m, L, src, n, m->corr_req);
+      const MarchAct a = march_next(m, L, src, n, corr_req);
       if (a.kind == MA_HALF || a.kind == MA_DONE) break;
       if (a.kind == MA_VISIT) {
         if (prof) prof_begin(m, m->prof_march_visit);
         if (launch_relax_visit(m->st, m->opt, *L.da, *L.da_alt, L.res, *L.sg, nl, *L.rc, kwalls, *src->da, *src->sg, mc))
           m->sticky = MSOM_ERR_ARG;
         if (prof) prof_end(m, m->prof_march_visit);
-        m->corr_done = 1;
-        return;
+        return true;
       } else if (a.kind == MA_REDPROL) {
         if (prof) prof_begin(m, m->prof_redprol);
         launch_relax_red_prolong(m->st, m->opt, *L.da, *src->da, *src->sg, L.res, L.S, *L.sg, nl, *L.rc, m->uniformS, L.walls);
         if (prof) prof_end(m, m->prof_redprol);
       } else {
         const Lev *pl = a.kind == MA_PL ? src : nullptr;   // the pass reads the coarse level (and, deep, its halo) instead of L.da
-        if (pl && deep && !march_halo(m, pl->k, wrap, false, &ch)) return;
+        if (pl && deep && !march_halo(m, pl->k, wrap, false, &ch)) return false;
         march_pass(m, ovl, !prof ? nullptr : (pl ? &m->prof_march_pl : (a.corr ? &m->prof_march_corr : &m->prof_march[a.K])),
                    [&](int region) {
                      if (launch_relax_march(m->st, m->opt, pl ? nullptr : *L.da, *L.da_alt, L.res, *L.sg, nl, *L.rc, c, a.K, kwalls, m->opt.march_rows, deep ? &mh : nullptr,
@@ -1344,7 +1345,7 @@ void relax_sweeps(msom *m, Lev &L, const Lev *coarse, int nrelax, int corners_la
                      res_halo = false;
                      if (deep) fill_halo(pl ? pl->k : L.k, false);
                    });
-        if (a.corr) { m->corr_done = 1; return; }  // da of this level was consumed in registers; nothing reads it any more
+        if (a.corr) return true;  // da of this level was consumed in registers; nothing reads it any more
         std::swap(*L.da, *L.da_alt);
       }
       src = nullptr; n -= a.K; c = (c + a.K) & 1;
@@ -1357,7 +1358,7 @@ void relax_sweeps(msom *m, Lev &L, const Lev *coarse, int nrelax, int corners_la
     }
     // boundary_level(da, l) after the last half-sweep; it also carries the corner ghosts the prolongation reads
     if (L.tiled) STICKY(m, exch_split(m, *L.da, *L.sg, nl, corners_last));
-    return;
+    return false;
   }
   if (path == RP_BLOCK8) {
     int n = 2 * nrelax, c = 0;
@@ -1372,7 +1373,7 @@ void relax_sweeps(msom *m, Lev &L, const Lev *coarse, int nrelax, int corners_la
       // pass reads them, and so does the prolongation to the next finer level)
       if (L.walls & WALL_PER) launch_split_wrap(m->st, *L.da, *L.sg, nullptr, nullptr, make_split(L.sg->nx, MARCH_HALO), nl, MARCH_HALO, 2);
     }
-    return;
+    return false;
   }
   if (path == RP_BLOCK2) {
     for (; it + 2 <= nrelax; it += 2) {
@@ -1410,11 +1411,12 @@ void relax_sweeps(msom *m, Lev &L, const Lev *coarse, int nrelax, int corners_la
     }
     if (prof && !pl) prof_end(m, m->prof_sweep);
   }
+  return false;
 }
 
 // one level of the coarse-to-fine half of mg_cycle: initial guess (zero / prolongation), then
-// the relaxations
-static void level_solve(msom *m, Lev &L, const Lev *coarse, int nrelax, int corners_last) {
+// the relaxations (corr_req and the return value: see relax_sweeps)
+static bool level_solve(msom *m, Lev &L, const Lev *coarse, int nrelax, int corners_last, bool corr_req) {
   const int nl = m->nl;
   bool fused = false;
   if (!coarse) hipMemsetAsync(*L.da, 0, L.sg->ls * nl * sizeof(double), m->st);
@@ -1423,14 +1425,15 @@ static void level_solve(msom *m, Lev &L, const Lev *coarse, int nrelax, int corn
     launch_prolong(m->st, *coarse->da, *coarse->sg, *L.da, *L.sg, nl, L.walls);
     if (L.tiled) STICKY(m, exch_split(m, *L.da, *L.sg, nl, 0));
   }
-  relax_sweeps(m, L, fused ? coarse : nullptr, nrelax, corners_last);
+  return relax_sweeps(m, L, fused ? coarse : nullptr, nrelax, corners_last, corr_req);
 }
 
 // coarse-to-fine part of mg_cycle, mspg/elliptic.h:53-89 (minlevel = 1): restriction of the
 // residual to all levels (level 1 may already come out of the fused residual kernel), then
 // prolongation + nrelax relaxations per level.  With tiles, the levels >= agg_level are solved
 // on the gathered global coarse grid by every rank (identical arithmetic, no halo traffic).
-static void mg_cycle_levels(msom *m, int nrelax, int first_restrict) {
+// corr_req and the return value: see relax_sweeps (only the finest tile level can answer a request).
+static bool mg_cycle_levels(msom *m, int nrelax, int first_restrict, bool corr_req) {
   const int nl = m->nl, kc = m->agg_level >= 0 ? m->agg_level : m->nlev;
   const int kg = m->mgc_first;  // levels >= kg (of the gathered grid if kc < nlev, else of this tile): one launch
   const bool glob = kc < m->nlev;
@@ -1476,8 +1479,8 @@ static void mg_cycle_levels(msom *m, int nrelax, int first_restrict) {
     }
     for (int k = (kg >= 0 ? kg : m->nlev) - 1; k >= kc; k--) {
       Lev L = glob_lev(m, k);
-      if (k == m->nlev - 1) level_solve(m, L, nullptr, nrelax, 0);
-      else { Lev C = glob_lev(m, k + 1); level_solve(m, L, &C, nrelax, 0); }
+      if (k == m->nlev - 1) level_solve(m, L, nullptr, nrelax, 0, false);
+      else { Lev C = glob_lev(m, k + 1); level_solve(m, L, &C, nrelax, 0, false); }
     }
     // this rank's tile of the level-kc correction, with its ghost ring
     launch_extract_tile(m->st, m->gda[0], m->gsg[0], m->da[kc], tg, nl, m->ix * tg.nx, m->iy * tg.ny);
@@ -1485,11 +1488,13 @@ static void mg_cycle_levels(msom *m, int nrelax, int first_restrict) {
     launch_mg_coarse(m->st, m->d_cargs, nrelax, nl, m->uniformS, m->mgc_lean);
     if (hipGetLastError() != hipSuccess && !m->sticky) m->sticky = MSOM_ERR_HIP;
   }
+  bool corr_done = false;
   for (int k = (glob ? kc : (kg >= 0 ? kg : m->nlev)) - 1; k >= 0; k--) {
     Lev L = tile_lev(m, k);
-    if (k == m->nlev - 1) level_solve(m, L, nullptr, nrelax, k > 0);
-    else { Lev C = tile_lev(m, k + 1); level_solve(m, L, &C, nrelax, k > 0); }
+    if (k == m->nlev - 1) corr_done = level_solve(m, L, nullptr, nrelax, k > 0, corr_req);
+    else { Lev C = tile_lev(m, k + 1); corr_done = level_solve(m, L, &C, nrelax, k > 0, corr_req); }
   }
+  return corr_done;
 }
 
 static void clear_graphs(msom *m) {
@@ -1497,31 +1502,33 @@ static void clear_graphs(msom *m) {
   m->cyc_graph.clear();
 }
 // the cycle through a captured graph where that is possible (see use_graph); same launches, same order, same arguments
-static void mg_cycle(msom *m, int nrelax, int first_restrict) {
-  bool ok = m->use_graph && m->nranks == 1 && !m->profile;   // (corr_req only acts inside a marching pass, excluded below)
+// corr_req and the return value: see relax_sweeps.  A request acts inside a marching pass only and a captured cycle has none, so the
+// capture is made, and replayed, without one
+static bool mg_cycle(msom *m, int nrelax, int first_restrict, bool corr_req) {
+  bool ok = m->use_graph && m->nranks == 1 && !m->profile;
   for (int k = 0; ok && k < m->nlev; k++) {
     Lev L = tile_lev(m, k);
     if (sweep_path(m, L) != RP_COLOUR) ok = false;   // those passes ping-pong between two buffers: pointers differ from cycle to cycle
   }
-  if (!ok) { mg_cycle_levels(m, nrelax, first_restrict); return; }
+  if (!ok) return mg_cycle_levels(m, nrelax, first_restrict, corr_req);
   const long key = (long)nrelax * 8 + first_restrict;
   auto it = m->cyc_graph.find(key);
   if (it == m->cyc_graph.end()) {
     hipGraph_t g = nullptr;
     hipGraphExec_t ex = nullptr;
-    if (hipStreamBeginCapture(m->st, hipStreamCaptureModeThreadLocal) != hipSuccess) { m->use_graph = 0; mg_cycle_levels(m, nrelax, first_restrict); return; }
-    mg_cycle_levels(m, nrelax, first_restrict);
+    if (hipStreamBeginCapture(m->st, hipStreamCaptureModeThreadLocal) != hipSuccess) { m->use_graph = 0; return mg_cycle_levels(m, nrelax, first_restrict, false); }
+    mg_cycle_levels(m, nrelax, first_restrict, false);
     if (hipStreamEndCapture(m->st, &g) != hipSuccess || !g || hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) != hipSuccess) {
       if (g) (void)hipGraphDestroy(g);
       (void)hipGetLastError();
       m->use_graph = 0;                 // nothing was executed during the capture: run the cycle eagerly now
-      mg_cycle_levels(m, nrelax, first_restrict);
-      return;
+      return mg_cycle_levels(m, nrelax, first_restrict, false);
     }
     (void)hipGraphDestroy(g);
     it = m->cyc_graph.emplace(key, ex).first;
   }
   if (hipGraphLaunch(it->second, m->st) != hipSuccess && !m->sticky) m->sticky = MSOM_ERR_HIP;
+  return false;
 }
 
 void residual(msom *m, const double *a, const double *b, int slot, int want_sum) {
@@ -1546,11 +1553,12 @@ void residual2(msom *m, int mode, const double *b, int slot, int want_sum) {
 
 // max-residual slots (RES0, RES1) and the rhs sum (BSUM) -> host, reduced over the tiles
 // (the reference's foreach(reduction(max:maxres)) / reduction(+:sum) are MPI all-reduces)
-static int read_residuals(msom *m) {
+// published: k_step_dt copied the scalars to the host beside the speculative pass -- spin on its sequence word
+static int read_residuals(msom *m, bool published = false) {
   if (m->nranks == 1) {
     // one copy of the whole scalar block (sums, residuals, max|u|, the device's dt) and one wait
     if (m->dbg_nosync) return MSOM_OK;
-    if (m->spec_launched) {   // the scalars were published by k_step_dt in front of the speculative pass: spin on its sequence word
+    if (published) {
       volatile long *seq = reinterpret_cast<volatile long *>(m->h_pub + SC_COUNT);
       const double t0 = wall_seconds();
       while (*seq != m->pub_seq) {
@@ -1585,7 +1593,9 @@ static int read_residuals(msom *m) {
 // correction a += da is folded into the post-cycle residual (written to a second psi buffer
 // that then becomes psi), and the post-cycle pass only produces max|res|; the residual field
 // is regenerated only if another cycle turns out to be needed.
-static int mg_solve(msom *m, const double *b, msom_mgstats *s) {
+// sp: the tendency pass to queue behind the first cycle, before the host knows the residual (struct SpecPass); null: none
+static void spec_queue(msom *m, SpecPass *sp);
+static int mg_solve(msom *m, const double *b, msom_mgstats *s, SpecPass *sp = nullptr) {
   const Params &p = m->p;
   const bool fused = m->mg_fused && m->nlev > 1;
   s->i = 0; s->nrelax = 4;
@@ -1623,28 +1633,24 @@ static int mg_solve(msom *m, const double *b, msom_mgstats *s) {
     have_first = true;
   }
   for (s->i = 0; s->i < p.nitermax && (s->i < p.nitermin || s->resa > p.tolerance); s->i++) {
-    m->corr_req = corr_wanted(m);
-    m->corr_done = 0;
     // restrictions still to do: from level 1 (plain path), 2 (the residual pass restricted once) or 3 (twice; not when the residual
     // came out of the tendency pass, option rhs_resid)
-    mg_cycle(m, s->nrelax, fused ? ((restrict2_ok(m) && !(have_res && s->i == 0)) ? 3 : 2) : 1);
-    m->corr_req = 0;
+    const bool corr_done = mg_cycle(m, s->nrelax, fused ? ((restrict2_ok(m) && !(have_res && s->i == 0)) ? 3 : 2) : 1, corr_wanted(m));
     if (s->i > 0) HIPCHK(hipMemsetAsync(m->d_scal + SC_RES1, 0, sizeof(double), m->st));
-    if (m->corr_done) {  // a_new = a + da already sits in psi_alt (last smoother pass): boundary(a), then max |res|, max |u|
+    if (corr_done) {  // a_new = a + da already sits in psi_alt (last smoother pass): boundary(a), then max |res|, max |u|
       std::swap(m->f[MSOM_PSI], m->psi_alt);
       if (m->nranks > 1) STICKY(m, exch_nat(m, m->f[MSOM_PSI], m->nl, m->bc, 1));
       else if (m->bc == BC_PERIODIC) launch_fill_periodic(m->st, m->f[MSOM_PSI], m->g, m->nl, 1);
       else launch_fill_ghost(m->st, m->f[MSOM_PSI], m->g, m->nl, m->bc, m->walls);   // the LDS-DMA pass leaves the wall ghosts to this
       // option rhs_close: the speculative tendency pass queued below reads this psi anyway and forms max|res| (second stage: max|u|
       // too) on the side.  First stage: dt comes from max|u|, which therefore stays in front of the pass, from psi alone
-      const int cls = (s->i == 0 && m->spec_hook && m->nranks == 1) ? rhs_close_mode(m) : 0;
-      m->close_cls = !cls ? 0 : (m->dt_dev ? 1 : (cls >= 2 ? 2 : 0));
-      m->close_b = b;
-      if (m->close_cls == 2) {   // the pass accumulates into the block zeroed with the solve's scalars
+      const int mode = (s->i == 0 && sp && m->nranks == 1) ? rhs_close_mode(m) : 0, cls = !mode ? 0 : (sp->stage == 1 ? 1 : (mode >= 2 ? 2 : 0));
+      if (cls) { sp->pass.cls = cls; sp->pass.cls_b = b; }
+      if (cls == 2) {   // the pass accumulates into the block zeroed with the solve's scalars
         if (!m->umax_clean) HIPCHK(hipMemsetAsync(m->d_scal + SC_UMAX, 0, m->nl * sizeof(double), m->st));
         m->umax_clean = 0;
       }
-      else residual2(m, m->close_cls ? 8 | 16 : 8, b, SC_RES1, 0);
+      else residual2(m, cls ? 8 | 16 : 8, b, SC_RES1, 0);
       m->umax_ready = 1;
     } else if (fused) {
       residual2(m, 1, b, SC_RES1, 0);            // a_new = a + da -> psi_alt, max |res(a_new)|, max |u(a_new)|
@@ -1656,17 +1662,13 @@ static int mg_solve(msom *m, const double *b, msom_mgstats *s) {
       if (m->nranks > 1) STICKY(m, exch_nat(m, m->f[MSOM_PSI], m->nl, m->bc, 1));  // boundary(a)
       residual(m, m->f[MSOM_PSI], b, SC_RES1, 0);
     }
-    if (s->i == 0 && m->spec_hook && m->umax_ready && m->nranks == 1) {   // the tendency pass, queued before the host knows the residual
-      m->spec_hook([&]() {});
-      m->spec_launched = 1;
-    }
-    m->close_cls = 0;
-    int rr = read_residuals(m);
-    if (rr) { m->spec_launched = 0; return rr; }
-    if (m->spec_launched) {   // its output counts only if this solve ends here
+    const bool queued = s->i == 0 && sp && m->umax_ready && m->nranks == 1;
+    if (queued) spec_queue(m, sp);
+    int rr = read_residuals(m, queued);
+    if (rr) return rr;
+    if (queued) {   // its output counts only if this solve ends here
       const double ra = m->h_scal[SC_RES1];
-      m->spec_valid = !(s->i + 1 < p.nitermax && (s->i + 1 < p.nitermin || ra > p.tolerance));
-      m->spec_launched = 0;
+      sp->counts = !(s->i + 1 < p.nitermax && (s->i + 1 < p.nitermin || ra > p.tolerance));
     }
     if (!have_first) {
       resb = s->resb = m->h_scal[SC_RES0];
@@ -1694,26 +1696,14 @@ static int mg_solve(msom *m, const double *b, msom_mgstats *s) {
 }
 
 // invertq, msqg/qg.h:114-163 (the trailing boundary(pol) is already done by the correction)
-int invertq(msom *m, const double *q) {
-  if (m->mode_pv_invert) return helm_solve(m, q);
-  return mg_solve(m, q, &m->mg);
+int invertq(msom *m, const double *q, SpecPass *sp) {
+  if (m->mode_pv_invert) return helm_solve(m, q);   // (spec_ok: never with a pass to queue)
+  return mg_solve(m, q, &m->mg, sp);
 }
 
 // ------------------------------------------------------------------ RHS
 
-double limiter(msom *m, double umax, double dtmax) {
-  // timestep() [Basilisk; algorithm text newqg/qg.h:202-219]
-  const double D = m->p.L0 / m->gnx;
-  dtmax /= m->p.CFL;
-  if (umax != 0.) {
-    const double dt = D / umax;
-    if (dt < dtmax) dtmax = dt;
-  }
-  dtmax *= m->p.CFL;
-  if (dtmax > m->previous) dtmax = (m->previous + 0.1 * dtmax) / 1.1;
-  m->previous = dtmax;
-  return dtmax;
-}
+double limiter(msom *m, double umax, double dtmax) { return step_limit(umax, dtmax, m->p.L0 / m->gnx, m->p.CFL, &m->previous); }
 
 void comp_del2(msom *m, int in, int out, double add, double fac) {
   const double D = m->p.L0 / m->gnx;
@@ -1726,15 +1716,15 @@ void comp_stretch(msom *m, int in, int out, double add, double fac) {
   fill_bc(m, out);
 }
 
-// tendency terms after the inversion: comp_del2, advection_pv, dissip, ekman_friction,
-// surface_forcing, [qforcing], [bottom_topography]   (msqg/qg.h:622-630 / qg_bfn.h:67-76)
-// adv_out >= 0 asks for q[adv_out] = q[adv_in] + adv_dt * dq in the same pass (the corrector's
-// advance_qg); *advanced tells the caller whether that happened (fused path) or not.
+// tendency terms after the inversion, as struct RhsPass (msom_host.h) asks for them; ps.advanced tells the caller whether the
+// advance rode in the pass (fused path) or not.
 static int stoch_prepare(msom *m, double dt, double *dts);
-int rhs_terms(msom *m, int qfield, int dqfield, int with_qforcing, double iRe, double iRe4, double Eks, double Ekb, int adv_out,
-                     int adv_in, double adv_dt, int *advanced) {
-  if (advanced) *advanced = 0;
+int rhs_terms(msom *m, RhsPass &ps) {
+  ps.advanced = false;
   const Params &p = m->p;
+  const int qfield = ps.qfield, dqfield = ps.dqfield, with_qforcing = ps.with_qforcing, adv_in = ps.adv_in;
+  int adv_out = ps.adv_out;
+  const double iRe = p.iRe, iRe4 = p.iRe4, Eks = p.Eks, Ekb = p.Ekb, adv_dt = ps.adv_dt;
   const double D = p.L0 / m->gnx;
   const int nl = m->nl;
   // stochastic runs (msqg/qg_stochastic.h) ride in the same kernel when the advance does: the relaxation -q/tau and the
@@ -1755,13 +1745,13 @@ int rhs_terms(msom *m, int qfield, int dqfield, int with_qforcing, double iRe, d
     // the advance rides along: the pass can also emit the first residual of the inversion of q[adv_out]
     // (k_rhs_lpw's RES instantiation, or the LDS-tile kernel's): one tile with walls and even sides, one residual consumer per solve
     const int variant = m->rhs_variant;
-    const bool use_rr = adv_out >= 0 && rhs_resid_emits(m);
+    const bool use_rr = adv_out >= 0 && rhs_resid_emits(m, ps.emit_resid);
     RhsResid rr;
     if (use_rr) {
       rr.res = m->res[0]; rr.res_c = m->res[1]; rr.res_max = m->d_scal + SC_RESF; rr.bsum_partial = m->partial_rr;
       rr.sg = m->sg[0]; rr.cg = m->sg[1];
-      if (m->close_cls) {   // the speculative pass of mg_solve: max|res| of the solve that made psi, as k_resmax_march would leave it
-        rr.cls = m->close_cls; rr.cls_b = m->close_b; rr.cls_max = m->d_scal + SC_RES1; rr.cls_umax = m->d_scal + SC_UMAX;
+      if (ps.cls) {   // the speculative pass of mg_solve: max|res| of the solve that made psi, as k_resmax_march would leave it
+        rr.cls = ps.cls; rr.cls_b = ps.cls_b; rr.cls_max = m->d_scal + SC_RES1; rr.cls_umax = m->d_scal + SC_UMAX;
       }
     }
     // the psi halo exchange of a tile around the launch(es) of the pass; splittable: the kernel takes a region argument
@@ -1792,7 +1782,7 @@ int rhs_terms(msom *m, int qfield, int dqfield, int with_qforcing, double iRe, d
                        m->f[adv_out], adv_dt, 1, m->f[qfield], m->f[MSOM_NOISE], -adv_dt * p.itr_stoch, dts, region);
       });
       prof_end(m, m->prof_rhs);
-      if (advanced) *advanced = 1;
+      ps.advanced = true;
       return MSOM_OK;
     }
     prof_begin(m, m->prof_rhs);
@@ -1801,15 +1791,15 @@ int rhs_terms(msom *m, int qfield, int dqfield, int with_qforcing, double iRe, d
                        nullptr, m->g, nl, m->walls & WALL_ALL, m->uniformS, m->rc[0].S, with_qforcing && m->have_qforc, D, p.beta, iRe,
                        iRe4, Eks / (p.Rom * 2 * m->dhf[0]), Ekb / (p.Rom * 2 * m->dhf[nl - 1]),
                        p.sbc > 0 ? p.sbc / ((0.5 * p.sbc + 1) * D * D) : 0., m->lc, variant, adv_out >= 0 ? m->f[adv_in] : nullptr,
-                       adv_out >= 0 ? (m->adv_out_override ? m->adv_out_override : m->f[adv_out]) : nullptr, adv_dt, use_rr ? &rr : nullptr, region,
-                       variant == 6 ? m->dt_dev : nullptr);
+                       adv_out >= 0 ? (ps.out ? ps.out : m->f[adv_out]) : nullptr, adv_dt, use_rr ? &rr : nullptr, region,
+                       variant == 6 ? ps.dt_dev : nullptr);
     });
     prof_end(m, m->prof_rhs);
     if (use_rr) {
       m->res_ready = adv_out;
       m->rr_nparts = variant == 6 ? rhs_lpw_blocks(m->opt, m->g, nl) : rhs_pipe_blocks(m->g);
     }
-    if (advanced && adv_out >= 0) *advanced = 1;
+    ps.advanced = adv_out >= 0;
     return MSOM_OK;
   }
   HIPCHK(hipMemsetAsync(m->f[dqfield], 0, m->g.ls * nl * sizeof(double), m->st));  // updates = 0, msqg/qg.h:611-613
@@ -1836,42 +1826,19 @@ static int tracer_update(msom *m, int cfield);
 // advection_pv (:383-391): 2*nl limiter calls (psi_l then psipg_l) sharing one static
 // `previous`.  max|u| of psi comes out of the solver's last pass (k_residual2<CORRECT>), so dt
 // is known BEFORE the tendency pass and the advance can ride in it.
-// The same on the device, for the speculative tendency pass of the first RK stage: the 2 nl limiter calls of advection_pv
-// (timestep(), newqg/qg.h:202-219) on max|u| of psi (d_scal) and of psi_pg, then dtnext() of run().  Same operations in the
-// same order as limiter() / dtnext() on the host, no contraction, correctly rounded divisions: the same numbers.
+// The same on the device, for the speculative tendency pass of the first RK stage: the 2 nl limiter calls of advection_pv on
+// max|u| of psi (d_scal) and of psi_pg, then dtnext() of run() -- the functions of step_dt_inl.h that the host calls.
 // The kernel also PUBLISHES the scalar block to the host: 64 threads copy the 64 slots into coherent pinned memory, a system-scope
 // fence, then a sequence word the host spins on -- no copy command and no event between the residual pass and the tendency pass.
 struct StepDtArgs { double umax_pg[MSOM_MAXNL]; double D, CFL, previous, dtmax, t, tnext; int nl, with_dt; long seq; };
 __global__ void __launch_bounds__(64) k_step_dt(double *scal, StepDtArgs a, double *pub) {
-#pragma clang fp contract(off)
   if (threadIdx.x == 0 && a.with_dt) {
-  const double *umax = scal + SC_UMAX;
-  double *out = scal + SC_SPEC;
-  double dtmax = a.dtmax, previous = a.previous;
-  for (int k = 0; k < 2 * a.nl; k++) {
-    const double u = (k & 1) ? a.umax_pg[k >> 1] : umax[k >> 1];
-    dtmax /= a.CFL;
-    if (u != 0.) {
-      const double dt = a.D / u;
-      if (dt < dtmax) dtmax = dt;
-    }
-    dtmax *= a.CFL;
-    if (dtmax > previous) dtmax = (previous + 0.1 * dtmax) / 1.1;
-    previous = dtmax;
-  }
-  double dt = dtmax, tnext = a.tnext;
-  if (tnext != HUGE_VAL && tnext > a.t) {
-    const unsigned int n = (unsigned int)((tnext - a.t) / dt);
-    if (n == 0) dt = tnext - a.t;
-    else {
-      const double dt1 = (tnext - a.t) / n;
-      if (dt1 > dt * (1. + 1e-9)) dt = (tnext - a.t) / (n + 1);
-      else if (dt1 < dt) dt = dt1;
-      tnext = a.t + dt;
-    }
-  } else
-    tnext = a.t + dt;
-  out[0] = dtmax; out[1] = dt; out[2] = tnext; out[3] = dt / 2.;
+    const double *umax = scal + SC_UMAX;
+    double *out = scal + SC_SPEC;
+    double dtmax = a.dtmax, previous = a.previous, tnext;
+    for (int k = 0; k < 2 * a.nl; k++) dtmax = step_limit((k & 1) ? a.umax_pg[k >> 1] : umax[k >> 1], dtmax, a.D, a.CFL, &previous);
+    const double dt = step_dtnext(a.t, a.tnext, dtmax, &tnext);
+    out[0] = dtmax; out[1] = dt; out[2] = tnext; out[3] = dt / 2.;
   }
   __syncthreads();
   if (pub) {
@@ -1883,11 +1850,35 @@ __global__ void __launch_bounds__(64) k_step_dt(double *scal, StepDtArgs a, doub
 }
 static_assert(SC_COUNT == 64, "k_step_dt publishes one slot per thread");
 
-static double solve_and_dt(msom *m, int qfield, double dtmax) {
+// mg_solve's speculative pass: the tendency pass sp->pass and, beside it, k_step_dt.  Stage 1: the kernel computes dt in front of the
+// pass, which reads it from the device.  Either stage: the kernel publishes the scalars in front of the pass, or -- the pass closes the
+// solve (cls: max|res|, stage 2 max|u| too, come out of it) -- behind it
+static void spec_queue(msom *m, SpecPass *sp) {
+  const Params &p = m->p;
+  const bool closes = sp->pass.cls != 0;
+  StepDtArgs a;
+  memset(&a, 0, sizeof a);
+  if (sp->stage == 1) {
+    for (int l = 0; l < MSOM_MAXNL; l++) a.umax_pg[l] = m->umax_pg[l];
+    a.D = p.L0 / m->gnx; a.CFL = p.CFL; a.previous = m->previous; a.dtmax = p.DT; a.t = m->t; a.tnext = m->tnext; a.nl = m->nl;
+    a.with_dt = 1;
+  }
+  a.seq = ++m->pub_seq;
+  if (a.with_dt || !closes) hipLaunchKernelGGL(k_step_dt, dim3(1), dim3(64), 0, m->st, m->d_scal, a, closes ? nullptr : m->d_pub);
+  sp->rc = rhs_terms(m, sp->pass);
+  if (!sp->pass.advanced && !sp->rc) sp->rc = MSOM_ERR_STATE;
+  if (closes) {
+    a.with_dt = 0;
+    hipLaunchKernelGGL(k_step_dt, dim3(1), dim3(64), 0, m->st, m->d_scal, a, m->d_pub);
+  }
+  sp->launched = true;
+}
+
+// sp: see mg_solve.  Where its pass counts in the first RK stage, the device has run the limiter as well
+static double solve_and_dt(msom *m, int qfield, double dtmax, SpecPass *sp = nullptr) {
   const int nl = m->nl;
-  m->spec_valid = 0;
-  if (invertq(m, m->f[qfield])) return -1;
-  if (m->spec_valid && m->dt_dev) {   // the device ran the limiter (first RK stage): adopt its state
+  if (invertq(m, m->f[qfield], sp)) return -1;
+  if (sp && sp->counts && sp->stage == 1) {   // adopt its state
     m->previous = m->h_scal[SC_SPEC];
     return m->h_scal[SC_SPEC];
   }
@@ -1905,11 +1896,11 @@ static double solve_and_dt(msom *m, int qfield, double dtmax) {
 
 // update_qg, msqg/qg.h:609-650
 static double update_qg(msom *m, int qfield, int dqfield, double dtmax) {
-  const Params &p = m->p;
   dtmax = solve_and_dt(m, qfield, dtmax);
   if (dtmax < 0) return -1;
-  if (rhs_terms(m, qfield, dqfield, 1, p.iRe, p.iRe4, p.Eks, p.Ekb)) return -1;
-  if (p.nptr > 0 && tracer_update(m, qfield == MSOM_QPRED ? MSOM_PTR_PRED : MSOM_PTR)) return -1;
+  RhsPass ps{qfield, dqfield, 1};
+  if (rhs_terms(m, ps)) return -1;
+  if (m->p.nptr > 0 && tracer_update(m, qfield == MSOM_QPRED ? MSOM_PTR_PRED : MSOM_PTR)) return -1;
   return dtmax;
 }
 
@@ -2053,6 +2044,14 @@ int check_shape(msom *m, int a, int b, int c) {
   return MSOM_OK;
 }
 
+// the signs of the dissipation and of the drag for an integration forward (direction > 0) or backward in time, msqg/qg_bfn.h:30-41
+static void bfn_direction(Params &p, double direction) {
+  const double s = direction > 0 ? 1 : -1;
+  p.iRe = p.Re == 0 ? 0. : s / p.Re;
+  p.iRe4 = p.Re4 == 0 ? 0. : -s / p.Re4;
+  p.Eks = s * fabs(p.Eks); p.Ekb = s * fabs(p.Ekb);
+}
+
 // msqg/qg_bfn.h:21-80
 extern "C" int pystep_bfn(msom_t *m, double *varin_py, int len1, int len2, int len3, double *tend_py, int len4, int len5, int len6,
                           double direction, int vartype) {
@@ -2062,20 +2061,13 @@ extern "C" int pystep_bfn(msom_t *m, double *varin_py, int len1, int len2, int l
   if (check_shape(m, len1, len2, len3) || check_shape(m, len4, len5, len6)) return MSOM_ERR_ARG;
   Params &p = m->p;
   int r;
-  if (direction > 0) {
-    p.iRe = p.Re == 0 ? 0. : 1 / p.Re;
-    p.iRe4 = p.Re4 == 0 ? 0. : -1 / p.Re4;
-    p.Eks = fabs(p.Eks); p.Ekb = fabs(p.Ekb);
-  } else {
-    p.iRe = p.Re == 0 ? 0. : -1 / p.Re;
-    p.iRe4 = p.Re4 == 0 ? 0. : 1 / p.Re4;
-    p.Eks = -fabs(p.Eks); p.Ekb = -fabs(p.Ekb);
-  }
+  bfn_direction(p, direction);
   if (vartype != 1) HIPCHK(hipMemsetAsync(m->f[MSOM_DQ], 0, m->g.ls * m->nl * sizeof(double), m->st));  // reset_layer_var(bfn_tendl)
   if (vartype == 1) {
     if ((r = upload(m, MSOM_Q, varin_py))) return r;
     if (solve_and_dt(m, MSOM_Q, p.DT) < 0) return MSOM_ERR_HIP;  // invertq + the dt limiter inside advection_pv
-    if ((r = rhs_terms(m, MSOM_Q, MSOM_DQ, 0, p.iRe, p.iRe4, p.Eks, p.Ekb))) return r;
+    RhsPass ps{MSOM_Q, MSOM_DQ, 0};
+    if ((r = rhs_terms(m, ps))) return r;
   } else if (!m->quiet)
     fprintf(stdout, "temporary disabled psi tendency\n");  // msqg/qg_bfn.h:48
   return download(m, MSOM_DQ, tend_py);
@@ -2127,25 +2119,17 @@ extern "C" int msom_bfn_steps(msom_t *m, int nsteps, double dt, double direction
   if (nsteps == 0) return MSOM_OK;
   Params &p = m->p;
   int r;
-  if (direction > 0) {   // msqg/qg_bfn.h:30-41, as pystep_bfn
-    p.iRe = p.Re == 0 ? 0. : 1 / p.Re;
-    p.iRe4 = p.Re4 == 0 ? 0. : -1 / p.Re4;
-    p.Eks = fabs(p.Eks); p.Ekb = fabs(p.Ekb);
-  } else {
-    p.iRe = p.Re == 0 ? 0. : -1 / p.Re;
-    p.iRe4 = p.Re4 == 0 ? 0. : 1 / p.Re4;
-    p.Eks = -fabs(p.Eks); p.Ekb = -fabs(p.Ekb);
-  }
+  bfn_direction(p, direction);   // as pystep_bfn
   const double dt12 = dt / 12;
   const double *obs = k != 0 ? m->f[MSOM_BFN_OBS] : nullptr, *gain = (k != 0 && m->bfn_gain_set) ? m->f[MSOM_BFN_GAIN] : nullptr;
   for (int n = 0; n < nsteps; n++) {
     if (solve_and_dt(m, MSOM_Q, p.DT) < 0) return m->sticky ? m->sticky : MSOM_ERR_HIP;  // invertq + the dt limiter inside advection_pv
-    if ((r = rhs_terms(m, MSOM_Q, MSOM_BFN_F1, 0, p.iRe, p.iRe4, p.Eks, p.Ekb))) return r;   // the tendency goes straight into the F1 slot
+    RhsPass ps{MSOM_Q, MSOM_BFN_F1, 0};   // the tendency goes straight into the F1 slot
+    if ((r = rhs_terms(m, ps))) return r;
     launch_bfn_ab3(m->st, m->f[MSOM_Q], m->f[MSOM_BFN_F1], m->f[MSOM_BFN_F2], m->f[MSOM_BFN_F3], obs, gain, m->g, m->nl, dt12, k);
     fill_bc(m, MSOM_Q);    // boundary(q), as upload does after its pack
     m->res_ready = -1;     // what the handle caches from q
     m->umax_ready = 0;
-    m->spec_valid = 0;
     double *f1 = m->f[MSOM_BFN_F1];   // F3 = F2; F2 = F1 (:72-73) as a rotation of the slots
     m->f[MSOM_BFN_F1] = m->f[MSOM_BFN_F3];
     m->f[MSOM_BFN_F3] = m->f[MSOM_BFN_F2];
@@ -2169,23 +2153,7 @@ extern "C" int msom_bfn_misfit(msom_t *m, double *misfit) {
 
 // ------------------------------------------------------------------ time loop
 
-// dtnext() [Basilisk, SURVEY App. B]
-double dtnext(msom *m, double dt, double *tnext_out) {
-  double tnext = m->tnext, t = m->t;
-  if (tnext != HUGE_VAL && tnext > t) {
-    unsigned int n = (unsigned int)((tnext - t) / dt);
-    if (n == 0) dt = tnext - t;
-    else {
-      double dt1 = (tnext - t) / n;
-      if (dt1 > dt * (1. + 1e-9)) dt = (tnext - t) / (n + 1);
-      else if (dt1 < dt) dt = dt1;
-      tnext = t + dt;
-    }
-  } else
-    tnext = t + dt;
-  *tnext_out = tnext;
-  return dt;
-}
+double dtnext(msom *m, double dt, double *tnext_out) { return step_dtnext(m->t, m->tnext, dt, tnext_out); }
 
 // tracer part of update_qg (msqg/qg.h:634-647): dpdt = ptr_rhs(tracers, psi) with `updates` zeroed
 static int tracer_update(msom *m, int cfield) {
@@ -2213,92 +2181,63 @@ static bool spec_ok(const msom *m) {
          m->nl <= MSOM_FASTNL && !m->have_pg && !m->have_zpg && !m->flag_topo && !m->stochastic && m->p.nptr == 0 && m->p.nitermin >= 1 && !m->dbg_nosync;
 }
 
+// One RK stage of msom_step: the solve with the stage's tendency + advance pass queued behind its first cycle (spec: struct
+// SpecPass), the same pass afterwards where that one does not count, then the tracers.
+//   stage 1: q -> psi, dt = dtnext(limiter), predictor = q + dt/2 dq; speculatively with dt computed and read on the device
+//   stage 2: predictor -> psi, q += dt dq; speculatively into q_alt, which becomes q only if the solve ended after its first cycle
+static int rk_stage(msom *m, int stage, bool spec, double *tnext) {
+  const bool first = stage == 1;
+  const int qf = first ? MSOM_Q : MSOM_QPRED, out = first ? MSOM_QPRED : MSOM_Q;
+  RhsPass ps{qf, MSOM_DQ, 1, out, MSOM_Q};
+  SpecPass sp{stage, ps};
+  if (first) sp.pass.dt_dev = m->d_scal + SC_SPEC + 3;
+  else { sp.pass.adv_dt = m->dt; sp.pass.out = m->q_alt; }
+  const double d = solve_and_dt(m, qf, first ? m->p.DT : m->dt, spec ? &sp : nullptr);
+  const bool hit = spec && sp.counts && !sp.rc;
+  // a speculative pass may have emitted the next solve's first residual (rhs_resid): it counts only with the pass itself.  Discarded:
+  // the solve went on and regenerated res[0], res[1] behind it; the re-run below emits them again.  Kept in stage 2: the residual
+  // of q_alt, which is q from here on, is what the next step's first solve is handed
+  if (!hit) m->res_ready = -1;
+  if (d < 0) return m->sticky ? m->sticky : MSOM_ERR_HIP;
+  if (first) {
+    if (hit) {   // the device's dtnext
+      m->dt = m->h_scal[SC_SPEC + 1];
+      *tnext = m->h_scal[SC_SPEC + 2];
+    } else
+      m->dt = dtnext(m, d, tnext);
+  } else if (hit)
+    std::swap(m->f[MSOM_Q], m->q_alt);
+  const double adv_dt = first ? m->dt / 2. : m->dt;
+  int r;
+  if (!hit) {
+    ps.adv_dt = adv_dt;
+    if ((r = rhs_terms(m, ps))) return r;
+    if (!ps.advanced && (r = advance_qg(m, out, MSOM_Q, MSOM_DQ, adv_dt))) return r;
+  }
+  // option "stats": one sample of (q_n, psi_n = what the first inversion left, dt_n) before stage 2 overwrites psi.  Queued behind the
+  // stage's tendency pass; on the speculative path the weight is the device scalar k_step_dt wrote (no host value is waited for)
+  if (first && m->stats_on && m->stats_count++ % m->stats_every == 0) {
+    stats_sample(m, hit ? m->d_scal + SC_SPEC + 1 : nullptr, m->dt);
+    m->stats_ndev += hit;
+  }
+  if (m->p.nptr > 0 && ((r = tracer_update(m, first ? MSOM_PTR : MSOM_PTR_PRED)) || (r = tracer_advance(m, first ? MSOM_PTR_PRED : MSOM_PTR, MSOM_PTR, adv_dt))))
+    return r;
+  return MSOM_OK;
+}
+
 extern "C" int msom_step(msom_t *m, double *dt_used) {
   if (m && m->model) return nq_step(m, dt_used);
   NEED_CONST(m);
   if (m->stats_on && !m->stats_mask) { msom_set_error("msom_step: option stats = 1 and no msom_stats_begin since msom_set_const"); return MSOM_ERR_STATE; }
-  const Params &p = m->p;
   double tnext;
-  int r, advanced = 0;
+  int r;
   const bool spec = spec_ok(m);
-  int spec_rc = 0;
-  if (spec) {   // stage 1: dt on the device, predictor = q + dt/2 dq
-    m->dt_dev = m->d_scal + SC_SPEC + 3;
-    m->spec_hook = [&](const std::function<void()> &host_read) {
-      StepDtArgs a;
-      for (int l = 0; l < MSOM_MAXNL; l++) a.umax_pg[l] = m->umax_pg[l];
-      a.D = p.L0 / m->gnx; a.CFL = p.CFL; a.previous = m->previous; a.dtmax = p.DT; a.t = m->t; a.tnext = m->tnext; a.nl = m->nl;
-      a.with_dt = 1; a.seq = ++m->pub_seq;
-      // (rhs_close: max|res| comes out of the pass, so the scalars are published behind it)
-      hipLaunchKernelGGL(k_step_dt, dim3(1), dim3(64), 0, m->st, m->d_scal, a, m->close_cls ? nullptr : m->d_pub);
-      host_read();
-      int adv = 0;
-      spec_rc = rhs_terms(m, MSOM_Q, MSOM_DQ, 1, p.iRe, p.iRe4, p.Eks, p.Ekb, MSOM_QPRED, MSOM_Q, 0., &adv);
-      if (!adv && !spec_rc) spec_rc = MSOM_ERR_STATE;
-      if (m->close_cls) {
-        a.with_dt = 0;
-        hipLaunchKernelGGL(k_step_dt, dim3(1), dim3(64), 0, m->st, m->d_scal, a, m->d_pub);
-      }
-    };
+  if ((r = rk_stage(m, 1, spec, &tnext))) return r;
+  if (spec && !m->q_alt) {   // pads and ghost cells as q has them: the pass writes interior cells only
+    HIPCHK(hipMalloc(&m->q_alt, m->g.ls * m->nl * sizeof(double)));
+    HIPCHK(hipMemcpyAsync(m->q_alt, m->f[MSOM_Q], m->g.ls * m->nl * sizeof(double), hipMemcpyDeviceToDevice, m->st));
   }
-  const double d = solve_and_dt(m, MSOM_Q, p.DT);
-  m->spec_hook = nullptr;
-  const bool hit1 = spec && m->spec_valid && !spec_rc;
-  m->dt_dev = nullptr;
-  // a speculative pass may have emitted the next solve's first residual (rhs_resid): it counts only with the pass itself.  Discarded:
-  // the solve went on and regenerated res[0], res[1] behind it; the re-run below emits them again
-  if (!hit1) m->res_ready = -1;
-  if (d < 0) return m->sticky ? m->sticky : MSOM_ERR_HIP;
-  if (hit1) {
-    m->dt = m->h_scal[SC_SPEC + 1];
-    tnext = m->h_scal[SC_SPEC + 2];
-  } else {
-    m->dt = dtnext(m, d, &tnext);
-    if ((r = rhs_terms(m, MSOM_Q, MSOM_DQ, 1, p.iRe, p.iRe4, p.Eks, p.Ekb, MSOM_QPRED, MSOM_Q, m->dt / 2., &advanced))) return r;
-    if (!advanced && (r = advance_qg(m, MSOM_QPRED, MSOM_Q, MSOM_DQ, m->dt / 2.))) return r;
-  }
-  // option "stats": one sample of (q_n, psi_n = what the first inversion left, dt_n) before stage 2 overwrites psi.  Queued behind the
-  // stage's tendency pass; on the speculative path the weight is the device scalar k_step_dt wrote (no host value is waited for)
-  if (m->stats_on && m->stats_count++ % m->stats_every == 0) {
-    stats_sample(m, hit1 ? m->d_scal + SC_SPEC + 1 : nullptr, m->dt);
-    m->stats_ndev += hit1;
-  }
-  const bool tracers = m->p.nptr > 0;
-  if (tracers && ((r = tracer_update(m, MSOM_PTR)) || (r = tracer_advance(m, MSOM_PTR_PRED, MSOM_PTR, m->dt / 2.)))) return r;
-  spec_rc = 0;
-  if (spec) {   // stage 2: dt is known; q + dt dq goes to a spare buffer that replaces q only if the solve ends after its first cycle
-    if (!m->q_alt) {   // pads and ghost cells as q has them: the pass writes interior cells only
-      HIPCHK(hipMalloc(&m->q_alt, m->g.ls * m->nl * sizeof(double)));
-      HIPCHK(hipMemcpyAsync(m->q_alt, m->f[MSOM_Q], m->g.ls * m->nl * sizeof(double), hipMemcpyDeviceToDevice, m->st));
-    }
-    m->spec_hook = [&](const std::function<void()> &host_read) {
-      StepDtArgs a;
-      memset(&a, 0, sizeof a);
-      a.with_dt = 0; a.seq = ++m->pub_seq;
-      // publish only: in front of the pass, or (rhs_close: max|res| and max|u| come out of the pass) behind it
-      if (!m->close_cls) hipLaunchKernelGGL(k_step_dt, dim3(1), dim3(64), 0, m->st, m->d_scal, a, m->d_pub);
-      host_read();
-      int adv = 0;
-      m->adv_out_override = m->q_alt;
-      spec_rc = rhs_terms(m, MSOM_QPRED, MSOM_DQ, 1, p.iRe, p.iRe4, p.Eks, p.Ekb, MSOM_Q, MSOM_Q, m->dt, &adv);
-      m->adv_out_override = nullptr;
-      if (!adv && !spec_rc) spec_rc = MSOM_ERR_STATE;
-      if (m->close_cls) hipLaunchKernelGGL(k_step_dt, dim3(1), dim3(64), 0, m->st, m->d_scal, a, m->d_pub);
-    };
-  }
-  const double d2 = solve_and_dt(m, MSOM_QPRED, m->dt);
-  m->spec_hook = nullptr;
-  if (d2 < 0) return m->sticky ? m->sticky : MSOM_ERR_HIP;
-  const bool rr2 = m->res_ready == MSOM_Q;   // the speculative pass emitted the residual of what it wrote, and that is q_alt
-  m->res_ready = -1;
-  if (spec && m->spec_valid && !spec_rc) {
-    std::swap(m->f[MSOM_Q], m->q_alt);
-    if (rr2) m->res_ready = MSOM_Q;   // q_alt is q now: what the next step's first solve is handed
-  } else {
-    if ((r = rhs_terms(m, MSOM_QPRED, MSOM_DQ, 1, p.iRe, p.iRe4, p.Eks, p.Ekb, MSOM_Q, MSOM_Q, m->dt, &advanced))) return r;
-    if (!advanced && (r = advance_qg(m, MSOM_Q, MSOM_Q, MSOM_DQ, m->dt))) return r;
-  }
-  if (tracers && ((r = tracer_update(m, MSOM_PTR_PRED)) || (r = tracer_advance(m, MSOM_PTR, MSOM_PTR, m->dt)))) return r;
+  if ((r = rk_stage(m, 2, spec, &tnext))) return r;
   // With the speculative tendency pass the host already follows the GPU solve by solve (it waits for the published residual of every
   // solve) and everything it returns -- dt, t -- is known: with step_sync = 0 the last tendency pass is left running and the next step's
   // launches queue up behind it (every call that hands device data to the host synchronises the stream itself, msom_sync on request)

@@ -172,7 +172,6 @@ int helm_solve(msom *m, const double *q) {
   if (r) return r;
   m->res_ready = -1;
   m->umax_ready = 0;
-  m->spec_valid = 0;
   if ((r = helm_project(m, q, m->helm_qm, 1))) return r;
   if ((r = helm_run(m, m->helm_pm, m->helm_qm))) return r;
   m->helm_solved = 1;

@@ -35,7 +35,7 @@ extern "C" int msom_dbg_relax(msom_t *m, int lev, double *da, const double *res,
   m->profile = 0;
   {
     Lev L = tile_lev(m, lev);
-    relax_sweeps(m, L, nullptr, nsweeps, 0);
+    relax_sweeps(m, L, nullptr, nsweeps, 0, false);
   }
   m->profile = prof;
   return split_download(m, m->da[lev], m->sg[lev], da, m->nl);
@@ -48,15 +48,13 @@ extern "C" int msom_dbg_rhs_resid(msom_t *m, int fused, double dt, double *res0,
   if (m) m->res_ready = -1;
   NEED_CONST(m);
   if (!res0 || !res1 || m->nlev < 2) return MSOM_ERR_ARG;
-  const Params &p = m->p;
   for (int k = 0; k < 2; k++) HIPCHK(hipMemsetAsync(m->res[k], 0xFF, m->sg[k].ls * m->nl * sizeof(double), m->st));
   HIPCHK(hipMemsetAsync(m->d_scal, 0, (SC_UMAX + MSOM_MAXNL) * sizeof(double), m->st));
-  const int keep = m->rhs_resid;
-  m->rhs_resid = fused ? 1 : 0;
-  int adv = 0;
-  int r = rhs_terms(m, MSOM_Q, MSOM_DQ, 1, p.iRe, p.iRe4, p.Eks, p.Ekb, MSOM_QPRED, MSOM_Q, dt, &adv);
-  m->rhs_resid = keep;
+  RhsPass ps{MSOM_Q, MSOM_DQ, 1, MSOM_QPRED, MSOM_Q, dt};
+  ps.emit_resid = fused ? 1 : 0;
+  int r = rhs_terms(m, ps);
   if (r) return r;
+  const bool adv = ps.advanced;
   const bool emitted = m->res_ready == MSOM_QPRED;
   m->res_ready = -1;
   if (!adv || (fused && !emitted)) { msom_set_error("msom_dbg_rhs_resid: this handle's tendency pass does not %s", adv ? "emit the residual" : "advance"); return MSOM_ERR_CONFIG; }
@@ -256,7 +254,8 @@ extern "C" int msom_bench_kernel(msom_t *m, const char *kernel, int reps, double
     } else if (!strcmp(kernel, "block2p")) {
       launch_relax_block2(m->st, m->opt, m->da[0], m->da[1], m->sg[1], m->res[0], m->da_alt[0], m->sg[0], m->nl, m->rc[0], m->walls, 1);
     } else if (!strcmp(kernel, "rhs")) {
-      rhs_terms(m, MSOM_Q, MSOM_DQ, 1, m->p.iRe, m->p.iRe4, m->p.Eks, m->p.Ekb);
+      RhsPass ps{MSOM_Q, MSOM_DQ, 1};
+      rhs_terms(m, ps);
     } else if (!strcmp(kernel, "resid_correct")) {
       residual2(m, 1, m->f[MSOM_Q], SC_RES1, 0);
     } else if (!strcmp(kernel, "resid_restrict")) {
@@ -264,8 +263,8 @@ extern "C" int msom_bench_kernel(msom_t *m, const char *kernel, int reps, double
     } else if (!strcmp(kernel, "red_prolong")) {
       launch_relax_red_prolong(m->st, m->opt, m->da[0], m->da[1], m->sg[1], m->res[0], m->S[0], m->sg[0], m->nl, m->rc[0], m->uniformS, m->walls);
     } else if (!strcmp(kernel, "rhs_adv")) {
-      int adv = 0;
-      rhs_terms(m, MSOM_Q, MSOM_DQ, 1, m->p.iRe, m->p.iRe4, m->p.Eks, m->p.Ekb, MSOM_QPRED, MSOM_Q, 1e-9, &adv);
+      RhsPass ps{MSOM_Q, MSOM_DQ, 1, MSOM_QPRED, MSOM_Q, 1e-9};
+      rhs_terms(m, ps);
     } else if (!strcmp(kernel, "advance")) {
       launch_advance(m->st, m->f[MSOM_QPRED], m->f[MSOM_Q], m->f[MSOM_DQ], nullptr, m->g, m->nl, 1e-9, 0.);
     } else if (!strcmp(kernel, "modes_project")) {   // in place on the staging buffer, in the form the handle holds

@@ -16,7 +16,6 @@
 #include <cmath>
 #include <string>
 #include <utility>
-#include <functional>
 #include <map>
 #include <vector>
 
@@ -64,25 +63,14 @@ struct msom {
   int comm_hold = 0;     // see comm_begin
   int dbg_nosync = 0;    // option dbg_nosync (timing experiment)
   KernelOpts opt;        // options that pick kernel variants and launch shapes (kernels.h)
-  // Speculative tendency pass (round 3, one tile): right after the first multigrid cycle of a solve the tendency kernel is queued
-  // BEFORE the host has read max|res| and max|u| -- with dt computed on the device (k_step_dt) in the first RK stage -- so the
-  // GPU works through the host round trip instead of idling (0.49 -> 0.43 ms per step at 256^2 x 3 with the read skipped
-  // altogether, tools/ab_nosync.py).  If the solve turns out to need another cycle the pass is simply run again afterwards:
-  // its output went to the predictor (stage 1) or to a spare buffer that only replaces q when the solve had converged (stage 2).
-  int async_solve = 1;               // option
+  int async_solve = 1;               // option: msom_step queues its tendency passes speculatively (struct SpecPass below)
   int step_sync = -1;                // option: 0 = msom_step returns without waiting for its last tendency pass (async_solve only; with rhs_close = 2
                                      // that pass carries the solve's closing residual and the host has waited for it anyway), 1 = it waits,
                                      // -1 (default) = it waits on grids of >= 2^23 cell-layers.  Measured (same process): 128^2 x 1 0.203 -> 0.185 ms per
                                      // step, 512^2 x 3 0.374 -> 0.352, 2048^2 x 3 1.238 -> 1.226, 4096^2 x 6 6.15 -> 6.20 (worse)
-  std::function<void(const std::function<void()> &)> spec_hook;   // queued by mg_solve after the first cycle's residual pass; calls its
-                                     // argument (the host's read of the scalars) between the dt kernel and the tendency pass
-  int spec_launched = 0, spec_valid = 0;
-  hipEvent_t ev_spec = nullptr;
   double *h_pub = nullptr, *d_pub = nullptr;   // coherent pinned host block the device publishes the scalars into (+ a sequence word), and its device address
   long pub_seq = 0;
   double *q_alt = nullptr;           // stage 2 writes q + dt dq here
-  double *adv_out_override = nullptr;
-  const double *dt_dev = nullptr;
   int nb[8];  // neighbour ranks by direction (DIR_*), -1 = none
   int nl = 1, nlm = 1;
   int bc = BC_DIRICHLET0;
@@ -146,7 +134,6 @@ struct msom {
   int march_min_tiled = 22;  // the same threshold on tiles (see sweep_path)
   int march_min = 23;    // log2 of the cell-layers a level needs for the chained pass (2^23: 2048^2 x 3 1.83 -> 1.78 ms/step, and the 2048 x 1024 x 6 tiles of BASELINE's 2 x 4 layout qualify; 2^22 loses: 1024^2 x 6 2.76 -> 2.87)
   int march_correct = 1; // the last pass of the finest level writes psi + da instead of da (psi rows by LDS-DMA, deferred write): 7.02 -> 6.86 ms per step at 4096^2 x 6
-  int corr_req = 0, corr_done = 0;  // set around mg_cycle_levels by mg_solve / by the pass that did it
   int march_visit = 1;   // the finest level's visit (PL + 4, 4 + correction) in one launch on its interior chunks (k_relax_visit);
                          // 1: on levels of at least 2^march_visit_min cell-layers, 2: wherever it applies (tests)
   int march_visit_min = 25;  // 4096^2 x 6: 1.01 -> 0.87 ms per visit; 2048^2 x 3 (2^23.6) loses: 0.17 -> 0.21 ms (too few chunks to hide latency)
@@ -181,8 +168,6 @@ struct msom {
   int rr_nparts = 0;   // partial sums of q_out the last such pass wrote
   int rhs_close = -1;  // the speculative tendency pass also closes the solve in front of it (k_rhs_lpw CLS, max|res| of the solve's b) in place of
                        // k_resmax_march: 0 never, 1 first RK stage (a psi-only max|u| pass stays), 2 both stages, -1 = where it measurably wins
-  int close_cls = 0;   // set by mg_solve around its call of spec_hook: the CLS form this speculative pass takes (nothing outlives the solve)
-  const double *close_b = nullptr;   // ... and the solve's right-hand side
   // back-and-forth nudging loop on the device (msom_bfn_*)
   int bfn_begun = 0;                      // msom_bfn_begin since the last msom_set_const
   int bfn_obs_set = 0, bfn_gain_set = 0;  // MSOM_BFN_OBS / MSOM_BFN_GAIN came in through msom_set_field (gain never set: 1 everywhere)
@@ -253,6 +238,34 @@ struct msom {
   ProfSlot prof_rhs, prof_redprol, prof_rescorr, prof_respre;   // tendency pass, finest red+prolongation, post- / pre-cycle residual passes
 };
 
+// ---- what travels with one call (nothing of it is kept on the handle)
+// One tendency pass as rhs_terms is asked for it: comp_del2, advection_pv, dissip, ekman_friction, surface_forcing, [qforcing],
+// [bottom_topography] (msqg/qg.h:622-630 / qg_bfn.h:67-76) with the coefficients iRe, iRe4, Eks, Ekb of m->p.
+struct RhsPass {
+  int qfield, dqfield, with_qforcing;
+  int adv_out = -1, adv_in = -1;     // adv_out >= 0 asks for q[adv_out] = q[adv_in] + adv_dt * dq in the same pass (the corrector's advance_qg)
+  double adv_dt = 0.;
+  double *out = nullptr;             // written in place of f[adv_out]
+  const double *dt_dev = nullptr;    // adv_dt is read from this device scalar instead (k_rhs_lpw only)
+  int cls = 0;                       // the pass closes the solve that made psi (k_rhs_lpw CLS): 1 max|res|, 2 max|res| and max|u|, as
+  const double *cls_b = nullptr;     // k_resmax_march would leave them; cls_b: that solve's right-hand side
+  int emit_resid = -1;               // the first residual of the inversion of q[adv_out] as a by-product: -1 as option rhs_resid says, 1, 0
+  bool advanced = false;             // result: the advance did ride in the pass (else the caller runs advance_qg)
+};
+// Speculative tendency pass (one tile): right after the first multigrid cycle of a solve the tendency kernel is queued BEFORE the
+// host has read max|res| and max|u| -- with dt computed on the device (k_step_dt) in the first RK stage -- so the GPU works through
+// the host round trip instead of idling (0.49 -> 0.43 ms per step at 256^2 x 3 with the read skipped altogether,
+// tools/ab_nosync.py).  If the solve turns out to need another cycle the pass is simply run again afterwards: its output went to
+// the predictor (stage 1) or to a spare buffer that only replaces q when the solve had converged (stage 2).
+// mg_solve, invertq and solve_and_dt take a pointer to this description of what to queue; null: nothing.
+struct SpecPass {
+  int stage;               // 1: dt on the device (k_step_dt in front of the pass); 2: dt known, output to q_alt
+  RhsPass pass;
+  bool launched = false;   // results: the pass was queued,
+  int rc = MSOM_OK;        // ... what rhs_terms returned,
+  bool counts = false;     // ... and the solve ended after that cycle: the output of the pass stands
+};
+
 // slots of the modal solve's device scalar block (helm_scal): max |res_m| before the first cycle, after the last one, sum of q_m
 enum { HS_RES0 = 0, HS_RES1 = MSOM_MAXNL, HS_BSUM = 2 * MSOM_MAXNL, HS_COUNT = 3 * MSOM_MAXNL };
 
@@ -315,15 +328,14 @@ int upload(msom *m, int field, const double *a);
 int download(msom *m, int field, double *a);
 int build_coefs(msom *m);
 Lev tile_lev(const msom *m, int k);
-void relax_sweeps(msom *m, Lev &L, const Lev *coarse, int nrelax, int corners_last);
+bool relax_sweeps(msom *m, Lev &L, const Lev *coarse, int nrelax, int corners_last, bool corr_req);
 void residual(msom *m, const double *a, const double *b, int slot, int want_sum);
 void residual2(msom *m, int mode, const double *b, int slot, int want_sum);
-int invertq(msom *m, const double *q);
+int invertq(msom *m, const double *q, SpecPass *sp = nullptr);
 double limiter(msom *m, double umax, double dtmax);
 void comp_del2(msom *m, int in, int out, double add, double fac);
 void comp_stretch(msom *m, int in, int out, double add, double fac);
-int rhs_terms(msom *m, int qfield, int dqfield, int with_qforcing, double iRe, double iRe4, double Eks, double Ekb, int adv_out = -1,
-              int adv_in = -1, double adv_dt = 0., int *advanced = nullptr);
+int rhs_terms(msom *m, RhsPass &ps);
 int check_shape(msom *m, int a, int b, int c);
 double dtnext(msom *m, double dt, double *tnext_out);
 // msom_helm.hip

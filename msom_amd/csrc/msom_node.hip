@@ -5,6 +5,7 @@
 // comp_q :199-211, invert_q :217-225, init :449-510), qg_barotropic.h and the nodal multigrid
 // vpoisson (nodal-poisson.h:19-143) on top of the kernels of kernels_node.hip.  No CPU fallback.
 #include "msomn_host.h"
+#include "step_dt_inl.h"
 
 static void nprof_begin(msomn *m, int slot) {
   if (!m->profile) return;
@@ -845,13 +846,7 @@ static int adjust_dt(msomn *m, double dtmax, double *out) {
   // (tiles: a face on a shared edge is seen by both tiles, the maximum does not mind)
   int r = nt_reduce(m, NSC_UMAX, 1, RED_MAX);
   if (r) return r;
-  const double um = m->h_scal[NSC_UMAX];
-  dtmax /= m->p.CFL;
-  if (um != 0.) { const double dt = m->D / um; if (dt < dtmax) dtmax = dt; }
-  dtmax *= m->p.CFL;
-  if (dtmax > m->previous) dtmax = (m->previous + 0.1 * dtmax) / 1.1;
-  m->previous = dtmax;
-  *out = dtmax;
+  *out = step_limit(m->h_scal[NSC_UMAX], dtmax, m->D, m->p.CFL, &m->previous);
   return MSOM_OK;
 }
 
@@ -1271,22 +1266,6 @@ extern "C" int msomn_forcing(msomn_t *m) {
   HIPCHK(hipGetLastError());
   return MSOM_OK;
 }
-static double dtnext(msomn *m, double dt, double *tnext_out) {  // dtnext() [Basilisk, SURVEY App. B]
-  double tnext = m->tnext, t = m->t;
-  if (tnext != HUGE_VAL && tnext > t) {
-    unsigned int n = (unsigned int)((tnext - t) / dt);
-    if (n == 0) dt = tnext - t;
-    else {
-      double dt1 = (tnext - t) / n;
-      if (dt1 > dt * (1. + 1e-9)) dt = (tnext - t) / (n + 1);
-      else if (dt1 < dt) dt = dt1;
-      tnext = t + dt;
-    }
-  } else
-    tnext = t + dt;
-  *tnext_out = tnext;
-  return dt;
-}
 extern "C" int msomn_step(msomn_t *m, int with_forcing_event) {
   NEED_NCONST(m);
   if (m->stats_on && !m->stats_mask) { msom_set_error("msomn_step: option stats = 1 and no msomn_stats_begin since msomn_set_const"); return MSOM_ERR_STATE; }
@@ -1294,7 +1273,7 @@ extern "C" int msomn_step(msomn_t *m, int with_forcing_event) {
   double d, tn;
   if (with_forcing_event && (r = msomn_forcing(m))) return r;
   if ((r = msomn_update(m, MSOMN_Q, MSOMN_DQ, m->p.DT, &d))) return r;
-  m->dt = dtnext(m, d, &tn);
+  m->dt = step_dtnext(m->t, m->tnext, d, &tn);   // dtnext() [Basilisk, SURVEY App. B]
   // the automatic sample: q_n and the psi stage 1 inverted from it (masked, sides set, on tiles exchanged by the tendency), weight dt_n
   if (m->stats_on && m->stats_count++ % m->stats_every == 0 && (r = nstats_sample(m, m->dt))) return r;
   if ((r = msomn_advance(m, MSOMN_QPRED, MSOMN_Q, MSOMN_DQ, m->dt / 2.))) return r;

@@ -512,8 +512,6 @@ extern "C" int msom_state_load(msom_t *m, const char *path) {
   m->res_ready = -1;
   m->umax_ready = 0;
   m->umax_clean = 0;
-  m->spec_valid = 0;
-  m->spec_launched = 0;
   m->psi_ghosts_stale = ring_psi;
   if (!m->model) {
     if ((r = msom_set_option(m, "graph", (double)m->use_graph))) return r;   // drops the captured cycles
