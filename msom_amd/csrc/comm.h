@@ -8,17 +8,8 @@
 
 enum { COMM_NONE = 0, COMM_RCCL = 1, COMM_LOCAL = 2 };
 enum { RED_MAX = 0, RED_MIN = 1, RED_SUM = 2 };
-// directions of the 8 neighbours (buffer slots)
-enum { DIR_W = 0, DIR_E = 1, DIR_S = 2, DIR_N = 3, DIR_SW = 4, DIR_SE = 5, DIR_NW = 6, DIR_NE = 7 };
-
-// directions W E S N SW SE NW NE and their opposites
-static const int COMM_OPP[8] = {1, 0, 3, 2, 7, 6, 5, 4};
-struct Xfer {
-  int peer;        // rank of the neighbour
-  int tag;         // direction (DIR_*) of this tile's edge = direction the sent message travels in
-  double *send, *recv;
-  size_t count;    // doubles (same in both directions)
-};
+// DIR_*, COMM_OPP, Xfer and the rule by which the messages of an exchange pair up
+#include "comm_order_inl.h"
 
 struct Comm;
 int comm_unique_id(void *id128);

@@ -268,17 +268,10 @@ int comm_exchange(Comm *c, const Xfer *x, int nx) {
   if (!c || c->kind == COMM_NONE) return MSOM_OK;
   if (c->kind == COMM_RCCL) {
     if (nx == 0) return MSOM_OK;
-    // Within a group the sends of one rank to a peer pair up with that peer's receives in posting order.  When both neighbours
-    // of an axis are the same rank (periodic tiling, 1 or 2 tiles per side) two messages go to one peer: sends are posted in
-    // the order of their direction, receives in the order of the direction the incoming message travels in (the opposite).
-    int so[16], ro[16];
-    if (nx > 16) return MSOM_ERR_ARG;
-    for (int k = 0; k < nx; k++) so[k] = ro[k] = k;
-    for (int a = 1; a < nx; a++)
-      for (int b = a; b > 0; b--) {
-        if (x[so[b]].tag < x[so[b - 1]].tag) { const int t = so[b]; so[b] = so[b - 1]; so[b - 1] = t; }
-        if (COMM_OPP[x[ro[b]].tag & 7] < COMM_OPP[x[ro[b - 1]].tag & 7]) { const int t = ro[b]; ro[b] = ro[b - 1]; ro[b - 1] = t; }
-      }
+    // the posting order under which the library pairs every message with the one from the opposite edge: comm_order_inl.h
+    int so[COMM_MAX_XFER], ro[COMM_MAX_XFER];
+    if (nx > COMM_MAX_XFER) return MSOM_ERR_ARG;
+    comm_post_order(x, nx, so, ro);
     NCCLCHK(g_rccl.GroupStart());
     for (int k = 0; k < nx; k++) NCCLCHK(g_rccl.Send(x[so[k]].send, x[so[k]].count, ncclDouble, x[so[k]].peer, c->nccl, c->st));
     for (int k = 0; k < nx; k++) NCCLCHK(g_rccl.Recv(x[ro[k]].recv, x[ro[k]].count, ncclDouble, x[ro[k]].peer, c->nccl, c->st));
@@ -292,14 +285,29 @@ int comm_exchange(Comm *c, const Xfer *x, int nx) {
   h->posted_n[c->rank] = nx;
   h->barrier();
   int err = MSOM_OK;  // an error must not skip the closing barrier: the other tile threads are waiting in it
+  // Messages pair up by RCCL's rule and by nothing else (comm_order_inl.h): position in the posting order of comm_post_order, per
+  // peer.  The tag is only checked afterwards, so a posting order that RCCL would pair wrongly is an error here, not a silent success.
   for (int k = 0; k < nx && !err; k++) {
-    const Xfer *px = h->posted[x[k].peer];
-    const int pn = h->posted_n[x[k].peer];
-    const Xfer *src = nullptr;
-    for (int q = 0; q < pn; q++)
-      if (px[q].peer == c->rank && px[q].tag == COMM_OPP[x[k].tag & 7]) src = &px[q];
-    if (!src || src->count != x[k].count || x[k].count > c->bufcount) {
-      msom_set_error("local exchange: no matching message from rank %d tag %d", x[k].peer, x[k].tag);
+    int sr = -1, si = -1, nr = 0, ns = 0;
+    const int pe = comm_pair(h->posted.data(), h->posted_n.data(), h->n, c->rank, k, &sr, &si, &nr, &ns);
+    const Xfer *src = si >= 0 ? &h->posted[sr][si] : nullptr;
+    if (pe == COMM_PAIR_ARG) {
+      msom_set_error("local exchange: rank %d entry %d of %d: peer %d outside 0..%d or more than %d messages", c->rank, k, nx, x[k].peer, h->n - 1, (int)COMM_MAX_XFER);
+      err = MSOM_ERR_COMM;
+    } else if (pe == COMM_PAIR_NUMBER) {
+      msom_set_error("local exchange: rank %d posts %d receives from rank %d (tag %d among them), which posts %d sends to it: RCCL would hang",
+                     c->rank, nr, x[k].peer, x[k].tag, ns);
+      err = MSOM_ERR_COMM;
+    } else if (pe == COMM_PAIR_COUNT) {
+      msom_set_error("local exchange: rank %d tag %d receives %zu doubles, paired by posting order with rank %d tag %d sending %zu: RCCL would hang or overrun",
+                     c->rank, x[k].tag, x[k].count, sr, src->tag, src->count);
+      err = MSOM_ERR_COMM;
+    } else if (pe == COMM_PAIR_TAG) {
+      msom_set_error("local exchange: rank %d tag %d (%zu doubles) is paired by posting order with rank %d tag %d, not tag %d: a halo for the wrong edge",
+                     c->rank, x[k].tag, x[k].count, sr, src->tag, COMM_OPP[x[k].tag & 7]);
+      err = MSOM_ERR_COMM;
+    } else if (x[k].count > c->bufcount) {
+      msom_set_error("local exchange: rank %d tag %d: %zu doubles exceed the %zu of a message buffer", c->rank, x[k].tag, x[k].count, c->bufcount);
       err = MSOM_ERR_COMM;
     } else if (hipMemcpyAsync(x[k].recv, src->send, x[k].count * sizeof(double), hipMemcpyDeviceToDevice, c->st) != hipSuccess) {
       msom_set_error("local exchange: device copy failed");
@@ -435,9 +443,10 @@ void launch_split_wall_corners(hipStream_t st, double *f, const SplitGeom &g, in
 }
 
 // ------------------------------------------------------------------ RCCL wiring self-test
-// One-rank communicator on the current device: grouped ncclSend/ncclRecv to self (two messages,
-// as one exchange posts them), max/sum all-reduce and all-gather, through exactly the code paths
-// above.  Checks the dlopen()ed entry points, enum values and stream ordering on a single GPU,
+// One-rank communicator on the current device: grouped ncclSend/ncclRecv to self (the four face
+// messages of exch_split_raw without corners, W / E of n doubles and S / N of n / 2), max/sum
+// all-reduce and all-gather, through exactly the code paths above.  Checks the dlopen()ed entry
+// points, enum values, stream ordering and the posting order of comm_post_order on a single GPU,
 // where a 2-rank communicator cannot be formed.
 extern "C" int msom_dbg_rccl_selftest(void) {
   int r = rccl_load();
@@ -457,22 +466,25 @@ extern "C" int msom_dbg_rccl_selftest(void) {
   Comm c;
   c.kind = COMM_RCCL; c.rank = 0; c.n = 1; c.st = st2;
   NCCLCHK(g_rccl.CommInitRank(&c.nccl, 1, id, 0));
-  const int n = 1000;
+  const int n = 1000, n2 = n / 2;
   double *d = nullptr, *busy = nullptr;
   const size_t nbusy = (size_t)32 << 20;
-  HIPCHKC(hipMalloc(&d, 6 * n * sizeof(double)));
+  HIPCHKC(hipMalloc(&d, 7 * n * sizeof(double)));
   HIPCHKC(hipMalloc(&busy, nbusy * sizeof(double)));
-  std::vector<double> h(6 * n, 0.);
-  for (int k = 0; k < 2 * n; k++) h[k] = 1.5 * k - 7.;
+  // d: send W [0, n), E [n, 2n), S [2n, 2n + n2), N [2n + n2, 3n); receive W [3n, 4n), E [4n, 5n), S [5n, 5n + n2), N [5n + n2, 6n);
+  // all-gather [6n, 7n)
+  std::vector<double> h(7 * n, 0.);
+  for (int k = 0; k < 3 * n; k++) h[k] = 1.5 * k - 7.;
   int bad = 0;
   for (int rep = 0; rep < 3 && !bad; rep++) {
-    HIPCHKC(hipMemcpyAsync(d, h.data(), 6 * n * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHKC(hipMemcpyAsync(d, h.data(), 7 * n * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHKC(hipEventRecord(e1, st));              // comm_begin
     HIPCHKC(hipStreamWaitEvent(st2, e1, 0));
-    Xfer x[2] = {{0, DIR_W, d, d + 2 * n, (size_t)n}, {0, DIR_E, d + n, d + 3 * n, (size_t)n}};
-    if ((r = comm_exchange(&c, x, 2))) return r;
+    Xfer x[4] = {{0, DIR_W, d, d + 3 * n, (size_t)n}, {0, DIR_E, d + n, d + 4 * n, (size_t)n},
+                 {0, DIR_S, d + 2 * n, d + 5 * n, (size_t)n2}, {0, DIR_N, d + 2 * n + n2, d + 5 * n + n2, (size_t)n2}};
+    if ((r = comm_exchange(&c, x, 4))) return r;
     HIPCHKC(hipMemsetAsync(busy, rep, nbusy * sizeof(double), st));  // "interior" work beside the exchange
-    if ((r = comm_allgather(&c, d, d + 4 * n, n))) return r;
+    if ((r = comm_allgather(&c, d, d + 6 * n, n))) return r;
     HIPCHKC(hipEventRecord(e2, st2));             // comm_end
     HIPCHKC(hipStreamWaitEvent(st, e2, 0));
     double hs[2];
@@ -482,13 +494,15 @@ extern "C" int msom_dbg_rccl_selftest(void) {
     if ((r = comm_allreduce(&c, d + 1, hs, 2, RED_SUM))) return r;
     HIPCHKC(hipEventRecord(e2, st2));
     HIPCHKC(hipStreamWaitEvent(st, e2, 0));
-    std::vector<double> out(6 * n, 0.);
-    HIPCHKC(hipMemcpyAsync(out.data(), d, 6 * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    std::vector<double> out(7 * n, 0.);
+    HIPCHKC(hipMemcpyAsync(out.data(), d, 7 * n * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHKC(hipStreamSynchronize(st));
-    // a tile that is its own W and E neighbour (periodic, one tile per side): the W edge receives what the E edge sent and
-    // vice versa -- the pairing by direction of travel and posting order of comm_exchange, on the real library
-    for (int k = 0; k < n; k++) bad += out[2 * n + k] != 1.5 * (n + k) - 7. || out[3 * n + k] != 1.5 * k - 7.;
-    for (int k = 0; k < n; k++) bad += out[4 * n + k] != 1.5 * k - 7.;
+    // a tile that is its own neighbour on all four faces (periodic, one tile per side): the W edge receives what the E edge sent,
+    // the S edge what the N edge sent and vice versa -- the pairing by direction of travel and posting order of comm_exchange, four
+    // messages of two lengths to one peer, on the real library
+    for (int k = 0; k < n; k++) bad += out[3 * n + k] != 1.5 * (n + k) - 7. || out[4 * n + k] != 1.5 * k - 7.;
+    for (int k = 0; k < n2; k++) bad += out[5 * n + k] != 1.5 * (2 * n + n2 + k) - 7. || out[5 * n + n2 + k] != 1.5 * (2 * n + k) - 7.;
+    for (int k = 0; k < n; k++) bad += out[6 * n + k] != 1.5 * k - 7.;
     bad += hs[0] != 1.5 * 1 - 7. || hs[1] != 1.5 * 2 - 7.;
   }
   g_rccl.CommDestroy(c.nccl);

@@ -391,6 +391,37 @@ def test_periodic_domain_on_tiles(px, py, tile, nl, strict):
     assert np.array_equal(assemble(out, "psi", px, py), g.get(F["PSI"]))
 
 
+@pytest.mark.parametrize("px,py", [(2, 1), (1, 2), (2, 2)])
+@pytest.mark.parametrize("tx,ty", [(32, 16), (16, 32)])
+@pytest.mark.parametrize("strict", [True, False])
+def test_periodic_domain_on_tiles_that_are_not_square(px, py, tx, ty, strict):
+    """sbc = -1 with 1 or 2 tiles per side, where one peer gets both messages of an axis (or all four, the tile being its own
+    peer), on tiles of 32 x 16 and 16 x 32 cells: the W / E messages and the S / N messages differ in length on every level.  The
+    in-process transport pairs messages by posting order as RCCL does (comm_order_inl.h), so an order that hands a W / E strip
+    to a S / N edge is a count error here and one that swaps the two edges of an axis a tag error; with square tiles the first
+    cannot show.  Equal to the periodic single tile bit for bit, strict and product builds."""
+    nl = 2
+    gnx, gny = tx * px, ty * py
+    extra = (f"Ny = {gny}\n" if gny != gnx else "") + f"MGLEVELS = {int(np.log2(min(tx, ty)))}\nsbc = -1\nTOLERANCE = 1e-8\n" + ("tau0 = 0\n" if gny < gnx else "")
+    params = orc.double_gyre_params(gnx, nl, extra=extra)
+    x = (np.arange(gnx) + 0.5) / gnx
+    y = (np.arange(gny) + 0.5) / gny
+    psi = np.stack([1e-3 * (1 - 0.2 * l) * (np.outer(np.sin(2 * np.pi * y), np.cos(4 * np.pi * x)) + 0.5 * np.outer(np.cos(6 * np.pi * y + l), np.sin(2 * np.pi * x)))
+                    for l in range(nl)])
+    out = run_tiled(params, px, py, psi, nsteps=3, strict=strict)
+    g = QG(params, strict=strict)
+    g.option("quiet", 1)
+    g.set(F["PSI"], psi)
+    g.set_const()
+    g.set_tnext(float("inf"))
+    dts = [g.step() for _ in range(3)]
+    for r in range(px * py):
+        assert out[r]["dts"] == dts, r
+        assert (out[r]["st"].i, out[r]["st"].resa) == (g.mgstats().i, g.mgstats().resa)
+    assert np.array_equal(assemble(out, "q", px, py), g.get(F["Q"]))
+    assert np.array_equal(assemble(out, "psi", px, py), g.get(F["PSI"]))
+
+
 @pytest.mark.parametrize("px,py,tile,nl", [(2, 2, 32, 3), (2, 1, 32, 3), (1, 2, 32, 1), (4, 2, 16, 3), (2, 2, 16, 2)])
 @pytest.mark.parametrize("strict", [True, False])
 def test_periodic_tiles_with_the_large_scale_flow(px, py, tile, nl, strict):
