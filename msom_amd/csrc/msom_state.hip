@@ -1,11 +1,9 @@
 // msom_state.hip -- lossless checkpoint and bit-exact restart of a msom_t (include/msom_state.h; format: DESIGN "State file").
 // The model state of a handle goes to the file in fp64, field by field through kernels_state.hip; everything in the table of DESIGN
 // "State a handle keeps across calls" is dropped by a load and rebuilt by the plain path.  Nothing here runs inside msom_step.
-#include <unistd.h>
-
 #include "msom_host.h"
 #include "state_io.h"
-#include "state_pipe.h"
+#include "state_xfer.h"
 #include "../../include/msom_state.h"
 
 namespace {
@@ -41,75 +39,39 @@ int target_layers(const msom *m, const RecName &n) {
   return m->flayers[n.id];
 }
 
-struct Item { const char *name; const double *dev; int layers, ring; };
-struct Scal { const char *name; std::vector<double> v; };
+using sx::Field;
+using sx::Loaded;
+using sx::Pipe;
+using sx::Scal;
 
-StateChunk chunk_of(const msom *m, int ring, int layer, int y0, int rows, int sx0, int sw) {
-  StateChunk c;
-  c.g = m->g; c.ring = ring; c.layer = layer; c.y0 = y0; c.rows = rows; c.ox = m->ix * m->nx; c.oy = m->iy * m->ny;
-  c.gW = m->gnx + 2 * ring; c.gH = m->gny + 2 * ring; c.sx0 = sx0; c.sw = sw;
-  return c;
-}
+sx::RecView view_of(const msom *m, int ring) { return {m->g, ring, m->ix * m->nx, m->iy * m->ny, m->gnx, m->gny}; }
 
 // this rank's digest word, summed over the ranks (tiles: one all-gather of the words; integer sums, so the order is free)
 int digest_total(msom *m, Pipe &pp, uint64_t *out) {
   const int n = m->nranks;
-  if (n > 1) {
-    comm_begin(m);
-    const int r = comm_allgather(m->comm, (const double *)pp.dig, (double *)(pp.dig + 1), 1);
-    comm_end(m);
-    if (r) return r;
-  }
-  HIPCHK(hipMemcpyAsync(pp.h_dig, pp.dig, (size_t)(n > 1 ? n + 1 : 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, m->st));
+  if (n == 1) return sx::digest_word0(m->st, pp, out);
+  comm_begin(m);
+  const int r = comm_allgather(m->comm, (const double *)pp.dig, (double *)(pp.dig + 1), 1);
+  comm_end(m);
+  if (r) return r;
+  HIPCHK(hipMemcpyAsync(pp.h_dig, pp.dig, (size_t)(n + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, m->st));
   HIPCHK(hipStreamSynchronize(m->st));
-  uint64_t s = 0;
-  if (n > 1) for (int k = 1; k <= n; k++) s += pp.h_dig[k];
-  else s = pp.h_dig[0];
-  *out = s;
+  *out = 0;
+  for (int k = 1; k <= n; k++) *out += pp.h_dig[k];
   return MSOM_OK;
 }
 
 // ---- save
 
-// one tile: the record's rows go through the two chunk buffers -- while chunk c is packed and copied to the host on the second stream,
-// chunk c - 1 is written -- and the digest ends in pp.dig[0]
-int save_record_single(msom *m, Pipe &pp, const Item &it, FILE *fp, bool *io_ok) {
-  const int W = m->gnx + 2 * it.ring, H = m->gny + 2 * it.ring;
-  int rows_max = (int)std::min<size_t>(pp.cap / W, (size_t)H);
-  if (rows_max < 1) rows_max = 1;
-  struct C { int layer, y0, rows; };
-  std::vector<C> cs;
-  for (int l = 0; l < it.layers; l++)
-    for (int y = 0; y < H; y += rows_max) cs.push_back({l, y, std::min(rows_max, H - y)});
-  const int n = (int)cs.size();
-  for (int c = 0; c <= n; c++) {
-    if (c < n) {
-      const int b = c & 1;
-      launch_state_pack(m->st, it.dev, pp.d[b], chunk_of(m, it.ring, cs[c].layer, cs[c].y0, cs[c].rows, 0, W), pp.dig);
-      HIPCHK(hipEventRecord(pp.packed[b], m->st));
-      HIPCHK(hipStreamWaitEvent(pp.s2, pp.packed[b], 0));
-      HIPCHK(hipMemcpyAsync(pp.h[b], pp.d[b], (size_t)cs[c].rows * W * sizeof(double), hipMemcpyDeviceToHost, pp.s2));
-      HIPCHK(hipEventRecord(pp.copied[b], pp.s2));
-    }
-    if (c >= 1) {
-      const int b = (c - 1) & 1;
-      HIPCHK(hipEventSynchronize(pp.copied[b]));   // the next pack into d[b] is launched after this: no event needed the other way
-      const size_t cnt = (size_t)cs[c - 1].rows * W;
-      if (*io_ok && fwrite(pp.h[b], sizeof(double), cnt, fp) != cnt) *io_ok = false;
-    }
-  }
-  return MSOM_OK;
-}
-
 // tiles (collective): every rank packs its tile with the global indices in the digest, the tiles are gathered as gather_global does
 // and rank 0 writes the global array
-int save_record_tiled(msom *m, Pipe &pp, const Item &it, FILE *fp, bool *io_ok) {
+int save_record_tiled(msom *m, Pipe &pp, const Field &it, FILE *fp, bool *io_ok) {
   const size_t cnt = (size_t)it.layers * m->nx * m->ny;
   double *send = nullptr, *recv = nullptr;
   HIPCHK(hipMalloc(&send, cnt * sizeof(double)));
   if (hipMalloc(&recv, cnt * m->nranks * sizeof(double)) != hipSuccess) { (void)hipFree(send); msom_set_error("msom_state_save: out of device memory"); return MSOM_ERR_HIP; }
   for (int l = 0; l < it.layers; l++)
-    launch_state_pack(m->st, it.dev, send + (size_t)l * m->nx * m->ny, chunk_of(m, 0, l, m->iy * m->ny, m->ny, m->ix * m->nx, m->nx), pp.dig);
+    launch_state_pack(m->st, it.dev, send + (size_t)l * m->nx * m->ny, sx::chunk_of(it.v, l, it.v.oy, m->ny, it.v.ox, m->nx), pp.dig);
   comm_begin(m);
   int r = comm_allgather(m->comm, send, recv, cnt);
   comm_end(m);
@@ -134,9 +96,9 @@ int save_record_tiled(msom *m, Pipe &pp, const Item &it, FILE *fp, bool *io_ok) 
   return MSOM_OK;
 }
 
-void collect(msom *m, unsigned flags, const double *run3, std::vector<Item> &items, std::vector<Scal> &scal) {
+void collect(msom *m, unsigned flags, const double *run3, std::vector<Field> &items, std::vector<Scal> &scal) {
   auto fld = [&](const char *name, int id, int ring = 0) {
-    if (m->f[id]) items.push_back({name, m->f[id], m->model ? 1 : m->flayers[id], ring});
+    if (m->f[id]) items.push_back({name, m->f[id], m->model ? 1 : m->flayers[id], view_of(m, ring)});
   };
   scal.push_back({"time", {m->t, m->dt, m->previous, m->tnext, (double)m->iter}});
   // without mgstats.sum: a sum over the grid whose order, and so whose last bit, depends on the path that made it (the cached and the
@@ -163,12 +125,12 @@ void collect(msom *m, unsigned flags, const double *run3, std::vector<Item> &ite
   scal.push_back({"bfn", {(double)m->bfn_begun, m->p.iRe, m->p.iRe4, m->p.Eks, m->p.Ekb}});
   static const char *acc[MSOM_ST_NACC] = {"st_acc0", "st_acc1", "st_acc2", "st_acc3", "st_acc4", "st_acc5", "st_acc6"};
   for (int k = 0; k < MSOM_ST_NACC; k++)
-    if (m->stats.s[k]) items.push_back({acc[k], m->stats.s[k], m->nl, 0});
-  if (m->stats_qme) items.push_back({"st_qme", m->stats_qme, m->nl, 0});
+    if (m->stats.s[k]) items.push_back({acc[k], m->stats.s[k], m->nl, view_of(m, 0)});
+  if (m->stats_qme) items.push_back({"st_qme", m->stats_qme, m->nl, view_of(m, 0)});
   if (m->stats_mask || m->stats_qme)   // W is read from the device by the caller, which fills slot 4
     scal.push_back({"stats", {(double)m->stats_mask, (double)m->stats_count, (double)m->stats_every, (double)m->stats_on, 0., (double)m->stats_ndev}});
   if (m->mode_pv_invert && m->helm_pm) {   // the modal solver's warm start, with the ghost values the last correction left
-    items.push_back({"helm_pm", m->helm_pm, m->nl, 1});
+    items.push_back({"helm_pm", m->helm_pm, m->nl, view_of(m, 1)});
     std::vector<double> v;
     for (int k = 0; k < m->nl; k++) {
       const msom_mgstats &s = m->helm.s[k];
@@ -207,67 +169,24 @@ int state_save_run(msom *m, const char *path, unsigned flags, const double *run3
   }
   int r = sync_stream(m);   // the lazy stream: nothing is read ahead of the step's last pass
   if (r) return r;
-  std::vector<Item> items;
+  std::vector<Field> items;
   std::vector<Scal> scal;
   collect(m, flags, run3, items, scal);
   for (Scal &s : scal)
     if (!strcmp(s.name, "stats") && m->stats_W) HIPCHK(hipMemcpy(&s.v[4], m->stats_W, sizeof(double), hipMemcpyDeviceToHost));
-  Pipe pp;
-  {
-    size_t cap = (size_t)(m->gnx + 2) * (m->gny + 2);   // at least a layer, at most CHUNK_DOUBLES (and never less than a row)
-    if (cap > CHUNK_DOUBLES) cap = std::max(CHUNK_DOUBLES, (size_t)m->gnx + 2);
-    if ((r = pp.init(m->nranks > 1 ? 8 : cap, m->nranks))) return r;
-  }
-  const bool root = m->rank == 0;
-  const std::string tmp = std::string(path) + ".tmp";
-  FILE *fp = root ? fopen(tmp.c_str(), "wb") : nullptr;
-  bool io_ok = !root || fp != nullptr;
   msom_sfile sf;
   memset(&sf, 0, sizeof sf);
   sf.version = MSOM_STATE_VERSION; sf.dialect = (uint32_t)m->model; sf.nx = (uint32_t)m->gnx; sf.ny = (uint32_t)m->gny; sf.nl = (uint32_t)m->nl;
   sf.nptr = (uint32_t)(m->p.nptr > 0 ? m->p.nptr : 0); sf.stochastic = (uint32_t)(m->stochastic != 0); sf.noise_mode = (uint32_t)m->noise_mode;
   sf.mode_pv_invert = (uint32_t)m->mode_pv_invert; sf.flag_topo = (uint32_t)(m->flag_topo != 0);
-  sf.nrec = (uint32_t)(items.size() + scal.size());
   sf.params_len = (uint32_t)m->params_text.size();
   sf.params = const_cast<char *>(m->params_text.c_str());
-  if (fp && msom_swrite_header(fp, &sf)) io_ok = false;
-  uint64_t dsum = 0;
-  for (const Scal &s : scal) {
-    msom_srec rec;
-    memset(&rec, 0, sizeof rec);
-    snprintf(rec.name, sizeof rec.name, "%s", s.name);
-    rec.kind = MSOM_SK_SCALARS; rec.layers = (uint32_t)s.v.size(); rec.ny = rec.nx = 1;
-    rec.nbytes = 8 * (uint64_t)s.v.size();
-    rec.digest = msom_state_digest(s.v.data(), s.v.size(), 0);
-    dsum += rec.digest;
-    if (fp && io_ok && (msom_swrite_rechdr(fp, &rec) || fwrite(s.v.data(), sizeof(double), s.v.size(), fp) != s.v.size())) io_ok = false;
-  }
-  for (const Item &it : items) {
-    msom_srec rec;
-    memset(&rec, 0, sizeof rec);
-    snprintf(rec.name, sizeof rec.name, "%s", it.name);
-    rec.kind = MSOM_SK_FIELD; rec.layers = (uint32_t)it.layers; rec.ny = (uint32_t)m->gny; rec.nx = (uint32_t)m->gnx; rec.ring = (uint32_t)it.ring;
-    rec.nbytes = 8 * msom_srec_count(&rec);
-    const long at = fp && io_ok ? ftell(fp) : -1;
-    if (fp && io_ok && msom_swrite_rechdr(fp, &rec)) io_ok = false;   // digest 0 for now: it is known after the payload
-    HIPCHK(hipMemsetAsync(pp.dig, 0, sizeof(unsigned long long), m->st));
-    r = m->nranks > 1 ? save_record_tiled(m, pp, it, fp, &io_ok) : save_record_single(m, pp, it, fp, &io_ok);
-    uint64_t d = 0;
-    if (!r) r = digest_total(m, pp, &d);
-    if (r) { if (fp) { fclose(fp); unlink(tmp.c_str()); } return r; }
-    rec.digest = d;
-    dsum += d;
-    if (fp && io_ok && (fseek(fp, at, SEEK_SET) || msom_swrite_rechdr(fp, &rec) || fseek(fp, 0, SEEK_END))) io_ok = false;
-  }
-  if (fp && io_ok && msom_swrite_trailer(fp, dsum)) io_ok = false;
-  if (fp && fclose(fp)) io_ok = false;
-  if (root && io_ok && rename(tmp.c_str(), path)) io_ok = false;
-  if (!io_ok) {
-    if (root) unlink(tmp.c_str());
-    msom_set_error("msom_state_save: cannot write %s", path);
-    return MSOM_ERR_IO;
-  }
-  return MSOM_OK;
+  const bool tiled = m->nranks > 1;   // the gather stages nothing: the pipe is there for its digest words
+  return sx::write_file("msom_state_save", path, m->rank == 0, m->st, tiled ? 8 : sx::pipe_capacity(m->gnx + 2, m->ny + 2), m->nranks, sf, scal, items,
+                        [&](Pipe &pp, const Field &f, FILE *fp, bool *io_ok) {
+                          return tiled ? save_record_tiled(m, pp, f, fp, io_ok) : sx::save_record(m->st, pp, f, fp, io_ok);
+                        },
+                        [&](Pipe &pp, uint64_t *d) { return digest_total(m, pp, d); });
 }
 
 extern "C" int msom_state_save(msom_t *m, const char *path, unsigned flags) { return state_save_run(m, path, flags, nullptr); }
@@ -282,15 +201,7 @@ extern "C" int msom_state_dbg_flip(msom_t *m, long element) {
 
 namespace {
 
-struct Loaded {   // a field record verified on the device, not yet in the handle
-  const RecName *n = nullptr;
-  const msom_srec *rec = nullptr;
-  double *nat = nullptr;
-};
-struct Temps {
-  std::vector<Loaded> v;
-  ~Temps() { for (Loaded &l : v) if (l.nat) (void)hipFree(l.nat); }
-};
+const RecName &nm(const Loaded &l) { return NAMES[l.name]; }
 
 double *target_ptr(msom *m, const RecName &n) {
   switch (n.target) {
@@ -301,59 +212,12 @@ double *target_ptr(msom *m, const RecName &n) {
   }
 }
 
-int read_scalars(const char *path, const msom_srec *r, std::vector<double> &v) {
-  v.resize(r->layers);
-  FILE *fp = fopen(path, "rb");
-  const bool ok = fp && !fseek(fp, r->offset, SEEK_SET) && fread(v.data(), sizeof(double), v.size(), fp) == v.size();
-  if (fp) fclose(fp);
-  if (!ok) { msom_set_error("state file %s: short read in record %s", path, r->name); return MSOM_ERR_IO; }
-  if (msom_state_digest(v.data(), v.size(), 0) != r->digest) { msom_set_error("state file %s: record %s: digest mismatch", path, r->name); return MSOM_ERR_IO; }
-  return MSOM_OK;
-}
-
-// the record's rows of this tile: file -> pinned chunk -> device chunk (second stream) -> natural layout, two chunks in flight; then
-// the digest of what the natural array holds
-int upload_record(msom *m, Pipe &pp, FILE *fp, const char *path, const msom_srec *rec, double *nat, bool flip, uint64_t *digest) {
-  const int ring = (int)rec->ring, W = m->gnx + 2 * ring, H = m->gny + 2 * ring;
-  const int ylo = ring ? 0 : m->iy * m->ny, yhi = ring ? H : ylo + m->ny;   // a ring record is one tile's (checked by the caller)
-  int rows_max = (int)std::min<size_t>(pp.cap / W, (size_t)(yhi - ylo));
-  if (rows_max < 1) rows_max = 1;
-  struct C { int layer, y0, rows; };
-  std::vector<C> cs;
-  for (int l = 0; l < (int)rec->layers; l++)
-    for (int y = ylo; y < yhi; y += rows_max) cs.push_back({l, y, std::min(rows_max, yhi - y)});
-  for (int c = 0; c < (int)cs.size(); c++) {
-    const int b = c & 1;
-    const size_t cnt = (size_t)cs[c].rows * W;
-    if (c >= 2) HIPCHK(hipEventSynchronize(pp.packed[b]));   // the unpack of chunk c - 2 has read d[b]; its copy has left h[b] before that
-    if (fseek(fp, rec->offset + (long)((((size_t)cs[c].layer * H + cs[c].y0) * W) * sizeof(double)), SEEK_SET) ||
-        fread(pp.h[b], sizeof(double), cnt, fp) != cnt) {
-      msom_set_error("state file %s: short read in record %s", path, rec->name);
-      return MSOM_ERR_IO;
-    }
-    HIPCHK(hipMemcpyAsync(pp.d[b], pp.h[b], cnt * sizeof(double), hipMemcpyHostToDevice, pp.s2));
-    HIPCHK(hipEventRecord(pp.copied[b], pp.s2));
-    HIPCHK(hipStreamWaitEvent(m->st, pp.copied[b], 0));
-    launch_state_unpack(m->st, pp.d[b], nat, chunk_of(m, ring, cs[c].layer, cs[c].y0, cs[c].rows, 0, W));
-    HIPCHK(hipEventRecord(pp.packed[b], m->st));
-  }
-  if (flip) {
-    const size_t e = (size_t)m->state_flip % ((size_t)m->nx * m->ny);
-    launch_state_flip(m->st, nat, nat_idx(m->g, 0, (int)(e / m->nx), (int)(e % m->nx)));
-  }
-  HIPCHK(hipMemsetAsync(pp.dig, 0, sizeof(unsigned long long), m->st));
-  for (int l = 0; l < (int)rec->layers; l++)
-    launch_state_digest(m->st, nat, chunk_of(m, ring, l, ylo, yhi - ylo, 0, W), pp.dig);
-  return digest_total(m, pp, digest);
-}
-
 // a verified array into the handle: the whole allocation (its pads are the target's own: the spare array began as a copy of it)
 int commit_field(msom *m, const Loaded &l) {
-  double *dst = target_ptr(m, *l.n);
-  HIPCHK(hipMemcpyAsync(dst, l.nat, m->g.ls * l.rec->layers * sizeof(double), hipMemcpyDeviceToDevice, m->st));
-  if (l.rec->ring || l.n->target != T_FIELD) return MSOM_OK;   // ghosts from the file, or never read
-  int r = fill_bc(m, l.n->id);
-  if (!r && m->model) r = nq_after_upload(m, l.n->id);
+  HIPCHK(hipMemcpyAsync(target_ptr(m, nm(l)), l.nat, l.bytes(), hipMemcpyDeviceToDevice, m->st));
+  if (l.rec->ring || nm(l).target != T_FIELD) return MSOM_OK;   // ghosts from the file, or never read
+  int r = fill_bc(m, nm(l).id);
+  if (!r && m->model) r = nq_after_upload(m, nm(l).id);
   return r;
 }
 
@@ -365,7 +229,6 @@ extern "C" int msom_state_load(msom_t *m, const char *path) {
   int r = msom_sfile_open(path, &sf, 0);   // the whole structure: header, every record header against the file size, trailer
   if (r) return r;
   struct Free { msom_sfile *s; ~Free() { msom_sfile_free(s); } } free_sf{&sf};
-  const bool flip = m->state_flip >= 0;
   // ---- everything that can be refused is refused before the handle changes
   if ((int)sf.dialect != m->model || (int)sf.nx != m->gnx || (int)sf.ny != m->gny || (int)sf.nl != m->nl ||
       (int)sf.nptr != (m->p.nptr > 0 ? m->p.nptr : 0)) {
@@ -382,17 +245,13 @@ extern "C" int msom_state_load(msom_t *m, const char *path) {
   }
   const bool take_const = !m->const_set;
   std::map<std::string, std::vector<double>> sc;
-  Temps tmp;
+  sx::Temps tmp;
+  const std::vector<sx::KnownScalar> known = {{"time", 5}, {"mgstats", 4}, {"noise_ctr", 3}, {"bfn", 5}, {"stats", 6}, {"helm_mg", 4 * sf.nl},
+                                              {"misc", 2}, {"run", 3}, {"dh", sf.nl}};
   for (uint32_t k = 0; k < sf.nrec; k++) {
     const msom_srec *rec = &sf.rec[k];
     if (rec->kind == MSOM_SK_SCALARS) {
-      static const struct { const char *name; uint32_t n; } known[] = {{"time", 5}, {"mgstats", 4}, {"noise_ctr", 3}, {"bfn", 5}, {"stats", 6},
-                                                                       {"helm_mg", 0}, {"misc", 2}, {"run", 3}, {"dh", 0}};
-      bool ok = false;
-      for (const auto &kn : known)
-        if (!strcmp(kn.name, rec->name)) ok = kn.n ? rec->layers == kn.n : rec->layers == (strcmp(kn.name, "dh") ? 4 * sf.nl : sf.nl);
-      if (!ok) { msom_set_error("msom_state_load: %s: scalar record %s with %u numbers is not one this library reads", path, rec->name, rec->layers); return MSOM_ERR_CONFIG; }
-      if ((r = read_scalars(path, rec, sc[rec->name]))) return r;
+      if ((r = sx::read_known_scalars("msom_state_load", path, rec, known, sc))) return r;
       continue;
     }
     const RecName *n = find_name(rec->name);
@@ -404,7 +263,9 @@ extern "C" int msom_state_load(msom_t *m, const char *path) {
     if (rec->ring && m->nranks > 1) { msom_set_error("msom_state_load: %s: record %s carries a ghost ring: one tile only", path, rec->name); return MSOM_ERR_CONFIG; }
     if (n->target == T_HELM && !m->mode_pv_invert) { msom_set_error("msom_state_load: %s: record helm_pm needs mode_pv_invert", path); return MSOM_ERR_CONFIG; }
     Loaded l;
-    l.n = n; l.rec = rec;
+    l.name = (int)(n - NAMES); l.rec = rec; l.v = view_of(m, (int)rec->ring);
+    l.ylo = rec->ring ? 0 : l.v.oy;   // a ring record is one tile's: all its rows
+    l.yhi = rec->ring ? l.v.H() : l.ylo + m->ny;
     tmp.v.push_back(l);
   }
   if (sc.count("stats") && sc["stats"][0] != 0 && (!(sc["stats"][0] > 0) || sc["stats"][0] >= (double)(1u << MSOM_ST_NACC))) {
@@ -413,45 +274,20 @@ extern "C" int msom_state_load(msom_t *m, const char *path) {
   }
   if ((r = sync_stream(m))) return r;
   // ---- every field into a spare natural array, its digest recomputed there on the device
-  {
-    Pipe pp;
-    size_t cap = (size_t)(m->gnx + 2) * (m->ny + 2);
-    if (cap > CHUNK_DOUBLES) cap = std::max(CHUNK_DOUBLES, (size_t)m->gnx + 2);
-    if ((r = pp.init(cap, m->nranks))) return r;
-    FILE *fp = fopen(path, "rb");
-    if (!fp) { msom_set_error("state file %s not found", path); return MSOM_ERR_IO; }
-    struct Close { FILE *f; ~Close() { fclose(f); } } close_fp{fp};
-    bool first = true;
-    for (Loaded &l : tmp.v) {
-      const size_t bytes = m->g.ls * l.rec->layers * sizeof(double);
-      HIPCHK(hipMalloc(&l.nat, bytes));
-      const double *cur = target_ptr(m, *l.n);
-      if (cur) HIPCHK(hipMemcpyAsync(l.nat, cur, bytes, hipMemcpyDeviceToDevice, m->st));
-      else HIPCHK(hipMemsetAsync(l.nat, 0, bytes, m->st));
-      uint64_t d = 0;
-      r = upload_record(m, pp, fp, path, l.rec, l.nat, flip && first, &d);
-      first = false;
-      if (r) { m->state_flip = -1; (void)hipStreamSynchronize(pp.s2); (void)hipStreamSynchronize(m->st); return r; }
-      if (d != l.rec->digest) {
-        m->state_flip = -1;
-        msom_set_error("msom_state_load: %s: record %s: the device holds digest %016llx, the file says %016llx", path, l.rec->name,
-                       (unsigned long long)d, (unsigned long long)l.rec->digest);
-        return MSOM_ERR_IO;
-      }
-    }
-  }
-  m->state_flip = -1;
+  if ((r = sx::stage_records("msom_state_load", path, m->st, sx::pipe_capacity(m->gnx + 2, m->ny + 2), m->nranks, tmp, &m->state_flip,
+                             [&](const Loaded &l) { return target_ptr(m, nm(l)); }, [&](Pipe &pp, uint64_t *d) { return digest_total(m, pp, d); })))
+    return r;
   // ---- commit.  Constants first (a handle that has none yet), msom_set_const, then the evolving state: set_const overwrites q
   m->res_ready = -1;
   if (take_const) {
     for (const Loaded &l : tmp.v) {
-      if (l.n->role != CONSTANT) continue;
+      if (nm(l).role != CONSTANT) continue;
       // through msom_set_field, which keeps the flags that go with a constant input: the array goes back to [layer][y][x] on the device
       double *flat = nullptr;
       const size_t per = (size_t)m->nx * m->ny;
       HIPCHK(hipMalloc(&flat, per * l.rec->layers * sizeof(double)));
       launch_unpack(m->st, l.nat, flat, m->g, (int)l.rec->layers);
-      r = msom_set_field(m, l.n->id, flat);
+      r = msom_set_field(m, nm(l).id, flat);
       (void)hipFree(flat);
       if (r) return r;
     }
@@ -462,10 +298,10 @@ extern "C" int msom_state_load(msom_t *m, const char *path) {
     // the statistics: the arrays the file holds, allocated as msom_stats_begin / msom_time_filter allocate them
     unsigned mask = sc.count("stats") ? (unsigned)sc["stats"][0] : 0;
     bool qme = false;
-    for (const Loaded &l : tmp.v) qme |= l.n->target == T_QME;
+    for (const Loaded &l : tmp.v) qme |= nm(l).target == T_QME;
     if (mask && mask != m->stats_mask && (r = msom_stats_begin(m, mask))) return r;
     for (const Loaded &l : tmp.v)
-      if (l.n->target == T_ACC && !m->stats.s[l.n->id]) { msom_set_error("msom_state_load: %s: accumulator %d is not in the file's mask", path, l.n->id); return MSOM_ERR_CONFIG; }
+      if (nm(l).target == T_ACC && !m->stats.s[nm(l).id]) { msom_set_error("msom_state_load: %s: accumulator %d is not in the file's mask", path, nm(l).id); return MSOM_ERR_CONFIG; }
     if (qme && !m->stats_qme) HIPCHK(hipMalloc(&m->stats_qme, m->g.ls * m->nl * sizeof(double)));
     if (sc.count("stats")) {
       const std::vector<double> &s = sc["stats"];
@@ -474,15 +310,15 @@ extern "C" int msom_state_load(msom_t *m, const char *path) {
       if ((r = sync_stream(m))) return r;   // s lives until the end of the call, the copy is done here all the same
     }
     for (const Loaded &l : tmp.v) {
-      if (l.n->target == T_FIELD && !m->f[l.n->id] && (r = ensure_field(m, l.n->id))) return r;   // qof, the budgets, the AB3 history
-      if (l.n->target == T_HELM && !m->helm_pm && (r = helm_ensure(m))) return r;
+      if (nm(l).target == T_FIELD && !m->f[nm(l).id] && (r = ensure_field(m, nm(l).id))) return r;   // qof, the budgets, the AB3 history
+      if (nm(l).target == T_HELM && !m->helm_pm && (r = helm_ensure(m))) return r;
     }
   }
   int ring_psi = 0;
   for (const Loaded &l : tmp.v) {
-    if (l.n->role == CONSTANT) continue;
+    if (nm(l).role == CONSTANT) continue;
     if ((r = commit_field(m, l))) return r;
-    if (l.n->target == T_FIELD && l.n->id == MSOM_PSI) ring_psi = (int)l.rec->ring;
+    if (nm(l).target == T_FIELD && nm(l).id == MSOM_PSI) ring_psi = (int)l.rec->ring;
   }
   if (sc.count("time")) {
     const std::vector<double> &v = sc["time"];
@@ -542,7 +378,7 @@ extern "C" msom_t *msom_create_from_state(const char *path) {
       std::vector<double> v;
       if (!r) r = msom_set_option(m, "stochastic", 1);
       if (!r) r = msom_set_option(m, "noise_mode", sf.noise_mode);
-      if (!r && nc && !(r = read_scalars(path, nc, v))) r = msom_set_option(m, "seed", v[0]);
+      if (!r && nc && !(r = sx::read_scalars(path, nc, v))) r = msom_set_option(m, "seed", v[0]);
     }
     if (!r && sf.mode_pv_invert) r = msom_set_option(m, "mode_pv_invert", 1);
     if (!r && sf.flag_topo) r = msom_set_option(m, "flag_topo", 1);
@@ -550,9 +386,7 @@ extern "C" msom_t *msom_create_from_state(const char *path) {
   msom_sfile_free(&sf);
   if (m && !r) r = msom_state_load(m, path);
   if (m && r) {
-    const std::string keep = msom_last_error();
-    msom_destroy(m);
-    msom_set_error("%s", keep.c_str());
+    sx::destroy_keeping_error([&] { msom_destroy(m); });
     return nullptr;
   }
   return m;

@@ -252,9 +252,12 @@ def test_used_and_fresh_handles_load_alike(case, strict, tmp_path):
 
 # ------------------------------------------------------------------ 4. digest and layout
 
-@pytest.mark.parametrize("strict", [True, False])
-@pytest.mark.parametrize("nl", [1, 2, 3])
-@pytest.mark.parametrize("N", [16, 32, 64])
+# every small shape on both builds; and, on one build, the smallest at which a layer does not fit one staging chunk of 4 Mi doubles:
+# 2049 vertices a side, so 2047 rows in the first chunk and 2 in the second
+LAYOUT_SHAPES = [(N, nl, strict) for strict in (True, False) for nl in (1, 2, 3) for N in (16, 32, 64)] + [(2048, 1, True)]
+
+
+@pytest.mark.parametrize("N,nl,strict", LAYOUT_SHAPES)
 def test_digest_and_layout(N, nl, strict, tmp_path):
     par = orn.node_params(N, nl, bc_fac=1.0, extra=STOCH)
     c = dict(par=par, mask=True, topo=nl > 1, opts=dict(stochastic=1, noise_mode=1, seed=5), stochastic=True)
@@ -295,6 +298,11 @@ def test_digest_and_layout(N, nl, strict, tmp_path):
     for a, b in zip(before, (g.get("PSI"), g.get("Q"), g.t, g.noise())):
         assert np.array_equal(a, b)
     g.close()
+    h = configure(c, strict)   # and a handle that has nothing but the file
+    h.load_state(p)
+    for a, b in zip(before, (h.get("PSI"), h.get("Q"), h.t, h.noise())):
+        assert np.array_equal(a, b)
+    h.close()
 
 
 # ------------------------------------------------------------------ 5. refusals leave the handle as it was
@@ -397,6 +405,22 @@ def test_node_from_state(case, strict, tmp_path):
     run_b_first(c, strict, p, False)
     with pytest.raises(MsomError, match="MSOM_STATE_CONSTANTS"):
         node_from_state(p, strict=strict)
+
+
+@pytest.mark.parametrize("strict", [True, False])
+def test_a_handle_made_from_a_file_saves_the_same_file(strict, tmp_path):
+    """save with the constants, msomn_create_from_state, save again with the same flags: the two files are equal byte for byte"""
+    c = CASES["n32x1"]
+    pa, pb = str(tmp_path / "a.msom"), str(tmp_path / "b.msom")
+    run_b_first(c, strict, pa, True)
+    g = node_from_state(pa, strict=strict)
+    g.save_state(pb, constants=True)
+    g.close()
+    a, b = read_state(pa), read_state(pb)
+    assert list(a["records"]) == list(b["records"])
+    for k in a["records"]:     # record by record first, so that a failure names the record
+        assert np.array_equal(a["records"][k], b["records"][k], equal_nan=True), k
+    assert open(pa, "rb").read() == open(pb, "rb").read()
 
 
 # ------------------------------------------------------------------ 7. the golden file

@@ -313,6 +313,27 @@ def test_from_state_makes_the_handle_from_the_file_alone(strict, tmp_path):
     g.close()
 
 
+@gpu
+@pytest.mark.parametrize("strict", BUILDS)
+def test_a_handle_made_from_a_file_saves_the_same_file(strict, tmp_path):
+    """save with the constants, msom_create_from_state, save again with the same flags: the two files are equal byte for byte"""
+    c = CASES["dg32x3"]
+    g = c.make(strict)
+    c.setup(g)
+    for n in range(c.nsplit):
+        c.advance(g, n)
+    g.save_state(tmp_path / "a.msom", constants=True)
+    g.close()
+    h = from_state(tmp_path / "a.msom", strict=strict)
+    h.save_state(tmp_path / "b.msom", constants=True)
+    h.close()
+    a, b = read_state(tmp_path / "a.msom"), read_state(tmp_path / "b.msom")
+    assert list(a["records"]) == list(b["records"])
+    for k in a["records"]:     # record by record first, so that a failure names the record
+        assert np.array_equal(a["records"][k], b["records"][k], equal_nan=True), k
+    assert (tmp_path / "a.msom").read_bytes() == (tmp_path / "b.msom").read_bytes()
+
+
 # ------------------------------------------------------------------ 2. save is pure and ordered; load is a mutating row
 
 def save_call(h, rng, ctx):
@@ -383,10 +404,14 @@ def test_load_sends_the_next_solve_back_to_the_residual_pass(grid, strict, tmp_p
 
 # ------------------------------------------------------------------ 3. digest and layout
 
+# every small shape on both builds; and, on one build, the smallest at which a layer does not fit one staging chunk of 4 Mi doubles:
+# 4096 wide, so 1024 rows a chunk and two chunks for the 2048 rows of the layer
+LAYOUT_SHAPES = [(nx, ny, nl, strict) for strict in BUILDS for nl in (1, 2, 3) for nx, ny in ((16, 16), (32, 16), (64, 32), (128, 64))]
+LAYOUT_SHAPES.append((4096, 2048, 1, False))
+
+
 @gpu
-@pytest.mark.parametrize("strict", BUILDS)
-@pytest.mark.parametrize("nl", [1, 2, 3])
-@pytest.mark.parametrize("nx,ny", [(16, 16), (32, 16), (64, 32), (128, 64)])
+@pytest.mark.parametrize("nx,ny,nl,strict", LAYOUT_SHAPES)
 def test_digest_and_layout(nx, ny, nl, strict, tmp_path):
     g = QG(params(nx, ny, nl), strict=strict)
     g.option("quiet", 1)
@@ -413,6 +438,11 @@ def test_digest_and_layout(nx, ny, nl, strict, tmp_path):
     g.load_state(p)                        # the aid is spent: the same file loads
     assert np.array_equal(g.get(F["PSI"]), psi) and np.array_equal(g.get(F["Q"]), q)
     g.close()
+    h = QG(params(nx, ny, nl), strict=strict)   # and a handle that has nothing but the file
+    h.option("quiet", 1)
+    h.load_state(p)
+    assert np.array_equal(h.get(F["PSI"]), psi) and np.array_equal(h.get(F["Q"]), q)
+    h.close()
 
 
 # ------------------------------------------------------------------ 4. refusals
