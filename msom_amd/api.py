@@ -88,6 +88,16 @@ def load_library(strict=False):
         "msom_stats_weight": (ci, [vp, _dp]),
         "msom_stats_get": (ci, [vp, ci, vp]),
         "msom_time_filter": (ci, [vp, cd]),
+        # Lagrangian floats (include/msom_floats.h)
+        "msom_floats_begin": (ci, [vp, ci, vp, vp, vp]),
+        "msom_floats_end": (ci, [vp]),
+        "msom_floats_get": (ci, [vp, vp, vp]),
+        "msom_floats_velocity": (ci, [vp, vp, vp]),
+        "msom_floats_sample": (ci, [vp, ci, vp]),
+        "msom_floats_stage": (ci, [vp, ci, cd]),
+        "msom_floats_record": (ci, [vp, ci, ci]),
+        "msom_floats_track": (ci, [vp, ci, ci, _dp, vp, vp]),
+        "msom_floats_dbg_ghosted": (ci, [vp, ci, vp]),
         "msom_modes_compute": (ci, [vp]),
         "msom_modes_layers": (ci, [vp, ci]),
         "msom_modes_get": (ci, [vp, ci, vp]),
@@ -449,6 +459,65 @@ class QG:
     def time_filter(self, dt):
         """qo_me = (1 - a) * qo_me + a * Q, a = dt / tau_f (option "tau_f", 20); read it back with stats_get(STATS["QME"])"""
         self._chk(self.L.msom_time_filter(self.h, float(dt)))
+
+    # -- Lagrangian floats advected on the device with the model's RK2 stages (include/msom_floats.h)
+    def floats_begin(self, x, y, layer):
+        """n floats at (x, y) in domain coordinates, layer[k] in [0, nl); host arrays or device tensors (float64, float64, int32).
+        From here on every step() moves them; option("floats", 0) pauses that"""
+        if not hasattr(layer, "data_ptr"):
+            layer = np.ascontiguousarray(layer, dtype=np.int32)
+        x, y = _f64(x), _f64(y)
+        n = int(x.shape[0])
+        if tuple(x.shape) != (n,) or tuple(y.shape) != (n,) or tuple(layer.shape) != (n,):
+            raise ValueError(f"x, y, layer of shapes {tuple(x.shape)}, {tuple(y.shape)}, {tuple(layer.shape)}: want three [n]")
+        self._chk(self.L.msom_floats_begin(self.h, n, _ptr(x), _ptr(y), _ptr(layer)))
+
+    def floats_end(self):
+        self._chk(self.L.msom_floats_end(self.h))
+
+    def _floats_n(self):
+        return max(int(self.param("floats")), 0)
+
+    def floats_get(self):
+        """(x, y): the current positions in the caller's order"""
+        x, y = np.empty(self._floats_n()), np.empty(self._floats_n())
+        self._chk(self.L.msom_floats_get(self.h, _ptr(x), _ptr(y)))
+        return x, y
+
+    def floats_velocity(self):
+        """(u, v) at the current positions from the PSI the model holds now"""
+        u, v = np.empty(self._floats_n()), np.empty(self._floats_n())
+        self._chk(self.L.msom_floats_velocity(self.h, _ptr(u), _ptr(v)))
+        return u, v
+
+    def floats_sample(self, field):
+        """the bilinear interpolation of a field of nl layers at the floats, each in its layer"""
+        out = np.empty(self._floats_n())
+        self._chk(self.L.msom_floats_sample(self.h, int(field), _ptr(out)))
+        return out
+
+    def floats_stage(self, stage, dt):
+        """the advection by hand: stage 1 (xh = x + dt / 2 U(x)) after the first update(), stage 2 (x += dt U(xh)) after the second"""
+        self._chk(self.L.msom_floats_stage(self.h, int(stage), float(dt)))
+
+    def floats_record(self, every=1, capacity=1):
+        """a trajectory buffer of `capacity` records on the device: record 0 now, then one behind every `every`-th step()"""
+        self._chk(self.L.msom_floats_record(self.h, int(every), int(capacity)))
+
+    def floats_track(self, first=0, count=None):
+        """(t[count], x[count][n], y[count][n]) of records first .. first + count - 1 (count None: all that are written)"""
+        if count is None:
+            count = int(self.param("floats_records")) - first
+        n = self._floats_n()
+        t, x, y = np.empty(max(count, 0)), np.empty((max(count, 0), n)), np.empty((max(count, 0), n))
+        self._chk(self.L.msom_floats_track(self.h, int(first), int(count), t.ctypes.data_as(_dp), _ptr(x), _ptr(y)))
+        return t, x, y
+
+    def floats_ghosted(self, field):
+        """[nl][ny + 2][nx + 2]: a field of nl layers with its one-cell ghost ring, as the float kernels read it"""
+        out = np.empty((self.nl, self.ny + 2, self.nx + 2))
+        self._chk(self.L.msom_floats_dbg_ghosted(self.h, int(field), _ptr(out)))
+        return out
 
     # -- vertical normal modes of the stretching operator on the device (MODES), msqg/eigmode.h
     def modes_compute(self):

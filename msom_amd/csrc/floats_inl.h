@@ -1,0 +1,101 @@
+// floats_inl.h -- arithmetic of the Lagrangian floats (msom_floats_*).  Plain C++, no HIP header: the device
+// kernels (kernels_floats.hip), the host calls (msom_floats.hip) and tools/floats_host_check.cpp (AddressSanitizer + UBSan) read
+// the same functions; tests/floats_ref.py restates them in numpy.
+//
+// Cells are square, Delta = L0 / gnx, idx = gnx / L0 rounded once on the host; cell centre i sits at (i + 1/2) Delta.  A float at
+// (x, y) in layer l lies in the dual cell whose corners are the centres (i0, j0) .. (i0 + 1, j0 + 1):
+//     xi = x * idx - 0.5;  i0 = floor(xi);  a = xi - i0          (eta, j0, b likewise from y)
+//   walls:    i0 clamped to [-1, nx - 1], j0 to [-1, ny - 1]: the one-cell ghost ring is read (psi = 0 on the wall face)
+//   periodic: i0, j0 taken modulo nx, ny into [0, n - 1]; i0 + 1 may be the wrapped ghost column nx
+//     P00 = F[l][j0][i0], P10 = F[l][j0][i0 + 1], P01 = F[l][j0 + 1][i0], P11 = F[l][j0 + 1][i0 + 1]
+//     u = -((1 - a) * (P01 - P00) + a * (P11 - P10)) * idx
+//     v =  ((1 - b) * (P10 - P00) + b * (P11 - P01)) * idx
+// the exactly non-divergent velocity of the bilinear psi.  a is formed from the unclamped floor, so it lies in [0, 1] whatever x is;
+// the index is clamped as a double, before the conversion to int, so no input bits can take it out of [-1, n].
+#ifndef MSOM_FLOATS_INL_H
+#define MSOM_FLOATS_INL_H
+
+#include <math.h>
+
+#ifdef __HIPCC__
+#define FL_HD __host__ __device__
+#else
+#define FL_HD
+#endif
+
+struct FloatsGeom {
+  int nx, ny;      // cells of the domain
+  int periodic;    // sbc = -1: positions are kept unwrapped, indices wrap
+  double idx;      // gnx / L0
+  double Lx, Ly;   // L0, L0 * gny / gnx
+};
+// dual cell and weights of one position; ok = 0: the position is not finite (the float is lost, nothing may be read for it)
+struct FloatsCell {
+  int i0, j0;
+  double a, b;
+  int ok;
+};
+
+FL_HD static inline bool floats_finite(double x) { return x - x == 0.; }
+
+// one axis: index of the lower corner and the weight of the upper one
+FL_HD static inline bool floats_axis(double x, double idx, int n, int periodic, int *i0, double *a) {
+  *i0 = 0;
+  *a = 0.;
+  const double xi = x * idx - 0.5;
+  if (!floats_finite(xi)) return false;
+  double f = floor(xi);
+  *a = xi - f;
+  if (periodic) {
+    f = fmod(f, (double)n);   // exact; takes the sign of f
+    if (f < 0.) f += (double)n;
+    if (!(f >= 0.)) f = 0.;
+    if (f > (double)(n - 1)) f = (double)(n - 1);
+  } else {
+    if (!(f >= -1.)) f = -1.;
+    if (f > (double)(n - 1)) f = (double)(n - 1);
+  }
+  *i0 = (int)f;
+  return true;
+}
+
+FL_HD static inline FloatsCell floats_locate(double x, double y, const FloatsGeom &g) {
+  FloatsCell c;
+  const bool okx = floats_axis(x, g.idx, g.nx, g.periodic, &c.i0, &c.a);
+  const bool oky = floats_axis(y, g.idx, g.ny, g.periodic, &c.j0, &c.b);
+  c.ok = okx && oky;
+  return c;
+}
+
+FL_HD static inline void floats_uv(double P00, double P10, double P01, double P11, double a, double b, double idx, double *u, double *v) {
+  *u = -((1. - a) * (P01 - P00) + a * (P11 - P10)) * idx;
+  *v = ((1. - b) * (P10 - P00) + b * (P11 - P01)) * idx;
+}
+
+// the bilinear value itself (msom_floats_sample)
+FL_HD static inline double floats_bilinear(double P00, double P10, double P01, double P11, double a, double b) {
+  return (1. - b) * ((1. - a) * P00 + a * P10) + b * ((1. - a) * P01 + a * P11);
+}
+
+// One RK2 stage of one float: (bx, by) the position the step starts from, (u, v) the velocity at the position the stage evaluates,
+// h = dt / 2 (stage 1) or dt (stage 2).  On walls the result is clamped to the box.  Returns bit 0: clamped, bit 1: the result is not
+// finite (both coordinates become NaN).
+FL_HD static inline int floats_move(double bx, double by, double u, double v, double h, const FloatsGeom &g, double *ox, double *oy) {
+  double x = bx + h * u, y = by + h * v;
+  if (!floats_finite(x) || !floats_finite(y)) {
+    *ox = *oy = NAN;
+    return 2;
+  }
+  int flag = 0;
+  if (!g.periodic) {
+    if (x < 0.) { x = 0.; flag = 1; }
+    if (x > g.Lx) { x = g.Lx; flag = 1; }
+    if (y < 0.) { y = 0.; flag = 1; }
+    if (y > g.Ly) { y = g.Ly; flag = 1; }
+  }
+  *ox = x;
+  *oy = y;
+  return flag;
+}
+
+#endif

@@ -10,6 +10,7 @@
 
 #include "msom_internal.h"
 #include "modes_inl.h"   // ModesLayers, the per-column eigen routine
+#include "floats_inl.h"  // FloatsGeom, the arithmetic of the Lagrangian floats
 
 // Run-time value -> template argument.  with_int<LO, HI>(v, f) calls f(std::integral_constant<int, v>{}) and returns true when
 // LO <= v <= HI; otherwise it calls nothing and returns false.  The range is the list of instantiations a launcher has: a launcher
@@ -69,6 +70,21 @@ struct KernelOpts {
   int lpw_dbg = 0;            // bits 1, 2 timing experiments of k_rhs_lpw; 4: every wavefront takes the instantiation with the ghost-line code
 };
 int device_cu_count();   // CUs of the current device, asked once per device
+
+// ---- kernels_floats.hip: Lagrangian floats (msom_floats_*), one float per lane, structure of arrays
+struct FloatsDev {
+  double *x, *y;     // positions at the last step boundary
+  double *xh, *yh;   // positions after stage 1
+  const int *layer;
+  unsigned long long *cnt;   // [0] clamped to the box, [1] lost (not finite)
+};
+// stage 1: (xh, yh) = (x, y) + dt / 2 U(x, y); stage 2: (x, y) += dt U(xh, yh), also stored to rec[0 .. n), rec[n .. 2n) when rec is given.
+// U from psi (+ pg per corner when pg is given), natural layout with its ghost ring
+void launch_floats_stage(hipStream_t st, int stage, const FloatsDev &d, int n, const double *psi, const double *pg, const NatGeom &g,
+                         const FloatsGeom &fg, double dt, double *rec);
+// at (x, y): o0 = u, o1 = v of f (+ pg) when o1 is given, else o0 = the bilinear value of f
+void launch_floats_interp(hipStream_t st, const FloatsDev &d, int n, const double *f, const double *pg, const NatGeom &g, const FloatsGeom &fg,
+                          double *o0, double *o1);
 
 // ---- kernels_rhs.hip
 void launch_fill_ghost(hipStream_t st, double *f, const NatGeom &g, int nl, int bc, int walls, int depth = 1);

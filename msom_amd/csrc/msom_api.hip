@@ -505,6 +505,7 @@ extern "C" int msom_destroy(msom_t *m) {
   if (m->partial_rr) hipFree(m->partial_rr);
   if (m->bfn_partial) hipFree(m->bfn_partial);
   stats_drop(m);
+  floats_drop(m);
   modes_drop(m);
   spec_drop(m);
   if (m->modes_dev) hipFree(m->modes_dev);
@@ -606,6 +607,7 @@ extern "C" int msom_set_option(msom_t *m, const char *key, double v) {
     if (!(v >= 1)) { msom_set_error("option stats_every = %g", v); return MSOM_ERR_ARG; }
     m->stats_every = (int)v;
   }
+  else if (!strcmp(key, "floats")) m->fl_on = m->fl && (int)v != 0;   // pauses / resumes the floats of msom_step; without floats: nothing
   else if (!strcmp(key, "ckpt_steps")) {   // msom_run: <workdir>/state.msom every that many steps (msom_state.h); 0: off
     if (!(v >= 0)) { msom_set_error("option ckpt_steps = %g", v); return MSOM_ERR_ARG; }
     m->ckpt_steps = (int)v;
@@ -686,6 +688,7 @@ extern "C" double msom_get_param(msom_t *m, const char *key) {
     for (int k = 0; k < MSOM_ST_NACC; k++) n += m->stats.s[k] ? 1 : 0;
     return (double)n * m->nl * m->nx * m->ny * sizeof(double);
   }
+  if (double fv; floats_param(m, key, &fv)) return fv;
   if (!strcmp(key, "mode_pv_invert")) return m->mode_pv_invert;
   if (!strcmp(key, "modes_ready")) return m->const_set && m->modes_ready;
   if (!strcmp(key, "modes_compact")) return m->const_set && m->modes_ready ? m->modes_compact : (m->modes_compact_opt != 0 && m->fr_uniform);
@@ -1063,6 +1066,7 @@ extern "C" int msom_set_const(msom_t *m) {
   m->const_set = 1;
   m->bfn_begun = 0;
   stats_drop(m);
+  floats_drop(m);
   modes_drop(m);
   spec_drop(m);
   m->helm_solved = 0;
@@ -2220,6 +2224,8 @@ static int rk_stage(msom *m, int stage, bool spec, double *tnext) {
     stats_sample(m, hit ? m->d_scal + SC_SPEC + 1 : nullptr, m->dt);
     m->stats_ndev += hit;
   }
+  // the floats' RK2 stages ride behind the model's: stage 1 reads psi_n behind the first tendency pass, stage 2 psi_{n+1/2} behind the second
+  if (m->fl_on) floats_hook(m, stage, *tnext);
   if (m->p.nptr > 0 && ((r = tracer_update(m, first ? MSOM_PTR : MSOM_PTR_PRED)) || (r = tracer_advance(m, first ? MSOM_PTR_PRED : MSOM_PTR, MSOM_PTR, adv_dt))))
     return r;
   return MSOM_OK;

@@ -129,7 +129,7 @@ ModesLayers modes_layers(const msom *m) {
   return l;
 }
 const ModeCoef *modes_mc(const msom *m) { return m->modes_compact ? &m->modes_mc : nullptr; }
-static bool is_device_ptr(const void *p) {
+bool is_device_ptr(const void *p) {
   hipPointerAttribute_t a;
   if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // an address the runtime does not know: host
   return a.type == hipMemoryTypeDevice;

@@ -1,6 +1,6 @@
 // msom_host.h -- private to the host side of the layered model: struct msom, the error macros, the device scalar slots and the host
 // functions that one msom_*.hip unit calls in another.  Included by msom_api.hip, msom_helm.hip, msom_diag.hip, msom_newqg.hip,
-// msom_wavelet.hip, msom_io.hip, msom_state.hip and msom_hooks.hip, and by nothing else (no kernel file, not comm.hip, not msom_node.hip).
+// msom_wavelet.hip, msom_io.hip, msom_state.hip, msom_hooks.hip and msom_floats.hip, and by nothing else (no kernel file, not comm.hip, not msom_node.hip).
 #ifndef MSOM_HOST_H
 #define MSOM_HOST_H
 
@@ -181,6 +181,9 @@ struct msom {
   long stats_count = 0;                   // msom_step calls seen since msom_stats_begin (every stats_every-th one samples)
   long stats_ndev = 0;                    // ... of whose samples, those that read their weight from the device (tests ask: stats_dev_samples)
   double tau_f = 20;                      // option "tau_f" (msqg/qg.h:495)
+  // Lagrangian floats (msom_floats_*, msom_floats.hip); nothing is allocated until msom_floats_begin
+  struct FloatsState *fl = nullptr;       // positions, layers, counters and the trajectory buffer
+  int fl_on = 0;                          // floats begun and option "floats" not 0: rk_stage queues their two stages
   // vertical normal modes (msom_modes_*, msqg/eigmode.h); nothing is allocated until msom_modes_compute
   int modes_ready = 0;                    // a successful msom_modes_compute since the last msom_set_const
   int modes_compact = 0;                  // ... which left the compact form (modes_mc) rather than one array per number (modes_md)
@@ -236,6 +239,7 @@ struct msom {
   ProfSlot prof_march_visit;  // the finest level's fused visit (k_relax_visit and the two passes on the chunks around it)
   ProfSlot prof_march_corr, prof_resmax;  // last pass of the finest level with the correction folded in; max-only residual pass after it
   ProfSlot prof_rhs, prof_redprol, prof_rescorr, prof_respre;   // tendency pass, finest red+prolongation, post- / pre-cycle residual passes
+  ProfSlot prof_floats;   // the floats' stages queued by msom_step (k_floats_stage)
 };
 
 // ---- what travels with one call (nothing of it is kept on the handle)
@@ -361,6 +365,11 @@ int spec_ensure(msom *m);
 SpecIn spec_in_nat(const msom *m, int mode, const double *a, const double *b);
 void spec_batch_2d(msom *m, const SpecIn &in, int cnt, int kind, double *o2d);
 void spec_batch_1d(msom *m, int cnt);
+bool is_device_ptr(const void *p);
+// msom_floats.hip
+void floats_drop(msom *m);
+void floats_hook(msom *m, int stage, double tnext);   // one stage of msom_step's floats, queued on m->st with m->dt; no host wait
+bool floats_param(msom *m, const char *key, double *v);
 // msom_newqg.hip
 int nq_refuse(const char *fn);
 bool nq_has_field(int field);
