@@ -460,10 +460,14 @@ class QG:
         """qo_me = (1 - a) * qo_me + a * Q, a = dt / tau_f (option "tau_f", 20); read it back with stats_get(STATS["QME"])"""
         self._chk(self.L.msom_time_filter(self.h, float(dt)))
 
-    # -- Lagrangian floats advected on the device with the model's RK2 stages (include/msom_floats.h)
+    # -- Lagrangian floats advected on the device with the model's RK2 stages (include/msom_floats.h).  On a tiled handle they need
+    # option("floats_tiles", 1) before floats_begin (option("floats_msg_cap", K): records per migration message); every floats_* call
+    # and param("floats_clamped" / "floats_lost" / "floats_unsent" / "floats_migrated") is then collective: every rank makes the same
+    # calls in the same order, with the same global arrays, and receives the full arrays in the caller's order
     def floats_begin(self, x, y, layer):
         """n floats at (x, y) in domain coordinates, layer[k] in [0, nl); host arrays or device tensors (float64, float64, int32).
-        From here on every step() moves them; option("floats", 0) pauses that"""
+        From here on every step() moves them; option("floats", 0) pauses that (on tiles: alike on all ranks).  On tiles collective:
+        every rank passes the same global arrays and keeps the floats it owns"""
         if not hasattr(layer, "data_ptr"):
             layer = np.ascontiguousarray(layer, dtype=np.int32)
         x, y = _f64(x), _f64(y)
@@ -479,19 +483,21 @@ class QG:
         return max(int(self.param("floats")), 0)
 
     def floats_get(self):
-        """(x, y): the current positions in the caller's order"""
+        """(x, y): the current positions in the caller's order (on tiles collective: all n floats on every rank)"""
         x, y = np.empty(self._floats_n()), np.empty(self._floats_n())
         self._chk(self.L.msom_floats_get(self.h, _ptr(x), _ptr(y)))
         return x, y
 
     def floats_velocity(self):
-        """(u, v) at the current positions from the PSI the model holds now"""
+        """(u, v) at the current positions from the PSI the model holds now (on tiles collective, and not between a stage 1 and its
+        stage 2 by hand)"""
         u, v = np.empty(self._floats_n()), np.empty(self._floats_n())
         self._chk(self.L.msom_floats_velocity(self.h, _ptr(u), _ptr(v)))
         return u, v
 
     def floats_sample(self, field):
-        """the bilinear interpolation of a field of nl layers at the floats, each in its layer"""
+        """the bilinear interpolation of a field of nl layers at the floats, each in its layer (on tiles collective, as floats_velocity;
+        the ghost ring is the tile's, which the model exchanges for PSI but not for Q)"""
         out = np.empty(self._floats_n())
         self._chk(self.L.msom_floats_sample(self.h, int(field), _ptr(out)))
         return out

@@ -262,6 +262,13 @@ double *comm_sendbuf(Comm *c, int dir) { return c->sendbuf[dir]; }
 double *comm_recvbuf(Comm *c, int dir) { return c->recvbuf[dir]; }
 size_t comm_bufcount(const Comm *c) { return c->bufcount; }
 
+// one of the communicator's staging buffers (a caller may exchange buffers of its own, of any size: the floats' messages)
+static bool comm_owns(const Comm *c, const double *p) {
+  for (int d = 0; d < 8; d++)
+    if (p == c->sendbuf[d] || p == c->recvbuf[d]) return true;
+  return false;
+}
+
 // all messages of one exchange.  Entry k describes the edge in direction tag = d of this tile: its send buffer travels in
 // direction d, its receive buffer takes the peer's message travelling in direction OPP[d] (the peer's entry for OPP[d])
 int comm_exchange(Comm *c, const Xfer *x, int nx) {
@@ -306,7 +313,7 @@ int comm_exchange(Comm *c, const Xfer *x, int nx) {
       msom_set_error("local exchange: rank %d tag %d (%zu doubles) is paired by posting order with rank %d tag %d, not tag %d: a halo for the wrong edge",
                      c->rank, x[k].tag, x[k].count, sr, src->tag, COMM_OPP[x[k].tag & 7]);
       err = MSOM_ERR_COMM;
-    } else if (x[k].count > c->bufcount) {
+    } else if (x[k].count > c->bufcount && (comm_owns(c, x[k].send) || comm_owns(c, x[k].recv))) {
       msom_set_error("local exchange: rank %d tag %d: %zu doubles exceed the %zu of a message buffer", c->rank, x[k].tag, x[k].count, c->bufcount);
       err = MSOM_ERR_COMM;
     } else if (hipMemcpyAsync(x[k].recv, src->send, x[k].count * sizeof(double), hipMemcpyDeviceToDevice, c->st) != hipSuccess) {

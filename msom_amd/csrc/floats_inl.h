@@ -67,6 +67,31 @@ FL_HD static inline FloatsCell floats_locate(double x, double y, const FloatsGeo
   return c;
 }
 
+// ---- on tiles ("On tiles").  The domain of g.nx x g.ny cells is cut into px x py tiles of tnx x tny cells; tile
+// (ix, iy) has the origin (ix * tnx, iy * tny).  A float belongs to the tile that holds the lower corner of its dual cell, the ghost
+// column -1 of a wall counted to the first tile: with i0 of floats_axis on the GLOBAL geometry (walls: [-1, gnx - 1], periodic:
+// [0, gnx - 1]) the owner column is max(i0, 0) / tnx, rows likewise.  The owner then reads the local corners i0 - ox, i0 + 1 - ox in
+// [-1, tnx]: its own cells, the wall ghost or the exchanged ghost column -- the numbers the single tile reads.
+struct FloatsTiling {
+  int px, py;      // tiles per side
+  int ix, iy;      // this tile
+  int tnx, tny;    // cells of a tile
+};
+FL_HD static inline int floats_owner_axis(int i0, int tn) { return (i0 > 0 ? i0 : 0) / tn; }
+// the tile of a located position: column and row
+FL_HD static inline void floats_owner(const FloatsCell &c, const FloatsTiling &t, int *col, int *row) {
+  *col = floats_owner_axis(c.i0, t.tnx);
+  *row = floats_owner_axis(c.j0, t.tny);
+}
+// One axis of a migration phase: the tile at `at` of `p` per side holds a float owned by `own`.  0: it stays; -1 / +1: it goes to
+// the lower / upper neighbour (periodic: the wrapped one; where both are the same tile, the upper); 2: farther than a neighbour.
+FL_HD static inline int floats_hop(int own, int at, int p, int periodic) {
+  if (own == at) return 0;
+  if (own == at + 1 || (periodic && own == (at + 1) % p)) return 1;
+  if (own == at - 1 || (periodic && own == (at - 1 + p) % p)) return -1;
+  return 2;
+}
+
 FL_HD static inline void floats_uv(double P00, double P10, double P01, double P11, double a, double b, double idx, double *u, double *v) {
   *u = -((1. - a) * (P01 - P00) + a * (P11 - P10)) * idx;
   *v = ((1. - b) * (P10 - P00) + b * (P11 - P01)) * idx;

@@ -76,15 +76,38 @@ struct FloatsDev {
   double *x, *y;     // positions at the last step boundary
   double *xh, *yh;   // positions after stage 1
   const int *layer;
-  unsigned long long *cnt;   // [0] clamped to the box, [1] lost (not finite)
+  unsigned long long *cnt;   // [0] clamped to the box, [1] lost (not finite); on tiles also [2] unsent, [3] records sent
+};
+// on tiles the arrays above are n slots: slot k < *hw with live[k] != 0 holds float id[k]; (ox, oy) is the tile's origin in cells
+struct FloatsTileDev {
+  const int *id, *live, *hw;
+  int ox, oy;
+};
+// the same slots as the migration kernels write them, with the free stack and the record counters of the two messages of a phase
+struct FloatsMig {
+  double *x, *y, *xh, *yh;
+  int *layer, *id, *live;
+  int *hw, *nfree, *free;    // high-water mark; the slots below it that are empty
+  int *msgcnt;               // [2]: records taken in the lo (W / S) and the hi (E / N) message
+  unsigned long long *cnt;
 };
 // stage 1: (xh, yh) = (x, y) + dt / 2 U(x, y); stage 2: (x, y) += dt U(xh, yh), also stored to rec[0 .. n), rec[n .. 2n) when rec is given.
-// U from psi (+ pg per corner when pg is given), natural layout with its ghost ring
+// U from psi (+ pg per corner when pg is given), natural layout with its ghost ring.  t (tiles): over the slots, fg the global
+// geometry, the record indexed by id with rec[2n + id] = 1
 void launch_floats_stage(hipStream_t st, int stage, const FloatsDev &d, int n, const double *psi, const double *pg, const NatGeom &g,
-                         const FloatsGeom &fg, double dt, double *rec);
-// at (x, y): o0 = u, o1 = v of f (+ pg) when o1 is given, else o0 = the bilinear value of f
+                         const FloatsGeom &fg, double dt, double *rec, const FloatsTileDev *t = nullptr);
+// at (x, y): o0 = u, o1 = v of f (+ pg) when o1 is given, else o0 = the bilinear value of f.  t (tiles): o0 is [3][n], indexed by id:
+// the one or two results and the presence word
 void launch_floats_interp(hipStream_t st, const FloatsDev &d, int n, const double *f, const double *pg, const NatGeom &g, const FloatsGeom &fg,
-                          double *o0, double *o1);
+                          double *o0, double *o1, const FloatsTileDev *t = nullptr);
+// one phase (x: W / E, y: S / N) of the migration pass: records of 6 doubles into the messages mlo, mhi (1 + 6 K doubles each, the
+// header word written by a one-lane launch behind it; null: no neighbour), then the records of the received messages into free slots
+void launch_floats_emigrate(hipStream_t st, const FloatsMig &s, int n, const FloatsGeom &fg, const FloatsTiling &t, int yphase, int half, double *mlo,
+                            double *mhi, int K);
+void launch_floats_immigrate(hipStream_t st, const FloatsMig &s, int n, int nl, const double *rlo, const double *rhi, int K);
+// out [3][n] (zeroed): a, b of the live slots by id and the presence word; all [nranks][3][n] -> o0, o1 [n] (o1 may be null)
+void launch_floats_scatter(hipStream_t st, const double *a, const double *b, const FloatsTileDev &t, int n, double *out);
+void launch_floats_select(hipStream_t st, const double *all, int nranks, int n, double *o0, double *o1);
 
 // ---- kernels_rhs.hip
 void launch_fill_ghost(hipStream_t st, double *f, const NatGeom &g, int nl, int bc, int walls, int depth = 1);

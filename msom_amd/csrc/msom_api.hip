@@ -65,18 +65,18 @@ static bool prof_on(const msom *m, const ProfSlot &ps) {
   if (m->profile == 2) return &ps == &m->prof_march_corr || &ps == &m->prof_march_visit || (&ps >= &m->prof_march[0] && &ps <= &m->prof_march[4]);
   return m->profile != 0;
 }
-void prof_begin(msom *m, ProfSlot &ps) {
+void prof_begin(msom *m, ProfSlot &ps, hipStream_t st) {
   if (!prof_on(m, ps)) return;
   if (ps.used + 2 > ps.ev.size()) {
     hipEvent_t a, b;
     hipEventCreate(&a); hipEventCreate(&b);
     ps.ev.push_back(a); ps.ev.push_back(b);
   }
-  hipEventRecord(ps.ev[ps.used], m->st);
+  hipEventRecord(ps.ev[ps.used], st ? st : m->st);
 }
-void prof_end(msom *m, ProfSlot &ps) {
+void prof_end(msom *m, ProfSlot &ps, hipStream_t st) {
   if (!prof_on(m, ps)) return;
-  hipEventRecord(ps.ev[ps.used + 1], m->st);
+  hipEventRecord(ps.ev[ps.used + 1], st ? st : m->st);
   ps.used += 2;
 }
 void prof_collect(msom *m, ProfSlot &ps) {
@@ -608,6 +608,11 @@ extern "C" int msom_set_option(msom_t *m, const char *key, double v) {
     m->stats_every = (int)v;
   }
   else if (!strcmp(key, "floats")) m->fl_on = m->fl && (int)v != 0;   // pauses / resumes the floats of msom_step; without floats: nothing
+  else if (!strcmp(key, "floats_tiles")) m->fl_tiles = (int)v != 0;   // before msom_floats_begin, alike on all ranks (msom_floats.h)
+  else if (!strcmp(key, "floats_msg_cap")) {
+    if (!(v >= 0) || v > 1e8) { msom_set_error("option floats_msg_cap = %g", v); return MSOM_ERR_ARG; }
+    m->fl_msg_cap = (int)v;
+  }
   else if (!strcmp(key, "ckpt_steps")) {   // msom_run: <workdir>/state.msom every that many steps (msom_state.h); 0: off
     if (!(v >= 0)) { msom_set_error("option ckpt_steps = %g", v); return MSOM_ERR_ARG; }
     m->ckpt_steps = (int)v;

@@ -174,7 +174,8 @@ std::vector<std::pair<const char *, ProfSlot *>> prof_slots(msom *m) {
           {"march3", &m->prof_march[3]}, {"march4", &m->prof_march[4]}, {"march_pl", &m->prof_march_pl}, {"march_corr", &m->prof_march_corr},
           {"march_visit", &m->prof_march_visit}, {"resid_max", &m->prof_resmax}, {"rhs", &m->prof_rhs}, {"red_prolong", &m->prof_redprol},
           {"resid_correct", &m->prof_rescorr}, {"resid_restrict", &m->prof_respre}, {"helm_relax", &m->prof_helm_relax},
-          {"helm_residual", &m->prof_helm_resid}, {"helm_coarse", &m->prof_helm_coarse}, {"floats", &m->prof_floats}};
+          {"helm_residual", &m->prof_helm_resid}, {"helm_coarse", &m->prof_helm_coarse}, {"floats", &m->prof_floats},
+          {"floats_emigrate", &m->prof_floats_emig}, {"floats_immigrate", &m->prof_floats_immig}};
 }
 extern "C" int msom_profile_reset(msom_t *m) {
   if (!m) return MSOM_ERR_ARG;

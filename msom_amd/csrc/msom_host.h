@@ -184,6 +184,8 @@ struct msom {
   // Lagrangian floats (msom_floats_*, msom_floats.hip); nothing is allocated until msom_floats_begin
   struct FloatsState *fl = nullptr;       // positions, layers, counters and the trajectory buffer
   int fl_on = 0;                          // floats begun and option "floats" not 0: rk_stage queues their two stages
+  int fl_tiles = 0;                       // option "floats_tiles": on more than one rank the floats calls are accepted and collective
+  int fl_msg_cap = 0;                     // option "floats_msg_cap": records per migration message (0: the default of msom_floats_begin)
   // vertical normal modes (msom_modes_*, msqg/eigmode.h); nothing is allocated until msom_modes_compute
   int modes_ready = 0;                    // a successful msom_modes_compute since the last msom_set_const
   int modes_compact = 0;                  // ... which left the compact form (modes_mc) rather than one array per number (modes_md)
@@ -240,6 +242,7 @@ struct msom {
   ProfSlot prof_march_corr, prof_resmax;  // last pass of the finest level with the correction folded in; max-only residual pass after it
   ProfSlot prof_rhs, prof_redprol, prof_rescorr, prof_respre;   // tendency pass, finest red+prolongation, post- / pre-cycle residual passes
   ProfSlot prof_floats;   // the floats' stages queued by msom_step (k_floats_stage)
+  ProfSlot prof_floats_emig, prof_floats_immig;   // on tiles, per phase of the migration pass: k_floats_emigrate with its header launch, k_floats_immigrate
 };
 
 // ---- what travels with one call (nothing of it is kept on the handle)
@@ -315,8 +318,8 @@ struct Lev {
 #pragma GCC visibility push(hidden)
 // msom_api.hip (core)
 int sync_stream(msom *m);
-void prof_begin(msom *m, ProfSlot &ps);
-void prof_end(msom *m, ProfSlot &ps);
+void prof_begin(msom *m, ProfSlot &ps, hipStream_t st = nullptr);   // st: the stream the timed launches go to (default: m->st)
+void prof_end(msom *m, ProfSlot &ps, hipStream_t st = nullptr);
 void prof_collect(msom *m, ProfSlot &ps);
 NatGeom make_nat(int nx, int ny);
 void comm_begin(msom *m);
