@@ -65,28 +65,9 @@ static bool prof_on(const msom *m, const ProfSlot &ps) {
   if (m->profile == 2) return &ps == &m->prof_march_corr || &ps == &m->prof_march_visit || (&ps >= &m->prof_march[0] && &ps <= &m->prof_march[4]);
   return m->profile != 0;
 }
-void prof_begin(msom *m, ProfSlot &ps, hipStream_t st) {
-  if (!prof_on(m, ps)) return;
-  if (ps.used + 2 > ps.ev.size()) {
-    hipEvent_t a, b;
-    hipEventCreate(&a); hipEventCreate(&b);
-    ps.ev.push_back(a); ps.ev.push_back(b);
-  }
-  hipEventRecord(ps.ev[ps.used], st ? st : m->st);
-}
-void prof_end(msom *m, ProfSlot &ps, hipStream_t st) {
-  if (!prof_on(m, ps)) return;
-  hipEventRecord(ps.ev[ps.used + 1], st ? st : m->st);
-  ps.used += 2;
-}
-void prof_collect(msom *m, ProfSlot &ps) {
-  hipStreamSynchronize(m->st);
-  for (size_t k = 0; k + 1 < ps.used; k += 2) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, ps.ev[k], ps.ev[k + 1]) == hipSuccess) { ps.total_ms += ms; ps.launches++; }
-  }
-  ps.used = 0;
-}
+void prof_begin(msom *m, ProfSlot &ps, hipStream_t st) { prof_slot_begin(ps, st ? st : m->st, prof_on(m, ps)); }
+void prof_end(msom *m, ProfSlot &ps, hipStream_t st) { prof_slot_end(ps, st ? st : m->st, prof_on(m, ps)); }
+void prof_collect(msom *m, ProfSlot &ps) { prof_slot_collect(ps, m->st); }
 
 static double wall_seconds() {
   struct timespec ts;

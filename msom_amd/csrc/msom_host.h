@@ -21,6 +21,7 @@
 
 #include "comm.h"
 #include "kernels.h"
+#include "prof_slot.h"
 #include "spec_inl.h"
 #include "helm_inl.h"
 
@@ -42,13 +43,6 @@
 // RES0, RES1 and UMAX[nl] are contiguous: one max all-reduce / one copy brings them to the host
 enum { SC_BSUM = 2, SC_KE = 3, SC_SCRATCH = 4, SC_RES0 = 6, SC_RES1 = 7, SC_UMAX = 8 /* MAXNL */, SC_RESF = 8 + MSOM_MAXNL /* max|res| from the fused tendency pass */, SC_LSUM = 32 /* MAXNL */, SC_SPEC = 48 /* k_step_dt: dt limit, dt, tnext, dt / 2 */, SC_COUNT = 64 };
 static_assert(SC_RESF < SC_LSUM && SC_LSUM + MSOM_MAXNL <= SC_SPEC && SC_SPEC + 4 <= SC_COUNT, "scalar slots overlap");
-
-struct ProfSlot {
-  std::vector<hipEvent_t> ev;  // pairs (start, stop)
-  size_t used = 0;
-  double total_ms = 0;
-  long launches = 0;
-};
 
 struct msom {
   Params p;

@@ -7,30 +7,14 @@
 #include "msomn_host.h"
 #include "step_dt_inl.h"
 
-static void nprof_begin(msomn *m, int slot) {
-  if (!m->profile) return;
-  NProf &ps = m->prof[slot];
-  if (ps.used + 2 > ps.ev.size()) {
-    hipEvent_t a, b;
-    hipEventCreate(&a); hipEventCreate(&b);
-    ps.ev.push_back(a); ps.ev.push_back(b);
-  }
-  hipEventRecord(ps.ev[ps.used], m->st);
-}
-static void nprof_end(msomn *m, int slot) {
-  if (!m->profile) return;
-  NProf &ps = m->prof[slot];
-  hipEventRecord(ps.ev[ps.used + 1], m->st);
-  ps.used += 2;
-}
-static void nprof_collect(msomn *m, NProf &ps) {
-  hipStreamSynchronize(m->st);
-  for (size_t k = 0; k + 1 < ps.used; k += 2) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, ps.ev[k], ps.ev[k + 1]) == hipSuccess) { ps.total_ms += ms; ps.launches++; }
-  }
-  ps.used = 0;
-}
+// option profile: the launches queued while a Timed lives count as one launch of the slot (on = false: not timed)
+struct Timed {
+  msomn *m;
+  ProfSlot &ps;
+  const bool on;
+  Timed(msomn *m, int slot, bool on = true) : m(m), ps(m->prof[slot]), on(on && m->profile) { prof_slot_begin(ps, m->st, this->on); }
+  ~Timed() { prof_slot_end(ps, m->st, on); }
+};
 
 // the square grid of n x n cells (msomn_tiles.hip has the rectangular forms a tile uses)
 static NatGeom node_geom(int n) { return node_geom_rect(n, n); }
@@ -173,7 +157,6 @@ static msomn *node_create(const NodeParams &p, const char *text, int px = 1, int
   m->D = p.L0 / p.N;
   m->tolerance = p.TOLERANCE;
   m->nlev = ntile_nlev(p.N);  // coarsest level: 2 x 2 cells, one interior vertex
-  m->kg = m->nlev;
   memset(&m->lc, 0, sizeof m->lc);
   if (hipStreamCreate(&m->st) != hipSuccess) { msom_set_error("hipStreamCreate failed"); delete m; return nullptr; }
   if (nt_setup(m, px, py, rank, id128) != MSOM_OK || node_alloc(m) != MSOM_OK) { msomn_destroy(m); return nullptr; }
@@ -265,7 +248,7 @@ extern "C" int msomn_profile_read(msomn_t *m, const char *slot, double *avg_ms, 
   if (!m || !slot) return MSOM_ERR_ARG;
   for (int k = 0; k < NP_COUNT; k++)
     if (!strcmp(slot, NP_NAMES[k])) {
-      nprof_collect(m, m->prof[k]);
+      prof_slot_collect(m->prof[k], m->st);
       if (avg_ms) *avg_ms = m->prof[k].launches ? m->prof[k].total_ms / m->prof[k].launches : 0.;
       if (launches) *launches = m->prof[k].launches;
       return MSOM_OK;
@@ -409,10 +392,8 @@ static int need_psi_alt(msomn *m) {
 // rhs_pv_baroclinic qg_baroclinic_ms.h:104-196 / rhs_pv_barotropic qg_barotropic.h:16-29
 static int rhs_pv_body(msomn *m, double *q, double *dq);
 static int rhs_pv(msomn *m, double *q, double *dq) {
-  nprof_begin(m, NP_RHS);
-  const int r = rhs_pv_body(m, q, dq);
-  nprof_end(m, NP_RHS);
-  return r;
+  Timed t(m, NP_RHS);
+  return rhs_pv_body(m, q, dq);
 }
 static int rhs_pv_body(msomn *m, double *q, double *dq) {
   const NodeParams &p = m->p;
@@ -466,107 +447,78 @@ static int rhs_pv_body(msomn *m, double *q, double *dq) {
 }
 
 // ---- nodal multigrid
-static void relax_level(msomn *m, int k, double *da, const double *res) {
+// one colour half-sweep of level k on L.da, in the level's layout.  timed = false: the left-over half-sweep of a chained path
+static void colour_pass(msomn *m, int k, int c, bool timed = true) {
   NLevel &L = m->lev[k];
-  for (int c = 0; c < 2; c++) {
-    if (k == 0) nprof_begin(m, NP_RELAX);
-    if (L.sp) launch_n_relax(m->st, da, res, L.mask_s, L.S2_s, L.ga, m->nl, c, L.D, m->iRd2_low, m->lc, 1, L.S2row, L.walls);
-    else launch_n_relax(m->st, da, res, L.mask, L.S2, L.g, m->nl, c, L.D, m->iRd2_low, m->lc, 0, L.S2row, L.walls);
-    if (k == 0) nprof_end(m, NP_RELAX);
-    // a tiled level: the other colour of the neighbours reads this one across the edge (an error stays in msom_last_error and
-    // stops the solve at its next reduction)
-    if (L.tiled && nt_exchange(m, da, L.ga, L.sp, m->nl)) m->tile_err = 1;
+  {
+    Timed t(m, NP_RELAX, timed && k == 0);
+    if (L.sp) launch_n_relax(m->st, L.da, L.res, L.mask_s, L.S2_s, L.ga, m->nl, c, L.D, m->iRd2_low, m->lc, 1, L.S2row, L.walls);
+    else launch_n_relax(m->st, L.da, L.res, L.mask, L.S2, L.g, m->nl, c, L.D, m->iRd2_low, m->lc, 0, L.S2row, L.walls);
   }
+  // a tiled level: the other colour of the neighbours reads this one across the edge (an error stays in msom_last_error and
+  // stops the solve at its next reduction)
+  if (L.tiled && nt_exchange(m, L.da, L.ga, L.sp, m->nl)) m->tile_err = 1;
 }
-// nsweeps red-black sweeps of level k on L.da.  Wide levels: LDS-tiled passes of 2 (or 1) sweeps, out of place
-// (L.da <-> L.da2 swap, L.da always the current one); narrow levels: one launch per colour.
+// nh colour half-sweeps of L, the first of colour c, as out-of-place passes of up to kmax: pass(c, K, left) goes from L.da to L.da2,
+// which then change places (L.da always the current one); `left` half-sweeps follow it.  A single left-over half-sweep runs in
+// place as the colour pass single(c); no_tail: a pass gives one half-sweep away so that none is left over
+template <class Pass, class Single>
+static void chained_passes(NLevel &L, int nh, int c, int kmax, bool no_tail, Pass pass, Single single) {
+  while (nh >= 2) {
+    int K = nh < kmax ? nh : kmax;
+    if (no_tail && nh - K == 1 && K > 2) K--;
+    pass(c, K, nh - K);
+    std::swap(L.da, L.da2);
+    nh -= K; c = (c + K) & 1;
+  }
+  if (nh == 1) single(c);
+}
+// nsweeps red-black sweeps of level k on L.da, by the path sweep_path names.
 // prolong = 1: the correction of level k + 1 has not been prolongated yet; the first colour pass does it on the fly (split levels)
 static void relax_sweeps(msomn *m, int k, int nsweeps, int prolong = 0) {
   NLevel &L = m->lev[k];
-  const int path = sweep_path(m, k);
-  if (path == NRP_MARCH_S) {
-    // chained colour half-sweeps (round 3): the first colour may ride with the prolongation as before; the remaining 2 nsweeps - 1
-    // (or 2 nsweeps) half-sweeps go in passes of up to 4, ping-ponging between the two correction buffers; a pass that is
-    // followed by more half-sweeps stores only the colour of its last one; a single left-over half-sweep runs in place
-    int nh = 2 * nsweeps, c = 0;
-    if (prolong && nsweeps >= 1) {
-      const NLevel &C = m->lev[k + 1];
-      if (k == 0) nprof_begin(m, NP_RELAX_PROLONG);
-      launch_n_relax_prolong(m->st, L.da, L.res, L.mask_s, L.S2_s, L.ga, m->nl, L.D, m->iRd2_low, m->lc, L.S2row, C.da, C.ga, C.sp);
-      if (k == 0) nprof_end(m, NP_RELAX_PROLONG);
-      nh--; c = 1;
-    }
-    while (nh >= 2) {
-      const int kmax = node_march_kmax(m, L);
-      int K = nh < kmax ? nh : kmax;
-      if (nh - K == 1 && K > 2 && !m->node_march_tail1) K--;   // leave no single half-sweep behind (node_march_tail1 = 1: do, it then runs as a colour pass)
-      if (k == 0) nprof_begin(m, NP_MARCH);
-      // a pass stores only the colour of its last half-sweep if ANOTHER PASS follows (which recomputes the other colour before anything
-      // reads it); a single colour pass that follows updates interior vertices only, so the pass before it stores both colours
-      launch_n_relax_march_s(m->st, L.da, L.da2, L.res, L.mask_s, L.ga, m->nl, c, K, L.D, m->iRd2_low, m->lc, L.S2row, nh - K >= 2, m->node_march_rows);
-      if (k == 0) nprof_end(m, NP_MARCH);
+  int path = sweep_path(m, k);
+  if (path == NRP_TILE_S && nsweeps < 2) path = NRP_SPLIT;
+  int nh = 2 * nsweeps, c = 0;
+  if (prolong && nsweeps >= 1) {
+    const NLevel &C = m->lev[k + 1];
+    Timed t(m, NP_RELAX_PROLONG, k == 0);
+    launch_n_relax_prolong(m->st, L.da, L.res, L.mask_s, L.S2_s, L.ga, m->nl, L.D, m->iRd2_low, m->lc, L.S2row, C.da, C.ga, C.sp);
+    nh--; c = 1;
+  }
+  const auto single = [&](int c1) { colour_pass(m, k, c1, false); };
+  switch (path) {
+  case NRP_MARCH_S:
+    // chained colour half-sweeps (round 3) in passes of up to node_march_kmax; node_march_tail1 = 1 lets a single half-sweep stay
+    // behind (9 as 4 + 4 + 1, not 4 + 3 + 2).  A pass stores only the colour of its last half-sweep if ANOTHER PASS follows (which
+    // recomputes the other colour before anything reads it); a single colour pass that follows updates interior vertices only, so
+    // the pass before it stores both colours
+    chained_passes(L, nh, c, node_march_kmax(m, L), !m->node_march_tail1, [&](int c1, int K, int left) {
+      Timed t(m, NP_MARCH, k == 0);
+      launch_n_relax_march_s(m->st, L.da, L.da2, L.res, L.mask_s, L.ga, m->nl, c1, K, L.D, m->iRd2_low, m->lc, L.S2row, left >= 2, m->node_march_rows);
+    }, single);
+    return;
+  case NRP_TILE_S:
+    // launch-bound split levels (round 3): LDS-tiled passes (k_n_relax_tile_s) of up to node_tile_k half-sweeps; a left-over single
+    // half-sweep is cheaper as a colour pass than as a tile pass
+    chained_passes(L, nh, c, m->node_tile_k, false, [&](int c1, int K, int) {
+      Timed t(m, NP_RELAX, k == 0);
+      launch_n_relax_tile_s(m->st, L.da, L.da2, L.res, L.mask_s, L.ga, m->nl, c1, K, L.D, m->iRd2_low, m->lc, L.S2row);
+    }, single);
+    return;
+  case NRP_MARCH:   // natural layout, passes of up to 4, never a single half-sweep left behind
+    chained_passes(L, nh, c, 4, true, [&](int c1, int K, int) {
+      launch_n_relax_march(m->st, L.da, L.da2, L.res, L.mask, L.S2, L.g, m->nl, c1, K, L.D, m->iRd2_low, m->lc, m->node_march_rows);
+    }, [&](int c1) { launch_n_relax(m->st, L.da, L.res, L.mask, L.S2, L.g, m->nl, c1, L.D, m->iRd2_low, m->lc); });
+    return;
+  case NRP_TILE:    // natural layout, LDS-tiled passes of 2 (or 1) whole sweeps
+    for (int s = 0; s < nsweeps;) {
+      s += launch_n_relax_tile(m->st, L.da, L.da2, L.res, L.mask, L.S2, L.g, m->nl, nsweeps - s >= 2 ? 2 : 1, L.D, m->iRd2_low, m->lc);
       std::swap(L.da, L.da2);
-      nh -= K; c = (c + K) & 1;
-    }
-    if (nh == 1) launch_n_relax(m->st, L.da, L.res, L.mask_s, L.S2_s, L.ga, m->nl, c, L.D, m->iRd2_low, m->lc, 1, L.S2row);
-    return;
-  }
-  if (path == NRP_TILE_S && nsweeps >= 2) {
-    // launch-bound split levels (round 3): first colour with the prolongation as before, then LDS-tiled passes
-    // (k_n_relax_tile_s, out of place; up to node_tile_k = 8 half-sweeps each), a single left-over half-sweep as a colour pass
-    int nh = 2 * nsweeps, c = 0;
-    if (prolong) {
-      const NLevel &C = m->lev[k + 1];
-      if (k == 0) nprof_begin(m, NP_RELAX_PROLONG);
-      launch_n_relax_prolong(m->st, L.da, L.res, L.mask_s, L.S2_s, L.ga, m->nl, L.D, m->iRd2_low, m->lc, L.S2row, C.da, C.ga, C.sp);
-      if (k == 0) nprof_end(m, NP_RELAX_PROLONG);
-      nh--; c = 1;
-    }
-    while (nh >= 2) {
-      const int K = nh < m->node_tile_k ? nh : m->node_tile_k;   // a left-over single half-sweep is cheaper as a colour pass than as a tile pass
-      if (k == 0) nprof_begin(m, NP_RELAX);
-      launch_n_relax_tile_s(m->st, L.da, L.da2, L.res, L.mask_s, L.ga, m->nl, c, K, L.D, m->iRd2_low, m->lc, L.S2row);
-      if (k == 0) nprof_end(m, NP_RELAX);
-      std::swap(L.da, L.da2);
-      nh -= K; c = (c + K) & 1;
-    }
-    if (nh == 1) launch_n_relax(m->st, L.da, L.res, L.mask_s, L.S2_s, L.ga, m->nl, c, L.D, m->iRd2_low, m->lc, 1, L.S2row);
-    return;
-  }
-  if (path == NRP_SPLIT || path == NRP_TILE_S) {  // split layout: a colour pass already moves only the bytes it uses
-    for (int s = 0; s < nsweeps; s++) {
-      if (prolong && s == 0) {
-        const NLevel &C = m->lev[k + 1];
-        if (k == 0) nprof_begin(m, NP_RELAX_PROLONG);
-        launch_n_relax_prolong(m->st, L.da, L.res, L.mask_s, L.S2_s, L.ga, m->nl, L.D, m->iRd2_low, m->lc, L.S2row, C.da, C.ga, C.sp);
-        if (k == 0) { nprof_end(m, NP_RELAX_PROLONG); nprof_begin(m, NP_RELAX); }
-        launch_n_relax(m->st, L.da, L.res, L.mask_s, L.S2_s, L.ga, m->nl, 1, L.D, m->iRd2_low, m->lc, 1, L.S2row);
-        if (k == 0) nprof_end(m, NP_RELAX);
-      } else relax_level(m, k, L.da, L.res);
     }
     return;
-  }
-  if (path == NRP_MARCH) {
-    // 2 nsweeps colour half-sweeps (red, black, red, ...) in passes of up to 4, ping-ponging between the two correction buffers
-    int nh = 2 * nsweeps, c = 0;
-    while (nh >= 2) {
-      int K = nh < 4 ? nh : 4;
-      if (nh - K == 1) K--;            // never leave a single half-sweep behind
-      launch_n_relax_march(m->st, L.da, L.da2, L.res, L.mask, L.S2, L.g, m->nl, c, K, L.D, m->iRd2_low, m->lc, m->node_march_rows);
-      std::swap(L.da, L.da2);
-      nh -= K; c = (c + K) & 1;
-    }
-    if (nh == 1) launch_n_relax(m->st, L.da, L.res, L.mask, L.S2, L.g, m->nl, c, L.D, m->iRd2_low, m->lc);
-    return;
-  }
-  if (path == NRP_COLOR) {
-    for (int s = 0; s < nsweeps; s++) relax_level(m, k, L.da, L.res);
-    return;
-  }
-  for (int s = 0; s < nsweeps;) {
-    const int want = nsweeps - s >= 2 ? 2 : 1;
-    s += launch_n_relax_tile(m->st, L.da, L.da2, L.res, L.mask, L.S2, L.g, m->nl, want, L.D, m->iRd2_low, m->lc);
-    std::swap(L.da, L.da2);
+  default:          // NRP_COLOR, NRP_SPLIT: one launch per colour (the split layout already moves only the bytes a colour uses)
+    for (; nh > 0; nh--, c ^= 1) colour_pass(m, k, c);
   }
 }
 // layout of the correction / residual of every level (option node_split; da and res hold nothing between cycles, so the choice
@@ -601,29 +553,32 @@ static int choose_layouts(msomn *m) {
   HIPCHK(hipGetLastError());
   return MSOM_OK;
 }
-// tiles: levels below the gather level kg hold the tile's window, kg and up the global grid (the same values on every rank, the ones
-// the single tile holds): the level-kg mask and S2 are restricted on the tiles, gathered once, and the coarser ones built from them
-static int build_levels_tiled(msomn *m) {
+// mask and S2 of every level from those of level 0.  Tiles: levels below the gather level kg hold the tile's window, kg and up the
+// global grid (the same values on every rank, the ones the single tile holds): the level-kg mask and S2 are restricted on the tiles,
+// gathered once, and the coarser ones built from them as the single tile builds all of its levels (kg = 0, allocated by node_alloc)
+static int build_levels(msomn *m) {
   int r;
-  m->kg = ntile_kg(m->N, m->px, m->py, m->mg_coarse);
-  for (int k = 0; k < m->nlev; k++) free_level(m->lev[k], k);
-  nt_free_gather(m);
-  for (int k = 0; k <= m->nlev; k++) {   // k == nlev: the piece, the tile's window of level kg
-    const bool piece = k == m->nlev;
-    if (!piece && k >= m->kg) { if ((r = alloc_level(m, m->lev[k], k, node_geom(m->N >> k)))) return r; m->lev[k].tiled = 0; m->lev[k].walls = WALL_ALL; continue; }
-    const NodeTile t = ntile_level(m->N, m->px, m->py, m->rank, piece ? m->kg : k);
-    NLevel &L = piece ? m->piece : m->lev[k];
-    if ((r = alloc_level(m, L, piece ? m->kg : k, node_geom_rect(t.tx, t.ty)))) return r;
-    L.tiled = 1; L.walls = m->walls;
+  m->kg = m->ntiles > 1 ? ntile_kg(m->N, m->px, m->py, m->mg_coarse) : 0;
+  if (m->ntiles > 1) {   // which levels live on the tile depends on the option mg_coarse: allocated here
+    for (int k = 0; k < m->nlev; k++) free_level(m->lev[k], k);
+    nt_free_gather(m);
+    for (int k = 0; k <= m->nlev; k++) {   // k == nlev: the piece, the tile's window of level kg
+      const bool piece = k == m->nlev;
+      if (!piece && k >= m->kg) { if ((r = alloc_level(m, m->lev[k], k, node_geom(m->N >> k)))) return r; m->lev[k].tiled = 0; m->lev[k].walls = WALL_ALL; continue; }
+      const NodeTile t = ntile_level(m->N, m->px, m->py, m->rank, piece ? m->kg : k);
+      NLevel &L = piece ? m->piece : m->lev[k];
+      if ((r = alloc_level(m, L, piece ? m->kg : k, node_geom_rect(t.tx, t.ty)))) return r;
+      L.tiled = 1; L.walls = m->walls;
+    }
+    m->gcount = (size_t)(m->nl > m->nlm ? m->nl : m->nlm) * m->piece.g.nx * m->piece.g.ny;
+    HIPCHK(hipMalloc((void **)&m->gsend, m->gcount * sizeof(double)));
+    HIPCHK(hipMalloc((void **)&m->grecv, m->gcount * m->ntiles * sizeof(double)));
   }
-  m->gcount = (size_t)(m->nl > m->nlm ? m->nl : m->nlm) * m->piece.g.nx * m->piece.g.ny;
-  HIPCHK(hipMalloc((void **)&m->gsend, m->gcount * sizeof(double)));
-  HIPCHK(hipMalloc((void **)&m->grecv, m->gcount * m->ntiles * sizeof(double)));
   launch_n_bnd_const(m->st, m->f[MSOMN_MASK], m->g, 1, 0., 0, m->walls);
   // the static fields the tendency reads across the tile edges (the inputs were transformed in place since msomn_set_field)
   for (int f : {MSOMN_MASK, MSOMN_S2, MSOMN_TOPO, MSOMN_PSIPG})
     if ((r = nt_exchange(m, m->f[f], m->g, 0, m->fl[f]))) return r;
-  for (int k = 1; k <= m->kg; k++) {
+  for (int k = 1; k <= m->kg; k++) {   // the tiled levels (one tile: none)
     NLevel &F = m->lev[k - 1], &C = k < m->kg ? m->lev[k] : m->piece;
     launch_n_restrict(m->st, F.mask, F.g, C.mask, C.g, 1, 1);   // the 9-point full weighting reads the halo with its corners
     launch_n_bnd_const(m->st, C.mask, C.g, 1, 0., 0, m->walls);
@@ -634,19 +589,9 @@ static int build_levels_tiled(msomn *m) {
     }
   }
   NLevel &G = m->lev[m->kg];
-  if ((r = nt_gather(m, m->piece.mask, m->piece.g, 1, G.mask, G.g))) return r;
-  if (m->nl > 1 && (r = nt_gather(m, m->piece.S2, m->piece.g, m->nlm, G.S2, G.g))) return r;
-  for (int k = m->kg + 1; k < m->nlev; k++) {
-    launch_n_restrict(m->st, m->lev[k - 1].mask, m->lev[k - 1].g, m->lev[k].mask, m->lev[k].g, 1, 1);
-    launch_n_bnd_const(m->st, m->lev[k].mask, m->lev[k].g, 1, 0.);
-    if (m->nl > 1) launch_n_restrict(m->st, m->lev[k - 1].S2, m->lev[k - 1].g, m->lev[k].S2, m->lev[k].g, m->nlm, 2);
-  }
-  return choose_layouts(m);
-}
-static int build_levels(msomn *m) {
-  if (m->ntiles > 1) return build_levels_tiled(m);
-  launch_n_bnd_const(m->st, m->f[MSOMN_MASK], m->g, 1, 0.);
-  for (int k = 1; k < m->nlev; k++) {
+  if (m->ntiles > 1 && (r = nt_gather(m, m->piece.mask, m->piece.g, 1, G.mask, G.g))) return r;
+  if (m->ntiles > 1 && m->nl > 1 && (r = nt_gather(m, m->piece.S2, m->piece.g, m->nlm, G.S2, G.g))) return r;
+  for (int k = m->kg + 1; k < m->nlev; k++) {   // the levels that live whole on this rank
     launch_n_restrict(m->st, m->lev[k - 1].mask, m->lev[k - 1].g, m->lev[k].mask, m->lev[k].g, 1, 1);
     launch_n_bnd_const(m->st, m->lev[k].mask, m->lev[k].g, 1, 0.);
     if (m->nl > 1) launch_n_restrict(m->st, m->lev[k - 1].S2, m->lev[k - 1].g, m->lev[k].S2, m->lev[k].g, m->nlm, 2);
@@ -666,58 +611,100 @@ static int download_lev(msomn *m, NLevel &L, const double *src, double *a) {
   launch_n_relayout(m->st, src, L.ga, 1, L.da2, L.g, 0, m->nl);
   return download_g(m, L.da2, L.g, m->nl, a);
 }
-// The levels kg .. nlev - 1 of a tiled handle's cycle, on the global grid and the same on every rank: lev[kg].res -> lev[kg].da by the
-// launches the single tile makes for these levels -- the one-launch group where coarse_first qualifies (it starts at kg at the
-// earliest), level by level otherwise
-static int gathered_solve(msomn *m, int nrelax) {
-  const int nl = m->nl, nlev = m->nlev, kg = m->kg;
-  const int kc = std::max(coarse_first(m), kg);
-  for (int k = kg + 1; k < nlev && k <= kc; k++) launch_n_restrict(m->st, m->lev[k - 1].res, m->lev[k - 1].ga, m->lev[k].res, m->lev[k].ga, nl, 0, 0, 0, 1);
-  if (kc < nlev) {
-    NCoarseArgs ca;
-    ca.n = nlev - kc; ca.iRd2 = m->iRd2_low; ca.lc = m->lc;
-    for (int k = kc; k < nlev; k++) {
-      NLevel &L = m->lev[k];
-      ca.lev[k - kc] = NCoarseLev{L.da, L.res, L.mask, L.S2, L.g, L.D * L.D};
-    }
-    nprof_begin(m, NP_COARSE);
-    launch_n_mg_coarse(m->st, ca, nrelax, nl);
-    nprof_end(m, NP_COARSE);
-    if (kc > kg) launch_n_prolong(m->st, m->lev[kc].da, m->lev[kc].ga, m->lev[kc - 1].da, m->lev[kc - 1].ga, nl);
-  } else HIPCHK(hipMemsetAsync(m->lev[nlev - 1].da, 0, m->lev[nlev - 1].g.ls * nl * sizeof(double), m->st));
-  for (int k = (kc < nlev ? kc : nlev) - 1; k >= kg; k--) {
-    relax_sweeps(m, k, nrelax);
-    if (k > kg) launch_n_prolong(m->st, m->lev[k].da, m->lev[k].ga, m->lev[k - 1].da, m->lev[k - 1].ga, nl);
+// the passes over level 0 with the model's field a: each carries the layout of res / da, the row tables and the tile's walls
+static void residual_pass(msomn *m, const double *a, const double *b, int zb) {
+  NLevel &L = m->lev[0];
+  launch_n_residual(m->st, a, b, L.mask, L.S2, L.res, m->d_scal + NSC_RES, m->g, m->nl, m->D, m->iRd2_low, m->lc, L.sp ? &L.ga : nullptr, L.S2row, zb, m->walls);
+}
+static void correct_pass(msomn *m, double *a) {
+  NLevel &L = m->lev[0];
+  Timed t(m, NP_CORRECT);
+  launch_n_correct(m->st, a, L.da, m->g, m->nl, m->psi_bc, L.sp ? &L.ga : nullptr, m->walls);
+}
+// The levels k0 .. nlev - 1 of a cycle, which live whole on this rank (one tile: k0 = 0; tiles: k0 = kg, the gathered global grid, the
+// same on every rank): lev[k0].res -> lev[k0].da.  Down to the one-launch group where coarse_first qualifies (it starts at k0 at the
+// earliest), level by level otherwise; every level in its own layout.  whole_restrict is the way down on its own: the single tile
+// queues it before it knows whether the cycle runs
+static void whole_restrict(msomn *m, int k0) {
+  const int kc = std::max(coarse_first(m), k0);
+  for (int k = k0 + 1; k < m->nlev && k <= kc; k++) {
+    NLevel &F = m->lev[k - 1], &C = m->lev[k];
+    launch_n_restrict(m->st, F.res, F.ga, C.res, C.ga, m->nl, 0, F.sp, C.sp, 1);
   }
-  HIPCHK(hipGetLastError());
+}
+static void coarse_group(msomn *m, int kc, int nrelax) {
+  NCoarseArgs ca;
+  ca.n = m->nlev - kc; ca.iRd2 = m->iRd2_low; ca.lc = m->lc;
+  for (int k = kc; k < m->nlev; k++) {
+    NLevel &L = m->lev[k];
+    ca.lev[k - kc] = NCoarseLev{L.da, L.res, L.mask, L.S2, L.g, L.D * L.D};
+  }
+  Timed t(m, NP_COARSE);
+  launch_n_mg_coarse(m->st, ca, nrelax, m->nl);
+}
+static int whole_solve(msomn *m, int k0, int nrelax, bool restricted) {
+  const int nl = m->nl, nlev = m->nlev, kc = std::max(coarse_first(m), k0);
+  if (!restricted) whole_restrict(m, k0);
+  if (kc < nlev) coarse_group(m, kc, nrelax);
+  else HIPCHK(hipMemsetAsync(m->lev[nlev - 1].da, 0, m->lev[nlev - 1].g.ls * nl * sizeof(double), m->st));
+  // prolongation into level kf: a launch, or (split levels, option node_pfused) left to the first colour pass of that level
+  auto prolong_into = [&](int kf) -> int {
+    NLevel &C = m->lev[kf + 1], &F = m->lev[kf];
+    if (F.sp && m->node_pfused && nrelax >= 1) return 1;
+    launch_n_prolong(m->st, C.da, C.ga, F.da, F.ga, nl, C.sp, F.sp);
+    return 0;
+  };
+  int pending = (kc < nlev && kc > k0) ? prolong_into(kc - 1) : 0;
+  for (int k = (kc < nlev ? kc : nlev) - 1; k >= k0; k--) {
+    relax_sweeps(m, k, nrelax, pending);
+    pending = k > k0 ? prolong_into(k - 1) : 0;
+  }
   return MSOM_OK;
 }
-// vpoisson on tiles.  Per cycle: halo of a, residual, all-reduce of max |res| (every rank takes the same decision); the residual goes
-// down the tiled levels (halo, restriction), the level-kg pieces are gathered, every rank solves the gathered levels, takes its
-// window of the level-kg correction and goes up the tiled levels (prolongation, halo, colour passes with a halo each); a += da.
-static int vpoisson_tiled(msomn *m, double *&a, const double *b) {
+// vpoisson, nodal-poisson.h:19-143: residual first, then (unless converged) one cycle; the correction a += da of a cycle waits for
+// the next residual pass, or for the end of the loop.  On tiles (kg > 0) every rank takes the same decision from the all-reduced
+// max |res|; the residual then goes down the tiled levels (halo, restriction), the level-kg pieces are gathered, every rank solves
+// the gathered levels, takes its window of the level-kg correction and goes up the tiled levels (prolongation, halo, colour passes
+// with a halo each).  One tile: kg = 0, no tiled levels, no gather, the exchanges are no-ops.
+static int vpoisson(msomn *m, double *&a, const double *b) {
   msom_mgstats mg;
   mg.sum = HUGE_VAL; mg.resa = HUGE_VAL; mg.resb = 0; mg.nrelax = m->nrelax;
   const int nl = m->nl, kg = m->kg;
+  const bool tiles = m->ntiles > 1;
   NLevel &L0 = m->lev[0], &P = m->piece, &G = m->lev[kg];
   const NodeTile tg = ntile_level(m->N, m->px, m->py, m->rank, kg);
   bool pending_correct = false;
   int r;
   m->tile_err = 0;
-  auto correct = [&]() {
-    nprof_begin(m, NP_CORRECT);
-    launch_n_correct(m->st, a, L0.da, m->g, nl, m->psi_bc, L0.sp ? &L0.ga : nullptr, m->walls);
-    nprof_end(m, NP_CORRECT);
-  };
   for (mg.i = 0; mg.i < m->nitermax; mg.i++) {
     HIPCHK(hipMemsetAsync(m->d_scal + NSC_RES, 0, sizeof(double), m->st));
-    if (pending_correct) correct();
+    // the correction of the previous cycle rides in this residual pass (option node_corr_fused, off on tiles; a second psi buffer)
+    if (pending_correct && m->node_corr_fused) {
+      if ((r = need_psi_alt(m))) return r;
+      Timed t(m, NP_CORR_RES);
+      launch_n_correct_residual(m->st, a, m->psi_alt, L0.da, L0.sp ? &L0.ga : nullptr, m->psi_bc, b, L0.mask, L0.S2, L0.res, m->d_scal + NSC_RES, m->g, nl, m->D,
+                                m->iRd2_low, m->lc, L0.sp ? &L0.ga : nullptr, L0.S2row, node_corr_march(m));
+      std::swap(a, m->psi_alt);
+    } else {
+      if (pending_correct) correct_pass(m, a);
+      if ((r = nt_exchange(m, a, m->g, 0, nl))) return r;
+      Timed t(m, NP_RESIDUAL);
+      residual_pass(m, a, b, 1);
+    }
     pending_correct = false;
-    if ((r = nt_exchange(m, a, m->g, 0, nl))) return r;
-    nprof_begin(m, NP_RESIDUAL);
-    launch_n_residual(m->st, a, b, L0.mask, L0.S2, L0.res, m->d_scal + NSC_RES, m->g, nl, m->D, m->iRd2_low, m->lc, L0.sp ? &L0.ga : nullptr, L0.S2row, 1, m->walls);
-    nprof_end(m, NP_RESIDUAL);
-    if ((r = nt_reduce(m, NSC_RES, 1, RED_MAX))) return r;
+    if (tiles) {   // reduce, decide, and only then post the exchanges of the cycle
+      if ((r = nt_reduce(m, NSC_RES, 1, RED_MAX))) return r;
+    } else {
+      // max |res| travels to the host; the restrictions of the cycle that follows unless the solve ends here are queued behind the copy
+      // (round 3): the GPU works through them while the host waits for the number and decides -- they write nothing but the coarse levels'
+      // residuals, which nobody reads if the solve is over.  (boundary_level of the residual: the pass above stored 0 on the boundary
+      // vertices, zb = 1; the boundary vertices of every coarser level end up 0 as well)
+      HIPCHK(hipMemcpyAsync(m->h_scal + NSC_RES, m->d_scal + NSC_RES, sizeof(double), hipMemcpyDeviceToHost, m->st));
+      if (!m->ev_res) HIPCHK(hipEventCreateWithFlags(&m->ev_res, hipEventDisableTiming));
+      HIPCHK(hipEventRecord(m->ev_res, m->st));
+      whole_restrict(m, 0);
+      HIPCHK(hipEventSynchronize(m->ev_res));
+    }
     const double max = m->h_scal[NSC_RES];
     mg.resa = max;
     if (mg.i == 0) mg.resb = max;
@@ -727,8 +714,9 @@ static int vpoisson_tiled(msomn *m, double *&a, const double *b) {
       if ((r = nt_exchange(m, F.res, F.ga, F.sp, nl))) return r;
       launch_n_restrict(m->st, F.res, F.ga, C.res, C.ga, nl, 0, F.sp, C.sp, 1, m->walls);
     }
-    if ((r = nt_gather(m, P.res, P.g, nl, G.res, G.g)) || (r = gathered_solve(m, mg.nrelax))) return r;
-    launch_n_extract(m->st, G.da, G.g, P.da, P.g, nl, tg.ox, tg.oy);
+    if (tiles && (r = nt_gather(m, P.res, P.g, nl, G.res, G.g))) return r;
+    if ((r = whole_solve(m, kg, mg.nrelax, !tiles))) return r;
+    if (tiles) launch_n_extract(m->st, G.da, G.g, P.da, P.g, nl, tg.ox, tg.oy);
     for (int k = kg - 1; k >= 0; k--) {
       NLevel &C = k + 1 < kg ? m->lev[k + 1] : P, &L = m->lev[k];
       launch_n_prolong(m->st, C.da, C.ga, L.da, L.ga, nl, C.sp, L.sp, m->walls);
@@ -738,89 +726,7 @@ static int vpoisson_tiled(msomn *m, double *&a, const double *b) {
     }
     pending_correct = true;
   }
-  if (pending_correct) correct();
-  HIPCHK(hipGetLastError());
-  if (mg.resa > m->tolerance && !m->quiet)
-    fprintf(stderr, "Convergence for psi not reached.\nmg.i = %d, mg.resb: %g mg.resa: %g\n", mg.i, mg.resb, mg.resa);
-  m->mg = mg;
-  return MSOM_OK;
-}
-// vpoisson, nodal-poisson.h:19-143: residual first, then (unless converged) one cycle
-static int vpoisson(msomn *m, double *&a, const double *b) {
-  if (m->ntiles > 1) return vpoisson_tiled(m, a, b);
-  msom_mgstats mg;
-  mg.sum = HUGE_VAL; mg.resa = HUGE_VAL; mg.resb = 0; mg.nrelax = m->nrelax;
-  const int nl = m->nl, nlev = m->nlev;
-  bool pending_correct = false;
-  for (mg.i = 0; mg.i < m->nitermax; mg.i++) {
-    HIPCHK(hipMemsetAsync(m->d_scal + NSC_RES, 0, sizeof(double), m->st));
-    // the correction of the previous cycle rides in this residual pass (option node_corr_fused; a second psi buffer)
-    if (pending_correct && m->node_corr_fused) {
-      int ra = need_psi_alt(m);
-      if (ra) return ra;
-      nprof_begin(m, NP_CORR_RES);
-      launch_n_correct_residual(m->st, a, m->psi_alt, m->lev[0].da, m->lev[0].sp ? &m->lev[0].ga : nullptr, m->psi_bc, b, m->lev[0].mask, m->lev[0].S2,
-                                m->lev[0].res, m->d_scal + NSC_RES, m->g, nl, m->D, m->iRd2_low, m->lc, m->lev[0].sp ? &m->lev[0].ga : nullptr, m->lev[0].S2row,
-                                node_corr_march(m));
-      nprof_end(m, NP_CORR_RES);
-      std::swap(a, m->psi_alt);
-    } else {
-      if (pending_correct) {
-        nprof_begin(m, NP_CORRECT);
-        launch_n_correct(m->st, a, m->lev[0].da, m->g, nl, m->psi_bc, m->lev[0].sp ? &m->lev[0].ga : nullptr);
-        nprof_end(m, NP_CORRECT);
-      }
-      nprof_begin(m, NP_RESIDUAL);
-      launch_n_residual(m->st, a, b, m->lev[0].mask, m->lev[0].S2, m->lev[0].res, m->d_scal + NSC_RES, m->g, nl, m->D, m->iRd2_low, m->lc,
-                        m->lev[0].sp ? &m->lev[0].ga : nullptr, m->lev[0].S2row, 1);
-      nprof_end(m, NP_RESIDUAL);
-    }
-    pending_correct = false;
-    // max |res| travels to the host; the restrictions of the cycle that follows unless the solve ends here are queued behind the copy
-    // (round 3): the GPU works through them while the host waits for the number and decides -- they write nothing but the coarse levels'
-    // residuals, which nobody reads if the solve is over.  (boundary_level of the residual: the pass above stored 0 on the boundary
-    // vertices, zb = 1; the boundary vertices of every coarser level end up 0 as well)
-    HIPCHK(hipMemcpyAsync(m->h_scal + NSC_RES, m->d_scal + NSC_RES, sizeof(double), hipMemcpyDeviceToHost, m->st));
-    if (!m->ev_res) HIPCHK(hipEventCreateWithFlags(&m->ev_res, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(m->ev_res, m->st));
-    // kc: first level of the group that one workgroup handles in one launch (<= 33^2 vertices, at least two levels)
-    const int kc = coarse_first(m);
-    for (int k = 1; k < nlev && k <= kc; k++)
-      launch_n_restrict(m->st, m->lev[k - 1].res, m->lev[k - 1].ga, m->lev[k].res, m->lev[k].ga, nl, 0, m->lev[k - 1].sp, m->lev[k].sp, 1);
-    HIPCHK(hipEventSynchronize(m->ev_res));
-    const double max = m->h_scal[NSC_RES];
-    mg.resa = max;
-    if (mg.i == 0) mg.resb = max;
-    if (max < m->tolerance && mg.i >= m->nitermin) break;
-    if (kc < nlev) {
-      NCoarseArgs ca;
-      ca.n = nlev - kc; ca.iRd2 = m->iRd2_low; ca.lc = m->lc;
-      for (int k = kc; k < nlev; k++) {
-        NLevel &L = m->lev[k];
-        ca.lev[k - kc] = NCoarseLev{L.da, L.res, L.mask, L.S2, L.g, L.D * L.D};
-      }
-      nprof_begin(m, NP_COARSE);
-      launch_n_mg_coarse(m->st, ca, mg.nrelax, nl);
-      nprof_end(m, NP_COARSE);
-    } else HIPCHK(hipMemsetAsync(m->lev[nlev - 1].da, 0, m->lev[nlev - 1].g.ls * nl * sizeof(double), m->st));
-    // prolongation into level kf: a launch, or (split levels) left to the first colour pass of that level
-    auto prolong_into = [&](int kf) -> int {
-      if (m->lev[kf].sp && m->node_pfused && mg.nrelax >= 1) return 1;
-      launch_n_prolong(m->st, m->lev[kf + 1].da, m->lev[kf + 1].ga, m->lev[kf].da, m->lev[kf].ga, nl, m->lev[kf + 1].sp, m->lev[kf].sp);
-      return 0;
-    };
-    int pending = (kc < nlev && kc > 0) ? prolong_into(kc - 1) : 0;
-    for (int k = (kc < nlev ? kc : nlev) - 1; k >= 0; k--) {
-      relax_sweeps(m, k, mg.nrelax, pending);
-      pending = k > 0 ? prolong_into(k - 1) : 0;
-    }
-    pending_correct = true;   // a += da: with the next residual, or below if the iteration count ends the loop
-  }
-  if (pending_correct) {
-    nprof_begin(m, NP_CORRECT);
-    launch_n_correct(m->st, a, m->lev[0].da, m->g, nl, m->psi_bc, m->lev[0].sp ? &m->lev[0].ga : nullptr);
-    nprof_end(m, NP_CORRECT);
-  }
+  if (pending_correct) correct_pass(m, a);
   HIPCHK(hipGetLastError());
   if (mg.resa > m->tolerance && !m->quiet)
     fprintf(stderr, "Convergence for psi not reached.\nmg.i = %d, mg.resb: %g mg.resa: %g\n", mg.i, mg.resb, mg.resa);
@@ -1333,8 +1239,7 @@ extern "C" int msomn_dbg_residual(msomn_t *m, const double *a, const double *b, 
   if ((r = upload_g(m, m->f[MSOMN_TMP], m->g, m->nl, a)) || (r = upload_g(m, m->f[MSOMN_DQ], m->g, m->nl, b))) return r;
   HIPCHK(hipMemsetAsync(m->d_scal + NSC_RES, 0, sizeof(double), m->st));
   if ((r = nt_exchange(m, m->f[MSOMN_TMP], m->g, 0, m->nl))) return r;
-  launch_n_residual(m->st, m->f[MSOMN_TMP], m->f[MSOMN_DQ], m->lev[0].mask, m->lev[0].S2, m->lev[0].res, m->d_scal + NSC_RES, m->g, m->nl, m->D, m->iRd2_low,
-                    m->lc, m->lev[0].sp ? &m->lev[0].ga : nullptr, m->lev[0].S2row, 0, m->walls);
+  residual_pass(m, m->f[MSOMN_TMP], m->f[MSOMN_DQ], 0);
   if ((r = nt_reduce(m, NSC_RES, 1, RED_MAX))) return r;
   if (maxres) *maxres = m->h_scal[NSC_RES];
   return download_lev(m, m->lev[0], m->lev[0].res, res);

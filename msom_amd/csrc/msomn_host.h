@@ -1,6 +1,6 @@
 // msomn_host.h -- the vertex-grid handle (struct msomn) and the host helpers its units share: msom_node.hip (model and multigrid),
 // msomn_tiles.hip (the model on tiles: decomposition, halo exchange, gather), msomn_io.hip (NetCDF IO and the driver msomn_run),
-// msomn_state.hip (state file, include/msomn_state.h).  Not installed.
+// msomn_state.hip (state file, include/msomn_state.h).  The profile slots (prof_slot.h) are the layered model's.  Not installed.
 #ifndef MSOMN_HOST_H
 #define MSOMN_HOST_H
 
@@ -18,6 +18,7 @@
 #include "comm.h"
 #include "kernels.h"
 #include "node_tile_inl.h"
+#include "prof_slot.h"
 
 #define HIPCHK(x)                                                                          \
   do {                                                                                     \
@@ -47,19 +48,13 @@ struct NLevel {
 enum { NSC_RES = 0, NSC_UMAX = 1, NSC_KE = 2, NSC_DIAG = 3 /* 3 slots */, NSC_COUNT = 8 };
 
 // option profile: HIP-event pairs around the finest-level launches of the vertex model (bench.py's per-kernel entries)
-struct NProf {
-  std::vector<hipEvent_t> ev;
-  size_t used = 0;
-  double total_ms = 0;
-  long launches = 0;
-};
 enum { NP_RELAX, NP_RELAX_PROLONG, NP_RESIDUAL, NP_CORRECT, NP_RHS, NP_COARSE, NP_MARCH, NP_CORR_RES, NP_COUNT };
 static const char *const NP_NAMES[NP_COUNT] = {"relax_fine", "relax_prolong_fine", "residual", "correct", "rhs", "coarse", "march_fine", "correct_residual"};
 
 struct msomn {
   NodeParams p;
   int profile = 0;
-  NProf prof[NP_COUNT];
+  ProfSlot prof[NP_COUNT];
   std::string params_text;
   int N = 0, nl = 1, nlm = 1;
   double D = 0, psi_bc = 0., iRd2_low = 0.;
@@ -120,7 +115,7 @@ struct msomn {
   // no communicator, and none of the rest is used
   int px = 1, py = 1, rank = 0, ntiles = 1, walls = WALL_ALL;
   int ox = 0, oy = 0;          // global index of the tile's vertex (0, 0)
-  int kg = 0;                  // gather level (msomn_set_const): levels below live on the tiles, kg and up on the global grid on every rank
+  int kg = 0;                  // gather level (msomn_set_const): levels below live on the tiles, kg and up on the global grid on every rank; one tile: 0
   Comm *comm = nullptr;
   int nb[4] = {-1, -1, -1, -1};   // ranks behind the W, E, S, N sides (DIR_* of comm.h), -1: wall
   NLevel piece;                // the tile's window of level kg in the natural layout: what the rank gives to and takes from the gather

@@ -376,7 +376,7 @@ def test_split_layout_levels(nl, N, split, s2x, strict):
 @pytest.mark.parametrize("nl,N", [(1, 128), (3, 256), (6, 128), (2, 512), (3, 1024)])
 def test_chained_half_sweeps_in_the_split_layout(nl, N, strict):
     """k_n_relax_march_s (round 3): K = 2..4 colour half-sweeps of a split level per pass, lane = vertex pair, residual and mask in
-    register delay lines, S2 by row tables.  1, 2, 3 and 5 sweeps against the oracle's colour-by-colour sweeps and against the
+    register delay lines, S2 by row tables.  1 to 5 sweeps against the oracle's colour-by-colour sweeps and against the
     colour-per-launch kernels, level by level; then whole RK2 steps (prolongation folded into the first colour, then passes of
     4 + 4 + one single colour) against the oracle and against the run without the pass"""
     if nl not in orn.NODE_LAYERS:
@@ -390,17 +390,21 @@ def test_chained_half_sweeps_in_the_split_layout(nl, N, strict):
             continue
         da, res = rng.standard_normal((nl, n1, n1)), rng.standard_normal((nl, n1, n1))
         da[:, 0, :] = da[:, -1, :] = da[:, :, 0] = da[:, :, -1] = 0      # the correction's boundary vertices are 0 (boundary_level)
-        for ns in (1, 2, 3, 5):
+        for ns in (1, 2, 3, 4, 5):
             g.set_option("node_march_s", 65)
             got, ref = g.dbg_relax(k, da, res, ns), o.relax(k, da, res, ns)
             same(got, ref, strict, 1e-10)
-            g.set_option("node_march_s", 0)         # -> LDS-tiled passes of up to 4 half-sweeps (k_n_relax_tile_s), nl <= 4
+            g.set_option("node_march_s", 0)         # -> LDS-tiled passes of up to 8 half-sweeps (k_n_relax_tile_s), nl <= 4
             tiled = g.dbg_relax(k, da, res, ns)
             same(tiled, ref, strict, 1e-10)
+            g.set_option("node_tile_k", 3)          # -> of up to 3: 2, 4, 6, 8, 10 half-sweeps as 2 / 3+1 / 3+3 / 3+3+2 / 3+3+3+1
+            tiled3 = g.dbg_relax(k, da, res, ns)
+            g.set_option("node_tile_k", 8)
+            same(tiled3, ref, strict, 1e-10)
             g.set_option("node_tile_s", 0)          # -> one launch per colour
             plain = g.dbg_relax(k, da, res, ns)
             g.set_option("node_tile_s", 65)
-            assert (np.array_equal(got, plain) and np.array_equal(tiled, plain)) or not strict
+            assert (np.array_equal(got, plain) and np.array_equal(tiled, plain) and np.array_equal(tiled3, plain)) or not strict
     g.set_option("node_march_s", 65)
     o.set_tnext(float("inf")); g.set_tnext(float("inf"))
     for _ in range(2):

@@ -3,6 +3,7 @@ in-process transport.  Gate of SURVEY 8(e): the tiled result equals the single-t
 a tile holds the vertices on its interior edges, every holder computes them, and the assembly checks that all holders agree.
 The inputs are not symmetric about any seam: noise on psi, an island across a vertical seam, land over the cross point, a bay in
 the land along the north wall, topography, psi_pg and the time-dependent wind."""
+import functools
 import os
 import threading
 import time
@@ -241,6 +242,94 @@ def test_calls_one_by_one_equal_the_single_tile():
         assert (o["st_inv"], o["dt"], o["st_upd"]) == (ref["st_inv"], ref["dt"], ref["st_upd"])
     for f in ("q0", "psi1", "dq", "qpred"):
         assert np.array_equal(node_assemble([o[f] for o in out], N, px, py, check_shared=True), ref[f]), f
+
+
+def exits_body(g, rank):
+    """One q, inverted from psi = 0 four times, so that the solve's loop leaves by each of its ways: the iteration count, NITERMIN
+    holding it open, convergence, and converged before the first cycle.  Per solve: mgstats, psi, halo exchanges posted."""
+    q = g.get("Q")
+    res = dict(opts={k: g.param(k) for k in OPTION_KEYS}, agg=g.param("agg_level"))
+
+    def solve(tag, zero_psi=True, **opts):
+        for k, v in dict(dict(NITERMAX=100, NITERMIN=1), **opts).items():
+            g.set_option(k, v)
+        if zero_psi:
+            g.set("PSI", np.zeros(g.shape("PSI")))
+        g.set("Q", q)
+        before = g.param("exchanges")
+        s = g.invert_q()
+        res[tag] = dict(st=(s.i, s.resb, s.resa), psi=g.get("PSI"), exchanges=g.param("exchanges") - before)
+    solve("itermax", NITERMAX=2, TOLERANCE=1e-30)
+    solve("itermin", NITERMIN=3, TOLERANCE=1e-1)
+    solve("converged", TOLERANCE=1e-9)
+    solve("again", zero_psi=False, NITERMIN=0, TOLERANCE=1e-9)   # NITERMIN = 0: the loop may leave before its first cycle
+    return res
+
+
+@functools.lru_cache(maxsize=None)
+def solve_exits(px, py, strict):
+    N, nl = 64, 2
+    par, inp = params(N, nl), inputs(N, nl)
+    out = run_tiled(par, px, py, inp, strict, exits_body, opts=dict(mg_coarse=8))
+    assert out[0]["agg"] == 3
+    ref = exits_body(single(par, inp, strict, out[0]["opts"]), 0)
+    for tag in ("itermax", "itermin", "converged", "again"):
+        print(px, py, strict, tag, "tiles", out[0][tag]["st"], out[0][tag]["exchanges"], "one tile", ref[tag]["st"])
+    return out, ref
+
+
+def assembled_psi(out, tag, px, py):
+    return node_assemble([o[tag]["psi"] for o in out], 64, px, py, check_shared=True)
+
+
+EXIT_CASES = [(2, 2), (2, 1)]
+
+
+@pytest.mark.parametrize("strict", [True, False])
+@pytest.mark.parametrize("px,py", EXIT_CASES)
+def test_solve_ended_by_the_iteration_count(px, py, strict):
+    out, ref = solve_exits(px, py, strict)
+    assert ref["itermax"]["st"][0] == 2 and ref["itermax"]["st"][2] > 1e-30
+    assert all(o["itermax"]["st"] == ref["itermax"]["st"] for o in out)
+    # the correction of the last cycle is applied after the loop
+    assert np.array_equal(assembled_psi(out, "itermax", px, py), ref["itermax"]["psi"])
+    assert np.any(ref["itermax"]["psi"] != 0)
+
+
+@pytest.mark.parametrize("strict", [True, False])
+@pytest.mark.parametrize("px,py", EXIT_CASES)
+def test_solve_that_starts_converged_runs_no_cycle(px, py, strict):
+    out, ref = solve_exits(px, py, strict)
+    for r in [ref] + out:
+        assert r["converged"]["st"][0] >= 1 and r["converged"]["st"][2] < 1e-9
+        assert r["again"]["st"][0] == 0
+        assert np.array_equal(r["again"]["psi"], r["converged"]["psi"])
+    assert all(o["again"]["st"] == ref["again"]["st"] for o in out)
+    assert np.array_equal(assembled_psi(out, "converged", px, py), ref["converged"]["psi"])
+
+
+@pytest.mark.parametrize("strict", [True, False])
+@pytest.mark.parametrize("px,py", EXIT_CASES)
+def test_nitermin_holds_the_solve_open(px, py, strict):
+    out, ref = solve_exits(px, py, strict)
+    assert ref["itermin"]["st"][0] == 3
+    assert all(o["itermin"]["st"] == ref["itermin"]["st"] for o in out)
+    assert np.array_equal(assembled_psi(out, "itermin", px, py), ref["itermin"]["psi"])
+
+
+@pytest.mark.parametrize("strict", [True, False])
+@pytest.mark.parametrize("px,py", EXIT_CASES)
+def test_exchanges_of_a_solve(px, py, strict):
+    """Per cycle one exchange of psi for the residual pass, kg of the residual going down and, per tiled level going up, one after the
+    prolongation and one per colour of the nrelax = 5 sweeps: 1 + 12 kg.  A solve that ends by convergence has posted the exchange of
+    its last residual pass and nothing of the cycle it does not run; one that ends by NITERMAX has not computed another residual."""
+    out, ref = solve_exits(px, py, strict)
+    per_cycle = 1 + 12 * int(out[0]["agg"])
+    for o in out:
+        assert o["itermax"]["exchanges"] == o["itermax"]["st"][0] * per_cycle
+        for tag in ("itermin", "converged", "again"):
+            assert o[tag]["exchanges"] == o[tag]["st"][0] * per_cycle + 1, tag
+    assert all(ref[tag]["exchanges"] == 0 for tag in ("itermax", "itermin", "converged", "again"))
 
 
 ERR_CONFIG = -3
