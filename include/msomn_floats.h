@@ -1,0 +1,77 @@
+/*
+ * msomn_floats.h -- Lagrangian floats of the vertex-grid model (msomn_*, qg-node/), advected on the device with the model's own RK2
+ * stages; one tile; exported by both libraries.  The twin of msom_floats.h on the grid that has a land mask, islands and coastlines.
+ * DESIGN.md section 8l has the arithmetic, where the stages sit in msomn_step and the counted memory traffic.
+ *
+ * A float is a position (x, y) in the domain [0, L0] x [0, L0] and a layer in [0, nl).  The domain has N x N cells, vertex i sits at
+ * i * Delta and psi lives on the vertices, so the velocity is that of the bilinear psi of the grid cell the float is in: no ghost
+ * ring is read.  With idx = N / L0 (rounded once),
+ *     xi = x * idx;  f = floor(xi) clamped to [0, N - 1];  i0 = (int) f;  a = xi - f clamped to [0, 1]      (j0, b likewise from y)
+ *     u = -((1 - a) * (P01 - P00) + a * (P11 - P10)) * idx
+ *     v =  ((1 - b) * (P10 - P00) + b * (P11 - P01)) * idx    Pcd = P[layer][j0 + d][i0 + c]
+ *   P is MSOMN_PSI as the handle holds it, plus MSOMN_PSIPG per corner where a psi_pg has been set.  It is not multiplied by the mask:
+ *   the model has masked psi already, and the floats read what the model holds.  A float at x = L0 reads column N with weight exactly
+ *   1; no column beyond N is ever read, whatever the bits of x.  Inside a cell u = -dpsi/dy does not depend on y, v = dpsi/dx not on x,
+ *   and du/dx = -dv/dy = -(P11 - P10 - P01 + P00) * idx^2: the velocity of the bilinear psi is non-divergent.  Three things follow:
+ *   - a cell with four land corners has velocity exactly +-0 when no psi_pg is set: a float started there stays, bit for bit;
+ *   - the velocity normal to an edge along which P is constant is exactly +-0 on that edge: a float on a domain wall, or on a coast
+ *     edge between two land vertices, slides along it;
+ *   - x * idx is a single rounding with nothing to fuse: the product and the strict build locate the same cell for the same position.
+ * One msomn_step moves every float by its two stages, with the step's dt and the two stream functions the step inverts:
+ *     stage 1: (xh, yh) = (x, y) + dt / 2 U(x, y; psi_n)        stage 2: (x, y) += dt U(xh, yh; psi_{n + 1/2})
+ *   Stage 1 is queued behind the step's first msomn_update (psi_n inverted, masked, sides set; dt fixed), stage 2 behind its second
+ *   msomn_update AND its final msomn_advance; no host wait is added, and a handle without floats makes the launches it always made.
+ *   Both results are clamped to the box (counted in "floats_clamped", once per float and stage).  A result that is not finite makes
+ *   the float lost: both coordinates become NaN and stay so, nothing is read for it, "floats_lost" counts it once.
+ *
+ * msomn_floats_begin: n >= 1 floats after msomn_set_const (else MSOM_ERR_STATE).  x, y [n] doubles, layer [n] ints, host or device
+ *   pointers.  A value that is not finite, a position outside the box or a layer outside [0, nl): MSOM_ERR_ARG, nothing is allocated
+ *   and earlier floats stay.  A start in a land cell is accepted.  A second begin replaces the first.  Sets option "floats" = 1.
+ * msomn_floats_end: frees everything (as msomn_destroy and msomn_set_const do); without floats: MSOM_OK.
+ * msomn_floats_get: the current positions in the caller's order, x, y [n], host or device.  Waits for the stream.
+ * msomn_floats_velocity: (u, v) [n] at the current positions from the psi (+ psi_pg) the handle holds now.
+ * msomn_floats_sample: out [n] = (1 - b) * ((1 - a) * P00 + a * P10) + b * ((1 - a) * P01 + a * P11) of any field of nl layers, in
+ *   each float's layer, as the handle holds it.  A lost float gives NaN in both calls.
+ * msomn_floats_stage: the advection by hand, for callers that drive msomn_update / msomn_advance themselves: stage 1 or 2 above with
+ *   the psi the handle holds at the call.  Stage 2 without a stage 1 since msomn_floats_begin or the last stage 2: MSOM_ERR_STATE.
+ * msomn_floats_record: a trajectory buffer [capacity][2 or 3][n] on the device; field: a field of nl layers to record along the
+ *   trajectories, or < 0 for positions only.  Record 0 is the positions at the call and the sample of the field at them; after that
+ *   one record is written behind every `every`-th msomn_step that moves the floats, by its stage-2 kernel: the new position and the
+ *   bilinear value of the field there, in the float's layer.  At that point MSOMN_Q is q_{n + 1}, so a recorded q is q_{n + 1} at
+ *   x_{n + 1}: PV on parcels.  Any other field is sampled as the handle holds it then; MSOMN_PSI is psi_{n + 1/2}.  A full buffer
+ *   stops recording: "floats_dropped" counts the records that found no room.  Times are kept on the host.
+ * msomn_floats_track: records first .. first + count - 1: t [count] (host memory), x, y, val [count][n] (host or device); any of the
+ *   four may be NULL.  val on a recording without a field: MSOM_ERR_ARG.
+ * msomn_get_param: "floats" (n, 0: none), "floats_records", "floats_dropped"; "floats_clamped", "floats_lost" (each waits for the
+ *   stream); "floats_on_land": the floats that are not lost and whose current cell has mask == 0 at all four corners, counted on
+ *   the device at the call.  msomn_set_option("floats", 0) pauses the stages of msomn_step, 1 resumes them; accepted and without
+ *   effect on a handle without floats.
+ * Errors: null handle or array, n < 1, stage not 1 or 2, dt not finite, every < 1, capacity < 1, a field that has not nl layers, a
+ *   range outside the records written: MSOM_ERR_ARG; any call but begin / end without floats: MSOM_ERR_STATE; a handle of more than
+ *   one tile: MSOM_ERR_CONFIG from every call, no field changed.  Every call names itself in msom_last_error.
+ * The floats are not part of the state file: msomn_state_save writes the same bytes with and without them, msomn_state_load leaves
+ *   them alone, and msomn_floats_get before the save, msomn_floats_begin after the load, at a step boundary, continues with the same
+ *   bits.
+ */
+#ifndef MSOMN_FLOATS_H
+#define MSOMN_FLOATS_H
+
+#include "msom.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+int msomn_floats_begin(msomn_t *m, int n, const double *x, const double *y, const int *layer);
+int msomn_floats_end(msomn_t *m);
+int msomn_floats_get(msomn_t *m, double *x, double *y);
+int msomn_floats_velocity(msomn_t *m, double *u, double *v);
+int msomn_floats_sample(msomn_t *m, int field, double *out);
+int msomn_floats_stage(msomn_t *m, int stage, double dt);
+int msomn_floats_record(msomn_t *m, int every, int capacity, int field);
+int msomn_floats_track(msomn_t *m, int first, int count, double *t, double *x, double *y, double *val);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

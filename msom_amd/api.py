@@ -209,6 +209,15 @@ def load_library(strict=False):
         "msomn_state_load": (ci, [vp, cs]),
         "msomn_create_from_state": (vp, [cs]),
         "msomn_state_dbg_flip": (ci, [vp, C.c_long]),
+        # Lagrangian floats of the vertex model (include/msomn_floats.h)
+        "msomn_floats_begin": (ci, [vp, ci, vp, vp, vp]),
+        "msomn_floats_end": (ci, [vp]),
+        "msomn_floats_get": (ci, [vp, vp, vp]),
+        "msomn_floats_velocity": (ci, [vp, vp, vp]),
+        "msomn_floats_sample": (ci, [vp, ci, vp]),
+        "msomn_floats_stage": (ci, [vp, ci, cd]),
+        "msomn_floats_record": (ci, [vp, ci, ci, ci]),
+        "msomn_floats_track": (ci, [vp, ci, ci, _dp, vp, vp, vp]),
     }
     for fn, (res, args) in sig.items():
         f = getattr(L, fn)  # AttributeError if the library does not export a declared symbol
@@ -1056,6 +1065,65 @@ class NodeQG:
         a = np.empty((self.nl, self.ny, self.nx)) if out is None else out
         self._chk(self.L.msomn_stats_get(self.h, int(which), _ptr(a)))
         return a
+
+    # -- Lagrangian floats advected on the device with the model's RK2 stages (include/msomn_floats.h); one tile
+    def floats_begin(self, x, y, layer):
+        """n floats at (x, y) in [0, L0]^2, layer[k] in [0, nl); host arrays or device tensors (float64, float64, int32).  From here
+        on every step() moves them; set_option("floats", 0) pauses that.  A start on land is accepted"""
+        if not hasattr(layer, "data_ptr"):
+            layer = np.ascontiguousarray(layer, dtype=np.int32)
+        x, y = _f64(x), _f64(y)
+        n = int(x.shape[0])
+        if tuple(x.shape) != (n,) or tuple(y.shape) != (n,) or tuple(layer.shape) != (n,):
+            raise ValueError(f"x, y, layer of shapes {tuple(x.shape)}, {tuple(y.shape)}, {tuple(layer.shape)}: want three [n]")
+        self._chk(self.L.msomn_floats_begin(self.h, n, _ptr(x), _ptr(y), _ptr(layer)))
+        self._floats_field = False   # a begin drops the trajectory buffer
+
+    def floats_end(self):
+        self._chk(self.L.msomn_floats_end(self.h))
+
+    def _floats_n(self):
+        return max(int(self.param("floats")), 0)
+
+    def floats_get(self):
+        """(x, y): the current positions in the caller's order"""
+        x, y = np.empty(self._floats_n()), np.empty(self._floats_n())
+        self._chk(self.L.msomn_floats_get(self.h, _ptr(x), _ptr(y)))
+        return x, y
+
+    def floats_velocity(self):
+        """(u, v) at the current positions from the PSI (+ PSIPG) the model holds now"""
+        u, v = np.empty(self._floats_n()), np.empty(self._floats_n())
+        self._chk(self.L.msomn_floats_velocity(self.h, _ptr(u), _ptr(v)))
+        return u, v
+
+    def floats_sample(self, field):
+        """the bilinear interpolation of a field of nl layers at the floats, each in its layer"""
+        out = np.empty(self._floats_n())
+        self._chk(self.L.msomn_floats_sample(self.h, self._fid(field), _ptr(out)))
+        return out
+
+    def floats_stage(self, stage, dt):
+        """the advection by hand: stage 1 (xh = x + dt / 2 U(x)) after the first update(), stage 2 (x += dt U(xh)) after the second
+        update() and the final advance()"""
+        self._chk(self.L.msomn_floats_stage(self.h, int(stage), float(dt)))
+
+    def floats_record(self, every=1, capacity=1, field=None):
+        """a trajectory buffer of `capacity` records on the device: record 0 now, then one behind every `every`-th step(); field: a
+        field of nl layers whose value at the new positions is recorded with them ("Q": PV on parcels)"""
+        self._chk(self.L.msomn_floats_record(self.h, int(every), int(capacity), -1 if field is None else self._fid(field)))
+        self._floats_field = field is not None
+
+    def floats_track(self, first=0, count=None):
+        """(t[count], X[count][n], Y[count][n]) of records first .. first + count - 1 (count None: all that are written), and
+        V[count][n] as a fourth when a field is recorded"""
+        if count is None:
+            count = int(self.param("floats_records")) - first
+        n, c = self._floats_n(), max(count, 0)
+        t, x, y = np.empty(c), np.empty((c, n)), np.empty((c, n))
+        v = np.empty((c, n)) if getattr(self, "_floats_field", False) else None
+        self._chk(self.L.msomn_floats_track(self.h, int(first), int(count), t.ctypes.data_as(_dp), _ptr(x), _ptr(y), _ptr(v)))
+        return (t, x, y) if v is None else (t, x, y, v)
 
     def diag1d(self):
         out = (C.c_double * 3)()

@@ -123,4 +123,46 @@ FL_HD static inline int floats_move(double bx, double by, double u, double v, do
   return flag;
 }
 
+// ---- on the vertex grid (msomn_floats_*, include/msomn_floats.h).  The domain [0, L0]^2 has N x N cells, vertex i
+// sits at i Delta and psi lives on the vertices: the bilinear psi of a grid cell is the interpolant, no ghost ring is read and no
+// - 0.5 appears.  With idx = N / L0 rounded once on the host, one axis is
+//     xi = x * idx;  f = floor(xi) clamped as a double to [0, N - 1];  i0 = (int)f;  a = xi - f clamped to [0, 1]
+// and the corners are Pcd = P[layer][j0 + d][i0 + c], vertices in [0, N].  a is clamped, so a float at x = L0 reads column N with weight
+// exactly 1 even if L0 * idx rounds above N, and no pad column is ever read; f is clamped as a double, before the conversion to int,
+// for the reason floats_axis gives.  Velocity, value and stage move are floats_uv, floats_bilinear and floats_move with
+// FloatsGeom{N, N, 0, idx, L0, L0}.  What follows:
+//   - a cell whose four corners hold the same P (land: psi is masked to 0 there and no psipg is set) has velocity exactly +-0: every
+//     difference in floats_uv is an exact zero;
+//   - along an edge on which P is constant (a domain wall, a coast edge between two land vertices) the normal velocity is exactly +-0:
+//     on the edge the weight is exactly 0 (or 1), the other edge's difference is multiplied by it and the edge's own difference is 0;
+//   - x * idx is one rounding, formed without contraction in both builds: the product and the strict build locate the same cell for
+//     the same position.
+// (contraction is switched off here because the product is also the operand of floats_finite's xi - xi: fused, that difference would be
+// fma(x, idx, -xi), the rounding error of the product instead of zero, and every float with an inexact product would count as lost)
+FL_HD static inline bool nfloats_axis(double x, double idx, int n, int *i0, double *a) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+  *i0 = 0;
+  *a = 0.;
+  const double xi = x * idx;
+  if (!floats_finite(xi)) return false;
+  double f = floor(xi);
+  if (!(f >= 0.)) f = 0.;
+  if (f > (double)(n - 1)) f = (double)(n - 1);
+  double w = xi - f;
+  if (!(w >= 0.)) w = 0.;
+  if (w > 1.) w = 1.;
+  *i0 = (int)f;
+  *a = w;
+  return true;
+}
+FL_HD static inline FloatsCell nfloats_locate(double x, double y, const FloatsGeom &g) {
+  FloatsCell c;
+  const bool okx = nfloats_axis(x, g.idx, g.nx, &c.i0, &c.a);
+  const bool oky = nfloats_axis(y, g.idx, g.ny, &c.j0, &c.b);
+  c.ok = okx && oky;
+  return c;
+}
+
 #endif

@@ -109,6 +109,19 @@ void launch_floats_immigrate(hipStream_t st, const FloatsMig &s, int n, int nl, 
 void launch_floats_scatter(hipStream_t st, const double *a, const double *b, const FloatsTileDev &t, int n, double *out);
 void launch_floats_select(hipStream_t st, const double *all, int nranks, int n, double *o0, double *o1);
 
+// ---- kernels_node_floats.hip: Lagrangian floats of the vertex-grid model (msomn_floats_*).  g: the natural layout of the level-0
+// fields, fg = {N, N, 0, N / L0, L0, L0}; psi, pg, f, rf: fields of nl layers, mk: the mask (one layer)
+// stage 1: (xh, yh) = (x, y) + dt / 2 U(x, y); stage 2: (x, y) += dt U(xh, yh), also stored to rec[0 .. n), rec[n .. 2n) when rec is given,
+// with the bilinear value of rf at the new position in rec[2n .. 3n) when rf is given too
+void launch_nfloats_stage(hipStream_t st, int stage, const FloatsDev &d, int n, const double *psi, const double *pg, const NatGeom &g,
+                          const FloatsGeom &fg, double dt, double *rec, const double *rf);
+// at (x, y): o0 = u, o1 = v of f (+ pg) when o1 is given, else o0 = the bilinear value of f
+void launch_nfloats_interp(hipStream_t st, const FloatsDev &d, int n, const double *f, const double *pg, const NatGeom &g, const FloatsGeom &fg,
+                           double *o0, double *o1);
+// *out += the floats that are not lost and whose cell has mk == 0 at all four corners
+void launch_nfloats_on_land(hipStream_t st, const FloatsDev &d, int n, const double *mk, const NatGeom &g, const FloatsGeom &fg,
+                            unsigned long long *out);
+
 // ---- kernels_rhs.hip
 void launch_fill_ghost(hipStream_t st, double *f, const NatGeom &g, int nl, int bc, int walls, int depth = 1);
 void launch_fill_periodic(hipStream_t st, double *f, const NatGeom &g, int nl, int depth);

@@ -73,6 +73,7 @@ extern "C" void msomn_destroy(msomn_t *m) {
   for (size_t k = 0; k < m->lev.size(); k++) free_level(m->lev[k], (int)k);
   nt_free(m);
   nstats_drop(m);
+  nfloats_drop(m);
   for (size_t k = 0; k < m->cs.size(); k++) {
     if (m->cs[k]) (void)hipFree(m->cs[k]);
     if (m->cr[k]) (void)hipFree(m->cr[k]);
@@ -235,6 +236,9 @@ extern "C" int msomn_set_option(msomn_t *m, const char *key, double v) {
     if (!(v >= 1)) { msom_set_error("option stats_every = %g", v); return MSOM_ERR_ARG; }
     m->stats_every = (int)v;
   }
+  else if (!strcmp(key, "floats")) {   // pauses and resumes the stages of msomn_step; without floats it has no effect
+    if (m->floats) m->floats_on = (int)v != 0;
+  }
   else if (!strcmp(key, "seed")) { m->seed = (unsigned)v; srand(m->seed); }
   else if (!strcmp(key, "noise_mode")) {
     if (v != 0. && v != 1.) { msom_set_error("noise_mode = %g: 0 (serial rand() stream on the host) or 1 (device generator)", v); return MSOM_ERR_ARG; }
@@ -317,6 +321,8 @@ extern "C" double msomn_get_param(msomn_t *m, const char *k) {
   if (!strcmp(k, "stats_mask")) return m->stats_mask;
   if (!strcmp(k, "stats_bytes")) return (double)__builtin_popcount(m->stats_mask) * m->nl * m->g.ny * m->g.nx * 8;
   if (!strcmp(k, "stats_samples")) return (double)m->stats_samples;
+  // Lagrangian floats (include/msomn_floats.h): floats, floats_records, floats_dropped, floats_clamped, floats_lost, floats_on_land
+  if (double fv; nfloats_param(m, k, &fv)) return fv;
   if (!strcmp(k, "mg_coarse")) return m->mg_coarse;
   if (!strcmp(k, "node_split")) return m->node_split;
   if (!strcmp(k, "node_pfused")) return m->node_pfused;
@@ -1103,6 +1109,7 @@ extern "C" int msomn_set_const(msomn_t *m) {
   int r;
   HIPCHK(hipStreamSynchronize(m->st));   // a sample may still be running into the arrays that go
   nstats_drop(m);
+  nfloats_drop(m);
   if ((r = node_const_inputs(m)) || (r = node_const_derived(m))) return r;
   m->noise_draw = 0;
   if ((r = comp_q(m, m->f[MSOMN_PSI], m->f[MSOMN_Q]))) return r;
@@ -1182,9 +1189,13 @@ extern "C" int msomn_step(msomn_t *m, int with_forcing_event) {
   m->dt = step_dtnext(m->t, m->tnext, d, &tn);   // dtnext() [Basilisk, SURVEY App. B]
   // the automatic sample: q_n and the psi stage 1 inverted from it (masked, sides set, on tiles exchanged by the tendency), weight dt_n
   if (m->stats_on && m->stats_count++ % m->stats_every == 0 && (r = nstats_sample(m, m->dt))) return r;
+  // the floats' stage 1 reads the same psi_n, before the second update overwrites it
+  if (m->floats_on && (r = nfloats_hook(m, 1, tn))) return r;
   if ((r = msomn_advance(m, MSOMN_QPRED, MSOMN_Q, MSOMN_DQ, m->dt / 2.))) return r;
   if ((r = msomn_update(m, MSOMN_QPRED, MSOMN_DQ, m->dt, &d))) return r;
   if ((r = msomn_advance(m, MSOMN_Q, MSOMN_Q, MSOMN_DQ, m->dt))) return r;
+  // ... and their stage 2 psi_{n + 1/2}, behind the final advance: a recorded sample of q is q_{n + 1} at x_{n + 1}
+  if (m->floats_on && (r = nfloats_hook(m, 2, tn))) return r;
   m->t = tn;
   m->iter++;
   return MSOM_OK;

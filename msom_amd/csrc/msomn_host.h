@@ -1,6 +1,6 @@
 // msomn_host.h -- the vertex-grid handle (struct msomn) and the host helpers its units share: msom_node.hip (model and multigrid),
 // msomn_tiles.hip (the model on tiles: decomposition, halo exchange, gather), msomn_io.hip (NetCDF IO and the driver msomn_run),
-// msomn_state.hip (state file, include/msomn_state.h).  The profile slots (prof_slot.h) are the layered model's.  Not installed.
+// msomn_state.hip (state file, include/msomn_state.h), msomn_floats.hip (Lagrangian floats, include/msomn_floats.h).  The profile slots (prof_slot.h) are the layered model's.  Not installed.
 #ifndef MSOMN_HOST_H
 #define MSOMN_HOST_H
 
@@ -136,6 +136,9 @@ struct msomn {
   int stats_on = 0, stats_every = 1;      // options "stats", "stats_every"
   long stats_count = 0;                   // msomn_step calls seen since msomn_stats_begin (every stats_every-th one samples)
   long stats_samples = 0;                 // samples taken since msomn_stats_begin, automatic and by hand
+  // Lagrangian floats (msomn_floats_*, msomn_floats.hip); nothing is allocated until msomn_floats_begin
+  struct NFloatsState *floats = nullptr;
+  int floats_on = 0;                      // option "floats": msomn_step queues the two stages
 };
 
 // ---- msom_node.hip
@@ -169,6 +172,11 @@ int nt_refuse(const msomn *m, const char *call);
 // ---- msomn_stats.hip
 void nstats_drop(msomn *m);               // frees everything msomn_stats_begin allocated (msomn_set_const, msomn_destroy)
 int nstats_sample(msomn *m, double w);    // one sample of MSOMN_PSI / MSOMN_Q as held (halo of psi fresh), W = W + w; queued, not synchronised
+
+// ---- msomn_floats.hip
+void nfloats_drop(msomn *m);                          // frees everything msomn_floats_begin allocated (msomn_set_const, msomn_destroy)
+int nfloats_hook(msomn *m, int stage, double tnext);  // one stage of msomn_step's floats, queued on m->st with m->dt; no host wait
+bool nfloats_param(msomn *m, const char *key, double *v);   // the "floats*" keys of msomn_get_param
 
 // ---- msomn_state.hip
 // msomn_state_save with the driver record `run` (run6: tout, tdiag, tflt, directory number, records of vars.nc, bytes of diag_1d.dat)
