@@ -1,6 +1,7 @@
 /*
  * msomn_floats.h -- Lagrangian floats of the vertex-grid model (msomn_*, qg-node/), advected on the device with the model's own RK2
- * stages; one tile; exported by both libraries.  The twin of msom_floats.h on the grid that has a land mask, islands and coastlines.
+ * stages; on one tile, and with option floats_tiles on tiles; exported by both libraries.  The twin of msom_floats.h on the grid that
+ * has a land mask, islands and coastlines.
  * DESIGN.md section 8l has the arithmetic, where the stages sit in msomn_step and the counted memory traffic.
  *
  * A float is a position (x, y) in the domain [0, L0] x [0, L0] and a layer in [0, nl).  The domain has N x N cells, vertex i sits at
@@ -48,10 +49,38 @@
  *   effect on a handle without floats.
  * Errors: null handle or array, n < 1, stage not 1 or 2, dt not finite, every < 1, capacity < 1, a field that has not nl layers, a
  *   range outside the records written: MSOM_ERR_ARG; any call but begin / end without floats: MSOM_ERR_STATE; a handle of more than
- *   one tile: MSOM_ERR_CONFIG from every call, no field changed.  Every call names itself in msom_last_error.
+ *   one tile without option floats_tiles: MSOM_ERR_CONFIG from every call, no field changed.  Every call names itself in
+ *   msom_last_error.
  * The floats are not part of the state file: msomn_state_save writes the same bytes with and without them, msomn_state_load leaves
  *   them alone, and msomn_floats_get before the save, msomn_floats_begin after the load, at a step boundary, continues with the same
  *   bits.
+ *
+ * On tiles (msomn_create_tiled, more than one tile): msomn_set_option(m, "floats_tiles", 1), set before msomn_floats_begin and alike on
+ *   every rank, makes the eight calls above accepted and COLLECTIVE: every rank makes the same call with the same arguments in the
+ *   same order, as with msomn_step.  Default 0: MSOM_ERR_CONFIG as before.  On one tile the option has no effect.  The promise is the
+ *   tile layer's: for every float id, positions, velocities, samples, records and the counters equal the single tile's bit for bit, in
+ *   the strict and the product build.
+ *   Owner: with i0, j0 of the formulas above on the GLOBAL grid, a float belongs to tile (i0 / Tx, j0 / Ty), Tx x Ty the cells of a
+ *     tile.  The owner's corners are vertices it holds, its shared edges included, so no halo is read and nothing is exchanged for the
+ *     floats but the floats themselves.  A position whose x * idx lies exactly on a seam belongs to the upper tile, x = L0 to the last.
+ *     A float is homed by the position its next stage evaluates: (xh, yh) behind stage 1, (x, y) behind stage 2.  Behind every stage,
+ *     in msomn_step and in msomn_floats_stage, one migration pass of two phases (W / E, then S / N over all residents, arrivals
+ *     included: a diagonal move needs no diagonal message) takes every float to its owner, on the handle's stream and with no host
+ *     wait but the transport's own.  Every id is resident on exactly one rank; a lost float stays where it is and is never read.
+ *   Messages have the fixed size 1 + 6 K doubles; K is option "floats_msg_cap", 0 (default): min(n, max(1024, n / 16)).  A float that
+ *     finds its message full, or whose owner is farther than a neighbouring tile, becomes lost on the sender: NaN from then on,
+ *     counted in "floats_unsent" (and not in "floats_lost").
+ *   msomn_floats_begin takes the same global arrays on every rank and keeps what the rank owns; ranks that pass different n, or of
+ *     which one refuses its arrays, all answer MSOM_ERR_ARG before any float message is posted.  get, velocity, sample and track hand
+ *     every rank the full arrays in the caller's order.  velocity and sample between a stage 1 and its stage 2 answer MSOM_ERR_STATE:
+ *     the float is homed by (xh, yh) then, and (x, y) may lie on another tile; so does msomn_floats_record with a field.  A record's
+ *     positions are written by the rank the float is resident on before the stage's pass, its field value by the new position's owner
+ *     behind it.
+ *   msomn_get_param: "floats_clamped", "floats_lost", "floats_unsent", "floats_migrated" (records sent) and "floats_on_land" are sums
+ *     over the ranks and collective; "floats_resident" is the rank's own count; "floats_tiles", "floats_msg_cap" (the K in use once
+ *     floats are begun).  On one tile: resident = n, unsent = migrated = 0.
+ *   msomn_set_const and msomn_destroy drop the floats, as on one tile.  The model is untouched: Q, PSI, dt, the multigrid statistics
+ *     and the count of halo exchanges of a run with floats equal those of the run without.
  */
 #ifndef MSOMN_FLOATS_H
 #define MSOMN_FLOATS_H

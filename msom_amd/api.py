@@ -1066,10 +1066,14 @@ class NodeQG:
         self._chk(self.L.msomn_stats_get(self.h, int(which), _ptr(a)))
         return a
 
-    # -- Lagrangian floats advected on the device with the model's RK2 stages (include/msomn_floats.h); one tile
+    # -- Lagrangian floats advected on the device with the model's RK2 stages (include/msomn_floats.h).  On a tiled handle they need
+    # set_option("floats_tiles", 1) before floats_begin (set_option("floats_msg_cap", K): records per migration message); every
+    # floats_* call and param("floats_clamped" / "floats_lost" / "floats_unsent" / "floats_migrated" / "floats_on_land") is then
+    # collective: every rank makes the same calls in the same order
     def floats_begin(self, x, y, layer):
         """n floats at (x, y) in [0, L0]^2, layer[k] in [0, nl); host arrays or device tensors (float64, float64, int32).  From here
-        on every step() moves them; set_option("floats", 0) pauses that.  A start on land is accepted"""
+        on every step() moves them; set_option("floats", 0) pauses that (on tiles: alike on all ranks).  A start on land is accepted.
+        On tiles collective: every rank passes the same global arrays and keeps the floats it owns"""
         if not hasattr(layer, "data_ptr"):
             layer = np.ascontiguousarray(layer, dtype=np.int32)
         x, y = _f64(x), _f64(y)
@@ -1086,19 +1090,21 @@ class NodeQG:
         return max(int(self.param("floats")), 0)
 
     def floats_get(self):
-        """(x, y): the current positions in the caller's order"""
+        """(x, y): the current positions in the caller's order (on tiles collective: all n floats on every rank)"""
         x, y = np.empty(self._floats_n()), np.empty(self._floats_n())
         self._chk(self.L.msomn_floats_get(self.h, _ptr(x), _ptr(y)))
         return x, y
 
     def floats_velocity(self):
-        """(u, v) at the current positions from the PSI (+ PSIPG) the model holds now"""
+        """(u, v) at the current positions from the PSI (+ PSIPG) the model holds now (on tiles collective, each float on its owner;
+        not between a stage 1 and its stage 2)"""
         u, v = np.empty(self._floats_n()), np.empty(self._floats_n())
         self._chk(self.L.msomn_floats_velocity(self.h, _ptr(u), _ptr(v)))
         return u, v
 
     def floats_sample(self, field):
-        """the bilinear interpolation of a field of nl layers at the floats, each in its layer"""
+        """the bilinear interpolation of a field of nl layers at the floats, each in its layer (on tiles collective, as
+        floats_velocity)"""
         out = np.empty(self._floats_n())
         self._chk(self.L.msomn_floats_sample(self.h, self._fid(field), _ptr(out)))
         return out
@@ -1116,7 +1122,7 @@ class NodeQG:
 
     def floats_track(self, first=0, count=None):
         """(t[count], X[count][n], Y[count][n]) of records first .. first + count - 1 (count None: all that are written), and
-        V[count][n] as a fourth when a field is recorded"""
+        V[count][n] as a fourth when a field is recorded (on tiles collective: every record of all n floats on every rank)"""
         if count is None:
             count = int(self.param("floats_records")) - first
         n, c = self._floats_n(), max(count, 0)

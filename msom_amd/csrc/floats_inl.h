@@ -165,4 +165,27 @@ FL_HD static inline FloatsCell nfloats_locate(double x, double y, const FloatsGe
   return c;
 }
 
+// ---- the vertex grid on tiles ("On tiles").  The N x N cells are cut into px x py tiles of tnx x tny cells; a
+// tile HOLDS the (tnx + 1) x (tny + 1) vertices of its cells, the ones on its shared edges included (node_tile_inl.h).  A float
+// belongs to the tile that holds its grid cell: with i0 of nfloats_axis on the GLOBAL geometry, in [0, N - 1], the owner column is
+// i0 / tnx, rows likewise.  The owner's local corners i0 - ox, i0 + 1 - ox then lie in [0, tnx]: vertices the tile holds, so the
+// gathers read no halo, and every holder of a shared vertex carries the same bits, so they read the single tile's numbers.  The
+// owner line is the seam itself: xi exactly on a seam gives i0 = the seam's vertex, the first cell of the upper tile; x = L0 gives
+// i0 = N - 1, the last tile, column tnx with weight exactly 1.  The domain has walls on all four sides: floats_hop with periodic = 0.
+FL_HD static inline int nfloats_owner_axis(int i0, int tn, int p) {
+  int o = (i0 > 0 ? i0 : 0) / tn;
+  return o < p ? o : p - 1;   // i0 <= N - 1 by nfloats_axis: never taken, but the owner is a tile whatever i0 is
+}
+FL_HD static inline void nfloats_owner(const FloatsCell &c, const FloatsTiling &t, int *col, int *row) {
+  *col = nfloats_owner_axis(c.i0, t.tnx, t.px);
+  *row = nfloats_owner_axis(c.j0, t.tny, t.py);
+}
+// the located cell in the indices of the tile whose vertex (0, 0) is global vertex (ox, oy) and which holds (tx + 1) x (ty + 1)
+// vertices; false: a corner is not a vertex the tile holds (the float is not at home: nothing may be read for it)
+FL_HD static inline bool nfloats_local(FloatsCell *c, int ox, int oy, int tx, int ty) {
+  c->i0 -= ox;
+  c->j0 -= oy;
+  return c->i0 >= 0 && c->i0 <= tx - 1 && c->j0 >= 0 && c->j0 <= ty - 1;
+}
+
 #endif

@@ -79,6 +79,7 @@ struct FloatsDev {
   unsigned long long *cnt;   // [0] clamped to the box, [1] lost (not finite); on tiles also [2] unsent, [3] records sent
 };
 // on tiles the arrays above are n slots: slot k < *hw with live[k] != 0 holds float id[k]; (ox, oy) is the tile's origin in cells
+// (vertex model: in vertices)
 struct FloatsTileDev {
   const int *id, *live, *hw;
   int ox, oy;
@@ -101,26 +102,30 @@ void launch_floats_stage(hipStream_t st, int stage, const FloatsDev &d, int n, c
 void launch_floats_interp(hipStream_t st, const FloatsDev &d, int n, const double *f, const double *pg, const NatGeom &g, const FloatsGeom &fg,
                           double *o0, double *o1, const FloatsTileDev *t = nullptr);
 // one phase (x: W / E, y: S / N) of the migration pass: records of 6 doubles into the messages mlo, mhi (1 + 6 K doubles each, the
-// header word written by a one-lane launch behind it; null: no neighbour), then the records of the received messages into free slots
+// header word written by a one-lane launch behind it; null: no neighbour), then the records of the received messages into free slots.
+// node: the vertex grid's owner rule (nfloats_locate, nfloats_owner) in place of floats_locate, floats_owner
 void launch_floats_emigrate(hipStream_t st, const FloatsMig &s, int n, const FloatsGeom &fg, const FloatsTiling &t, int yphase, int half, double *mlo,
-                            double *mhi, int K);
+                            double *mhi, int K, bool node = false);
 void launch_floats_immigrate(hipStream_t st, const FloatsMig &s, int n, int nl, const double *rlo, const double *rhi, int K);
 // out [3][n] (zeroed): a, b of the live slots by id and the presence word; all [nranks][3][n] -> o0, o1 [n] (o1 may be null)
 void launch_floats_scatter(hipStream_t st, const double *a, const double *b, const FloatsTileDev &t, int n, double *out);
 void launch_floats_select(hipStream_t st, const double *all, int nranks, int n, double *o0, double *o1);
 
 // ---- kernels_node_floats.hip: Lagrangian floats of the vertex-grid model (msomn_floats_*).  g: the natural layout of the level-0
-// fields, fg = {N, N, 0, N / L0, L0, L0}; psi, pg, f, rf: fields of nl layers, mk: the mask (one layer)
+// fields, fg = {N, N, 0, N / L0, L0, L0}; psi, pg, f, rf: fields of nl layers, mk: the mask (one layer).  t (tiles): over the slots,
+// g the tile's layout, fg still the global geometry, t->ox, t->oy the tile's vertex origin
 // stage 1: (xh, yh) = (x, y) + dt / 2 U(x, y); stage 2: (x, y) += dt U(xh, yh), also stored to rec[0 .. n), rec[n .. 2n) when rec is given,
-// with the bilinear value of rf at the new position in rec[2n .. 3n) when rf is given too
+// with the bilinear value of rf at the new position in rec[2n .. 3n) when rf is given too.  t: the record is indexed by id with
+// rec[2n + id] = 1, and rf is not read
 void launch_nfloats_stage(hipStream_t st, int stage, const FloatsDev &d, int n, const double *psi, const double *pg, const NatGeom &g,
-                          const FloatsGeom &fg, double dt, double *rec, const double *rf);
-// at (x, y): o0 = u, o1 = v of f (+ pg) when o1 is given, else o0 = the bilinear value of f
+                          const FloatsGeom &fg, double dt, double *rec, const double *rf, const FloatsTileDev *t = nullptr);
+// at (x, y): o0 = u, o1 = v of f (+ pg) when o1 is given, else o0 = the bilinear value of f.  t: o0 is [3][n], indexed by id: the one
+// or two results and the presence word
 void launch_nfloats_interp(hipStream_t st, const FloatsDev &d, int n, const double *f, const double *pg, const NatGeom &g, const FloatsGeom &fg,
-                           double *o0, double *o1);
-// *out += the floats that are not lost and whose cell has mk == 0 at all four corners
+                           double *o0, double *o1, const FloatsTileDev *t = nullptr);
+// *out += the floats that are not lost and whose cell has mk == 0 at all four corners.  t: those of the rank's live slots
 void launch_nfloats_on_land(hipStream_t st, const FloatsDev &d, int n, const double *mk, const NatGeom &g, const FloatsGeom &fg,
-                            unsigned long long *out);
+                            unsigned long long *out, const FloatsTileDev *t = nullptr);
 
 // ---- kernels_rhs.hip
 void launch_fill_ghost(hipStream_t st, double *f, const NatGeom &g, int nl, int bc, int walls, int depth = 1);

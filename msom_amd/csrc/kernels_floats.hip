@@ -137,21 +137,25 @@ __global__ void __launch_bounds__(FL_THREADS) k_floats_interp_tiled(FloatsDev d,
 // after stage 1 (half), else (x, y) -- and, when that is a neighbour along the phase's axis, takes a record of the message of its
 // direction (lo: W / S, hi: E / N) with one atomicAdd, clears its live flag and pushes its slot on the free stack.  A float that finds
 // the message full, or whose owner is farther than a neighbour, is made lost here: NaN, resident, counted in cnt[2].  A float that is
-// lost already (a position that cannot be located) stays where it is
+// lost already (a position that cannot be located) stays where it is.  NODE: the vertex grid (msomn_floats_*, section 8l): its cell and
+// its owner rule, walls on every side
 __device__ __forceinline__ void fl_make_lost(const FloatsMig &s, int k) {
   s.x[k] = s.y[k] = s.xh[k] = s.yh[k] = NAN;
   atomicAdd(&s.cnt[2], 1ull);
 }
-template <bool YPH>
+template <bool YPH, bool NODE>
 __global__ void __launch_bounds__(FL_THREADS) k_floats_emigrate(FloatsMig s, int n, FloatsGeom fg, FloatsTiling t, int half, double *__restrict__ mlo,
                                                                 double *__restrict__ mhi, int K) {
   const int k = blockIdx.x * FL_THREADS + threadIdx.x;
   if (k >= n || k >= *s.hw || !s.live[k]) return;
-  const FloatsCell c = floats_locate(half ? s.xh[k] : s.x[k], half ? s.yh[k] : s.y[k], fg);
+  const double hx = half ? s.xh[k] : s.x[k], hy = half ? s.yh[k] : s.y[k];
+  const FloatsCell c = NODE ? nfloats_locate(hx, hy, fg) : floats_locate(hx, hy, fg);
   if (!c.ok) return;
   int col, row;
-  floats_owner(c, t, &col, &row);
-  const int hop = YPH ? floats_hop(row, t.iy, t.py, fg.periodic) : floats_hop(col, t.ix, t.px, fg.periodic);
+  if constexpr (NODE) nfloats_owner(c, t, &col, &row);
+  else floats_owner(c, t, &col, &row);
+  const int per = NODE ? 0 : fg.periodic;
+  const int hop = YPH ? floats_hop(row, t.iy, t.py, per) : floats_hop(col, t.ix, t.px, per);
   if (hop == 0) return;
   double *msg = hop == 1 ? mhi : hop == -1 ? mlo : nullptr;
   const int r = msg ? atomicAdd(&s.msgcnt[hop == 1], 1) : K;
@@ -269,10 +273,13 @@ void launch_floats_interp(hipStream_t st, const FloatsDev &d, int n, const doubl
 }
 
 void launch_floats_emigrate(hipStream_t st, const FloatsMig &s, int n, const FloatsGeom &fg, const FloatsTiling &t, int yphase, int half, double *mlo,
-                            double *mhi, int K) {
+                            double *mhi, int K, bool node) {
   const dim3 gr((n + FL_THREADS - 1) / FL_THREADS);
-  if (yphase) hipLaunchKernelGGL(k_floats_emigrate<true>, gr, dim3(FL_THREADS), 0, st, s, n, fg, t, half, mlo, mhi, K);
-  else hipLaunchKernelGGL(k_floats_emigrate<false>, gr, dim3(FL_THREADS), 0, st, s, n, fg, t, half, mlo, mhi, K);
+  with_bool(yphase != 0, [&](auto YPH) {
+    with_bool(node, [&](auto NODE) {
+      hipLaunchKernelGGL((k_floats_emigrate<YPH.value, NODE.value>), gr, dim3(FL_THREADS), 0, st, s, n, fg, t, half, mlo, mhi, K);
+    });
+  });
   hipLaunchKernelGGL(k_floats_header, dim3(1), dim3(64), 0, st, s, mlo, mhi, K);
 }
 void launch_floats_immigrate(hipStream_t st, const FloatsMig &s, int n, int nl, const double *rlo, const double *rhi, int K) {

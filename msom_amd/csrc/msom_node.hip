@@ -239,6 +239,11 @@ extern "C" int msomn_set_option(msomn_t *m, const char *key, double v) {
   else if (!strcmp(key, "floats")) {   // pauses and resumes the stages of msomn_step; without floats it has no effect
     if (m->floats) m->floats_on = (int)v != 0;
   }
+  else if (!strcmp(key, "floats_tiles")) m->floats_tiles = (int)v != 0;   // before msomn_floats_begin, alike on every rank (msomn_floats.h)
+  else if (!strcmp(key, "floats_msg_cap")) {
+    if (!(v >= 0)) { msom_set_error("option floats_msg_cap = %g", v); return MSOM_ERR_ARG; }
+    m->floats_msg_cap = (int)v;
+  }
   else if (!strcmp(key, "seed")) { m->seed = (unsigned)v; srand(m->seed); }
   else if (!strcmp(key, "noise_mode")) {
     if (v != 0. && v != 1.) { msom_set_error("noise_mode = %g: 0 (serial rand() stream on the host) or 1 (device generator)", v); return MSOM_ERR_ARG; }
@@ -321,7 +326,8 @@ extern "C" double msomn_get_param(msomn_t *m, const char *k) {
   if (!strcmp(k, "stats_mask")) return m->stats_mask;
   if (!strcmp(k, "stats_bytes")) return (double)__builtin_popcount(m->stats_mask) * m->nl * m->g.ny * m->g.nx * 8;
   if (!strcmp(k, "stats_samples")) return (double)m->stats_samples;
-  // Lagrangian floats (include/msomn_floats.h): floats, floats_records, floats_dropped, floats_clamped, floats_lost, floats_on_land
+  // Lagrangian floats (include/msomn_floats.h): floats, floats_records, floats_dropped, floats_clamped, floats_lost, floats_on_land,
+  // floats_tiles, floats_msg_cap, floats_resident, floats_unsent, floats_migrated
   if (double fv; nfloats_param(m, k, &fv)) return fv;
   if (!strcmp(k, "mg_coarse")) return m->mg_coarse;
   if (!strcmp(k, "node_split")) return m->node_split;

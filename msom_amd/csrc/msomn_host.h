@@ -45,7 +45,7 @@ struct NLevel {
   // the sides of g that are sides of the domain
   int tiled = 0, walls = WALL_ALL;
 };
-enum { NSC_RES = 0, NSC_UMAX = 1, NSC_KE = 2, NSC_DIAG = 3 /* 3 slots */, NSC_COUNT = 8 };
+enum { NSC_RES = 0, NSC_UMAX = 1, NSC_KE = 2, NSC_DIAG = 3 /* 3 slots */, NSC_FLOATS = 6 /* 2 slots */, NSC_COUNT = 8 };
 
 // option profile: HIP-event pairs around the finest-level launches of the vertex model (bench.py's per-kernel entries)
 enum { NP_RELAX, NP_RELAX_PROLONG, NP_RESIDUAL, NP_CORRECT, NP_RHS, NP_COARSE, NP_MARCH, NP_CORR_RES, NP_COUNT };
@@ -139,6 +139,8 @@ struct msomn {
   // Lagrangian floats (msomn_floats_*, msomn_floats.hip); nothing is allocated until msomn_floats_begin
   struct NFloatsState *floats = nullptr;
   int floats_on = 0;                      // option "floats": msomn_step queues the two stages
+  int floats_tiles = 0;                   // option "floats_tiles": on more than one tile the floats calls are accepted and collective
+  int floats_msg_cap = 0;                 // option "floats_msg_cap": records per migration message (0: the default of msomn_floats_begin)
 };
 
 // ---- msom_node.hip
@@ -176,7 +178,7 @@ int nstats_sample(msomn *m, double w);    // one sample of MSOMN_PSI / MSOMN_Q a
 // ---- msomn_floats.hip
 void nfloats_drop(msomn *m);                          // frees everything msomn_floats_begin allocated (msomn_set_const, msomn_destroy)
 int nfloats_hook(msomn *m, int stage, double tnext);  // one stage of msomn_step's floats, queued on m->st with m->dt; no host wait
-bool nfloats_param(msomn *m, const char *key, double *v);   // the "floats*" keys of msomn_get_param
+bool nfloats_param(msomn *m, const char *key, double *v);   // the "floats*" keys of msomn_get_param (on tiles the counters are collective)
 
 // ---- msomn_state.hip
 // msomn_state_save with the driver record `run` (run6: tout, tdiag, tflt, directory number, records of vars.nc, bytes of diag_1d.dat)
