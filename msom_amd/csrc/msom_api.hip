@@ -588,12 +588,7 @@ extern "C" int msom_set_option(msom_t *m, const char *key, double v) {
     if (!(v >= 1)) { msom_set_error("option stats_every = %g", v); return MSOM_ERR_ARG; }
     m->stats_every = (int)v;
   }
-  else if (!strcmp(key, "floats")) m->fl_on = m->fl && (int)v != 0;   // pauses / resumes the floats of msom_step; without floats: nothing
-  else if (!strcmp(key, "floats_tiles")) m->fl_tiles = (int)v != 0;   // before msom_floats_begin, alike on all ranks (msom_floats.h)
-  else if (!strcmp(key, "floats_msg_cap")) {
-    if (!(v >= 0) || v > 1e8) { msom_set_error("option floats_msg_cap = %g", v); return MSOM_ERR_ARG; }
-    m->fl_msg_cap = (int)v;
-  }
+  else if (!strncmp(key, "floats", 6)) return fh::set_option(m->floats, key, v);   // floats, floats_tiles, floats_msg_cap (msom_floats.h)
   else if (!strcmp(key, "ckpt_steps")) {   // msom_run: <workdir>/state.msom every that many steps (msom_state.h); 0: off
     if (!(v >= 0)) { msom_set_error("option ckpt_steps = %g", v); return MSOM_ERR_ARG; }
     m->ckpt_steps = (int)v;
@@ -2211,7 +2206,7 @@ static int rk_stage(msom *m, int stage, bool spec, double *tnext) {
     m->stats_ndev += hit;
   }
   // the floats' RK2 stages ride behind the model's: stage 1 reads psi_n behind the first tendency pass, stage 2 psi_{n+1/2} behind the second
-  if (m->fl_on) floats_hook(m, stage, *tnext);
+  if (m->floats.on) floats_hook(m, stage, *tnext);
   if (m->p.nptr > 0 && ((r = tracer_update(m, first ? MSOM_PTR : MSOM_PTR_PRED)) || (r = tracer_advance(m, first ? MSOM_PTR_PRED : MSOM_PTR, MSOM_PTR, adv_dt))))
     return r;
   return MSOM_OK;

@@ -129,11 +129,6 @@ ModesLayers modes_layers(const msom *m) {
   return l;
 }
 const ModeCoef *modes_mc(const msom *m) { return m->modes_compact ? &m->modes_mc : nullptr; }
-bool is_device_ptr(const void *p) {
-  hipPointerAttribute_t a;
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // an address the runtime does not know: host
-  return a.type == hipMemoryTypeDevice;
-}
 
 extern "C" int msom_modes_compute(msom_t *m) {
   if (m) m->res_ready = -1;   // nothing cached from psi and q outlives a call that may change them or the solver path

@@ -1,6 +1,7 @@
 // msom_host.h -- private to the host side of the layered model: struct msom, the error macros, the device scalar slots and the host
 // functions that one msom_*.hip unit calls in another.  Included by msom_api.hip, msom_helm.hip, msom_diag.hip, msom_newqg.hip,
-// msom_wavelet.hip, msom_io.hip, msom_state.hip, msom_hooks.hip and msom_floats.hip, and by nothing else (no kernel file, not comm.hip, not msom_node.hip).
+// msom_wavelet.hip, msom_io.hip, msom_state.hip, msom_hooks.hip and msom_floats.hip, and by nothing else (no kernel file, not comm.hip, not
+// msom_node.hip, not the floats' host engine floats_host.hip, whose header this one includes for fh::Opts).
 #ifndef MSOM_HOST_H
 #define MSOM_HOST_H
 
@@ -20,6 +21,7 @@
 #include <vector>
 
 #include "comm.h"
+#include "floats_host.h"
 #include "kernels.h"
 #include "prof_slot.h"
 #include "spec_inl.h"
@@ -176,10 +178,7 @@ struct msom {
   long stats_ndev = 0;                    // ... of whose samples, those that read their weight from the device (tests ask: stats_dev_samples)
   double tau_f = 20;                      // option "tau_f" (msqg/qg.h:495)
   // Lagrangian floats (msom_floats_*, msom_floats.hip); nothing is allocated until msom_floats_begin
-  struct FloatsState *fl = nullptr;       // positions, layers, counters and the trajectory buffer
-  int fl_on = 0;                          // floats begun and option "floats" not 0: rk_stage queues their two stages
-  int fl_tiles = 0;                       // option "floats_tiles": on more than one rank the floats calls are accepted and collective
-  int fl_msg_cap = 0;                     // option "floats_msg_cap": records per migration message (0: the default of msom_floats_begin)
+  fh::Opts floats;                        // the state and the options "floats", "floats_tiles", "floats_msg_cap" (floats_host.h)
   // vertical normal modes (msom_modes_*, msqg/eigmode.h); nothing is allocated until msom_modes_compute
   int modes_ready = 0;                    // a successful msom_modes_compute since the last msom_set_const
   int modes_compact = 0;                  // ... which left the compact form (modes_mc) rather than one array per number (modes_md)
@@ -362,8 +361,7 @@ int spec_ensure(msom *m);
 SpecIn spec_in_nat(const msom *m, int mode, const double *a, const double *b);
 void spec_batch_2d(msom *m, const SpecIn &in, int cnt, int kind, double *o2d);
 void spec_batch_1d(msom *m, int cnt);
-bool is_device_ptr(const void *p);
-// msom_floats.hip
+// msom_floats.hip (is_device_ptr: floats_host.h)
 void floats_drop(msom *m);
 void floats_hook(msom *m, int stage, double tnext);   // one stage of msom_step's floats, queued on m->st with m->dt; no host wait
 bool floats_param(msom *m, const char *key, double *v);

@@ -236,14 +236,7 @@ extern "C" int msomn_set_option(msomn_t *m, const char *key, double v) {
     if (!(v >= 1)) { msom_set_error("option stats_every = %g", v); return MSOM_ERR_ARG; }
     m->stats_every = (int)v;
   }
-  else if (!strcmp(key, "floats")) {   // pauses and resumes the stages of msomn_step; without floats it has no effect
-    if (m->floats) m->floats_on = (int)v != 0;
-  }
-  else if (!strcmp(key, "floats_tiles")) m->floats_tiles = (int)v != 0;   // before msomn_floats_begin, alike on every rank (msomn_floats.h)
-  else if (!strcmp(key, "floats_msg_cap")) {
-    if (!(v >= 0)) { msom_set_error("option floats_msg_cap = %g", v); return MSOM_ERR_ARG; }
-    m->floats_msg_cap = (int)v;
-  }
+  else if (!strncmp(key, "floats", 6)) return fh::set_option(m->floats, key, v);   // floats, floats_tiles, floats_msg_cap (msomn_floats.h)
   else if (!strcmp(key, "seed")) { m->seed = (unsigned)v; srand(m->seed); }
   else if (!strcmp(key, "noise_mode")) {
     if (v != 0. && v != 1.) { msom_set_error("noise_mode = %g: 0 (serial rand() stream on the host) or 1 (device generator)", v); return MSOM_ERR_ARG; }
@@ -1196,12 +1189,12 @@ extern "C" int msomn_step(msomn_t *m, int with_forcing_event) {
   // the automatic sample: q_n and the psi stage 1 inverted from it (masked, sides set, on tiles exchanged by the tendency), weight dt_n
   if (m->stats_on && m->stats_count++ % m->stats_every == 0 && (r = nstats_sample(m, m->dt))) return r;
   // the floats' stage 1 reads the same psi_n, before the second update overwrites it
-  if (m->floats_on && (r = nfloats_hook(m, 1, tn))) return r;
+  if (m->floats.on && (r = nfloats_hook(m, 1, tn))) return r;
   if ((r = msomn_advance(m, MSOMN_QPRED, MSOMN_Q, MSOMN_DQ, m->dt / 2.))) return r;
   if ((r = msomn_update(m, MSOMN_QPRED, MSOMN_DQ, m->dt, &d))) return r;
   if ((r = msomn_advance(m, MSOMN_Q, MSOMN_Q, MSOMN_DQ, m->dt))) return r;
   // ... and their stage 2 psi_{n + 1/2}, behind the final advance: a recorded sample of q is q_{n + 1} at x_{n + 1}
-  if (m->floats_on && (r = nfloats_hook(m, 2, tn))) return r;
+  if (m->floats.on && (r = nfloats_hook(m, 2, tn))) return r;
   m->t = tn;
   m->iter++;
   return MSOM_OK;

@@ -1,6 +1,7 @@
 // msomn_host.h -- the vertex-grid handle (struct msomn) and the host helpers its units share: msom_node.hip (model and multigrid),
 // msomn_tiles.hip (the model on tiles: decomposition, halo exchange, gather), msomn_io.hip (NetCDF IO and the driver msomn_run),
 // msomn_state.hip (state file, include/msomn_state.h), msomn_floats.hip (Lagrangian floats, include/msomn_floats.h).  The profile slots (prof_slot.h) are the layered model's.  Not installed.
+// The floats' host engine (floats_host.hip) does not include it; its header is included here for fh::Opts.
 #ifndef MSOMN_HOST_H
 #define MSOMN_HOST_H
 
@@ -16,6 +17,7 @@
 #include <vector>
 
 #include "comm.h"
+#include "floats_host.h"
 #include "kernels.h"
 #include "node_tile_inl.h"
 #include "prof_slot.h"
@@ -137,10 +139,7 @@ struct msomn {
   long stats_count = 0;                   // msomn_step calls seen since msomn_stats_begin (every stats_every-th one samples)
   long stats_samples = 0;                 // samples taken since msomn_stats_begin, automatic and by hand
   // Lagrangian floats (msomn_floats_*, msomn_floats.hip); nothing is allocated until msomn_floats_begin
-  struct NFloatsState *floats = nullptr;
-  int floats_on = 0;                      // option "floats": msomn_step queues the two stages
-  int floats_tiles = 0;                   // option "floats_tiles": on more than one tile the floats calls are accepted and collective
-  int floats_msg_cap = 0;                 // option "floats_msg_cap": records per migration message (0: the default of msomn_floats_begin)
+  fh::Opts floats;                        // the state and the options "floats", "floats_tiles", "floats_msg_cap" (floats_host.h)
 };
 
 // ---- msom_node.hip

@@ -365,3 +365,89 @@ def test_newqg_stays_refused_with_the_option(strict):
     assert n.L.msom_floats_begin(n.h, 1, one.ctypes.data, one.ctypes.data, lay.ctypes.data) == ERR_CONFIG
     assert n.L.msom_floats_get(n.h, one.ctypes.data, one.ctypes.data) == ERR_CONFIG
     n.close()
+
+
+# ------------------------------------------------------------------ the host side the two models share: record slots, begin, the cap
+
+PER3 = "sbc = -1\ntau0 = 0\nbeta = 0\nupg = [0.3,-0.2,0.1]\nvpg = [0.1,0.25,-0.15]\nflsrv = 1\n"
+CAP = 40
+
+
+@functools.lru_cache(maxsize=None)
+def shared_case(kind):
+    """32 x 32 x 3, 160 floats of which 48 start beside a seam or beside the cell-centre line where the owner changes"""
+    nl, gn, n = 3, 32, 160
+    params = double_gyre_params(gn, nl, extra="MGLEVELS = 4\n" + (PER3 if kind == "periodic" else ""))
+    psi = synthetic_psi(nl, gn, gn, amp=5.0)
+    x, y, lay = fr.seeded_floats(fr.Geom(gn, gn, L0, periodic=kind == "periodic"), n, nl, seed=5)
+    D = L0 / gn
+    x[:24] = L0 / 2 + np.tile([-0.03, 0.02, 0.47, 0.53], 6) * D
+    y[:24] = (np.arange(24) + 0.31) * L0 / 24
+    y[24:48] = L0 / 2 + np.tile([-0.03, 0.02, 0.47, 0.53], 6) * D
+    x[24:48] = (np.arange(24) + 0.31) * L0 / 24
+    dmax = max(np.abs(np.diff(psi, axis=1)).max(), np.abs(np.diff(psi, axis=2)).max())
+    return params, psi, (x, y, lay), 0.4 * D * D / dmax      # a stage by hand moves a float by at most about 0.4 cells
+
+
+def shared_calls(g, fl, dt):
+    """the calls whose host code the two models share, alike on a single tile and on every rank of a tiling"""
+    from test_gpu_hooks import DevBuf
+
+    x, y, lay = fl
+    res = dict(cap=[g.param("floats_msg_cap")])      # the option, before any begin
+    bufs = [DevBuf(a) for a in fl]
+    g._chk(g.L.msom_floats_begin(g.h, x.size, *(b.ptr for b in bufs)))      # from device arrays
+    for b in bufs:
+        b.free()
+    res["cap"].append(g.param("floats_msg_cap"))
+    res["n0"] = g.param("floats_resident")
+    g.floats_record(every=2, capacity=3)      # records behind steps 2 and 4 fill the buffer, those of steps 6 and 8 are dropped
+    res["dts"] = [g.step() for _ in range(8)]
+    res.update(records=g.param("floats_records"), dropped=g.param("floats_dropped"), track=g.floats_track(), pos=g.floats_get(),
+               cnt={k: g.param(k) for k in COUNTERS}, resident=g.param("floats_resident"))
+    g.option("floats_msg_cap", 0)
+    g.floats_begin(x[:100], y[:100], lay[:100])      # a second begin with another n: messages and readouts follow it
+    res["cap"].append(g.param("floats_msg_cap"))
+    g.step()
+    res["pos2"] = g.floats_get()
+    g.floats_stage(1, dt)
+    g.floats_stage(1, dt)      # a stage 1 over a stage 1: the floats are homed by (x, y) again first
+    g.floats_stage(2, dt)
+    res.update(pos3=g.floats_get(), cnt3={k: g.param(k) for k in COUNTERS}, resident3=g.param("floats_resident"))
+    return res
+
+
+@functools.lru_cache(maxsize=None)
+def shared_single(kind, strict):
+    params, psi, fl, dt = shared_case(kind)
+    g = single(params, psi, strict, dict(ON, floats_msg_cap=CAP))
+    res = shared_calls(g, fl, dt)
+    g.close()
+    return res
+
+
+@pytest.mark.parametrize("strict", [True, False])
+@pytest.mark.parametrize("px,py", [(2, 1), (1, 2), (2, 2)])
+@pytest.mark.parametrize("kind", ["walls", "periodic"])
+def test_record_slots_begin_and_the_cap_on_tiles_equal_the_single_tile(kind, px, py, strict):
+    params, psi, fl, dt = shared_case(kind)
+    n = fl[0].size
+    ref = shared_single(kind, strict)
+    assert ref["cap"] == [CAP, CAP, 0] and ref["records"] == 3 and ref["dropped"] == 2 and ref["track"][0].size == 3
+    assert not same(ref["track"][1][2], ref["track"][1][0]) and not same(ref["pos"][0], ref["track"][1][2]) and not same(ref["pos3"][0], ref["pos2"][0])
+    out = [o["extra"] for o in run_tiled(params, px, py, psi, 0, strict, fn=lambda g, rank: shared_calls(g, fl, dt), opts=dict(ON, floats_msg_cap=CAP))]
+    for r, o in enumerate(out):
+        # the option; K of a begin with it; K of a begin without it: min(n, max(1024, n / 16)) of the second begin's 100 floats
+        assert o["cap"] == [CAP, CAP, 100], (r, o["cap"])
+        assert o["dts"] == ref["dts"] and o["records"] == 3 and o["dropped"] == 2, r
+        assert np.array_equal(o["track"][0], ref["track"][0]) and same(o["track"][1], ref["track"][1]) and same(o["track"][2], ref["track"][2]), r
+        for key in ("pos", "pos2", "pos3"):
+            assert same(o[key][0], ref[key][0]) and same(o[key][1], ref[key][1]), (r, key)
+        for key in ("cnt", "cnt3"):
+            assert o[key]["floats_clamped"] == ref[key]["floats_clamped"] and o[key]["floats_lost"] == ref[key]["floats_lost"], (r, key)
+            assert o[key]["floats_unsent"] == 0 and o[key]["floats_migrated"] == out[0][key]["floats_migrated"], (r, key)
+    print(f"{kind} {px} x {py}: resident {[o['n0'] for o in out]} -> {[o['resident'] for o in out]}, migrated {out[0]['cnt']['floats_migrated']}, "
+          f"second begin {[o['resident3'] for o in out]}, migrated {out[0]['cnt3']['floats_migrated']}")
+    assert sum(o["n0"] for o in out) == n and sum(o["resident"] for o in out) == n - out[0]["cnt"]["floats_unsent"]
+    assert sum(o["resident3"] for o in out) == 100 - out[0]["cnt3"]["floats_unsent"]
+    assert out[0]["cnt"]["floats_migrated"] + out[0]["cnt3"]["floats_migrated"] > 0

@@ -238,6 +238,9 @@ def test_guards_on_tiles(strict):
 
     def body(g, rank):
         res = {}
+        g.set_option("floats_msg_cap", 7)    # a cap that is no int is refused, as on a layered handle, and the option stays
+        res["cap"] = (g.L.msomn_set_option(g.h, b"floats_msg_cap", 2e8), g.L.msom_last_error(), g.param("floats_msg_cap"))
+        g.set_option("floats_msg_cap", 0)
         g.set_option("floats_tiles", 0)      # without the option: refused as before
         res["off"] = begin(g, c.n, c.x, c.y, c.layer) + (g.param("floats"), g.param("floats_tiles"))
         g.set_option("floats_tiles", 1)
@@ -270,6 +273,7 @@ def test_guards_on_tiles(strict):
     x, y = g.floats_get()
     g.close()
     for r, o in enumerate(out):
+        assert o["cap"][0] == ERR_ARG and b"option floats_msg_cap" in o["cap"][1] and o["cap"][2] == 7, (r, o["cap"])
         assert o["off"][0] == ERR_CONFIG and b"msomn_floats_begin is not available on a tiled" in o["off"][1] and o["off"][2:] == (0, 0), r
         assert o["n"][0] == ERR_ARG and b"msomn_floats_begin: n = " in o["n"][1] and o["n"][2] == 0, (r, o["n"])
         assert o["bad"][0] == ERR_ARG and o["bad"][2] == 0 and (b"msomn_floats_begin: float 3" if r == 1 else b"another rank refuses") in o["bad"][1], (r, o["bad"])
@@ -298,3 +302,106 @@ def test_a_one_by_one_tiled_handle_with_the_option_behaves_as_the_plain_one(stri
     for k in range(2):
         assert same(o["pos"][k][0], ref["pos"][k][0]) and same(o["pos"][k][1], ref["pos"][k][1])
     assert o["cnt"] == ref["cnt"][1] and o["resident"] == c.n and o["tiles"] == 1 and np.isfinite(o["u"][0]).all()
+
+
+# ------------------------------------------------------------------ the host side the two models share: record slots, begin, the cap
+
+CAP = 40
+N32 = 32
+PAR32 = params(N32, nt.NL)
+
+
+@functools.lru_cache(maxsize=None)
+def shared_case():
+    """N = 32, 3 layers, 160 floats of which 48 start beside a seam of 2 tiles a side"""
+    import node_floats_ref as nr
+    from test_gpu_node_tiled import inputs
+
+    inp = inputs(N32, nt.NL)
+    geom = nr.Geom(N32, nt.L0)
+    x, y, lay = nr.seeded_floats(geom, 160, nt.NL, seed=5)
+    D = nt.L0 / N32
+    x[:24] = nt.L0 / 2 + np.tile([-0.03, 0.02, -0.4, 0.45], 6) * D
+    y[:24] = (np.arange(24) + 0.31) * nt.L0 / 24
+    y[24:48] = nt.L0 / 2 + np.tile([-0.03, 0.02, -0.4, 0.45], 6) * D
+    x[24:48] = (np.arange(24) + 0.31) * nt.L0 / 24
+    return inp, (x, y, lay), nt.stage_dt(geom, inp["PSI"] + inp["PSIPG"])
+
+
+def shared_calls(g, rank, field):
+    """the calls whose host code the two models share, alike on a single tile (rank -1) and on every rank of a tiling"""
+    import ctypes
+
+    from test_gpu_hooks import DevBuf
+
+    _, fl, dt = shared_case()
+    x, y, lay = fl
+    n = x.size
+    res = dict(cap=[g.param("floats_msg_cap")])      # the option, before any begin
+    bufs = [DevBuf(a) for a in fl]
+    g._chk(g.L.msomn_floats_begin(g.h, n, *(b.ptr for b in bufs)))      # from device arrays
+    for b in bufs:
+        b.free()
+    res["cap"].append(g.param("floats_msg_cap"))
+    res["n0"] = g.param("floats_resident")
+    g.floats_record(every=2, capacity=3, field=field)      # records behind steps 2 and 4 fill the buffer, those of steps 6 and 8 are dropped
+    res["dts"] = []
+    for _ in range(8):
+        g.step(True)
+        res["dts"].append(g.dt)
+    res.update(records=g.param("floats_records"), dropped=g.param("floats_dropped"))
+    # every rank makes the same gathers, whatever arrays it leaves out: rank 0 passes no x, rank 1 no val (no y when no field is recorded)
+    t, X, Y, V = np.empty(3), np.full((3, n), -1.0), np.full((3, n), -1.0), np.full((3, n), -1.0)
+    take = dict(x=rank != 0, y=not (rank == 1 and field is None), val=field is not None and rank != 1)
+    ptr = lambda a, on: a.ctypes.data if on else None
+    g._chk(g.L.msomn_floats_track(g.h, 0, 3, t.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ptr(X, take["x"]), ptr(Y, take["y"]), ptr(V, take["val"])))
+    res.update(take=take, track=dict(t=t, x=X, y=Y, val=V), pos=g.floats_get(), cnt={k: g.param(k) for k in COUNTERS}, resident=g.param("floats_resident"))
+    g.set_option("floats_msg_cap", 0)
+    g.floats_begin(x[:100], y[:100], lay[:100])      # a second begin with another n: messages and readouts follow it
+    res["cap"].append(g.param("floats_msg_cap"))
+    g.step(True)
+    res["pos2"] = g.floats_get()
+    g.floats_stage(1, dt)
+    g.floats_stage(1, dt)      # a stage 1 over a stage 1: the floats are homed by (x, y) again first
+    g.floats_stage(2, dt)
+    res.update(pos3=g.floats_get(), cnt3={k: g.param(k) for k in COUNTERS}, resident3=g.param("floats_resident"))
+    return res
+
+
+@functools.lru_cache(maxsize=None)
+def shared_single(field, strict):
+    g = single(PAR32, shared_case()[0], strict, dict(SINGLE_OPTS, floats_msg_cap=CAP))
+    res = shared_calls(g, -1, field)
+    g.close()
+    return res
+
+
+@pytest.mark.parametrize("strict", [True, False])
+@pytest.mark.parametrize("px,py", [(2, 1), (1, 2), (2, 2)])
+@pytest.mark.parametrize("field", [None, "Q"])
+def test_record_slots_begin_and_the_cap_on_tiles_equal_the_single_tile(field, px, py, strict):
+    inp, fl, _ = shared_case()
+    n = fl[0].size
+    ref = shared_single(field, strict)
+    assert ref["cap"] == [CAP, CAP, 0] and ref["records"] == 3 and ref["dropped"] == 2
+    assert not same(ref["track"]["x"][2], ref["track"]["x"][0]) and not same(ref["pos"][0], ref["track"]["x"][2]) and not same(ref["pos3"][0], ref["pos2"][0])
+    assert field is None or (np.isfinite(ref["track"]["val"]).all() and not same(ref["track"]["val"][2], ref["track"]["val"][0]))
+    out = run_tiled(PAR32, px, py, inp, strict, lambda g, rank: shared_calls(g, rank, field), opts=dict(TILE_OPTS, floats_msg_cap=CAP))
+    for r, o in enumerate(out):
+        # the option; K of a begin with it; K of a begin without it: min(n, max(1024, n / 16)) of the second begin's 100 floats
+        assert o["cap"] == [CAP, CAP, 100], (r, o["cap"])
+        assert o["dts"] == ref["dts"] and o["records"] == 3 and o["dropped"] == 2, r
+        assert np.array_equal(o["track"]["t"], ref["track"]["t"]), r
+        for key, on in o["take"].items():      # an array that was passed: the single tile's; one that was not: untouched
+            assert same(o["track"][key], ref["track"][key]) if on else (o["track"][key] == -1.0).all(), (r, key)
+        for key in ("pos", "pos2", "pos3"):
+            assert same(o[key][0], ref[key][0]) and same(o[key][1], ref[key][1]), (r, key)
+        for key in ("cnt", "cnt3"):
+            for c in ("floats_clamped", "floats_lost", "floats_on_land"):
+                assert o[key][c] == ref[key][c], (r, key, c)
+            assert o[key]["floats_unsent"] == 0 and o[key]["floats_migrated"] == out[0][key]["floats_migrated"], (r, key)
+    print(f"field {field} {px} x {py}: resident {[o['n0'] for o in out]} -> {[o['resident'] for o in out]}, migrated {out[0]['cnt']['floats_migrated']}, "
+          f"second begin {[o['resident3'] for o in out]}, migrated {out[0]['cnt3']['floats_migrated']}")
+    assert sum(o["n0"] for o in out) == n and sum(o["resident"] for o in out) == n - out[0]["cnt"]["floats_unsent"]
+    assert sum(o["resident3"] for o in out) == 100 - out[0]["cnt3"]["floats_unsent"]
+    assert out[0]["cnt"]["floats_migrated"] + out[0]["cnt3"]["floats_migrated"] > 0

@@ -2,8 +2,8 @@
 header the kernels compile) on awkward inputs -- every seam and its nextafter neighbours, 0 and L0, +-1e300, +-0, NaN, +-inf -- in a
 stand-alone program built with AddressSanitizer and UBSan (tools/node_floats_tiles_host_check.cpp), which reads the corners of every
 located cell from a heap array of exactly the vertices the owner tile holds and compares the owner with brute force.  And that the
-host (msomn_floats_begin) and the kernels take the owner and the local corners from those functions, not from arithmetic of their
-own.  No GPU."""
+host (begin's partition in floats_host.hip, for both models) and the kernels take the owner and the local corners from those
+functions, not from arithmetic of their own.  No GPU."""
 import os
 import re
 import subprocess
@@ -36,11 +36,16 @@ def test_host_and_kernels_read_the_same_functions():
     inl = code_of("floats_inl.h")
     for fn in ("nfloats_owner_axis", "nfloats_owner", "nfloats_local"):
         assert re.search(r"FL_HD static inline \w+ " + fn + r"\(", inl), fn
-    host, emig, kern = code_of("msomn_floats.hip"), code_of("kernels_floats.hip"), code_of("kernels_node_floats.hip")
-    # who owns a position: the host at msomn_floats_begin and the emigrate kernel, through the one function, on nfloats_locate's cell
+    host, emig, kern = code_of("floats_host.hip"), code_of("kernels_floats.hip"), code_of("kernels_node_floats.hip")
+    # who owns a position: the host at begin (the partition of floats_host.hip, for both models) and the emigrate kernel, through the
+    # one function, on nfloats_locate's cell; the layered model through floats_owner on floats_locate's
     assert "nfloats_owner(nfloats_locate(" in host and "nfloats_owner(c, t, &col, &row)" in emig and "nfloats_locate(hx, hy, fg)" in emig
+    assert " floats_owner(floats_locate(" in host
     # the local corners: every tiled kernel body through nfloats_local, none by a subtraction of its own
     assert kern.count("nfloats_local(&c, ") == 3 and "- t.ox" not in kern and "- tx0" not in kern
-    # neither the host file nor the kernels divide by a tile size themselves
-    for txt in (host, emig, kern):
-        assert "/ t.tnx" not in txt and "/ tl.tnx" not in txt and "/ t.tx" not in txt
+    # neither the engine, nor a model's host file, nor the kernels divide by a tile size themselves
+    for txt in (host, code_of("msom_floats.hip"), code_of("msomn_floats.hip"), emig, kern):
+        assert "/ t.tnx" not in txt and "/ tl.tnx" not in txt and "/ t.tx" not in txt and "/ c.tl.tnx" not in txt
+    # and the partition exists once: the models' files locate nothing
+    for name in ("msom_floats.hip", "msomn_floats.hip"):
+        assert "floats_locate(" not in code_of(name), name
