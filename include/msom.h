@@ -248,8 +248,13 @@ enum { MSOM_MD_IBU = 0,  /* iBu_m = -lambda_m, iBu_0 = 0 exactly (eigmode.h:256-
  *   Storage: a stratification that is the same in every column (no MSOM_FR / MSOM_RO / MSOM_S set, no varRo) is solved once, by the same
  *   kernel on cell (0, 0), and kept as nl*nl + nl doubles in the handle; otherwise nl*nl + nl arrays of one layer each are allocated on
  *   the first compute and freed by msom_destroy.  Option "modes_compact" [-1: automatic; 0: always per column].
- *   An interface whose S is not positive and finite (the spectrum is degenerate, the vectors are not unique), or an iteration that hits
- *   the cap: MSOM_ERR_CONFIG, no modes; the handle stays usable.  msom_set_const drops the modes.
+ *   An interface whose S is not positive and finite (the spectrum is degenerate, the vectors are not unique), an iteration that hits
+ *   the cap, or a column too weakly stratified: MSOM_ERR_CONFIG, no modes; the handle stays usable.  msom_set_const drops the modes.
+ *   Too weakly stratified: with lambda_0 <= lambda_1 <= ... <= lambda_max the computed eigenvalues of a column, nl >= 2 and
+ *   lambda_1 <= 8 nl 2^-52 lambda_max.  8 nl eps lambda_max is the eigenvalue error of the method; below it fp64 cannot separate the first
+ *   baroclinic mode from the barotropic one: the sign of lambda_1 (so Rd_1, and the sign of the mode's Helmholtz term) and which of the
+ *   two near-null vectors is mode 0 would be arbitrary.  An MSOM_FR of 1e-9 of its neighbours' does this; msom_last_error names the cause.
+ *   The surface entry vr[0][m] of a mode may be zero (never negative).
  * msom_modes_layers: arrays of `which` (nl or nl*nl).  msom_modes_get: those arrays, [layers][ny][nx], the local tile; the compact
  *   form is broadcast.
  * msom_modes_project: to_modes != 0: out_m = sum_k l2m[m][k] * in_k, else out_k = sum_m m2l[k][m] * in_m, accumulated as acc = 0;

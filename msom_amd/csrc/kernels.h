@@ -287,7 +287,9 @@ struct ModeCoef {
   double m2l[MSOM_MAXNL * MSOM_MAXNL], ibu[MSOM_MAXNL];   // m2l[k * nl + m]
 };
 // eigenproblem of every column of an ncx x ncy grid from S (geometry g); output array a at out[a * ols + (per_column ? cell : 0)];
-// *flag |= MODES_BAD_S / MODES_NOCONV.  -1: no kernel for nl
+// *flag |= MODES_BAD_S / MODES_NOCONV / MODES_WEAK (modes_inl.h) of any column, which then writes nothing.  MODES_WEAK: the column's
+// second smallest computed eigenvalue is <= 8 nl 2^-52 times its largest -- below the method's eigenvalue error, so the sign of
+// lambda_1 and the choice of the barotropic vector are undetermined.  -1: no kernel for nl
 int launch_modes_eig(hipStream_t st, const double *S, const NatGeom &g, int nl, int ncx, int ncy, double *out, size_t ols, int per_column,
                      const ModesLayers &l, int *flag);
 // arrays first .. first + cnt - 1 of MSOM_MD_`which` into out, contiguous [cnt][ny][nx]

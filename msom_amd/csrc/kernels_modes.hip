@@ -32,7 +32,8 @@ static inline dim3 block2d() { return dim3(BX, BY); }
 // One thread per column of an ncx x ncy grid (the tile, or 1 x 1 for the compact form: cell (0, 0)); 64 threads per workgroup.
 // NL <= MSOM_FASTNL: the vector matrix in registers; above: in LDS, element e of lane t at [e * 64 + t] (conflict-free, and a lane
 // only ever touches its own slots, so there is no barrier).  Output index: array * ols + (per_column ? cell : 0).
-// A column whose S is not positive and finite, or whose iteration hits the sweep cap, ORs its status into *flag and writes nothing.
+// A column whose S is not positive and finite, whose iteration hits the sweep cap, or whose first baroclinic eigenvalue is below the
+// rounding level of the matrix (MODES_WEAK, modes_inl.h) ORs its status into *flag and writes nothing.
 template <int NL>
 __global__ void __launch_bounds__(64) k_modes_eig(const double *__restrict__ S, NatGeom g, int ncx, int ncy, double *__restrict__ out, size_t ols,
                                                   int per_column, ModesLayers lay, int *flag) {

@@ -22,7 +22,10 @@
 #ifndef MODES_MAXNL
 #define MODES_MAXNL 16
 #endif
-#define MODES_MAXSWEEP 40   // nl <= 16 converges in 5 .. 10 sweeps; the cap only ends a run on data that cannot converge (NaN)
+// Passes of the sweep loop, the last of which only finds the off-diagonal sum zero, on the columns of tools/modes_host_check.cpp
+// (graded, nearly unstratified, thin layers; contracted or not): nl = 2: 2, nl = 3: 5 .. 7, nl = 6 .. 16: 7 .. 11.  The cap only ends
+// a run on data that cannot converge (NaN)
+#define MODES_MAXSWEEP 40
 
 // f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N - 1>{}): a loop whose index is a constant in every body,
 // whatever the optimiser's unrolling limits are (the rotation loop of 16 layers is 120 bodies)
@@ -38,7 +41,7 @@ MODES_HD void modes_static_for(F &&f) {
 constexpr int modes_pair_p(int t, int nl) { int p = 0; while (t >= nl - 1 - p) { t -= nl - 1 - p; p++; } return p; }
 constexpr int modes_pair_q(int t, int nl) { int p = 0; while (t >= nl - 1 - p) { t -= nl - 1 - p; p++; } return p + 1 + t; }
 
-enum { MODES_OK = 0, MODES_BAD_S = 1, MODES_NOCONV = 2 };
+enum { MODES_OK = 0, MODES_BAD_S = 1, MODES_NOCONV = 2, MODES_WEAK = 4 };   // bits: k_modes_eig ORs them into one word
 
 struct ModesLayers {
   double dhf[MODES_MAXNL], dhc[MODES_MAXNL];
@@ -83,8 +86,12 @@ struct ModesMemV {
 };
 
 // S[l] = (Fr_l / Ro)^2 of the nl - 1 interfaces of one column.  On MODES_OK: d[m] = eigenvalue lambda_m of amat, V(k * NL + m) =
-// vr[k][m] with Flierl's normalisation sum_k dhf_k vr_km^2 = htotal (= 1, eigmode.h:70) and vr[0][m] > 0 (sign(x) = x > 0 ? 1 : -1),
-// rank[m] = position of mode m in ascending order of the eigenvalues (ties by index).
+// vr[k][m] with Flierl's normalisation sum_k dhf_k vr_km^2 = htotal (= 1, eigmode.h:70) and vr[0][m] >= 0 (sign(x) = x > 0 ? 1 : -1;
+// a mode may vanish at the surface), rank[m] = position of mode m in ascending order of the eigenvalues (ties by index).
+// MODES_BAD_S: an S that is not positive and finite.  MODES_NOCONV: the sweep cap.  MODES_WEAK: with e0 <= e1 <= ... <= emax the computed
+// eigenvalues, NL >= 2 and e1 <= 8 NL 2^-52 emax -- the eigenvalue error bound of the method, so neither the sign of lambda_1 nor which
+// of the two near-null vectors is the barotropic one is determined (an interface too weakly stratified for fp64; a matrix entry that
+// overflowed to inf ends here as well, emax = inf, or in MODES_NOCONV).  On any of the three nothing of d, V, rank is meaningful.
 template <int NL, class VS>
 MODES_HD int modes_eig_column(const double *S, const ModesLayers &lay, VS &V, double (&d)[NL], int (&rank)[NL]) {
   const double htotal = 1.;
@@ -179,6 +186,17 @@ MODES_HD int modes_eig_column(const double *S, const ModesLayers &lay, VS &V, do
     }
     if (!(sm == 0.)) return MODES_NOCONV;
   }
+  int st = MODES_OK;
+  if (NL >= 2) {   // the two smallest and the largest eigenvalue, without an indexed read of d
+    double e0 = d[0], e1 = HUGE_VAL, emax = d[0];
+#pragma unroll
+    for (int m = 1; m < NL; m++) {
+      e1 = fmin(e1, fmax(e0, d[m]));
+      e0 = fmin(e0, d[m]);
+      emax = fmax(emax, d[m]);
+    }
+    if (e1 <= 8. * NL * 2.220446049250313e-16 * emax) st = MODES_WEAK;
+  }
 
   // back to the vectors of amat (D^-1/2), Flierl's normalisation and the surface sign, eigmode.h:213-222
 #pragma unroll
@@ -203,7 +221,7 @@ MODES_HD int modes_eig_column(const double *S, const ModesLayers &lay, VS &V, do
     for (int j = 0; j < NL; j++) r += (d[j] < d[m] || (d[j] == d[m] && j < m)) ? 1 : 0;
     rank[m] = r;
   }
-  return MODES_OK;
+  return st;
 }
 
 #endif

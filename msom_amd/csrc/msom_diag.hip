@@ -158,6 +158,9 @@ extern "C" int msom_modes_compute(msom_t *m) {
   if (flag) {
     modes_drop(m);
     if (flag & MODES_BAD_S) msom_set_error("msom_modes_compute: S = (Fr/Ro)^2 is not positive and finite on every interface: the spectrum is degenerate");
+    else if (flag & MODES_WEAK)
+      msom_set_error("msom_modes_compute: an interface is too weakly stratified for fp64 to separate the first baroclinic mode from the barotropic "
+                     "one (lambda_1 <= 8 nl eps lambda_max): neither its sign nor the barotropic vector is determined");
     else msom_set_error("msom_modes_compute: the Jacobi iteration did not converge within %d sweeps", MODES_MAXSWEEP);
     return MSOM_ERR_CONFIG;
   }
