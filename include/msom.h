@@ -577,13 +577,20 @@ msomn_t *msomn_create_str(const char *params_text);
  * set option mg_coarse before msomn_set_const.  The fused passes resolve to off (options node_pfused, node_tile_s, node_march_s,
  * node_march, tiled_relax, node_corr_fused, node_rhs_fused read 0 and stay 0); msomn_get_param "exchanges" counts halo exchanges.
  * msomn_dbg_relax / _residual / _restrict / _prolong / _level_mask work on the tiled levels with tile-sized arrays (a gathered
- * level: MSOM_ERR_ARG).  Refused with MSOM_ERR_CONFIG and a message naming the call, the handle unchanged: option stochastic,
- * msomn_noise_draw, msomn_dbg_noise, msomn_dbg_csig, msomn_wavelet_filter, msomn_dbg_wv_get / _apply, msomn_run, msomn_write_nc,
- * msomn_read_nc, msomn_state_save / _load, msomn_dbg_del2_zeta. */
+ * level: MSOM_ERR_ARG).  Refused with MSOM_ERR_CONFIG and a message naming the call, the handle unchanged: msomn_run, msomn_write_nc,
+ * msomn_read_nc, msomn_state_save / _load, msomn_dbg_del2_zeta, and, unless the option wavelet_tiles is 1: option stochastic,
+ * msomn_noise_draw, msomn_dbg_noise, msomn_dbg_csig, msomn_wavelet_filter, msomn_dbg_wv_get / _apply.
+ * Option wavelet_tiles [0] (0 or 1, else MSOM_ERR_ARG; on one tile accepted, no effect): with 1 those calls, and msomn_step /
+ * msomn_advance with the stochastic forcing, run on the tiles as COLLECTIVE calls with the single tile's bits.  The cell pyramids
+ * then hold the tile's window of (Tx >> k) x (Ty >> k) cells on the levels k < agg_level and the global level of (N >> k)^2 cells on
+ * every rank from agg_level on: msomn_dbg_noise and msomn_dbg_wv_apply take and give the tile's window [Ty][Tx] of cells,
+ * msomn_dbg_csig and msomn_dbg_wv_get the window below agg_level and the whole level from it on.  A transform posts 2 agg_level - 1
+ * halo exchanges and one all-gather.  noise_mode = 0 stays refused on more than one tile wherever a draw would be taken (the host's
+ * rand() stream is one state per process and cannot be shared by tiles): set noise_mode = 1. */
 msomn_t *msomn_create_tiled(const char *params_text, int px, int py, int rank, const void *id128);
 int msomn_tile_info(msomn_t *m, int *px, int *py, int *ix, int *iy, int *nx_local, int *ny_local);  /* vertices: Tx + 1, Ty + 1 */
 void msomn_destroy(msomn_t *m);                                 /* trash_vars qg.h:537-544 */
-/* keys: TOLERANCE NITERMAX NITERMIN (nodal-poisson.h:19-23) DT quiet stochastic seed (kept in the handle, and srand) noise_mode [0] (0: the
+/* keys: TOLERANCE NITERMAX NITERMIN (nodal-poisson.h:19-23) DT quiet wavelet_tiles [0] (msomn_create_tiled above) stochastic seed (kept in the handle, and srand) noise_mode [0] (0: the
  * noise is drawn from the serial rand() stream on the host, 1: on the device by k_n_noise; other values: MSOM_ERR_ARG); implementation switches (result-preserving in
  * the strict build): node_split [65] levels of >= that many vertices a side keep correction / residual / mask / S2 copies in the
  * x-parity split layout (0: off), s2_rows [1] row tables for an S2 that does not depend on x, node_pfused [1] prolongation folded into the first colour pass of the split levels, mg_coarse [32] levels of at most that
@@ -674,8 +681,8 @@ int msomn_run(msomn_t *m, const char *workdir, long nsteps_max);
  * invert q, masked wavelet transform (qg-node/wavelet_vertex.h:10-46) of the cell average of psi scaled by sig_lev
  * (:525-552; keys Lfmax, Lfmin, fac_filt_Rd), psi_f running mean, psi -= filtered part, q = comp_q(psi) */
 int msomn_wavelet_filter(msomn_t *m, double dtflt);
-int msomn_dbg_wv_get(msomn_t *m, int what /* 0 sig_lev, 1 mask_c */, int level, double *out /* [n][n], n = N >> level */);
-int msomn_dbg_wv_apply(msomn_t *m, const double *in, double *out /* cell fields [nl][N][N] */);
+int msomn_dbg_wv_get(msomn_t *m, int what /* 0 sig_lev, 1 mask_c */, int level, double *out /* [n][n], n = N >> level; tiles: msomn_create_tiled */);
+int msomn_dbg_wv_apply(msomn_t *m, const double *in, double *out /* cell fields [nl][N][N]; tiles: the window [nl][Ty][Tx] */);
 /* multigrid pieces on level arrays [layer][n_k+1][n_k+1] (level 0 = finest), for the parity tests */
 int msomn_dbg_relax(msomn_t *m, int level, double *da, const double *res, int nsweeps);
 int msomn_dbg_residual(msomn_t *m, const double *a, const double *b, double *res, double *maxres);

@@ -1185,10 +1185,18 @@ class NodeQG:
     def dbg_del2_zeta(self):
         self._chk(self.L.msomn_dbg_del2_zeta(self.h))
 
-    # stochastic forcing (cell scalars)
+    def _cshape(self, k=0):
+        """cells of level k of the noise / wavelet pyramids as this handle holds them: the tile's window ((ny - 1, nx - 1) >> k) below
+        the gather level (param agg_level), the global level (N >> k a side) at and above it; one tile: always the global level (and so without the option wavelet_tiles,
+        where the library refuses these calls on tiles)"""
+        if self.tile[0] * self.tile[1] > 1 and self.param("wavelet_tiles") == 1 and k < int(self.param("agg_level")):
+            return (self.ny - 1) >> k, (self.nx - 1) >> k
+        return self.N >> k, self.N >> k
+
+    # stochastic forcing (cell scalars; on tiles, option wavelet_tiles = 1: the tile's window, collective)
     def noise(self, set=None, filter=False):
-        out = np.empty((self.N, self.N))
-        a = None if set is None else _f64(set, (self.N, self.N))
+        out = np.empty(self._cshape())
+        a = None if set is None else _f64(set, self._cshape())
         self._chk(self.L.msomn_dbg_noise(self.h, _ptr(a), int(filter), _ptr(out)))
         return out
 
@@ -1198,8 +1206,7 @@ class NodeQG:
         self._chk(self.L.msomn_noise_draw(self.h, int(filter)))
 
     def csig(self, k):
-        n = self.N >> k
-        out = np.empty((n, n))
+        out = np.empty(self._cshape(k))
         self._chk(self.L.msomn_dbg_csig(self.h, k, _ptr(out)))
         return out
 
@@ -1208,13 +1215,12 @@ class NodeQG:
         self._chk(self.L.msomn_wavelet_filter(self.h, dtflt))
 
     def wv_get(self, what, k):
-        n = self.N >> k
-        out = np.empty((n, n))
+        out = np.empty(self._cshape(k))
         self._chk(self.L.msomn_dbg_wv_get(self.h, what, k, _ptr(out)))
         return out
 
     def wv_apply(self, cells):
-        cells = _f64(cells, (self.nl, self.N, self.N))
+        cells = _f64(cells, (self.nl,) + self._cshape())
         out = np.empty_like(cells)
         self._chk(self.L.msomn_dbg_wv_apply(self.h, _ptr(cells), _ptr(out)))
         return out

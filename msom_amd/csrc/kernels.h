@@ -444,6 +444,9 @@ void launch_n_pack_strip(hipStream_t st, const double *f, const NatGeom &g, int 
 void launch_n_unpack_strip(hipStream_t st, double *f, const NatGeom &g, int sp, int nl, int i0, int j0, int w, int h, const double *buf);
 void launch_n_assemble(hipStream_t st, const double *recv, double *f, const NatGeom &g, int nl, int N, int px, int py, int k);
 void launch_n_extract(hipStream_t st, const double *f, const NatGeom &g, double *t, const NatGeom &tg, int nl, int ox, int oy);
+// cell pyramids on tiles: the noise draw of a tile with its ring, keyed by the global cell; the gathered cell pieces -> a global level
+void launch_n_noise_tile(hipStream_t st, double *n, const NatGeom &g, double amp, unsigned seed, unsigned draw, int ox, int oy, int N);
+void launch_c_assemble(hipStream_t st, const double *recv, double *f, const NatGeom &g, int nl, int N, int px, int py, int k);
 
 // ---- kernels_node_stats.hip: running statistics of the vertex model (msomn_stats_*); StatsAcc as above, on the held vertices
 struct NStatsTile { int ox, oy, N; };   // global index of the tile's vertex (0, 0) and the global side in cells: i or j in {0, N} is the domain boundary

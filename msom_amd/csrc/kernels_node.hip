@@ -1571,3 +1571,28 @@ __global__ void k_n_extract(const double *__restrict__ f, NatGeom g, double *t, 
 void launch_n_extract(hipStream_t st, const double *f, const NatGeom &g, double *t, const NatGeom &tg, int nl, int ox, int oy) {
   hipLaunchKernelGGL(k_n_extract, grid2d(tg.nx + 2, tg.ny + 2), block2d(), 0, st, f, g, t, tg, nl, ox, oy);
 }
+
+// ---------------------------------------------------------------- cell pyramids on tiles (noise and scale filter, msomn_cells.hip)
+// k_n_noise on a tile of g.nx x g.ny cells with origin (ox, oy) in the grid of N x N cells: every cell of the tile and of its ring draws
+// with the counter of the GLOBAL cell it is or mirrors (ctile_noise_index), so the ring holds what the halo exchange and the Neumann
+// fill would bring and an unfiltered draw needs neither
+__global__ void k_n_noise_tile(double *n, NatGeom g, double amp, unsigned seed, unsigned draw, int ox, int oy, int N) {
+  const int ti = blockIdx.x * BX + threadIdx.x, tj = blockIdx.y * BY + threadIdx.y;
+  if (ti > g.nx + 1 || tj > g.ny + 1) return;
+  const int i = ti <= g.nx ? ti : -1, j = tj <= g.ny ? tj : -1;
+  n[nat_idx(g, 0, j, i)] = amp * philox_normal(ctile_noise_index(N, ox, oy, i, j), 0u, draw, seed);
+}
+void launch_n_noise_tile(hipStream_t st, double *n, const NatGeom &g, double amp, unsigned seed, unsigned draw, int ox, int oy, int N) {
+  hipLaunchKernelGGL(k_n_noise_tile, grid2d(g.nx + 2, g.ny + 2), block2d(), 0, st, n, g, amp, seed, draw, ox, oy, N);
+}
+// the gathered cell pieces of level k ([rank][l][ty][tx], comm_allgather) -> the global cell level in the natural layout; a cell
+// belongs to one tile, so there are no copies to choose between
+__global__ void k_c_assemble(const double *__restrict__ recv, double *f, NatGeom g, int nl, int N, int px, int py, int k) {
+  VTX(g, I, J);
+  for (int l = 0; l < nl; l++) f[nat_idx(g, l, J, I)] = recv[ctile_gather_src(N, px, py, k, nl, l, I, J)];
+}
+void launch_c_assemble(hipStream_t st, const double *recv, double *f, const NatGeom &g, int nl, int N, int px, int py, int k) {
+  hipLaunchKernelGGL(k_c_assemble, grid2d(g.nx, g.ny), block2d(), 0, st, recv, f, g, nl, N, px, py, k);
+}
+// (the way back, the tile's window of a global cell level with its ring, is k_n_extract as it stands: it copies [-1, nx] x [-1, ny] of
+// whatever geometry it is given, and beyond a wall it then reads the global ghost ring, which the boundary condition filled)

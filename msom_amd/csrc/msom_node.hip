@@ -81,6 +81,8 @@ extern "C" void msomn_destroy(msomn_t *m) {
   }
   for (auto *v : {&m->ws, &m->wr, &m->wsig, &m->wmc})
     for (double *q : *v) if (q) (void)hipFree(q);
+  ct_free_piece(m->cpiece);
+  ct_free_piece(m->wpiece);
   if (m->psi_alt) (void)hipFree(m->psi_alt);
   if (m->ev_res) (void)hipEventDestroy(m->ev_res);
   if (m->qeff) (void)hipFree(m->qeff);
@@ -199,7 +201,7 @@ extern "C" int msomn_set_option(msomn_t *m, const char *key, double v) {
     // the fused passes have no tiled form: they stay off, whatever is asked for (msomn_get_param shows the resolved value)
     for (const char *off : {"tiled_relax", "node_pfused", "node_corr_fused", "node_rhs_fused", "node_tile_s", "node_march", "node_march_s"})
       if (!strcmp(key, off)) return MSOM_OK;
-    if (!strcmp(key, "stochastic") && v != 0.) return nt_refuse(m, "option stochastic");
+    if (!strcmp(key, "stochastic") && v != 0. && !m->wavelet_tiles) return nt_refuse(m, "option stochastic");
     if (!strcmp(key, "mg_coarse") && m->const_set) {
       msom_set_error("option mg_coarse decides which levels live on the tiles: set it before msomn_set_const");
       return MSOM_ERR_STATE;
@@ -226,6 +228,10 @@ extern "C" int msomn_set_option(msomn_t *m, const char *key, double v) {
   else if (!strcmp(key, "node_march_rows")) m->node_march_rows = (int)v;
   else if (!strcmp(key, "mg_coarse")) { m->mg_coarse = (int)v; if (m->const_set) return choose_layouts(m); }
   else if (!strcmp(key, "stochastic")) m->stochastic = (int)v;
+  else if (!strcmp(key, "wavelet_tiles")) {   // the noise and the scale filter on tiles (msomn_cells.hip); one tile: accepted, no effect
+    if (v != 0. && v != 1.) { msom_set_error("wavelet_tiles = %g: 0 (the wavelet pyramid is refused on tiles) or 1", v); return MSOM_ERR_ARG; }
+    m->wavelet_tiles = (int)v;
+  }
   else if (!strcmp(key, "ckpt_steps")) m->ckpt_steps = (int)v;   // msomn_run, include/msomn_state.h
   else if (!strcmp(key, "resume")) m->resume = (int)v;
   else if (!strcmp(key, "stats")) {   // msomn_step takes one sample per stats_every steps (msomn_stats.hip)
@@ -310,6 +316,7 @@ extern "C" double msomn_get_param(msomn_t *m, const char *k) {
   if (!strcmp(k, "noise_mode")) return m->noise_mode;
   if (!strcmp(k, "seed")) return m->seed;
   if (!strcmp(k, "noise_draw")) return m->noise_draw;   // number of the next draw of the device generator
+  if (!strcmp(k, "wavelet_tiles")) return m->wavelet_tiles;
   // tiles: the decomposition, the gather level (levels below live on the tiles), halo exchanges since the last msomn_profile_reset
   if (!strcmp(k, "px")) return m->px;
   if (!strcmp(k, "py")) return m->py;
@@ -773,6 +780,7 @@ NatGeom cell_geom(int n) {
 static int stoch_setup(msomn *m) {  // pyramids of the cell scalar + wavelet coefficients of the uniform filter length L_filt
   const NodeParams &p = m->p;
   int r;
+  if (m->ntiles > 1) return ct_stoch_setup(m);   // windows below the gather level of this msomn_set_const, global levels from it on
   if (m->cnlev == 0) {
     int c = 1;
     while ((m->N >> c) >= 1) c++;
@@ -814,10 +822,21 @@ static int stoch_setup(msomn *m) {  // pyramids of the cell scalar + wavelet coe
   return MSOM_OK;
 }
 static void cell_bc(msomn *m, double *f, const NatGeom &g) { launch_fill_ghost(m->st, f, g, 1, BC_NEUMANN, WALL_ALL); }
+// the calls of the wavelet pyramid on a tiled handle: refused unless the option wavelet_tiles is on (then they are collective)
+static int wv_refuse(const msomn *m, const char *call) { return m && m->wavelet_tiles ? MSOM_OK : nt_refuse(m, call); }
+// noise_mode 0 is the serial rand() stream of the host: one state per process, while the in-process tiles are threads of one process,
+// so the tiles could not draw the single tile's numbers.  Asked before anything is posted
+static int noise_mode_refuse(const msomn *m, const char *call) {
+  if (m->ntiles == 1 || m->noise_mode == 1) return MSOM_OK;
+  msom_set_error("%s: noise_mode = 0 is not available on a tiled vertex-grid handle (%d x %d tiles): the host's rand() stream is one state per process "
+                 "and cannot be shared by tiles; set noise_mode = 1 (device generator)", call, m->px, m->py);
+  return MSOM_ERR_CONFIG;
+}
 void node_noise_ghosts(msomn *m) { cell_bc(m, m->cs[0], m->cg[0]); }
 // wavelet -> scale by sig_lev -> inverse wavelet of the cell field cs[0] (kernels_wavelet.hip, one layer, default BC)
 // ghosts_set: the ghost ring of cs[0] is already what cell_bc would write (k_n_noise)
 static int cell_wavelet_filter(msomn *m, int ghosts_set = 0) {
+  if (m->ntiles > 1) return ct_noise_filter(m, ghosts_set);
   const int K = m->cnlev;
   if (!ghosts_set) cell_bc(m, m->cs[0], m->cg[0]);
   for (int k = 1; k < K; k++) {
@@ -841,6 +860,7 @@ static int upload_cells(msomn *m, const double *a) {
   const NatGeom &g = m->cg[0];
   HIPCHK(hipMemcpy2DAsync(m->cs[0] + nat_idx(g, 0, 0, 0), g.pitch * sizeof(double), a, g.nx * sizeof(double), g.nx * sizeof(double), g.ny, hipMemcpyDefault, m->st));
   HIPCHK(hipStreamSynchronize(m->st));
+  if (m->ntiles > 1) return ct_ring(m, m->cs[0], g, 1, BC_NEUMANN);   // k_n_add_noise reads the ring
   cell_bc(m, m->cs[0], g);
   return MSOM_OK;
 }
@@ -849,8 +869,11 @@ static int upload_cells(msomn *m, const double *a) {
 // all queued on the handle's stream (no host buffer, no synchronisation)
 static int generate_noise(msomn *m, int filter = 1) {
   const int N = m->N;
+  if (int rt = noise_mode_refuse(m, "noise draw")) return rt;
   if (m->noise_mode == 1) {
-    launch_n_noise(m->st, m->cs[0], m->cg[0], m->p.amp_stoch, m->seed, m->noise_draw++);
+    // (tiles: every cell of the window and of its ring is keyed by the global cell it is or mirrors; the counter moves alike on all ranks)
+    if (m->ntiles > 1) launch_n_noise_tile(m->st, m->cs[0], m->cg[0], m->p.amp_stoch, m->seed, m->noise_draw++, m->ox, m->oy, N);
+    else launch_n_noise(m->st, m->cs[0], m->cg[0], m->p.amp_stoch, m->seed, m->noise_draw++);
     HIPCHK(hipGetLastError());
     return filter ? cell_wavelet_filter(m, 1) : MSOM_OK;
   }
@@ -864,13 +887,14 @@ static int generate_noise(msomn *m, int filter = 1) {
   return r || !filter ? r : cell_wavelet_filter(m);
 }
 extern "C" int msomn_noise_draw(msomn_t *m, int filter) {
-  if (int rt = nt_refuse(m, "msomn_noise_draw")) return rt;
+  if (int rt = wv_refuse(m, "msomn_noise_draw")) return rt;
   NEED_NCONST(m);
   if (m->cnlev == 0) { msom_set_error("stochastic forcing is off"); return MSOM_ERR_STATE; }
+  if (int rt = noise_mode_refuse(m, "msomn_noise_draw")) return rt;
   return generate_noise(m, filter);
 }
 extern "C" int msomn_dbg_noise(msomn_t *m, const double *set, int filter, double *get) {
-  if (int rt = nt_refuse(m, "msomn_dbg_noise")) return rt;
+  if (int rt = wv_refuse(m, "msomn_dbg_noise")) return rt;
   NEED_NCONST(m);
   if (m->cnlev == 0) { msom_set_error("stochastic forcing is off"); return MSOM_ERR_STATE; }
   int r;
@@ -884,7 +908,7 @@ extern "C" int msomn_dbg_noise(msomn_t *m, const double *set, int filter, double
   return MSOM_OK;
 }
 extern "C" int msomn_dbg_csig(msomn_t *m, int level, double *out) {
-  if (int rt = nt_refuse(m, "msomn_dbg_csig")) return rt;
+  if (int rt = wv_refuse(m, "msomn_dbg_csig")) return rt;
   NEED_NCONST(m);
   if (level < 0 || level >= m->cnlev || !out) { msom_set_error("bad level %d", level); return MSOM_ERR_ARG; }
   const NatGeom &g = m->cg[level];
@@ -898,6 +922,7 @@ extern "C" int msomn_dbg_csig(msomn_t *m, int level, double *out) {
 static int wv_setup(msomn *m) {
   const NodeParams &p = m->p;
   int r;
+  if (m->ntiles > 1) return ct_wv_setup(m);
   if (m->wg.empty()) {
     int c = 1;
     while ((m->N >> c) >= 1) c++;
@@ -956,6 +981,7 @@ static int wv_setup(msomn *m) {
 }
 // ws[0] <- inverse_wavelet_mask(sig_lev * wavelet_mask(ws[0])), all layers at once; dirichlet(0) ghost cells on every level
 static int wv_masked_apply(msomn *m) {
+  if (m->ntiles > 1) return ct_masked_apply(m);   // the result comes with its ring (k_wv_vertex_update reads it)
   const int K = (int)m->wg.size(), nl = m->nl;
   auto bc = [&](double *f, const NatGeom &g) { launch_fill_ghost(m->st, f, g, nl, BC_DIRICHLET0, WALL_ALL); };
   bc(m->ws[0], m->wg[0]);
@@ -979,7 +1005,7 @@ static int wv_masked_apply(msomn *m) {
 static int invert_q(msomn *m, double *q);
 static int comp_q(msomn *m, const double *psi, double *q);
 extern "C" int msomn_wavelet_filter(msomn_t *m, double dtflt) {
-  if (int rt = nt_refuse(m, "msomn_wavelet_filter")) return rt;
+  if (int rt = wv_refuse(m, "msomn_wavelet_filter")) return rt;
   NEED_NCONST(m);
   int r;
   if (!m->wv_ready && (r = wv_setup(m))) return r;
@@ -988,7 +1014,7 @@ extern "C" int msomn_wavelet_filter(msomn_t *m, double dtflt) {
   if ((r = wv_masked_apply(m))) return r;
   if (m->p.Lfmax < 1e30)  // `if (Lfmax < HUGE)`, :380
     launch_wv_vertex_update(m->st, m->f[MSOMN_PSI], m->f[MSOMN_PSIF], m->ws[0], m->f[MSOMN_MASK], m->g, m->wg[0], m->nl, dtflt, m->nbar, 1);
-  launch_n_bnd_const(m->st, m->f[MSOMN_PSI], m->g, m->nl, m->psi_bc);
+  launch_n_bnd_const(m->st, m->f[MSOMN_PSI], m->g, m->nl, m->psi_bc, 0, m->walls);
   if ((r = comp_q(m, m->f[MSOMN_PSI], m->f[MSOMN_Q]))) return r;
   m->nbar++;
   HIPCHK(hipStreamSynchronize(m->st));
@@ -996,7 +1022,7 @@ extern "C" int msomn_wavelet_filter(msomn_t *m, double dtflt) {
 }
 // what = 0: sig_lev as used at the cells, 1: mask_c; level k, out [n][n]
 extern "C" int msomn_dbg_wv_get(msomn_t *m, int what, int level, double *out) {
-  if (int rt = nt_refuse(m, "msomn_dbg_wv_get")) return rt;
+  if (int rt = wv_refuse(m, "msomn_dbg_wv_get")) return rt;
   NEED_NCONST(m);
   int r;
   if (!m->wv_ready && (r = wv_setup(m))) return r;
@@ -1009,7 +1035,7 @@ extern "C" int msomn_dbg_wv_get(msomn_t *m, int what, int level, double *out) {
 }
 // the masked transform pair alone on a cell field [nl][N][N]
 extern "C" int msomn_dbg_wv_apply(msomn_t *m, const double *in, double *out) {
-  if (int rt = nt_refuse(m, "msomn_dbg_wv_apply")) return rt;
+  if (int rt = wv_refuse(m, "msomn_dbg_wv_apply")) return rt;
   NEED_NCONST(m);
   int r;
   if (!m->wv_ready && (r = wv_setup(m))) return r;
@@ -1129,6 +1155,7 @@ extern "C" int msomn_update(msomn_t *m, int qf, int dqf, double dtmax, double *d
 }
 extern "C" int msomn_advance(msomn_t *m, int out, int in, int dq, double dt) {
   NEED_FIELD(m, out); NEED_FIELD(m, in); NEED_FIELD(m, dq);
+  if (m->stochastic && noise_mode_refuse(m, "msomn_advance")) return MSOM_ERR_CONFIG;
   launch_advance(m->st, m->f[out], m->f[in], m->f[dq], nullptr, m->g, m->nl, dt, 0.);
   if (m->stochastic) {  // qg-node/qg.h:306-320
     if (m->cnlev == 0) { msom_set_error("stochastic: call msomn_set_const after switching it on"); return MSOM_ERR_STATE; }
@@ -1183,6 +1210,7 @@ extern "C" int msomn_step(msomn_t *m, int with_forcing_event) {
   if (m->stats_on && !m->stats_mask) { msom_set_error("msomn_step: option stats = 1 and no msomn_stats_begin since msomn_set_const"); return MSOM_ERR_STATE; }
   int r;
   double d, tn;
+  if (m->stochastic && (r = noise_mode_refuse(m, "msomn_step"))) return r;
   if (with_forcing_event && (r = msomn_forcing(m))) return r;
   if ((r = msomn_update(m, MSOMN_Q, MSOMN_DQ, m->p.DT, &d))) return r;
   m->dt = step_dtnext(m->t, m->tnext, d, &tn);   // dtnext() [Basilisk, SURVEY App. B]

@@ -47,6 +47,12 @@ struct NLevel {
   // the sides of g that are sides of the domain
   int tiled = 0, walls = WALL_ALL;
 };
+// a tile's window of level kg of a cell pyramid with its ring: what the rank gives to the gather (s) and takes back from the gathered
+// levels (s and r), msomn_cells.hip
+struct CellPiece {
+  NatGeom g;
+  double *s = nullptr, *r = nullptr;
+};
 enum { NSC_RES = 0, NSC_UMAX = 1, NSC_KE = 2, NSC_DIAG = 3 /* 3 slots */, NSC_FLOATS = 6 /* 2 slots */, NSC_COUNT = 8 };
 
 // option profile: HIP-event pairs around the finest-level launches of the vertex model (bench.py's per-kernel entries)
@@ -124,6 +130,10 @@ struct msomn {
   double *gsend = nullptr, *grecv = nullptr;   // gather buffers: one piece, ntiles pieces
   size_t gcount = 0;           // doubles of gsend
   int tile_err = 0;            // a halo exchange inside a sweep failed: the solve answers with it
+  // option wavelet_tiles: the noise and the scale filter run on tiles (msomn_cells.hip); the pyramids above then hold the tile's windows
+  // below the gather level and the global levels from it on
+  int wavelet_tiles = 0;
+  CellPiece cpiece, wpiece;
   long nexch = 0;              // halo exchanges since the last msomn_profile_reset (msomn_get_param("exchanges"))
   // state file and the driver's checkpoints (include/msomn_state.h)
   long state_flip = -1;             // msomn_state_dbg_flip: element the next load flips on the device (< 0: off)
@@ -169,6 +179,16 @@ void nt_free_gather(msomn *m);   // the piece and the gather buffers (msomn_set_
 void nt_free(msomn *m);
 // MSOM_ERR_CONFIG with a message naming the call if the handle has more than one tile
 int nt_refuse(const msomn *m, const char *call);
+
+// ---- msomn_cells.hip: the cell pyramids on tiles (option wavelet_tiles), all collective
+NatGeom cell_geom_rect(int nx, int ny);   // natural layout of a tile of nx x ny cells
+int nt_exchange_cells(msomn *m, double *f, const NatGeom &g, int nl);   // ring of a cell field: the neighbours' edge cells, corners included
+int ct_ring(msomn *m, double *f, const NatGeom &g, int nl, int bc);     // the boundary condition on the tile's walls, then the exchange
+int ct_stoch_setup(msomn *m);                  // stoch_setup: the noise pyramid and csig
+int ct_wv_setup(msomn *m);                     // wv_setup: the filter pyramid, wsig and wmc
+int ct_noise_filter(msomn *m, int ghosts_set); // cell_wavelet_filter: 2 kg - 1 exchanges and one all-gather
+int ct_masked_apply(msomn *m);                 // wv_masked_apply: the same
+void ct_free_piece(CellPiece &P);
 
 // ---- msomn_stats.hip
 void nstats_drop(msomn *m);               // frees everything msomn_stats_begin allocated (msomn_set_const, msomn_destroy)

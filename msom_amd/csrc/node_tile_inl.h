@@ -123,4 +123,43 @@ NT_HD static inline long ntile_gather_src(int N, int px, int py, int k, int nl, 
   return rank * ntile_piece_count(N, px, py, k, nl) + ((long)l * (ty + 1) + j) * (tx + 1) + i;
 }
 
+// ---- cell fields on tiles (the wavelet pyramids of the noise and of the scale filter; tools/node_cell_tile_host_check.cpp).
+// Level k of a cell pyramid has n_k = N >> k cells a side, down to the 1-cell root.  A cell belongs to exactly one tile: the tile of
+// ntile_level(.., k) holds the tx x ty cells [ox, ox + tx) x [oy, oy + ty), local cell (i, j) is global cell (ox + i, oy + j), nothing
+// is shared.  The halo is the ring i = -1, i = tx, j = -1, j = ty: beyond a seam the neighbour's edge cell (its local tx - 1 / 0 /
+// ty - 1 / 0, corners from the diagonal neighbour), beyond a wall the ghost cell of the boundary condition, which mirrors the edge
+// cell.  Levels k < kg (ntile_kg) live on the tiles, with >= 2 cells a side and an even origin; levels k >= kg on every rank.
+NT_HD static inline bool ctile_origin_even(const NodeTile &t) { return !(t.ox & 1) && !(t.oy & 1); }
+// where ring or interior cell (i, j), -1 <= i <= tx, -1 <= j <= ty, of the tile `rank` on level k gets its value from: the rank that
+// holds the cell and its local index there.  A cell beyond a wall is the mirror image of the cell inside (the boundary condition
+// gives it that cell's value or minus it), found by clamping against the GLOBAL grid
+NT_HD static inline int ctile_halo_src(int N, int px, int py, int rank, int k, int i, int j, int *si, int *sj) {
+  const NodeTile t = ntile_level(N, px, py, rank, k);
+  const int n = N >> k;
+  int I = t.ox + i, J = t.oy + j;
+  I = I < 0 ? 0 : I > n - 1 ? n - 1 : I;
+  J = J < 0 ? 0 : J > n - 1 ? n - 1 : J;
+  const int ix = I / t.tx, iy = J / t.ty;
+  *si = I - ix * t.tx; *sj = J - iy * t.ty;
+  return iy * px + ix;
+}
+// the gather of cell level k: every rank contributes its window, [nl][ty][tx] contiguous, lined up by rank
+NT_HD static inline long ctile_piece_count(int N, int px, int py, int k, int nl) { return (long)nl * ((N >> k) / px) * ((N >> k) / py); }
+// position of global cell (I, J) of layer l in the gathered buffer
+NT_HD static inline long ctile_gather_src(int N, int px, int py, int k, int nl, int l, int I, int J, int *rank_out = nullptr) {
+  const int tx = (N >> k) / px, ty = (N >> k) / py;
+  const int ix = I / tx, iy = J / ty, rank = iy * px + ix;
+  if (rank_out) *rank_out = rank;
+  return rank * ctile_piece_count(N, px, py, k, nl) + ((long)l * ty + (J - iy * ty)) * tx + (I - ix * tx);
+}
+// counter of the device noise generator for local cell (i, j) of a tile with origin (ox, oy), ring included: the index of the global
+// cell, clamped against the global N (k_n_noise on one tile: sj * N + si).  A ring cell beyond a seam is the neighbour's own draw, one
+// beyond a wall the Neumann copy
+NT_HD static inline unsigned ctile_noise_index(int N, int ox, int oy, int i, int j) {
+  int I = ox + i, J = oy + j;
+  I = I < 0 ? 0 : I > N - 1 ? N - 1 : I;
+  J = J < 0 ? 0 : J > N - 1 ? N - 1 : J;
+  return (unsigned)J * (unsigned)N + (unsigned)I;
+}
+
 #endif

@@ -109,6 +109,37 @@ def node_assemble(pieces, N, px, py, check_shared=True):
     return out
 
 
+def cell_tile_window(N, px, py, rank, k=0):
+    """(slice_y, slice_x) of this rank's cells in a global [.., N >> k, N >> k] array of level k of a cell pyramid of the vertex model
+    (the noise, the wavelet filter).  A cell belongs to exactly one tile: the windows do not overlap.  Level k must have at least one
+    cell a tile side (the library tiles the levels below param agg_level, which have two)."""
+    _node_tile_cells(N, px, py)
+    if not 0 <= rank < px * py:
+        raise ValueError(f"rank {rank} outside 0 .. {px * py - 1}")
+    n = N >> k
+    if k < 0 or n < px or n < py:
+        raise ValueError(f"level {k} of N = {N} has fewer than one cell a tile side on {px} x {py} tiles")
+    tx, ty = n // px, n // py
+    ix, iy = tile_of_rank(rank, px, py)
+    return slice(iy * ty, (iy + 1) * ty), slice(ix * tx, (ix + 1) * tx)
+
+
+def cell_assemble(pieces, N, px, py, k=0):
+    """Global [.., N >> k, N >> k] array of cell level k from the px * py tile windows [.., Ty >> k, Tx >> k] in rank order."""
+    if len(pieces) != px * py:
+        raise ValueError(f"{len(pieces)} pieces for {px} x {py} tiles")
+    pieces = [np.asarray(p) for p in pieces]
+    n = N >> k
+    out = np.empty(pieces[0].shape[:-2] + (n, n), pieces[0].dtype)
+    for rank, p in enumerate(pieces):
+        sy, sx = cell_tile_window(N, px, py, rank, k)
+        want = pieces[0].shape[:-2] + (sy.stop - sy.start, sx.stop - sx.start)
+        if p.shape != want:
+            raise ValueError(f"piece of rank {rank}: {p.shape}, expected {want}")
+        out[..., sy, sx] = p
+    return out
+
+
 def broadcast_unique_id(dist, make_id, device="cpu"):
     """Rank 0 creates the 128-byte communicator id (ncclUniqueId), everybody receives it."""
     import torch
