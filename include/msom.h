@@ -571,15 +571,24 @@ msomn_t *msomn_create_str(const char *params_text);
  * gives shared vertices the same values on every holder (not checked).  msomn_set_field, msomn_set_const and every call that
  * computes are COLLECTIVE: all ranks call them, in the same order.  Everything that depends on x or y uses the global vertex index.
  * px = py = 1 gives the plain handle.  NULL with msom_last_error set for px / py not a power of two, N not divisible, a tile side
- * below 2 cells, a bad rank, bc_fac = -1, sqg = 1 on more than one tile.
+ * below 2 cells, a bad rank, bc_fac = -1.  sqg = 1 runs on tiles as on one (S2S takes f at the global row; laplacian(bs) copies at walls
+ * of the domain only and reads the halo of bs on an interior edge).
  * On more than one tile the multigrid levels down to the gather level (msomn_get_param "agg_level": the first level of at most
  * max(mg_coarse, px, py) cells a side, at least level 1) live on the tiles, the coarser ones are gathered and solved on every rank;
  * set option mg_coarse before msomn_set_const.  The fused passes resolve to off (options node_pfused, node_tile_s, node_march_s,
  * node_march, tiled_relax, node_corr_fused, node_rhs_fused read 0 and stay 0); msomn_get_param "exchanges" counts halo exchanges.
  * msomn_dbg_relax / _residual / _restrict / _prolong / _level_mask work on the tiled levels with tile-sized arrays (a gathered
- * level: MSOM_ERR_ARG).  Refused with MSOM_ERR_CONFIG and a message naming the call, the handle unchanged: msomn_run, msomn_write_nc,
- * msomn_read_nc, msomn_state_save / _load, msomn_dbg_del2_zeta, and, unless the option wavelet_tiles is 1: option stochastic,
- * msomn_noise_draw, msomn_dbg_noise, msomn_dbg_csig, msomn_wavelet_filter, msomn_dbg_wv_get / _apply.
+ * level: MSOM_ERR_ARG).  Refused with MSOM_ERR_CONFIG and a message naming the call, the handle unchanged: msomn_dbg_del2_zeta; unless
+ * the option io_tiles is 1: msomn_run, msomn_write_nc, msomn_read_nc, msomn_state_save / _load; and, unless the option wavelet_tiles is
+ * 1: option stochastic, msomn_noise_draw, msomn_dbg_noise, msomn_dbg_csig, msomn_wavelet_filter, msomn_dbg_wv_get / _apply.
+ * Option io_tiles [0] (0 or 1, else MSOM_ERR_ARG; on one tile accepted, no effect): with 1 those five calls are COLLECTIVE.  A tile
+ * OWNS its local columns 0 .. Tx - 1, and column Tx too iff it is the last tile of its row of tiles, rows likewise: every global
+ * vertex is owned once.  Save and write_nc gather the owned windows and rank 0 writes the global arrays -- the files equal the single
+ * tile's byte for byte; load and read_nc: every rank reads the shared file and takes its window, shared vertices and halos included; a
+ * state file of any tiling loads on any other (include/msomn_state.h).  What one rank alone can see (rank 0's write, a short read)
+ * ends in one all-reduce: every rank returns the same code, the rank that saw the cause carries the message, the handle stays as it
+ * was.  msomn_run: rank 0 alone makes the output directory, prints and writes; it needs msomn_set_const or a state.msom to resume
+ * from (MSOM_ERR_STATE otherwise: the driver's cold start draws from the process-wide rand()), and wavelet_tiles = 1 when dtflt > 0.
  * Option wavelet_tiles [0] (0 or 1, else MSOM_ERR_ARG; on one tile accepted, no effect): with 1 those calls, and msomn_step /
  * msomn_advance with the stochastic forcing, run on the tiles as COLLECTIVE calls with the single tile's bits.  The cell pyramids
  * then hold the tile's window of (Tx >> k) x (Ty >> k) cells on the levels k < agg_level and the global level of (N >> k)^2 cells on
@@ -588,9 +597,12 @@ msomn_t *msomn_create_str(const char *params_text);
  * halo exchanges and one all-gather.  noise_mode = 0 stays refused on more than one tile wherever a draw would be taken (the host's
  * rand() stream is one state per process and cannot be shared by tiles): set noise_mode = 1. */
 msomn_t *msomn_create_tiled(const char *params_text, int px, int py, int rank, const void *id128);
+/* msomn_create_tiled of the params text in a state file (include/msomn_state.h), io_tiles = 1, wavelet_tiles = 1 if the file is
+ * stochastic or holds psi_f, the options the file records, msomn_state_load.  Collective; NULL on the errors of either call. */
+msomn_t *msomn_create_tiled_from_state(const char *path, int px, int py, int rank, const void *id128);
 int msomn_tile_info(msomn_t *m, int *px, int *py, int *ix, int *iy, int *nx_local, int *ny_local);  /* vertices: Tx + 1, Ty + 1 */
 void msomn_destroy(msomn_t *m);                                 /* trash_vars qg.h:537-544 */
-/* keys: TOLERANCE NITERMAX NITERMIN (nodal-poisson.h:19-23) DT quiet wavelet_tiles [0] (msomn_create_tiled above) stochastic seed (kept in the handle, and srand) noise_mode [0] (0: the
+/* keys: TOLERANCE NITERMAX NITERMIN (nodal-poisson.h:19-23) DT quiet wavelet_tiles [0] io_tiles [0] (both: msomn_create_tiled above) stochastic seed (kept in the handle, and srand) noise_mode [0] (0: the
  * noise is drawn from the serial rand() stream on the host, 1: on the device by k_n_noise; other values: MSOM_ERR_ARG); implementation switches (result-preserving in
  * the strict build): node_split [65] levels of >= that many vertices a side keep correction / residual / mask / S2 copies in the
  * x-parity split layout (0: off), s2_rows [1] row tables for an S2 that does not depend on x, node_pfused [1] prolongation folded into the first colour pass of the split levels, mg_coarse [32] levels of at most that

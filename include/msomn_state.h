@@ -34,6 +34,14 @@
  *   (msom_create_from_state of msom_state.h makes those, and returns NULL on a file of this dialect).
  * msomn_state_dbg_flip: test aid.  The next msomn_state_load on this handle flips the lowest mantissa bit of element `element` of the
  *   first field record on the device, between the upload and the device digest (element < 0: off).  That load must fail.
+ * On tiles (msomn_create_tiled, option io_tiles = 1; refused with MSOM_ERR_CONFIG without it): save and load are COLLECTIVE.  The file
+ *   does not know its tiling: a px x py handle writes, byte for byte, the file the single tile writes at the same point of the same run
+ *   (run with the option values the tiled handle reports), and a file of any tiling loads on any other.  A rank's digest word covers
+ *   the vertices it owns (include/msom.h), with their global indices; the words add up over the ranks, so every rank reaches the same
+ *   verdict.  Every rank returns the same code; a save has returned on no rank before the file is in place.  msomn_state_dbg_flip
+ *   takes its element modulo the tile's owned window.  msomn_create_tiled_from_state (declared in msom.h beside msomn_create_tiled):
+ *   msomn_create_tiled of the params text in the file, io_tiles = 1, wavelet_tiles = 1 when the file is stochastic or holds psi_f, the
+ *   options the file records, the load.
  * Options of msomn_set_option that use these calls: "ckpt_steps" [0 = off]: msomn_run writes <workdir>/state.msom (with constants and
  *   its own event schedule) every that many steps; "resume" [0]: msomn_run continues from <workdir>/state.msom if it exists, in the
  *   output directory the file names, with vars.nc and diag_1d.dat set back to what they held at the checkpoint.

@@ -208,6 +208,7 @@ def load_library(strict=False):
         "msomn_state_save": (ci, [vp, cs, C.c_uint]),
         "msomn_state_load": (ci, [vp, cs]),
         "msomn_create_from_state": (vp, [cs]),
+        "msomn_create_tiled_from_state": (vp, [cs, ci, ci, ci, vp]),
         "msomn_state_dbg_flip": (ci, [vp, C.c_long]),
         # Lagrangian floats of the vertex model (include/msomn_floats.h)
         "msomn_floats_begin": (ci, [vp, ci, vp, vp, vp]),
@@ -284,10 +285,16 @@ def from_state(path, strict=False):
     return g
 
 
-def node_from_state(path, strict=False):
-    """msomn_create_from_state: a vertex-grid model made from the params text in a state file saved with constants, loaded"""
+def node_from_state(path, strict=False, tiled=None):
+    """msomn_create_from_state: a vertex-grid model made from the params text in a state file saved with constants, loaded.
+    tiled = (px, py, rank, uid): msomn_create_tiled_from_state, this rank's tile of the file's grid (collective: every rank calls it with
+    the same file, whatever tiling wrote it); the handle has io_tiles = 1, and wavelet_tiles = 1 if the file is stochastic or filtered"""
     L = load_library(strict)
-    h = L.msomn_create_from_state(os.fsencode(path))
+    if tiled is not None:
+        px, py, rank, uid = tiled
+        h = L.msomn_create_tiled_from_state(os.fsencode(path), px, py, rank, uid)
+    else:
+        h = L.msomn_create_from_state(os.fsencode(path))
     if not h:
         raise MsomError(L.msom_last_error().decode())
     g = NodeQG.__new__(NodeQG)
@@ -921,7 +928,9 @@ class NodeQG:
     [layers][N+1][N+1] (qg-node/netcdf_vertex_bas.h:253).
     tiled = (px, py, rank, uid): this rank's tile of a px x py decomposition (msomn_create_tiled); field arrays are then the tile's
     [layers][ny][nx] with nx = N / px + 1, ny = N / py + 1 vertices, the ones on the interior edges included
-    (msom_amd.tiling.node_tile_window), and set(), set_const() and every call that computes are collective."""
+    (msom_amd.tiling.node_tile_window), and set(), set_const() and every call that computes are collective.  With
+    set_option("io_tiles", 1) so are save_state / load_state / write_nc / read_nc / run: rank 0 writes the single tile's files, every
+    rank reads its window of them (node_from_state(path, tiled=...) makes the tiles from a state file)."""
 
     def __init__(self, params=None, path=None, strict=False, tiled=None):
         self.L = load_library(strict)

@@ -177,17 +177,19 @@ void launch_n_stretch_sqg(hipStream_t st, const double *in, const double *bs, co
   hipLaunchKernelGGL(k_n_stretch_sqg, grid2d(g.nx, g.ny), block2d(), 0, st, in, bs, S2S, out, S2, g, nl, add, fac, lc);
 }
 // del2_bs of sqg_baroclinic_ms.h:160-168: laplacian(bs) on the inner vertices, neumann(0) on the four sides (the boundary
-// vertex takes the first interior value, x sides first, so a corner takes the diagonal neighbour)
-__global__ void k_n_lap_bs(const double *__restrict__ bs, double *out, NatGeom g, double D) {
+// vertex takes the first interior value, x sides first, so a corner takes the diagonal neighbour).  A tile (g rectangular): the copy
+// happens on the sides that are walls of the domain; a vertex on an interior edge takes the laplacian from the halo of bs
+__global__ void k_n_lap_bs(const double *__restrict__ bs, double *out, NatGeom g, double D, int walls) {
   VTX(g, i, j);
-  const int n = g.nx - 1;
-  const int ii = i == 0 ? 1 : (i == n ? n - 1 : i), jj = j == 0 ? 1 : (j == n ? n - 1 : j);
+  const int nx = g.nx - 1, ny = g.ny - 1;
+  const int ii = (i == 0 && (walls & WALL_W)) ? 1 : ((i == nx && (walls & WALL_E)) ? nx - 1 : i);
+  const int jj = (j == 0 && (walls & WALL_S)) ? 1 : ((j == ny && (walls & WALL_N)) ? ny - 1 : j);
   const size_t c = nat_idx(g, 0, jj, ii);
   const double D2 = D * D;
   out[nat_idx(g, 0, j, i)] = DIVC(LAPN(bs, c, g.pitch), D2, 1. / D2);
 }
-void launch_n_lap_bs(hipStream_t st, const double *bs, double *out, const NatGeom &g, double D) {
-  hipLaunchKernelGGL(k_n_lap_bs, grid2d(g.nx, g.ny), block2d(), 0, st, bs, out, g, D);
+void launch_n_lap_bs(hipStream_t st, const double *bs, double *out, const NatGeom &g, double D, int walls) {
+  hipLaunchKernelGGL(k_n_lap_bs, grid2d(g.nx, g.ny), block2d(), 0, st, bs, out, g, D, walls);
 }
 // right-hand side of the surface-QG inversion: q with the known surface term of the top layer removed
 __global__ void k_n_sqg_rhs(const double *__restrict__ q, const double *__restrict__ S2S, const double *__restrict__ bs, double *qeff, NatGeom g, int nl,

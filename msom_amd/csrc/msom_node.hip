@@ -145,7 +145,6 @@ static msomn *node_create(const NodeParams &p, const char *text, int px = 1, int
     msom_set_error("msomn_create_tiled: %s (N = %d, %d x %d tiles, rank %d)", why, p.N, px, py, rank);
     return nullptr;
   }
-  if (px * py > 1 && p.sqg) { msom_set_error("msomn_create_tiled: sqg = 1 is not available on more than one tile"); return nullptr; }
   if (px * py > 1 && !id128) { msom_set_error("msomn_create_tiled: null communicator id"); return nullptr; }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
@@ -232,6 +231,10 @@ extern "C" int msomn_set_option(msomn_t *m, const char *key, double v) {
     if (v != 0. && v != 1.) { msom_set_error("wavelet_tiles = %g: 0 (the wavelet pyramid is refused on tiles) or 1", v); return MSOM_ERR_ARG; }
     m->wavelet_tiles = (int)v;
   }
+  else if (!strcmp(key, "io_tiles")) {   // state files, NetCDF and msomn_run as collective calls (msomn_state.hip, msomn_io.hip); one tile: accepted, no effect
+    if (v != 0. && v != 1.) { msom_set_error("io_tiles = %g: 0 (state files, NetCDF and msomn_run are refused on tiles) or 1", v); return MSOM_ERR_ARG; }
+    m->io_tiles = (int)v;
+  }
   else if (!strcmp(key, "ckpt_steps")) m->ckpt_steps = (int)v;   // msomn_run, include/msomn_state.h
   else if (!strcmp(key, "resume")) m->resume = (int)v;
   else if (!strcmp(key, "stats")) {   // msomn_step takes one sample per stats_every steps (msomn_stats.hip)
@@ -317,6 +320,7 @@ extern "C" double msomn_get_param(msomn_t *m, const char *k) {
   if (!strcmp(k, "seed")) return m->seed;
   if (!strcmp(k, "noise_draw")) return m->noise_draw;   // number of the next draw of the device generator
   if (!strcmp(k, "wavelet_tiles")) return m->wavelet_tiles;
+  if (!strcmp(k, "io_tiles")) return m->io_tiles;
   // tiles: the decomposition, the gather level (levels below live on the tiles), halo exchanges since the last msomn_profile_reset
   if (!strcmp(k, "px")) return m->px;
   if (!strcmp(k, "py")) return m->py;
@@ -426,7 +430,7 @@ static int rhs_pv_body(msomn *m, double *q, double *dq) {
     std::swap(m->f[MSOMN_PSI], m->psi_alt);
     psi = m->f[MSOMN_PSI];
     launch_n_del2_bnd(m->st, zeta, tmp, m->g, nl, m->D, bcc(m), m->sqg ? 0 : 1, m->sqg ? m->psi_bc : 0.);
-    if (m->sqg) launch_n_lap_bs(m->st, m->f[MSOMN_BS], m->d2bs, m->g, m->D);
+    if (m->sqg) launch_n_lap_bs(m->st, m->f[MSOMN_BS], m->d2bs, m->g, m->D, m->walls);
     launch_n_rhs_all(m->st, psi, zeta, tmp, m->f[MSOMN_PSIPG], S2, m->f[MSOMN_TOPO], m->f[MSOMN_QFORC], m->forcing_3d ? m->f[MSOMN_QFORC3D] : nullptr,
                      m->f[MSOMN_MASK], m->sqg ? m->d2bs : nullptr, m->f[MSOMN_S2S], dq, m->g, nl, m->D, p.beta, drag, p.f0, p.dh[nl - 1], p.nu, -p.nu4, m->lc, m->pg_set, m->topo_set);
     HIPCHK(hipGetLastError());
@@ -440,7 +444,7 @@ static int rhs_pv_body(msomn *m, double *q, double *dq) {
   if ((rx = nt_exchange(m, zeta, m->g, 0, nl))) return rx;
   launch_n_rhs_main(m->st, psi, zeta, m->f[MSOMN_PSIPG], S2, m->f[MSOMN_TOPO], dq, m->g, nl, 1, 1, m->D, p.beta, drag, p.f0, p.dh[nl - 1], m->lc);
   if (m->sqg) {                                                                 // sqg_baroclinic_ms.h:160-174: del2_bs = laplacian(bs)
-    launch_n_lap_bs(m->st, m->f[MSOMN_BS], m->d2bs, m->g, m->D);
+    launch_n_lap_bs(m->st, m->f[MSOMN_BS], m->d2bs, m->g, m->D, m->walls);
     launch_n_stretch_sqg(m->st, zeta, m->d2bs, m->f[MSOMN_S2S], dq, S2, m->g, nl, 1., p.nu, m->lc);
   } else launch_n_stretch(m->st, zeta, dq, S2, m->g, nl, 1., p.nu, m->lc);      // :160
   launch_n_del2(m->st, zeta, tmp, m->g, nl, 0., 1.0, m->D);                     // :162 + boundary(tmp)
@@ -1075,10 +1079,10 @@ int node_const_inputs(msomn *m) {
   }
   if ((r = upload_g(m, m->f[MSOMN_S2], m->g, m->nlm, h.data()))) return r;
   if (m->sqg) {  // :545 surface layer: f / N^2 (f, not f^2)
-    std::vector<double> hs(n1 * n2);   // (sqg runs on one tile only: n2 = n1, oy = 0)
+    std::vector<double> hs(n1 * n2);
     if ((r = download_g(m, m->f[MSOMN_S2S], m->g, 1, hs.data()))) return r;
     for (size_t j = 0; j < n2; j++) {
-      const double f = p.f0 + p.flag_ms * p.beta * (j * m->D - 0.5 * p.L0);
+      const double f = p.f0 + p.flag_ms * p.beta * ((j + m->oy) * m->D - 0.5 * p.L0);
       for (size_t i = 0; i < n1; i++) hs[j * n1 + i] = f / hs[j * n1 + i];
     }
     if ((r = upload_g(m, m->f[MSOMN_S2S], m->g, 1, hs.data()))) return r;

@@ -134,6 +134,8 @@ struct msomn {
   // below the gather level and the global levels from it on
   int wavelet_tiles = 0;
   CellPiece cpiece, wpiece;
+  // option io_tiles: msomn_state_save / _load, msomn_write_nc / _read_nc and msomn_run are collective calls on tiles instead of refused
+  int io_tiles = 0;
   long nexch = 0;              // halo exchanges since the last msomn_profile_reset (msomn_get_param("exchanges"))
   // state file and the driver's checkpoints (include/msomn_state.h)
   long state_flip = -1;             // msomn_state_dbg_flip: element the next load flips on the device (< 0: off)
@@ -179,6 +181,16 @@ void nt_free_gather(msomn *m);   // the piece and the gather buffers (msomn_set_
 void nt_free(msomn *m);
 // MSOM_ERR_CONFIG with a message naming the call if the handle has more than one tile
 int nt_refuse(const msomn *m, const char *call);
+int nt_io_refuse(const msomn *m, const char *call);   // the same unless the option io_tiles is on
+// One code on every rank (collective; one tile: r as it is).  r is this rank's verdict on something only it could see, with its message
+// set; the ranks' codes meet in one all-reduce and every rank returns the lowest.  A rank that had nothing to object says so
+int nt_agree(msomn *m, int r, const char *call);
+// the owned window of `rank` (ntile_owned_range; cells = 1: its cells, which no other tile holds) of a field of layout g on the tile
+struct NodeOwned { NatGeom g; int ox, oy, gn; };   // g: the field's layout with nx, ny the owned extent; gn: the global side
+NodeOwned nt_owned(const msomn *m, const NatGeom &g, int cells, int rank);
+// The owned windows of dev ([layers] in geometry g) of all ranks -> the global [layers][gn][gn] array in `out` on rank 0 (the others:
+// left empty).  digest: device word that takes this rank's share of the record digest (k_state_rows).  Collective
+int nt_gather_owned(msomn *m, const double *dev, const NatGeom &g, int layers, int cells, unsigned long long *digest, std::vector<double> &out);
 
 // ---- msomn_cells.hip: the cell pyramids on tiles (option wavelet_tiles), all collective
 NatGeom cell_geom_rect(int nx, int ny);   // natural layout of a tile of nx x ny cells

@@ -2,6 +2,8 @@
 // Same container and the same device pass as msom_state.hip: k_state_rows of kernels_state.hip takes any natural geometry, so the
 // vertex fields go through it with the handle's NatGeom (nx = ny = N + 1, no ring, one tile: global offsets 0) and the cell-scalar
 // noise with the geometry of cs[0]; the transfers and the file writer are those of state_xfer.hip.  Nothing here runs inside msomn_step.
+// On tiles (option io_tiles) the calls are collective: a record is the global array, a rank's digest word covers the window it OWNS
+// (node_tile_inl.h) with the global indices, the words add up over the ranks, and what only one rank can see ends in nt_agree.
 #include "msomn_host.h"
 #include "state_xfer.h"
 #include "../../include/msomn_state.h"
@@ -43,18 +45,42 @@ using sx::Pipe;
 using sx::Scal;
 
 const RecName &nm(const Loaded &l) { return NAMES[l.name]; }
-sx::RecView view_of(const NatGeom &g) { return {g, 0, 0, 0, g.nx, g.ny}; }   // one tile, no ring: the record is the array
-NatGeom rec_geom(const msomn *m, const RecName &n) { return n.field == F_NOISE ? cell_geom(m->N) : m->g; }
+// no ring; the record is the global array (one tile: the handle's), the tile's window of it starts at (ox, oy)
+sx::RecView view_of(const msomn *m, const NatGeom &g, bool cells) { return {g, 0, m->ox, m->oy, cells ? m->N : m->N + 1, cells ? m->N : m->N + 1}; }
+NatGeom noise_geom(const msomn *m) {
+  if (m->ntiles == 1) return cell_geom(m->N);
+  const NodeTile t = ntile_level(m->N, m->px, m->py, m->rank, 0);
+  return cell_geom_rect(t.tx, t.ty);
+}
+NatGeom rec_geom(const msomn *m, const RecName &n) { return n.field == F_NOISE ? noise_geom(m) : m->g; }
 int rec_layers(const msomn *m, const RecName &n) { return n.field == F_NOISE ? 1 : is_acc(n) ? m->nl : m->fl[n.field]; }
-size_t pipe_cap(const msomn *m) { return sx::pipe_capacity(m->g.nx, m->g.ny); }
-sx::DigestTotal word0(msomn *m) {
-  return [m](Pipe &pp, uint64_t *d) { return sx::digest_word0(m->st, pp, d); };
+// a load stages whole record rows of the tile's rows; a tiled save stages nothing (the gather moves the tiles)
+size_t pipe_cap(const msomn *m) { return sx::pipe_capacity((size_t)m->N + 1, m->g.ny); }
+// this rank's digest word, summed over the ranks (tiles: one all-gather of the words; integer sums, so the order is free)
+sx::DigestTotal total_of(msomn *m) {
+  if (m->ntiles == 1) return [m](Pipe &pp, uint64_t *d) { return sx::digest_word0(m->st, pp, d); };
+  return [m](Pipe &pp, uint64_t *d) {
+    const int n = m->ntiles;
+    if (int r = comm_allgather(m->comm, (const double *)pp.dig, (double *)(pp.dig + 1), 1)) return r;
+    HIPCHK(hipMemcpyAsync(pp.h_dig, pp.dig, (size_t)(n + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, m->st));
+    HIPCHK(hipStreamSynchronize(m->st));
+    *d = 0;
+    for (int k = 1; k <= n; k++) *d += pp.h_dig[k];
+    return (int)MSOM_OK;
+  };
+}
+// tiles (collective): every rank packs the window it owns, the digest over it, the windows are gathered and rank 0 writes the record
+int save_record_tiled(msomn *m, Pipe &pp, const Field &f, FILE *fp, bool *io_ok) {
+  std::vector<double> g;
+  if (int r = nt_gather_owned(m, f.dev, f.v.g, f.layers, f.v.gnx == m->N, pp.dig, g)) return r;
+  if (fp && *io_ok && fwrite(g.data(), sizeof(double), g.size(), fp) != g.size()) *io_ok = false;
+  return MSOM_OK;
 }
 
 // ---- save
 
 void collect(msomn *m, unsigned flags, const double *run6, std::vector<Field> &items, std::vector<Scal> &scal) {
-  auto fld = [&](const char *name, int id) { items.push_back({name, m->f[id], m->fl[id], view_of(m->g)}); };
+  auto fld = [&](const char *name, int id) { items.push_back({name, m->f[id], m->fl[id], view_of(m, m->g, false)}); };
   scal.push_back({"time", {m->t, m->dt, m->previous, m->tnext, (double)m->iter}});
   // without mgstats.sum, as for msom_t: a loaded handle reports sum = 0 until its next solve
   scal.push_back({"mgstats", {(double)m->mg.i, m->mg.resb, m->mg.resa, (double)m->mg.nrelax}});
@@ -65,7 +91,7 @@ void collect(msomn *m, unsigned flags, const double *run6, std::vector<Field> &i
   fld("q", MSOMN_Q);
   fld("q_forcing", MSOMN_QFORC);
   if (m->nbar > 0) fld("psi_f", MSOMN_PSIF);
-  if (m->stochastic && m->cnlev > 0) items.push_back({"noise", m->cs[0], 1, view_of(m->cg[0])});
+  if (m->stochastic && m->cnlev > 0) items.push_back({"noise", m->cs[0], 1, view_of(m, m->cg[0], true)});
   // between the two stages of a step (only a stochastic handle knows that it is: corrector_step) the second update reads the predictor;
   // at a step boundary QPRED is scratch and is not written
   if (m->stochastic && m->corrector_step) fld("qpred", MSOMN_QPRED);
@@ -73,7 +99,7 @@ void collect(msomn *m, unsigned flags, const double *run6, std::vector<Field> &i
     scal.push_back({"stats", {(double)m->stats_mask, (double)m->stats_count, (double)m->stats_every, (double)m->stats_on, m->stats_W,
                               (double)m->stats_samples}});
     for (int k = 0; k < MSOM_ST_NACC; k++)
-      if (m->stats.s[k]) items.push_back({acc_name(k), m->stats.s[k], m->nl, view_of(m->g)});
+      if (m->stats.s[k]) items.push_back({acc_name(k), m->stats.s[k], m->nl, view_of(m, m->g, false)});
   }
   if (flags & MSOM_STATE_CONSTANTS) {
     fld("mask", MSOMN_MASK);
@@ -89,7 +115,7 @@ void collect(msomn *m, unsigned flags, const double *run6, std::vector<Field> &i
 
 int nstate_save_run(msomn *m, const char *path, unsigned flags, const double *run6) {
   if (!m || !path) { msom_set_error("msomn_state_save: null argument"); return MSOM_ERR_ARG; }
-  if (int rt = nt_refuse(m, "msomn_state_save")) return rt;
+  if (int rt = nt_io_refuse(m, "msomn_state_save")) return rt;
   if (!m->const_set) { msom_set_error("msomn_state_save: call msomn_set_const first"); return MSOM_ERR_STATE; }
   if (m->stochastic && m->noise_mode == 0) {
     msom_set_error("msomn_state_save: a stochastic run with noise_mode = 0 draws from libc's process-wide rand(), whose state cannot be "
@@ -106,8 +132,14 @@ int nstate_save_run(msomn *m, const char *path, unsigned flags, const double *ru
   sf.stochastic = (uint32_t)(m->stochastic != 0); sf.noise_mode = (uint32_t)m->noise_mode; sf.flag_topo = (uint32_t)(m->topo_set != 0);
   sf.params_len = (uint32_t)m->params_text.size();
   sf.params = const_cast<char *>(m->params_text.c_str());
-  return sx::write_file("msomn_state_save", path, true, m->st, pipe_cap(m), 1, sf, scal, items,
-                        [m](Pipe &pp, const Field &f, FILE *fp, bool *io_ok) { return sx::save_record(m->st, pp, f, fp, io_ok); }, word0(m));
+  const bool tiled = m->ntiles > 1;
+  const int r = sx::write_file("msomn_state_save", path, m->rank == 0, m->st, tiled ? 8 : pipe_cap(m), m->ntiles, sf, scal, items,
+                               [m, tiled](Pipe &pp, const Field &f, FILE *fp, bool *io_ok) {
+                                 return tiled ? save_record_tiled(m, pp, f, fp, io_ok) : sx::save_record(m->st, pp, f, fp, io_ok);
+                               },
+                               total_of(m));
+  // rank 0 alone knows whether the file is in place: nobody returns before it is, and everybody with its verdict
+  return nt_agree(m, r, "msomn_state_save");
 }
 
 extern "C" int msomn_state_save(msomn_t *m, const char *path, unsigned flags) { return nstate_save_run(m, path, flags, nullptr); }
@@ -130,99 +162,119 @@ double *target_ptr(msomn *m, const RecName &n) {
 }  // namespace
 
 extern "C" int msomn_state_load(msomn_t *m, const char *path) {
-  if (int rt = nt_refuse(m, "msomn_state_load")) return rt;
+  if (int rt = nt_io_refuse(m, "msomn_state_load")) return rt;
   if (!m || !path) { msom_set_error("msomn_state_load: null argument"); return MSOM_ERR_ARG; }
   msom_sfile sf;
-  int r = msom_sfile_open(path, &sf, 0);   // the whole structure: header, every record header against the file size, trailer
-  if (r) return r;
+  memset(&sf, 0, sizeof sf);
   struct Free { msom_sfile *s; ~Free() { msom_sfile_free(s); } } free_sf{&sf};
-  // ---- everything that can be refused is refused before the handle changes
-  if ((int)sf.dialect != NSTATE_DIALECT || (int)sf.nx != m->N + 1 || (int)sf.ny != m->N + 1 || (int)sf.nl != m->nl || sf.nptr != 0) {
-    msom_set_error("msomn_state_load: %s holds dialect %u, grid %u x %u, nl %u; the handle is dialect %d (vertex model), %d x %d vertices, nl %d", path,
-                   sf.dialect, sf.nx, sf.ny, sf.nl, (int)NSTATE_DIALECT, m->N + 1, m->N + 1, m->nl);
-    return MSOM_ERR_CONFIG;
-  }
-  if ((int)sf.stochastic != (m->stochastic != 0) || (sf.stochastic && (int)sf.noise_mode != m->noise_mode)) {
-    msom_set_error("msomn_state_load: %s was saved with stochastic %u, noise_mode %u; the handle has %d, %d", path, sf.stochastic, sf.noise_mode,
-                   m->stochastic != 0, m->noise_mode);
-    return MSOM_ERR_CONFIG;
-  }
-  if (m->const_set && m->stochastic && m->cnlev == 0) {
-    msom_set_error("msomn_state_load: stochastic was switched on after msomn_set_const: call msomn_set_const again first");
-    return MSOM_ERR_CONFIG;
-  }
   std::map<std::string, std::vector<double>> sc;
   sx::Temps tmp;
-  const std::vector<sx::KnownScalar> known = {{"time", 5}, {"mgstats", 4}, {"node", NS_COUNT}, {"run", 6}, {"stats", SS_N}};
-  for (uint32_t k = 0; k < sf.nrec; k++) {
-    const msom_srec *rec = &sf.rec[k];
-    if (rec->kind == MSOM_SK_SCALARS) {
-      if ((r = sx::read_known_scalars("msomn_state_load", path, rec, known, sc))) return r;
-      continue;
-    }
-    const RecName *n = find_name(rec->name);
-    Loaded l;
-    l.rec = rec;
-    if (n) { l.name = (int)(n - NAMES); l.v = view_of(rec_geom(m, *n)); l.yhi = l.v.gny; }
-    if (!n || tmp.find(rec->name) || rec->ring || (int)rec->layers != rec_layers(m, *n) || (int)rec->ny != l.v.gny || (int)rec->nx != l.v.gnx ||
-        (n->field == F_NOISE && !m->stochastic)) {
-      msom_set_error("msomn_state_load: %s: record %s [%u][%u][%u] has no place in this handle", path, rec->name, rec->layers, rec->ny, rec->nx);
-      return MSOM_ERR_CONFIG;
-    }
-    tmp.v.push_back(l);
-  }
   unsigned file_mask = 0;
-  {  // the statistics: a mask msomn_stats_begin would take, and exactly the accumulators it selects
-    unsigned recs = 0;
-    for (const Loaded &l : tmp.v) if (is_acc(nm(l))) recs |= 1u << (F_ACC0 - nm(l).field);
-    if (sc.count("stats")) {
-      const double fm = sc["stats"][SS_MASK];
-      if (!(fm >= 1) || fm >= (double)(1u << MSOM_ST_NACC) || fm != floor(fm)) { msom_set_error("msomn_state_load: %s: statistics mask %g", path, fm); return MSOM_ERR_CONFIG; }
-      file_mask = (unsigned)fm;
-    }
-    if (recs != file_mask) { msom_set_error("msomn_state_load: %s: accumulator records 0x%x, the mask of record `stats` is 0x%x", path, recs, file_mask); return MSOM_ERR_CONFIG; }
-  }
-  if (!sc.count("node") || !sc.count("time")) { msom_set_error("msomn_state_load: %s has no record `%s`", path, sc.count("node") ? "time" : "node"); return MSOM_ERR_CONFIG; }
-  const std::vector<double> &ns = sc["node"];
-  const bool file_const = tmp.find("mask") != nullptr, take_const = !m->const_set && file_const;
-  if ((ns[NS_SQG] != 0) != (m->sqg != 0) ||
-      (m->const_set && ((ns[NS_TOPO] != 0) != (m->topo_set != 0) || (ns[NS_PG] != 0) != (m->pg_set != 0) || (ns[NS_F3D] != 0) != (m->forcing_3d != 0)))) {
-    msom_set_error("msomn_state_load: %s was saved with sqg %g, topo_set %g, pg_set %g, forcing_3d %g; the handle has %d, %d, %d, %d", path, ns[NS_SQG],
-                   ns[NS_TOPO], ns[NS_PG], ns[NS_F3D], m->sqg, m->topo_set, m->pg_set, m->forcing_3d);
-    return MSOM_ERR_CONFIG;
-  }
-  {  // msomn_set_const clamps DT; a handle without constants will be clamped on the way
-    const double dt_handle = m->const_set ? m->p.DT : node_clamped_dt(m);
-    if (ns[NS_DT] != dt_handle) {
-      msom_set_error("msomn_state_load: %s was saved with DT = %.17g after the clamps of msomn_set_const; the handle has %.17g", path, ns[NS_DT], dt_handle);
+  bool take_const = false;
+  int r;
+  // ---- the host's part: the file and what it says against what the handle is.  Every rank reads the shared file; on tiles the verdicts
+  // meet in nt_agree before anything is posted
+  auto validate = [&]() -> int {
+    int r = msom_sfile_open(path, &sf, 0);   // the whole structure: header, every record header against the file size, trailer
+    if (r) return r;
+    // ---- everything that can be refused is refused before the handle changes
+    if ((int)sf.dialect != NSTATE_DIALECT || (int)sf.nx != m->N + 1 || (int)sf.ny != m->N + 1 || (int)sf.nl != m->nl || sf.nptr != 0) {
+      msom_set_error("msomn_state_load: %s holds dialect %u, grid %u x %u, nl %u; the handle is dialect %d (vertex model), %d x %d vertices, nl %d", path,
+                     sf.dialect, sf.nx, sf.ny, sf.nl, (int)NSTATE_DIALECT, m->N + 1, m->N + 1, m->nl);
       return MSOM_ERR_CONFIG;
     }
-  }
-  {  // the records this load needs
-    std::vector<const char *> need = {"psi", "q", "q_forcing"};
-    if (sf.stochastic) need.push_back("noise");
-    if (ns[NS_NBAR] > 0) need.push_back("psi_f");
-    if (sf.stochastic && ns[NS_CORRECTOR] != 0) need.push_back("qpred");
-    if (take_const) {
-      if (m->nl > 1) need.push_back("S2");
-      if (m->sqg) { need.push_back("S2S"); need.push_back("bs"); }
-      if (ns[NS_TOPO] != 0) need.push_back("topo");
-      if (ns[NS_PG] != 0) need.push_back("psi_pg");
-      if (ns[NS_F3D] != 0) need.push_back("q_forcing_3d");
+    if ((int)sf.stochastic != (m->stochastic != 0) || (sf.stochastic && (int)sf.noise_mode != m->noise_mode)) {
+      msom_set_error("msomn_state_load: %s was saved with stochastic %u, noise_mode %u; the handle has %d, %d", path, sf.stochastic, sf.noise_mode,
+                     m->stochastic != 0, m->noise_mode);
+      return MSOM_ERR_CONFIG;
     }
-    for (const char *name : need)
-      if (!tmp.find(name)) { msom_set_error("msomn_state_load: %s has no record `%s`", path, name); return MSOM_ERR_CONFIG; }
-  }
+    if (m->const_set && m->stochastic && m->cnlev == 0) {
+      msom_set_error("msomn_state_load: stochastic was switched on after msomn_set_const: call msomn_set_const again first");
+      return MSOM_ERR_CONFIG;
+    }
+    const std::vector<sx::KnownScalar> known = {{"time", 5}, {"mgstats", 4}, {"node", NS_COUNT}, {"run", 6}, {"stats", SS_N}};
+    for (uint32_t k = 0; k < sf.nrec; k++) {
+      const msom_srec *rec = &sf.rec[k];
+      if (rec->kind == MSOM_SK_SCALARS) {
+        if ((r = sx::read_known_scalars("msomn_state_load", path, rec, known, sc))) return r;
+        continue;
+      }
+      const RecName *n = find_name(rec->name);
+      Loaded l;
+      l.rec = rec;
+      if (n) {
+        const bool cells = n->field == F_NOISE;
+        l.name = (int)(n - NAMES); l.v = view_of(m, rec_geom(m, *n), cells);
+        l.ylo = m->oy; l.yhi = m->oy + l.v.g.ny;   // the rows the tile holds, shared ones included
+        if (m->ntiles > 1) {   // the digest word and the test flip: the window the tile owns
+          const NodeOwned o = nt_owned(m, l.v.g, cells, m->rank);
+          l.own_nx = o.g.nx; l.own_ny = o.g.ny;
+        }
+      }
+      if (!n || tmp.find(rec->name) || rec->ring || (int)rec->layers != rec_layers(m, *n) || (int)rec->ny != l.v.gny || (int)rec->nx != l.v.gnx ||
+          (n->field == F_NOISE && !m->stochastic)) {
+        msom_set_error("msomn_state_load: %s: record %s [%u][%u][%u] has no place in this handle", path, rec->name, rec->layers, rec->ny, rec->nx);
+        return MSOM_ERR_CONFIG;
+      }
+      tmp.v.push_back(l);
+    }
+    {  // the statistics: a mask msomn_stats_begin would take, and exactly the accumulators it selects
+      unsigned recs = 0;
+      for (const Loaded &l : tmp.v) if (is_acc(nm(l))) recs |= 1u << (F_ACC0 - nm(l).field);
+      if (sc.count("stats")) {
+        const double fm = sc["stats"][SS_MASK];
+        if (!(fm >= 1) || fm >= (double)(1u << MSOM_ST_NACC) || fm != floor(fm)) { msom_set_error("msomn_state_load: %s: statistics mask %g", path, fm); return MSOM_ERR_CONFIG; }
+        file_mask = (unsigned)fm;
+      }
+      if (recs != file_mask) { msom_set_error("msomn_state_load: %s: accumulator records 0x%x, the mask of record `stats` is 0x%x", path, recs, file_mask); return MSOM_ERR_CONFIG; }
+    }
+    if (!sc.count("node") || !sc.count("time")) { msom_set_error("msomn_state_load: %s has no record `%s`", path, sc.count("node") ? "time" : "node"); return MSOM_ERR_CONFIG; }
+    const std::vector<double> &ns = sc["node"];
+    const bool file_const = tmp.find("mask") != nullptr;
+    take_const = !m->const_set && file_const;
+    if ((ns[NS_SQG] != 0) != (m->sqg != 0) ||
+        (m->const_set && ((ns[NS_TOPO] != 0) != (m->topo_set != 0) || (ns[NS_PG] != 0) != (m->pg_set != 0) || (ns[NS_F3D] != 0) != (m->forcing_3d != 0)))) {
+      msom_set_error("msomn_state_load: %s was saved with sqg %g, topo_set %g, pg_set %g, forcing_3d %g; the handle has %d, %d, %d, %d", path, ns[NS_SQG],
+                     ns[NS_TOPO], ns[NS_PG], ns[NS_F3D], m->sqg, m->topo_set, m->pg_set, m->forcing_3d);
+      return MSOM_ERR_CONFIG;
+    }
+    {  // msomn_set_const clamps DT; a handle without constants will be clamped on the way
+      const double dt_handle = m->const_set ? m->p.DT : node_clamped_dt(m);
+      if (ns[NS_DT] != dt_handle) {
+        msom_set_error("msomn_state_load: %s was saved with DT = %.17g after the clamps of msomn_set_const; the handle has %.17g", path, ns[NS_DT], dt_handle);
+        return MSOM_ERR_CONFIG;
+      }
+    }
+    {  // the records this load needs
+      std::vector<const char *> need = {"psi", "q", "q_forcing"};
+      if (sf.stochastic) need.push_back("noise");
+      if (ns[NS_NBAR] > 0) need.push_back("psi_f");
+      if (sf.stochastic && ns[NS_CORRECTOR] != 0) need.push_back("qpred");
+      if (take_const) {
+        if (m->nl > 1) need.push_back("S2");
+        if (m->sqg) { need.push_back("S2S"); need.push_back("bs"); }
+        if (ns[NS_TOPO] != 0) need.push_back("topo");
+        if (ns[NS_PG] != 0) need.push_back("psi_pg");
+        if (ns[NS_F3D] != 0) need.push_back("q_forcing_3d");
+      }
+      for (const char *name : need)
+        if (!tmp.find(name)) { msom_set_error("msomn_state_load: %s has no record `%s`", path, name); return MSOM_ERR_CONFIG; }
+    }
+    return MSOM_OK;
+  };
+  if ((r = nt_agree(m, validate(), "msomn_state_load"))) return r;
+  const std::vector<double> &ns = sc["node"];
   HIPCHK(hipStreamSynchronize(m->st));
   // ---- every field into a spare natural array (pads: the target's own, or zero), its digest recomputed there on the device
-  if ((r = sx::stage_records("msomn_state_load", path, m->st, pipe_cap(m), 1, tmp, &m->state_flip,
-                             [m](const Loaded &l) { return target_ptr(m, nm(l)); }, word0(m))))
+  if ((r = sx::stage_records("msomn_state_load", path, m->st, pipe_cap(m), m->ntiles, tmp, &m->state_flip,
+                             [m](const Loaded &l) { return target_ptr(m, nm(l)); }, total_of(m))))
     return r;
   // ---- commit.  Constants first: the stored ones as they are and what follows from them (node_const_derived), or msomn_set_const on
   // what the handle holds if the file brings none; then the evolving state (msomn_set_const overwrites q)
+  // tiles: a model field gets the halo msomn_set_field would have given it (the spare array began with the handle's old one)
   auto put = [&](const Loaded &l, double *dst) -> int {
     HIPCHK(hipMemcpyAsync(dst, l.nat, l.bytes(), hipMemcpyDeviceToDevice, m->st));
-    return MSOM_OK;
+    return nm(l).field >= 0 ? nt_exchange(m, dst, m->g, 0, (int)l.rec->layers) : (int)MSOM_OK;
   };
   if (take_const) {
     for (const Loaded &l : tmp.v)
@@ -242,7 +294,10 @@ extern "C" int msomn_state_load(msomn_t *m, const char *path) {
     // psi through the live pointer.  The buffer that is not psi (psi_alt, if the handle has one yet) stays as it is: k_n_rhs_pre and
     // k_n_correct_residual write every vertex of it before anything reads it, and its pad cells are zero in both buffers
     if ((r = put(l, target_ptr(m, nm(l))))) return r;
-    if (nm(l).field == F_NOISE) node_noise_ghosts(m);
+    if (nm(l).field == F_NOISE) {
+      if (m->ntiles == 1) node_noise_ghosts(m);
+      else if ((r = ct_ring(m, m->cs[0], m->cg[0], 1, BC_NEUMANN))) return r;
+    }
   }
   const std::vector<double> &tv = sc["time"];
   m->t = tv[0]; m->dt = tv[1]; m->previous = tv[2]; m->tnext = tv[3]; m->iter = (int)tv[4];
@@ -259,23 +314,30 @@ extern "C" int msomn_state_load(msomn_t *m, const char *path) {
   return MSOM_OK;
 }
 
-extern "C" msomn_t *msomn_create_from_state(const char *path) {
-  if (!path) { msom_set_error("msomn_create_from_state: null path"); return nullptr; }
+namespace {
+
+// px * py = 0: the plain handle of msomn_create_from_state
+msomn_t *create_from_state(const char *entry, const char *path, int px, int py, int rank, const void *id128) {
+  if (!path) { msom_set_error("%s: null path", entry); return nullptr; }
   msom_sfile sf;
   if (msom_sfile_open(path, &sf, 0)) return nullptr;
   if (sf.dialect != NSTATE_DIALECT) {
-    msom_set_error("msomn_create_from_state: %s holds dialect %u, a cell-centred model: use msom_create_from_state", path, sf.dialect);
+    msom_set_error("%s: %s holds dialect %u, a cell-centred model: use msom_create_from_state", entry, path, sf.dialect);
     msom_sfile_free(&sf);
     return nullptr;
   }
   if (!msom_sfile_find(&sf, "mask")) {
-    msom_set_error("msomn_create_from_state: %s was saved without MSOM_STATE_CONSTANTS: create the handle, set its constants and call msomn_state_load", path);
+    msom_set_error("%s: %s was saved without MSOM_STATE_CONSTANTS: create the handle, set its constants and call msomn_state_load", entry, path);
     msom_sfile_free(&sf);
     return nullptr;
   }
-  msomn_t *m = msomn_create_str(sf.params);
+  msomn_t *m = px * py ? msomn_create_tiled(sf.params, px, py, rank, id128) : msomn_create_str(sf.params);
   int r = m ? MSOM_OK : MSOM_ERR_CONFIG;
-  if (m && sf.stochastic) {
+  if (m && px * py) {
+    r = msomn_set_option(m, "io_tiles", 1);
+    if (!r && (sf.stochastic || msom_sfile_find(&sf, "psi_f"))) r = msomn_set_option(m, "wavelet_tiles", 1);
+  }
+  if (m && !r && sf.stochastic) {
     const msom_srec *nr = msom_sfile_find(&sf, "node");
     std::vector<double> v;
     r = msomn_set_option(m, "stochastic", 1);
@@ -289,4 +351,13 @@ extern "C" msomn_t *msomn_create_from_state(const char *path) {
     return nullptr;
   }
   return m;
+}
+
+}  // namespace
+
+extern "C" msomn_t *msomn_create_from_state(const char *path) { return create_from_state("msomn_create_from_state", path, 0, 0, 0, nullptr); }
+
+extern "C" msomn_t *msomn_create_tiled_from_state(const char *path, int px, int py, int rank, const void *id128) {
+  if (px < 1 || py < 1) { msom_set_error("msomn_create_tiled_from_state: %d x %d tiles", px, py); return nullptr; }
+  return create_from_state("msomn_create_tiled_from_state", path, px, py, rank, id128);
 }

@@ -32,6 +32,63 @@ int nt_refuse(const msomn *m, const char *call) {
   return MSOM_ERR_CONFIG;
 }
 
+int nt_io_refuse(const msomn *m, const char *call) { return m && m->io_tiles ? MSOM_OK : nt_refuse(m, call); }
+
+int nt_agree(msomn *m, int r, const char *call) {
+  if (m->ntiles == 1) return r;
+  const double mine = (double)r;   // the codes are <= 0: the minimum is the gravest
+  HIPCHK(hipMemcpyAsync(m->d_scal + NSC_RES, &mine, sizeof mine, hipMemcpyHostToDevice, m->st));
+  HIPCHK(hipStreamSynchronize(m->st));
+  if (int rr = nt_reduce(m, NSC_RES, 1, RED_MIN)) return rr;
+  const int all = (int)m->h_scal[NSC_RES];
+  if (all && !r) msom_set_error("%s: another rank refuses (error %d): nothing was changed here", call, all);
+  return all;
+}
+
+NodeOwned nt_owned(const msomn *m, const NatGeom &g, int cells, int rank) {
+  const NodeTile t = ntile_level(m->N, m->px, m->py, rank, 0);
+  const NodeRange w = ntile_owned_range(m->N, m->px, m->py, rank, 0);
+  NodeOwned o;
+  o.g = g; o.ox = t.ox; o.oy = t.oy;
+  o.g.nx = cells ? t.tx : w.i1 + 1; o.g.ny = cells ? t.ty : w.j1 + 1;
+  o.gn = cells ? m->N : m->N + 1;
+  return o;
+}
+
+int nt_gather_owned(msomn *m, const double *dev, const NatGeom &g, int layers, int cells, unsigned long long *digest, std::vector<double> &out) {
+  const NodeOwned o = nt_owned(m, g, cells, m->rank);
+  const NodeTile t = ntile_level(m->N, m->px, m->py, m->rank, 0);
+  // every rank sends as much as the largest owned window takes
+  const size_t per = (size_t)(t.tx + 1) * (t.ty + 1), cnt = (size_t)layers * per, own = (size_t)o.g.nx * o.g.ny;
+  struct Bufs { double *send = nullptr, *recv = nullptr; ~Bufs() { if (send) (void)hipFree(send); if (recv) (void)hipFree(recv); } } b;
+  HIPCHK(hipMalloc(&b.send, cnt * sizeof(double)));
+  HIPCHK(hipMemsetAsync(b.send, 0, cnt * sizeof(double), m->st));
+  if (m->ntiles > 1) HIPCHK(hipMalloc(&b.recv, cnt * m->ntiles * sizeof(double)));
+  for (int l = 0; l < layers; l++) {
+    StateChunk c;
+    c.g = o.g; c.ring = 0; c.layer = l; c.y0 = o.oy; c.rows = o.g.ny; c.ox = o.ox; c.oy = o.oy; c.gW = c.gH = o.gn; c.sx0 = o.ox; c.sw = o.g.nx;
+    launch_state_pack(m->st, dev, b.send + (size_t)l * own, c, digest);
+  }
+  HIPCHK(hipGetLastError());
+  int r = m->ntiles > 1 ? comm_allgather(m->comm, b.send, b.recv, cnt) : MSOM_OK;
+  if (r) return r;
+  out.clear();
+  if (m->rank != 0) { HIPCHK(hipStreamSynchronize(m->st)); return MSOM_OK; }
+  std::vector<double> h(cnt * m->ntiles);
+  HIPCHK(hipMemcpyAsync(h.data(), m->ntiles > 1 ? b.recv : b.send, h.size() * sizeof(double), hipMemcpyDeviceToHost, m->st));
+  HIPCHK(hipStreamSynchronize(m->st));
+  const size_t gn = (size_t)o.gn;
+  out.resize((size_t)layers * gn * gn);
+  for (int q = 0; q < m->ntiles; q++) {
+    const NodeOwned oq = nt_owned(m, g, cells, q);
+    const size_t w = (size_t)oq.g.nx, hh = (size_t)oq.g.ny;
+    for (int l = 0; l < layers; l++)
+      for (size_t j = 0; j < hh; j++)
+        memcpy(&out[((size_t)l * gn + oq.oy + j) * gn + oq.ox], &h[q * cnt + ((size_t)l * hh + j) * w], w * sizeof(double));
+  }
+  return MSOM_OK;
+}
+
 int nt_setup(msomn *m, int px, int py, int rank, const void *id128) {
   const NodeTile t = ntile_level(m->N, px, py, rank, 0);
   m->px = px; m->py = py; m->rank = rank; m->ntiles = px * py;

@@ -4,7 +4,7 @@
 // The global grid has N x N cells and (N + 1)^2 vertices; level k has n_k = N >> k cells a side.  A px x py grid of tiles covers it,
 // rank r = tile (r % px, r / px) as msom_create_tiled.  A tile of level k has tx = n_k / px by ty = n_k / py cells and HOLDS
 // (tx + 1) x (ty + 1) vertices, the ones on its interior edges included: a vertex on a shared edge exists on both tiles (on all four
-// at a cross point), every holder computes it, nothing is owned.  Local vertex (i, j) is global vertex (ox + i, oy + j).  The halo
+// at a cross point), every holder computes it; only the I/O asks who OWNS it (ntile_owned_range).  Local vertex (i, j) is global vertex (ox + i, oy + j).  The halo
 // is the first pad column / row beyond an interior edge (i = -1, i = tx + 1, j = -1, j = ty + 1): the neighbour's local tx - 1 / 1 /
 // ty - 1 / 1.  Beyond a wall the pad stays 0.
 //
@@ -88,6 +88,17 @@ NT_HD static inline NodeRange ntile_sum_range(const NodeTile &t) {
   NodeRange r;
   r.i0 = 0; r.i1 = (t.walls & NT_WALL_E) ? t.tx : t.tx - 1;
   r.j0 = 0; r.j1 = (t.walls & NT_WALL_N) ? t.ty : t.ty - 1;
+  return r;
+}
+// the vertices a tile OWNS where each global vertex must be counted exactly once (the records and digests of a state file, the
+// gathers of msomn_write_nc; option io_tiles): local columns 0 .. tx - 1, and column tx too iff the tile is the last of its row of
+// tiles; rows likewise.  Over all ranks the owned windows cover the (N + 1)^2 vertices once; a shared vertex belongs to the holder
+// with the higher tile coordinate.  The same window as ntile_sum_range, stated with the tile grid instead of the wall bits
+NT_HD static inline NodeRange ntile_owned_range(int N, int px, int py, int rank, int k) {
+  const NodeTile t = ntile_level(N, px, py, rank, k);
+  NodeRange r;
+  r.i0 = 0; r.i1 = t.ix == px - 1 ? t.tx : t.tx - 1;
+  r.j0 = 0; r.j1 = t.iy == py - 1 ? t.ty : t.ty - 1;
   return r;
 }
 // the held vertices and one halo column / row beyond every interior edge: what a halo exchange leaves valid

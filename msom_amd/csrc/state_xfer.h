@@ -77,6 +77,8 @@ struct Loaded {   // a field record verified on the device, not yet in the handl
   const msom_srec *rec = nullptr;
   RecView v;
   int ylo = 0, yhi = 0;            // the record rows of this tile
+  int own_nx = 0, own_ny = 0;      // tiles that hold shared vertices: the part of the tile, from its origin, that this rank's digest
+                                   // word and the test flip cover (0: the whole tile)
   double *nat = nullptr;
   size_t bytes() const { return v.g.ls * rec->layers * sizeof(double); }
 };
@@ -88,7 +90,9 @@ struct Temps {
 
 // Every record of tmp into a spare natural array (pads: those of current(l), or zero where the handle has no such array yet) and its
 // digest recomputed there on the device: file -> pinned chunk -> device chunk (second stream) -> natural layout, two chunks in flight.
-// *state_flip >= 0 alters that element (modulo the tile) of layer 0 of the first record after its upload; it is -1 on return.
+// *state_flip >= 0 alters that element (modulo the tile, or its own_nx x own_ny part) of layer 0 of the first record after its upload;
+// it is -1 on return.  A short read on this rank does not keep it out of `total` (on tiles a collective): its word is spoilt first, so
+// that every rank ends the record with MSOM_ERR_IO.
 int stage_records(const char *entry, const char *path, hipStream_t st, size_t cap, int nranks, Temps &tmp, long *state_flip,
                   const std::function<const double *(const Loaded &)> &current, const DigestTotal &total);
 

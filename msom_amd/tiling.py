@@ -81,6 +81,17 @@ def node_tile_window(N, px, py, rank):
     return slice(iy * ty, (iy + 1) * ty + 1), slice(ix * tx, (ix + 1) * tx + 1)
 
 
+def node_owned_window(N, px, py, rank):
+    """(slice_y, slice_x) of the vertices this rank OWNS in a global [.., N + 1, N + 1] array: its held window without the
+    last column unless the tile is the last of its row of tiles, rows likewise (ntile_owned_range of node_tile_inl.h).  The
+    owned windows of all ranks cover every vertex exactly once: what a state file's records and digests count."""
+    tx, ty = _node_tile_cells(N, px, py)
+    if not 0 <= rank < px * py:
+        raise ValueError(f"rank {rank} outside 0 .. {px * py - 1}")
+    ix, iy = tile_of_rank(rank, px, py)
+    return slice(iy * ty, (iy + 1) * ty + (iy == py - 1)), slice(ix * tx, (ix + 1) * tx + (ix == px - 1))
+
+
 def node_assemble(pieces, N, px, py, check_shared=True):
     """Global [.., N + 1, N + 1] array from the px * py tile arrays [.., Ty + 1, Tx + 1] (in rank order) of the vertex model.
     check_shared: raise ValueError if two holders of a shared vertex disagree in any bit (-0. against 0. and different NaN
