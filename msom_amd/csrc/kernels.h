@@ -59,11 +59,11 @@ struct KernelOpts {
   int march_dbg = 0;          // timing experiments of the marching passes
   int march_lean = 2;         // interior chunks of the LDS-DMA pass take the lean body (2: requests two steps ahead where LDS allows)
   int march_dma = 2;          // LDS-DMA version of the pass (0 register-window kernel, 1 one strip, 2 four strips per workgroup)
-  int march_visit_rows = 0;   // chunk height of k_relax_visit (0: automatic)
+  int march_visit_rows = 0;   // chunk height of k_relax_visit (0: by rounds of wave-pair slots, relax_visit_rows; 28 on the finest level at 4096^2)
   int march_visit_pairs = 2;  // wave pairs per workgroup of k_relax_visit (1 or 2; 4096^2 x 6: 0.866 / 0.873 ms with 2, 0.881 / 0.883 with 1)
   int march_visit_ring = 2;   // the wall-ring chunks around k_relax_visit: 0 two launches over the whole chunk grid with a skip rectangle,
                               // 1 two launches over the ring chunks only, 2 workgroups of two k_relax_visit launches
-  int march_visit_split = 0;  // march_visit_ring = 2: fused chunk rows in the first of the two launches (0: a third of them; rounded down to even)
+  int march_visit_split = 0;  // march_visit_ring = 2: fused chunk rows in the first of the two launches (0: a third of them; rounded down to even; < 0: none)
   int resmax_rows = 0;        // rows per chunk of k_resmax_march (0: 32), -1: the LDS-tiled kernel instead
   int block_variant = 0;      // tile shape of k_relax_block (tools/bench_kernels.py)
   int rhs_dbg = 0;            // bits 128, 256, 512: plain residual / red-prolongation kernels; rows << 8 overrides k_rhs_lpw's chunk height
@@ -270,11 +270,16 @@ int launch_relax_march(hipStream_t st, const KernelOpts &o, const double *in, do
                        int K, int walls, int chunk_rows = 0, const MarchHalo *h = nullptr, const double *coarse = nullptr, const SplitGeom *cg = nullptr,
                        const MarchCorrect *mc = nullptr, int more_follow = 0, const MarchHalo *coarse_halo = nullptr, int region = 0,
                        const int *skip = nullptr, int skip_compact = 0);
-// the finest level's visit, 4 + 4 half-sweeps with the prolongation and the correction, fused where chunks are interior (k_relax_visit);
-// returns -1 (nothing launched) where it does not apply.  Chunk height and wave pairs per workgroup: options march_visit_rows / _pairs
+// a marched level's visit, 4 + 4 half-sweeps with the prolongation, fused where chunks are interior (k_relax_visit); mc: the finest
+// level, the second four apply the correction; nullptr: a level below it, they leave the level's correction in da.
+// Returns -1 (nothing launched) where it does not apply.  Chunk height and wave pairs per workgroup: options march_visit_rows / _pairs
 int launch_relax_visit(hipStream_t st, const KernelOpts &o, double *da, double *da_alt, const double *res, const SplitGeom &sg, int nl, const RelaxCoef &rc,
-                       int walls, const double *coarse, const SplitGeom &cg, const MarchCorrect &mc);
+                       int walls, const double *coarse, const SplitGeom &cg, const MarchCorrect *mc);
 bool relax_visit_fits(int nl, const SplitGeom &sg, int rows, int pairs);
+// the chunk height the visit takes on a level (option march_visit_rows; 0: by rounds of the device's wave-pair slots)
+int relax_visit_rows(const KernelOpts &o, int nl, const SplitGeom &sg, bool corr);
+// the rule by rounds as host arithmetic (no device; tests/test_visit_levels_host.py): -1 where no chunk fits
+extern "C" int msom_visit_rows(int hk, int ny, int pairs, int slots);
 // host arithmetic of the visit's chunk grid and of the ring chunks around it (no device; tests/test_visit_ring_host.py)
 extern "C" int msom_visit_ring(int hk, int ny, int march_rows, int visit_rows, int pairs, int corr, int *geom, int *bands);
 // can the lean interior body of the pass address every layer of the level (sg) and, with the correction, of psi (ng)?

@@ -367,14 +367,15 @@ __global__ void __launch_bounds__(64, 2) k_relax_march(MarchArgs p) {
 //    acknowledgements are no longer waited for.
 // Arithmetic: the expressions of the general body, same order => bit-identical (tests/test_gpu_march.py).
 // VIS (k_relax_visit): 0 a pass of its own; 1 the leading wave of a fused visit (its half-sweep K goes to the hand-over rows
-// in LDS instead of HBM); 2 the trailing wave (its input rows come from there; no input block in its ring)
+// in LDS instead of HBM); 2 the trailing wave (its input rows come from there; no input block in its ring).  The trailing wave
+// applies the correction (CORR, the finest level) or stores the level's correction, both colours, as a plain pass does
 template <int NL, int K, int HL, int WPB, bool PL, bool CORR, int VIS = 0>
 struct MarchLeanRows {
   static constexpr int NLE = (NL + 1) & ~1;                 // two layer-rows per DMA instruction; odd NL repeats its last layer
   static constexpr int CB = 2 * NLE;                        // PL: coarse ring (4 slots of NLE rows)
   static constexpr int PBL = (VIS == 2 ? 2 : 3) * NLE;      // CORR: psi block (NL x 128 doubles)
   static constexpr int XBL = PBL + 2 * NL;                  // CORR: values of half-sweep K waiting one step for their psi row
-  static constexpr int ROWS = PL ? CB + 4 * NLE : (CORR ? XBL + NL : 3 * NLE);
+  static constexpr int ROWS = PL ? CB + 4 * NLE : (CORR ? XBL + NL : (VIS == 2 ? 2 : 3) * NLE);
   // DEEP (requests two steps ahead; not with CORR, whose psi block and parked values leave no room): two buffers of
   // residual (+ input) rows; PL: then a coarse ring of two slots (slot = J & 1: the row a request overwrites was read
   // for the last time in the step that issues it)
@@ -389,7 +390,7 @@ typedef double v2d __attribute__((ext_vector_type(2)));
 template <int NL, int K, int HL, int WPB, bool PL, bool CORR, bool DEEP, int VIS = 0>
 __device__ __forceinline__ void march_lean(const MarchArgs &p, double (*ring)[64], const int lane, const int kx0, const int y0, const int y1,
                                            const bool down, double (*hand)[64] = nullptr) {
-  static_assert(VIS == 0 || (VIS == 1 && PL && !CORR) || (VIS == 2 && CORR), "fused visit: prolongation leads, correction trails");
+  static_assert(VIS == 0 || (VIS == 1 && PL && !CORR) || (VIS == 2 && !PL && !DEEP), "fused visit: prolongation leads, correction or plain store trails");
   using LR = MarchLeanRows<NL, K, HL, WPB, PL, CORR, VIS>;
   constexpr int D1 = K >= 3 ? 3 : 1, D2 = K >= 4 ? 3 : 1;
   static_assert(!(DEEP && CORR), "no LDS for a second buffer beside the psi block");
@@ -433,7 +434,7 @@ __device__ __forceinline__ void march_lean(const MarchArgs &p, double (*ring)[64
   long long rowoff = ((long long)(ra + 1) * p.g.rp + ((ra + p.c1) & 1) * p.g.hp) * 8;   // its colour half, in bytes
   const char *const res8 = reinterpret_cast<const char *>(p.res);
   const char *const resb8 = res8 - drp8;                               // row of half-sweep 2
-  const char *const in8 = PL ? nullptr : reinterpret_cast<const char *>(p.in) + drp8;   // the new input row
+  const char *const in8 = PL || VIS == 2 ? nullptr : reinterpret_cast<const char *>(p.in) + drp8;   // the new input row
   char *const outK8 = CORR ? nullptr : reinterpret_cast<char *>(p.out) - (long long)(K - 1) * drp8;   // row of half-sweep K
   // CORR: psi of the row half-sweep K finished one step ago, t - K in marching coordinates
   long long natoff = CORR ? ((long long)(ra - d * K + MSOM_YP) * p.ng.pitch) * 8 : 0;
@@ -1310,11 +1311,11 @@ __device__ __forceinline__ void xcd_remap_lin(const unsigned lin, const unsigned
 }
 // one role of the pair; everything from the launch coordinates, inside the role's branch (shared values live across both
 // bodies cost registers: 3 spilled VGPRs at nl = 6 when computed before the branch)
-template <int NL, int PAIRS, int VIS, int KIND>
+template <int NL, int PAIRS, int VIS, int KIND, bool CORR>
 __device__ __forceinline__ void visit_role(const MarchArgs &p, double (*lds)[64], const int pair) {
   constexpr int K = 4, HL = 8;
   constexpr int OW = 64 - 2 * HL;
-  constexpr int RA = MarchLeanRows<NL, K, HL, 2, true, false>::ROWSD, RB = MarchLeanRows<NL, K, HL, 2, false, true, 2>::ROWS;
+  constexpr int RA = MarchLeanRows<NL, K, HL, 2, true, false>::ROWSD, RB = MarchLeanRows<NL, K, HL, 2, false, CORR, 2>::ROWS;
   const int lane = threadIdx.x & 63;
   unsigned bx = blockIdx.x, by = blockIdx.y;
   if constexpr (KIND != 0) {   // mixed launch: the fused chunks follow the ring workgroups
@@ -1330,12 +1331,12 @@ __device__ __forceinline__ void visit_role(const MarchArgs &p, double (*lds)[64]
   const bool down = p.flip && (by & 1);
   double(*ring)[64] = lds + pair * (RA + RB + 2 * NL);
   double(*hand)[64] = ring + RA + RB;
-  if constexpr (VIS == 2) march_lean<NL, K, HL, 2, false, true, false, 2>(p, ring + RA, lane, kx0, y0, y1, down, hand);
+  if constexpr (VIS == 2) march_lean<NL, K, HL, 2, false, CORR, false, 2>(p, ring + RA, lane, kx0, y0, y1, down, hand);
   else march_lean<NL, K, HL, 2, true, false, true, 1>(p, ring, lane, kx0, y0 - K, y1 + K, down, hand);
 }
 // a ring workgroup of a mixed launch: each wavefront takes one chunk of the band table through the one-strip forms of the pass
 // (no workgroup barrier in them), with the ring role's own chunk height, lean option, input and output
-template <int NL, int KIND>
+template <int NL, int KIND, bool CORR>
 __device__ __forceinline__ void visit_ring_role(const MarchArgs &p, double (*lds)[64], const int wv, const int nwv) {
   constexpr int K = 4;
   const int i = (int)blockIdx.x * nwv + wv;
@@ -1349,27 +1350,28 @@ __device__ __forceinline__ void visit_ring_role(const MarchArgs &p, double (*lds
   q.rb.n = 0; q.region = 0; q.sy0 = q.sy1 = 0;
   const int lane = threadIdx.x & 63;
   if constexpr (KIND == 1) march_dma_chunk<NL, K, 4, 1, true, false>(q, lds + wv * MarchDmaRows<NL, K, 4, 1, true, false>::LROWS, lane, strip, by);
-  else march_dma_chunk<NL, K, 2, 1, false, true>(q, lds + wv * MarchDmaRows<NL, K, 2, 1, false, true>::LROWS, lane, strip, by);
+  else march_dma_chunk<NL, K, 2, 1, false, CORR>(q, lds + wv * MarchDmaRows<NL, K, 2, 1, false, CORR>::LROWS, lane, strip, by);
 }
-// KIND: 0 the fused chunks alone on a 2-D grid; 1 / 2 a mixed launch whose leading workgroups are the ring chunks of the PL / CORR
-// pass.  One kind per instantiation: each carries only the bodies it runs
-template <int NL, int PAIRS, int KIND>
+// KIND: 0 the fused chunks alone on a 2-D grid; 1 / 2 a mixed launch whose leading workgroups are the ring chunks of the PL / second
+// pass.  One kind per instantiation: each carries only the bodies it runs.  CORR: the trailing wave and the second ring apply the
+// correction (the finest level); otherwise they store the level's correction, both colours (the marched levels below it)
+template <int NL, int PAIRS, int KIND, bool CORR = true>
 __global__ void __launch_bounds__(128 * PAIRS, 2) k_relax_visit(MarchArgs p) {
   constexpr int K = 4, HL = 8;
-  constexpr int RA = MarchLeanRows<NL, K, HL, 2, true, false>::ROWSD, RB = MarchLeanRows<NL, K, HL, 2, false, true, 2>::ROWS;
+  constexpr int RA = MarchLeanRows<NL, K, HL, 2, true, false>::ROWSD, RB = MarchLeanRows<NL, K, HL, 2, false, CORR, 2>::ROWS;
   // the pair layout or, where it is larger (nl = 3), one ring per wavefront of a ring workgroup
-  constexpr int RPL = MarchDmaRows<NL, K, 4, 1, true, false>::LROWS, RCO = MarchDmaRows<NL, K, 2, 1, false, true>::LROWS;
+  constexpr int RPL = MarchDmaRows<NL, K, 4, 1, true, false>::LROWS, RCO = MarchDmaRows<NL, K, 2, 1, false, CORR>::LROWS;
   constexpr int RFUSED = PAIRS * (RA + RB + 2 * NL), RRING = KIND == 0 ? 0 : 2 * PAIRS * (KIND == 1 ? RPL : RCO);
   __shared__ __align__(16) double lds[RFUSED > RRING ? RFUSED : RRING][64];
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   if constexpr (KIND != 0) {
     if ((int)blockIdx.x < p.ring_wg) {   // uniform per workgroup
-      visit_ring_role<NL, KIND>(p, lds, wv, 2 * PAIRS);
+      visit_ring_role<NL, KIND, CORR>(p, lds, wv, 2 * PAIRS);
       return;
     }
   }
-  if (wv & 1) visit_role<NL, PAIRS, 2, KIND>(p, lds, wv >> 1);
-  else visit_role<NL, PAIRS, 1, KIND>(p, lds, wv >> 1);
+  if (wv & 1) visit_role<NL, PAIRS, 2, KIND, CORR>(p, lds, wv >> 1);
+  else visit_role<NL, PAIRS, 1, KIND, CORR>(p, lds, wv >> 1);
 }
 
 // the visit's chunk grid: nc chunks of H rows from row vy0, ns strips of 48 own lanes from kx = vx0 (a multiple of pairs)
@@ -1383,9 +1385,38 @@ static bool visit_geom(int hk, int ny, int rows, int pairs, VisitGeom &v) {
   v.ns = hk >= 64 ? ((hk - 64) / OW + 1) / pairs * pairs : 0;   // kx0 + 63 <= hk - 1
   return v.nc > 0 && v.ns > 0;
 }
+// Chunk height by rounds (march_visit_rows = 0).  All wave pairs of a launch take the same time, H + 4 K - 1 marching steps, and
+// `slots` of them are resident at once, so a level's fused chunks take ceil(pairs / slots) rounds of that many steps.  A level with
+// more than three rounds at 28 rows keeps 28 (the finest level at 4096^2: 5.9 rounds; short chunks even out its memory traffic and
+// the tail is a small share).  At or below three rounds the quantisation decides: the even H >= 14 with at least one chunk row that
+// minimises rounds x steps, the smallest such H on a tie.  Pure host arithmetic (tests/test_visit_levels_host.py)
+static int visit_rows_auto(int hk, int ny, int pairs, int slots) {
+  constexpr int K = 4;
+  VisitGeom v;
+  // a level too low for a 28-row chunk (ny < 44) has no rounds at 28 to count: it takes the minimiser like any level of few rounds
+  // (the caller asks whether the result fits); no slot count (no instantiation for nl): today's 28, or 14 where 28 does not fit
+  const bool fits28 = visit_geom(hk, ny, 28, pairs, v);
+  if (slots <= 0) return fits28 ? 28 : 14;
+  if (fits28 && (long long)v.nc * v.ns > 3LL * slots) return 28;
+  int best = 14;
+  long long cost = -1;
+  for (int H = 14; H <= ny; H += 2) {
+    if (!visit_geom(hk, ny, H, pairs, v)) break;   // no chunk row any more
+    const long long c = (((long long)v.nc * v.ns + slots - 1) / slots) * (H + 4 * K - 1);
+    if (cost < 0 || c < cost) { cost = c; best = H; }
+  }
+  return best;
+}
+extern "C" int msom_visit_rows(int hk, int ny, int pairs, int slots) {
+  if (hk <= 0 || ny <= 0 || (pairs != 1 && pairs != 2)) return -1;
+  VisitGeom v;
+  const int H = visit_rows_auto(hk, ny, pairs, slots);
+  return visit_geom(hk, ny, H, pairs, v) ? H : -1;
+}
+// rows = 0: the height follows the level (visit_rows_auto), never below 14 rows
 bool relax_visit_fits(int nl, const SplitGeom &sg, int rows, int pairs) {
   VisitGeom v;
-  return nl >= 2 && nl <= 6 && (pairs == 1 || pairs == 2) && visit_geom(sg.hk, sg.ny, rows, pairs, v);
+  return nl >= 2 && nl <= 6 && (pairs == 1 || pairs == 2) && visit_geom(sg.hk, sg.ny, rows > 0 ? rows : 14, pairs, v);
 }
 
 // The chunks of a pass around the visit (strips of ow own half-columns, chunks of H rows) that its skip rule admits: chunk
@@ -1431,37 +1462,83 @@ extern "C" int msom_visit_ring(int hk, int ny, int march_rows, int visit_rows, i
   return rb.n;
 }
 
+// corr: the trailing role applies the correction (the finest level) or stores the level's correction (k_relax_visit<.., CORR>)
 template <int NL>
-static void visit_dispatch(hipStream_t st, const MarchArgs &a, const VisitGeom &v, int pairs) {
+static void visit_dispatch(hipStream_t st, const MarchArgs &a, const VisitGeom &v, int pairs, bool corr) {
   // mixed launch (ring_kind): a 1-D grid, the ring workgroups first so that their latency-bound chains start with the launch
   const dim3 grid = a.ring_kind ? dim3(a.ring_wg + a.fnbx * a.fnby) : dim3(v.ns / pairs, v.nc);
+  if (!grid.x || !grid.y) return;
   // ring_kind is 0, 1 or 2 (launch_relax_visit), pairs 1 or 2 (relax_visit_fits)
   with_int<0, 2>(a.ring_kind, [&](auto R) {
     with_int<1, 2>(pairs, [&](auto P) {
       constexpr int PAIRS = decltype(P)::value;
-      hipLaunchKernelGGL((k_relax_visit<NL, PAIRS, decltype(R)::value>), grid, dim3(128 * PAIRS), 0, st, a);
+      if (corr) hipLaunchKernelGGL((k_relax_visit<NL, PAIRS, decltype(R)::value, true>), grid, dim3(128 * PAIRS), 0, st, a);
+      else hipLaunchKernelGGL((k_relax_visit<NL, PAIRS, decltype(R)::value, false>), grid, dim3(128 * PAIRS), 0, st, a);
     });
   });
 }
-static void visit_dispatch_nl(hipStream_t st, const MarchArgs &a, const VisitGeom &v, int pairs, int nl) {
-  // 2 .. 6: the visit is made of the K = 4 lean PL and CORR bodies, which exist up to 6 layers; relax_visit_fits admits this range
-  if (!with_int<2, 6>(nl, [&](auto N) { visit_dispatch<N()>(st, a, v, pairs); })) no_kernel("launch_relax_visit", nl);
+static void visit_dispatch_nl(hipStream_t st, const MarchArgs &a, const VisitGeom &v, int pairs, int nl, bool corr) {
+  // 2 .. 6: the visit is made of the K = 4 lean PL and CORR / plain bodies, which exist up to 6 layers; relax_visit_fits admits this range
+  if (!with_int<2, 6>(nl, [&](auto N) { visit_dispatch<N()>(st, a, v, pairs, corr); })) no_kernel("launch_relax_visit", nl);
+}
+// wave pairs of k_relax_visit<nl, pairs, kind, corr> the device holds at once: workgroups per CU from the occupancy calculator x pairs
+// per workgroup x CUs; asked once per (device, instantiation), as march_launch asks for its passes
+static int visit_slots(int nl, int pairs, int kind, bool corr) {
+  const void *kern = nullptr;
+  with_int<2, 6>(nl, [&](auto N) {
+    with_int<0, 2>(kind, [&](auto R) {
+      with_int<1, 2>(pairs, [&](auto P) {
+        constexpr int NL = decltype(N)::value, PAIRS = decltype(P)::value, KIND = decltype(R)::value;
+        kern = corr ? (const void *)k_relax_visit<NL, PAIRS, KIND, true> : (const void *)k_relax_visit<NL, PAIRS, KIND, false>;
+      });
+    });
+  });
+  if (!kern) return 0;
+  static std::mutex mu;
+  static std::map<std::pair<int, const void *>, int> cache;  // -> workgroups per CU
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  int per_cu = 0;
+  {
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = cache.find({dev, kern});
+    if (it == cache.end()) {
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 128 * pairs, 0) != hipSuccess || per_cu <= 0) per_cu = 4 / pairs;
+      cache[{dev, kern}] = per_cu;
+    } else {
+      per_cu = it->second;
+    }
+  }
+  return per_cu * pairs * device_cu_count();
+}
+// the chunk height launch_relax_visit takes for a level: option march_visit_rows or, 0, the rule by rounds
+int relax_visit_rows(const KernelOpts &o, int nl, const SplitGeom &sg, bool corr) {
+  if (o.march_visit_rows > 0) return (o.march_visit_rows + 1) & ~1;
+  const int pairs = o.march_visit_pairs;
+  if (nl < 2 || nl > 6 || (pairs != 1 && pairs != 2)) return 0;
+  // the instantiations that carry fused chunks: both mixed forms (march_visit_ring = 2), whose registers differ, or the 2-D grid's;
+  // the fewer slots of the two, so that a round counted here is a round in either launch
+  const int slots = o.march_visit_ring >= 2 ? std::min(visit_slots(nl, pairs, 1, corr), visit_slots(nl, pairs, 2, corr)) : visit_slots(nl, pairs, 0, corr);
+  return visit_rows_auto(sg.hk, sg.ny, pairs, slots);
 }
 
-// PL + 4 half-sweeps (colour 0 first) and 4 + correction, the prolongation from `coarse`; da_alt receives the first pass's values
-// where the two passes run, da is not used.  The passes run on the chunks that are not the visit's: the second one (CORR) on
-// those with own cells outside the visit's rows / columns; it reads the first one's values up to ring_rows + K rows and 64 lanes
-// from its own cells, so the first one runs on all chunks with own cells that far from the visit's interior (chunks of march_rows).
+// PL + 4 half-sweeps (colour 0 first) and 4 more, the prolongation from `coarse`.  mc != nullptr (the finest level): the second four
+// apply the correction and da is not used; mc == nullptr (a marched level below it): they store the level's correction, both colours,
+// in da.  da_alt receives the first pass's values where the two passes run.  The passes run on the chunks that are not the visit's: the
+// second one on those with own cells outside the visit's rows / columns; it reads the first one's values up to ring_rows + K rows and
+// 64 lanes from its own cells, so the first one runs on all chunks with own cells that far from the visit's interior (chunks of march_rows).
 // march_visit_ring: 0 the two passes launch their whole chunk grids around the fused launch and the chunks inside the skip
 // rectangles return at once; 1 they launch only the ring chunks (visit_ring_bands); 2 the ring chunks are workgroups of the fused
-// launches: launch A = ring PL + the first fused chunk rows, launch B = ring CORR + the other fused chunk rows.  The ring CORR
+// launches: launch A = ring PL + the first fused chunk rows, launch B = second ring + the other fused chunk rows.  The second ring's
 // chunks read what the ring PL chunks wrote, which the stream order of A and B provides; fused chunks depend on neither
 int launch_relax_visit(hipStream_t st, const KernelOpts &o, double *da, double *da_alt, const double *res, const SplitGeom &sg, int nl, const RelaxCoef &rc,
-                       int walls, const double *coarse, const SplitGeom &cg, const MarchCorrect &mc) {
-  const int rows = o.march_visit_rows, pairs = o.march_visit_pairs;
+                       int walls, const double *coarse, const SplitGeom &cg, const MarchCorrect *mc) {
+  const int pairs = o.march_visit_pairs;
+  const bool corr = mc != nullptr;
   VisitGeom v;
-  if (!relax_visit_fits(nl, sg, rows, pairs)) return -1;
-  visit_geom(sg.hk, sg.ny, rows, pairs, v);
+  if (!relax_visit_fits(nl, sg, o.march_visit_rows, pairs)) return -1;
+  const int rows = relax_visit_rows(o, nl, sg, corr);
+  if (!visit_geom(sg.hk, sg.ny, rows, pairs, v)) return -1;
   constexpr int K = 4;
   const int Hc = visit_ring_rows(o.march_rows);
   int skip_pl[4], skip_corr[4];
@@ -1473,33 +1550,35 @@ int launch_relax_visit(hipStream_t st, const KernelOpts &o, double *da, double *
   MarchArgs a{};
   a.res = res; a.g = sg; a.c1 = 0; a.walls = walls; a.rc = rc;
   a.coarse = coarse; a.cg = cg;
-  a.psi = mc.psi; a.psi_out = mc.psi_out; a.ng = mc.g;
-  a.partial = 1; a.lean = 2;
+  if (mc) { a.psi = mc->psi; a.psi_out = mc->psi_out; a.ng = mc->g; }
+  // (the leading wave stores nothing; the plain trailing wave stores both colours, as the last pass of a level does)
+  a.partial = corr ? 1 : 0; a.lean = 2;
+  a.out = corr ? nullptr : da;
   a.remap = o.march_xcd; a.flip = o.march_flip;
   a.H = v.H; a.vy0 = v.vy0; a.vx0 = v.vx0;
   if (ringopt >= 2) {
     const int nwv = 2 * pairs;
     a.fnbx = v.ns / pairs;
     a.rH = Hc;
-    a.rlean = o.march_lean ? o.march_lean * (int)march_lean_fits(nl, sg, &mc.g) : 0;
+    a.rlean = o.march_lean ? o.march_lean * (int)march_lean_fits(nl, sg, mc ? &mc->g : nullptr) : 0;
     // fused chunk rows of launch A: an even number, so that odd chunk rows stay the ones that march down.  A third of them:
-    // 4096^2 x 6 (145 chunk rows), ms per visit with 48 / 72 / 96 rows in launch A: 0.755 / 0.770 / 0.779
-    const int n1 = std::min(v.nc, (o.march_visit_split > 0 ? o.march_visit_split : v.nc / 3)) & ~1;
+    // 4096^2 x 6 (145 chunk rows), ms per visit with 48 / 72 / 96 rows in launch A: 0.755 / 0.770 / 0.779.  march_visit_split < 0: none
+    const int n1 = o.march_visit_split < 0 ? 0 : std::min(v.nc, (o.march_visit_split > 0 ? o.march_visit_split : v.nc / 3)) & ~1;
     a.ring_kind = 1;
     visit_ring_bands(sg.hk, sg.ny, 56, Hc, skip_pl, a.rb);
     a.ring_wg = (a.rb.n + nwv - 1) / nwv;
     a.fby0 = 0; a.fnby = n1;
     a.rin = nullptr; a.rout = da_alt;
-    visit_dispatch_nl(st, a, v, pairs, nl);
+    visit_dispatch_nl(st, a, v, pairs, nl, corr);
     a.ring_kind = 2;
     visit_ring_bands(sg.hk, sg.ny, 60, Hc, skip_corr, a.rb);
     a.ring_wg = (a.rb.n + nwv - 1) / nwv;
     a.fby0 = n1; a.fnby = v.nc - n1;
     a.rin = da_alt; a.rout = da;
-    visit_dispatch_nl(st, a, v, pairs, nl);
+    visit_dispatch_nl(st, a, v, pairs, nl, corr);
     return 0;
   }
   if (launch_relax_march(st, o, nullptr, da_alt, res, sg, nl, rc, 0, K, walls, Hc, nullptr, coarse, &cg, nullptr, 1, nullptr, 0, skip_pl, ringopt == 1)) return -1;
-  visit_dispatch_nl(st, a, v, pairs, nl);
-  return launch_relax_march(st, o, da_alt, da, res, sg, nl, rc, 0, K, walls, Hc, nullptr, nullptr, nullptr, &mc, 0, nullptr, 0, skip_corr, ringopt == 1);
+  visit_dispatch_nl(st, a, v, pairs, nl, corr);
+  return launch_relax_march(st, o, da_alt, da, res, sg, nl, rc, 0, K, walls, Hc, nullptr, nullptr, nullptr, mc, 0, nullptr, 0, skip_corr, ringopt == 1);
 }

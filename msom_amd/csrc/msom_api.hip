@@ -21,7 +21,12 @@
 // in front of it")
 #define RHS_CLOSE_MIN 23
 #define RHS_CLOSE_DEFAULT 2
-#define MARCH_HALO 4    // rows (= cells in x) of neighbour data a pass of up to 4 chained half-sweeps reads
+// option march_visit_levels = -1 (default): MARCH_VISIT_LEVELS_DEFAULT on levels below the finest of at least 2^MARCH_VISIT_LEVELS_MIN
+// cell-layers ("Fused visit below the finest level").  RK2 step on one MI355X, 0 -> 1: 4096^2 x 6 5.29 -> 5.10 ms (the
+// 2048^2 x 6 level: 0.318 -> 0.229 ms per visit), 4096^2 x 3 2.65 -> 2.61, 4096^2 x 2 (a level of 2^23 cell-layers) 1.948 -> 1.917
+#define MARCH_VISIT_LEVELS_DEFAULT 1
+#define MARCH_VISIT_LEVELS_MIN 23
+#define MARCH_HALO 4   // rows (= cells in x) of neighbour data a pass of up to 4 chained half-sweeps reads
 
 static void free_agglomeration(msom *m);
 
@@ -551,6 +556,7 @@ extern "C" int msom_set_option(msom_t *m, const char *key, double v) {
   else if (!strcmp(key, "march_correct")) m->march_correct = (int)v;
   else if (!strcmp(key, "march_visit")) m->march_visit = (int)v;
   else if (!strcmp(key, "march_visit_min")) m->march_visit_min = (int)v;
+  else if (!strcmp(key, "march_visit_levels")) m->march_visit_levels = (int)v;
   else if (!strcmp(key, "dbg_nosync")) m->dbg_nosync = (int)v;
   else if (!strcmp(key, "async_solve")) m->async_solve = (int)v;
   else if (!strcmp(key, "step_sync")) m->step_sync = (int)v;
@@ -631,6 +637,7 @@ static int march_levels(const msom *m);
 static int march_kmax(const msom *m);
 static bool march_lean_fine(const msom *m);
 static bool fine_visit_fused(const msom *m);
+static bool level_visit_fused(const msom *m, int k);
 static int level_path(const msom *m, int k);
 static bool restrict2_ok(const msom *m);
 static bool rhs_resid_emits(const msom *m, int want = -1);
@@ -681,6 +688,13 @@ extern "C" double msom_get_param(msom_t *m, const char *key) {
   if (!strcmp(key, "resmax_marching")) return m->uniformS && m->nl <= MSOM_FASTNL && m->g.nx >= 64 && m->g.ny >= 16 && m->opt.resmax_rows >= 0;
   // how the wall-ring chunks around the fused visit run (-1: no fused visit on this handle), as launch_relax_visit reads the option
   if (!strcmp(key, "march_visit_ring")) return !fine_visit_fused(m) ? -1 : (m->opt.march_visit_ring >= 2 ? 2 : (m->opt.march_visit_ring == 1 ? 1 : 0));
+  // level k's 4 + 4 half-sweeps take k_relax_visit (level 0: march_visit); the chunk height the launch then takes there
+  if (!strncmp(key, "march_visit_rows_", 17) && key[17] >= '0' && key[17] <= '9') {
+    const int k = atoi(key + 17);
+    return level_visit_fused(m, k) ? relax_visit_rows(m->opt, m->nl, m->sg[k], k == 0) : 0;
+  }
+  if (!strncmp(key, "march_visit_", 12) && key[12] >= '0' && key[12] <= '9') return level_visit_fused(m, atoi(key + 12));
+  if (!strcmp(key, "march_visit_levels")) return m->march_visit_levels;
   if (const int *o = kernel_opt(m->opt, key)) return *o;   // the handle's kernel options (march_rows, march_lean, ... rhs_dbg)
   if (!strcmp(key, "rhs_resid")) return rhs_resid_emits(m);   // the tendency + advance pass emits the next solve's first residual
   if (!strcmp(key, "rhs_close")) return rhs_close_mode(m);    // ... and closes the solve in front of it: 0 no, 1 first RK stage, 2 both
@@ -1176,6 +1190,12 @@ static int march_kmax(const msom *m) { return m->nl >= 7 && m->march_k > 3 ? 3 :
 // where a shorter one avoids it (K = 4 -> 3; a plain pass also 3 -> 2)
 enum { MA_DONE, MA_VISIT, MA_PL, MA_REDPROL, MA_PASS, MA_HALF };
 struct MarchAct { int kind, K; bool corr, partial; };
+// option march_visit_levels resolved for a level below the finest: asked for (1: wherever it applies), or (-1) the default on a level
+// big enough for the fused launch to gain
+static bool visit_levels_on(const msom *m, const Lev &L) {
+  if (m->march_visit_levels >= 0) return m->march_visit_levels > 0;
+  return MARCH_VISIT_LEVELS_DEFAULT && (size_t)L.sg->nx * L.sg->ny * m->nl >= ((size_t)1 << MARCH_VISIT_LEVELS_MIN);
+}
 static MarchAct march_next(const msom *m, const Lev &L, const Lev *coarse, int n, bool corr_req) {
   const int kmax = march_kmax(m), nl = m->nl;
   const bool deep = L.tiled || (L.walls & WALL_PER);   // the pass reads rows beyond the tile (relax_sweeps)
@@ -1194,6 +1214,12 @@ static MarchAct march_next(const msom *m, const Lev &L, const Lev *coarse, int n
         (m->march_visit >= 2 || (size_t)L.sg->nx * L.sg->ny * nl >= ((size_t)1 << m->march_visit_min)) && !L.tiled && L.walls == WALL_ALL &&
         march_lean_fine(m) && relax_visit_fits(nl, *L.sg, m->opt.march_visit_rows, m->opt.march_visit_pairs))
       return MarchAct{MA_VISIT, 8, true, false};
+    // ... and a marched level below the finest (option march_visit_levels): the same launch, its trailing wave storing the level's
+    // correction.  The same conditions without the correction; the lean body admitted for this level's fields
+    if (n == 8 && kmax == 4 && !L.fine && L.k > 0 && visit_levels_on(m, L) && m->opt.march_dma && m->uniformS && nl >= 2 && m->march_partial &&
+        !L.tiled && L.walls == WALL_ALL && m->opt.march_lean && march_lean_fits(nl, *L.sg, nullptr) &&
+        relax_visit_fits(nl, *L.sg, m->opt.march_visit_rows, m->opt.march_visit_pairs))
+      return MarchAct{MA_VISIT, 8, false, false};
     return pass(MA_PL, 3, false);
   }
   if (n >= 2) return pass(MA_PASS, 2, corr_req && L.fine);   // the very last pass of the finest level can apply the correction (mg_solve swaps)
@@ -1204,6 +1230,13 @@ static MarchAct march_next(const msom *m, const Lev &L, const Lev *coarse, int n
 static bool fine_visit_fused(const msom *m) {
   if (m->nlev < 2 || level_path(m, 0) != RP_MARCH) return false;
   const Lev L = tile_lev(m, 0), C = tile_lev(m, 1);
+  return march_next(m, L, fuse_prolong(m, L, 4) ? &C : nullptr, 8, corr_wanted(m)).kind == MA_VISIT;
+}
+// the same question for tile level k as mg_cycle_levels visits it with nrelax = 4 (msom_get_param("march_visit_<k>"))
+static bool level_visit_fused(const msom *m, int k) {
+  if (k == 0) return fine_visit_fused(m);
+  if (k < 0 || k + 1 >= m->nlev || level_path(m, k) != RP_MARCH) return false;
+  const Lev L = tile_lev(m, k), C = tile_lev(m, k + 1);
   return march_next(m, L, fuse_prolong(m, L, 4) ? &C : nullptr, 8, corr_wanted(m)).kind == MA_VISIT;
 }
 
@@ -1307,11 +1340,14 @@ bool relax_sweeps(msom *m, Lev &L, const Lev *coarse, int nrelax, int corners_la
       const MarchAct a = march_next(m, L, src, n, corr_req);
       if (a.kind == MA_HALF || a.kind == MA_DONE) break;
       if (a.kind == MA_VISIT) {
-        if (prof) prof_begin(m, m->prof_march_visit);
-        if (launch_relax_visit(m->st, m->opt, *L.da, *L.da_alt, L.res, *L.sg, nl, *L.rc, kwalls, *src->da, *src->sg, mc))
+        // the finest level: psi + da goes to psi_alt; a level below it: the visit leaves its correction in *L.da, ghost cells included
+        // (the wall chunks around the fused ones keep the general body), where the finer level's prolongation reads it
+        ProfSlot *ps = !m->profile ? nullptr : (a.corr ? &m->prof_march_visit : &m->prof_march_visit_coarse);
+        if (ps) prof_begin(m, *ps);
+        if (launch_relax_visit(m->st, m->opt, *L.da, *L.da_alt, L.res, *L.sg, nl, *L.rc, kwalls, *src->da, *src->sg, a.corr ? &mc : nullptr))
           m->sticky = MSOM_ERR_ARG;
-        if (prof) prof_end(m, m->prof_march_visit);
-        return true;
+        if (ps) prof_end(m, *ps);
+        return a.corr;
       } else if (a.kind == MA_REDPROL) {
         if (prof) prof_begin(m, m->prof_redprol);
         launch_relax_red_prolong(m->st, m->opt, *L.da, *src->da, *src->sg, L.res, L.S, *L.sg, nl, *L.rc, m->uniformS, L.walls);

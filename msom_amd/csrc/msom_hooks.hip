@@ -172,7 +172,7 @@ extern "C" int msom_dbg_op(msom_t *m, const char *op, int f_in, int f_out, doubl
 std::vector<std::pair<const char *, ProfSlot *>> prof_slots(msom *m) {
   return {{"sweep", &m->prof_sweep}, {"residual", &m->prof_resid}, {"block2", &m->prof_block}, {"march2", &m->prof_march[2]},
           {"march3", &m->prof_march[3]}, {"march4", &m->prof_march[4]}, {"march_pl", &m->prof_march_pl}, {"march_corr", &m->prof_march_corr},
-          {"march_visit", &m->prof_march_visit}, {"resid_max", &m->prof_resmax}, {"rhs", &m->prof_rhs}, {"red_prolong", &m->prof_redprol},
+          {"march_visit", &m->prof_march_visit}, {"march_visit_coarse", &m->prof_march_visit_coarse}, {"resid_max", &m->prof_resmax}, {"rhs", &m->prof_rhs}, {"red_prolong", &m->prof_redprol},
           {"resid_correct", &m->prof_rescorr}, {"resid_restrict", &m->prof_respre}, {"helm_relax", &m->prof_helm_relax},
           {"helm_residual", &m->prof_helm_resid}, {"helm_coarse", &m->prof_helm_coarse}, {"floats", &m->prof_floats},
           {"floats_emigrate", &m->prof_floats_emig}, {"floats_immigrate", &m->prof_floats_immig}};

@@ -132,7 +132,11 @@ struct msom {
   int march_correct = 1; // the last pass of the finest level writes psi + da instead of da (psi rows by LDS-DMA, deferred write): 7.02 -> 6.86 ms per step at 4096^2 x 6
   int march_visit = 1;   // the finest level's visit (PL + 4, 4 + correction) in one launch on its interior chunks (k_relax_visit);
                          // 1: on levels of at least 2^march_visit_min cell-layers, 2: wherever it applies (tests)
-  int march_visit_min = 25;  // 4096^2 x 6: 1.01 -> 0.87 ms per visit; 2048^2 x 3 (2^23.6) loses: 0.17 -> 0.21 ms (too few chunks to hide latency)
+  int march_visit_min = 23;  // 4096^2 x 6: 1.01 -> 0.87 ms per visit.  2048^2 x 3 (2^23.6) lost with three launches and 28-row chunks (0.17 -> 0.21 ms);
+                             // with the ring chunks inside the fused launches and the chunk height by rounds it wins: 0.162 -> 0.146 ms,
+                             // 2048^2 x 2 (2^23) 0.124 -> 0.109, 2048^2 x 6 0.349 -> 0.255
+  int march_visit_levels = -1;  // the same launch, its trailing wave storing the level's correction, on the marched levels below the finest:
+                                // 0 the finest level only, 1 every marched level that qualifies, -1 the default (MARCH_VISIT_LEVELS_DEFAULT)
   int march_prolong = 1; // whole levels: prolongation folded into the first pass ((PL + 4) + 4 half-sweeps; coarse rows by LDS-DMA, kernels_march.hip): 7.63 -> 7.09 ms per step at 4096^2 x 6
   int mg_fused = 1;  // fused residual+restriction and correction+residual passes of the multigrid cycle
   double *psi_alt = nullptr;  // second psi buffer (the fused correction writes out of place)
@@ -232,6 +236,7 @@ struct msom {
   ProfSlot prof_sweep, prof_resid, prof_block, prof_march[5];  // prof_march[K]: passes of K chained half-sweeps
   ProfSlot prof_march_pl;  // first pass of a level with the prolongation folded in
   ProfSlot prof_march_visit;  // the finest level's fused visit (k_relax_visit and the two passes on the chunks around it)
+  ProfSlot prof_march_visit_coarse;  // the fused visits of the marched levels below the finest (profile = 1)
   ProfSlot prof_march_corr, prof_resmax;  // last pass of the finest level with the correction folded in; max-only residual pass after it
   ProfSlot prof_rhs, prof_redprol, prof_rescorr, prof_respre;   // tendency pass, finest red+prolongation, post- / pre-cycle residual passes
   ProfSlot prof_floats;   // the floats' stages queued by msom_step (k_floats_stage)

@@ -9,7 +9,7 @@ g = QG(wl.double_gyre_params(N, nl, extra="NITERMAX = 1\n")); g.option("quiet", 
 g.set(F["PSI"], wl.synthetic_psi(nl, N, N)); g.set_const(); g.set_tnext(float("inf"))
 keys = sorted({kv.split("=")[0] for s in sets for kv in s.split(",") if kv})
 
-SLOTS = ("march_visit", "march_pl", "march_corr", "march4", "march3", "resid_restrict", "resid_max", "rhs")
+SLOTS = ("march_visit", "march_visit_coarse", "march_pl", "march_corr", "march4", "march3", "resid_restrict", "resid_max", "rhs")
 nst = 10 if N >= 2048 else 50
 for _ in range(2): g.step()
 for rep in range(2):
